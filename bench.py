@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Hot-path benchmark: LibriSpeech Conformer-12 + CTC training steps on synthetic 16 kHz audio.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = one optimizer update on one per-GPU batch of the recipe
@@ -265,6 +265,44 @@ def decode_cpu_baseline(model, d, n_utts=6, seconds=6.4, beam=10):
             "sample": f"{n_utts} x {seconds:.0f} s utterances, beam {beam}, fp32, oracle/decode_ref.py (fbank excluded), no LM fusion; {el:.1f} s"}
 
 
+DUMP_SAMPLE = 1 << 21  # values per sampled array of --dump-outputs (8 MB of float32 each, 24 MB for the three)
+
+
+def dump_outputs(out_dir, model, trainer, step_out, seed=0):
+    """--dump-outputs DIR: what the last timed update step handed back, as .npy files, so that two builds can be compared output for
+    output (the inputs are seeded: same arguments, same batches, same weights, same dropout seeds).
+      step.npy        float64 [4]  train_step's return value: sample_size, summed CTC loss, ntokens, nsentences
+      clip.npy        float64 [2]  the update's applied clip scale and gradient norm
+      params.npy      float32      the updated fp32 weights   } at one fixed, seeded sample of DUMP_SAMPLE positions of the
+      exp_avg.npy     float32      Adam's first moment        } trainable parameters laid end to end in named_parameters()
+      exp_avg_sq.npy  float32      Adam's second moment       } order (independent of the flat buffer's padding)
+      buffers.npy     float32      every floating-point buffer (BatchNorm running statistics), named_buffers() order"""
+    flat, opt = trainer.flat, trainer.optimizer
+    named = [(n, p) for n, p in model.named_parameters() if id(p) in flat.offsets]
+    sizes = np.array([p.numel() for _, p in named], dtype=np.int64)
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    total = int(starts[-1])
+    pick = np.sort(np.random.default_rng(seed).choice(total, size=min(DUMP_SAMPLE, total), replace=False))
+    bounds = np.searchsorted(pick, starts)
+    sampled = {"params": [], "exp_avg": [], "exp_avg_sq": []}
+    for j, (_, p) in enumerate(named):
+        local = pick[bounds[j]:bounds[j + 1]] - starts[j]
+        if len(local) == 0:
+            continue
+        idx = torch.from_numpy(local).to(p.device)
+        o, n = flat.offsets[id(p)], p.numel()
+        sampled["params"].append(p.detach().reshape(-1).index_select(0, idx))
+        sampled["exp_avg"].append(opt.exp_avg[o:o + n].index_select(0, idx))
+        sampled["exp_avg_sq"].append(opt.exp_avg_sq[o:o + n].index_select(0, idx))
+    arrays = {k: torch.cat(v).float().cpu().numpy() for k, v in sampled.items()}
+    arrays["step"] = step_out.double().cpu().numpy()
+    arrays["clip"] = trainer.last_coef.double().cpu().numpy()
+    arrays["buffers"] = torch.cat([b.detach().reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()]).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def spawn_ranks(n, fn, args=()):
     """`python bench.py --gpus N` outside torchrun: start N ranks of this node (one per GPU) with the rendezvous environment the
     driver's torch.distributed.run launch would provide, wait for them, propagate failures."""
@@ -312,7 +350,11 @@ def main(argv=None):
     ap.add_argument("--deferred-inline", action="store_true", help="A/B switch: deferred side work on the main stream (no overlap)")
     ap.add_argument("--no-conv-igemm", action="store_true", help="A/B switch: im2col + GEMM + col2im sub-sampler (round 1) instead of the implicit GEMM")
     ap.add_argument("--no-deferred", action="store_true", help="A/B switch: layer backward joins its side work inside every call")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed to DIR/*.npy (see dump_outputs; rank 0)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "RANK" not in os.environ:
         # not under torch.distributed.run: spawn one rank per GPU ourselves (rank 0 prints the line on the inherited stdout)
         os.dup2(json_fd, 1)
@@ -385,7 +427,7 @@ def main(argv=None):
     t0 = time.perf_counter()
     host_marks = [t0]
     for i in range(args.warmup, need):
-        trainer.train_step([samples[i]])
+        step_out = trainer.train_step([samples[i]])
         host_marks.append(time.perf_counter())  # (host clock only: nothing here waits for the device)
     host_enqueue = host_marks[-1] - t0  # time for the host to enqueue all steps (diagnostic only)
     # the host runs ahead of the device until the HIP queue is full and then blocks inside launches: the fastest steps show what
@@ -418,6 +460,8 @@ def main(argv=None):
         dist.all_gather(rows, row)
         probe = [[int(v) for v in r.tolist() if v > -9.0] for r in rows]
     loss_stats = trainer._stats.clone()
+    if args.dump_outputs and rank == 0:  # before the roofline replay below steps the trainer again
+        dump_outputs(args.dump_outputs, model, trainer, step_out)
 
     roofline = None
     if rank == 0 and not args.no_roofline:

@@ -735,3 +735,18 @@ def speech_lstm(feats, lengths, prev_tokens, sd, enc_residual=False, dec_residua
     sdd = {k: (v.float() if torch.is_tensor(v) and v.is_floating_point() and v.dtype != torch.float32 else v) for k, v in sd.items()}
     x, out_len = speech_lstm_encoder(feats, lengths, sdd, residual=enc_residual, training=training, update=update)
     return speech_lstm_decoder(prev_tokens, x, out_len, sdd, residual=dec_residual, pad_idx=pad_idx)[0], x, out_len
+
+
+def seeded_weights(params, seed):
+    """Weights for a fixture that stores the parameters' names and shapes instead of their values: `params` = [(name, shape)] in
+    a fixed order, one torch generator seeded with `seed` draws them in that order.  Matrices and kernels ~ N(0, 1 / fan_in);
+    vectors ~ N(0, 0.1^2), plus 1 for the scales (`*.weight`) of LayerNorm / BatchNorm."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for name, shape in params:
+        x = torch.randn(tuple(shape), generator=g)
+        if len(shape) >= 2:
+            sd[name] = x * (math.prod(shape[1:]) ** -0.5)
+        else:
+            sd[name] = 0.1 * x + (1.0 if name.endswith(".weight") else 0.0)
+    return sd

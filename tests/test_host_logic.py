@@ -719,19 +719,24 @@ def test_trainer_checkpoint_round_trip(tmp_path):
         make(4).load_checkpoint(str(tmp_path / "bad.pt"))
 
 
-_REF_RECIPES = "/root/reference/examples/asr_librispeech/config"
-
-
-@pytest.mark.skipif(not os.path.isdir(_REF_RECIPES), reason="the reference's recipe YAMLs are only present in the build container")
-def test_every_asr_recipe_of_the_reference_builds(tmp_path):
-    """Each ASR recipe YAML of the reference, read as it is, yields task + model + criterion + optimizer + schedule through the
-    training entry point's builders (what `fairseq-hydra-train --config-name <recipe>` resolves through hydra)."""
+def test_every_asr_recipe_of_the_reference_builds(tmp_path, golden_dir):
+    """Each ASR recipe YAML of the reference (examples/asr_librispeech/config, stored as parsed in tests/golden/ref_asr_recipes.json
+    and written back to YAML files here) yields task + model + criterion + optimizer + schedule through the training entry
+    point's builders (what `fairseq-hydra-train --config-name <recipe>` resolves through hydra)."""
     import glob
+    import json
+
+    import yaml
 
     from espresso_amd import speech_train as st
     from espresso_amd.config import load_config
     from espresso_amd.trainer import Trainer
 
+    recipes = tmp_path / "config"
+    recipes.mkdir()
+    with open(os.path.join(golden_dir, "ref_asr_recipes.json")) as f:
+        for name, body in json.load(f).items():
+            (recipes / (name + ".yaml")).write_text(yaml.safe_dump(body))
     (tmp_path / "dict.txt").write_text("".join(f"u{i} 1\n" for i in range(5000)))
     want = {  # recipe -> (model, criterion, dictionary size incl. specials [+ <s> as blank], schedule)
         "conformer_librispeech": ("speech_transformer_base", "label_smoothed_cross_entropy_v2", 5003, "TriStageLRSchedule"),
@@ -745,7 +750,7 @@ def test_every_asr_recipe_of_the_reference_builds(tmp_path):
         "lstm_lm_librispeech": ("lstm_lm_espresso", "cross_entropy", 5003, "ReduceLROnPlateauLRSchedule"),
     }
     seen = set()
-    for y in sorted(glob.glob(os.path.join(_REF_RECIPES, "*.yaml"))):
+    for y in sorted(glob.glob(os.path.join(recipes, "*.yaml"))):
         name = os.path.basename(y)[:-5]
         if name not in want:
             continue
@@ -767,7 +772,7 @@ def test_every_asr_recipe_of_the_reference_builds(tmp_path):
         del tr, model
     assert seen == set(want)
     # the headline recipe: 12 x 512 encoder; `model.encoder.layer_type=conformer` is the command-line override of run_torchaudio.sh
-    cfg = load_config(os.path.join(_REF_RECIPES, "transformer_ctc_librispeech.yaml"),
+    cfg = load_config(os.path.join(recipes, "transformer_ctc_librispeech.yaml"),
                       [f"task.data={tmp_path}", f"task.dict={tmp_path}/dict.txt", "bpe.sentencepiece_model=none", "model.encoder.layer_type=conformer"])
     cfg["bpe"] = {}
     task = st.build_task(cfg)

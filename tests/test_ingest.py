@@ -126,20 +126,18 @@ def test_flac_other_sample_sizes_and_wasted_bits(tmp_path):
     assert _lib.lib().ea_audio_verify(p.encode()) == 1
 
 
-REF_FLAC = "/root/reference/examples/hubert/tests/6313-76958-0021.flac"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_FLAC), reason="the reference tree (its LibriSpeech test utterance) is only in the build container")
-def test_flac_decoder_on_a_real_librispeech_file():
-    """libFLAC-encoded LibriSpeech audio from the reference's own test data: the MD5 of what this decoder produces must equal the
-    signature libFLAC stored in STREAMINFO, every frame CRC-16 must hold."""
+def test_flac_decoder_on_a_real_librispeech_file(golden_dir):
+    """libFLAC-encoded LibriSpeech audio (utterance 6313-76958-0021 of the reference's own test data, stored as it is under
+    tests/golden/): the MD5 of what this decoder produces must equal the signature libFLAC stored in STREAMINFO, every frame
+    CRC-16 must hold."""
     from espresso_amd import _lib
 
-    n, sr, ch, bits = AU.probe(REF_FLAC)
+    flac = os.path.join(golden_dir, "6313-76958-0021.flac")
+    n, sr, ch, bits = AU.probe(flac)
     assert (sr, ch, bits) == (16000, 1, 16) and n > 16000
-    assert _lib.lib().ea_audio_verify(REF_FLAC.encode()) == 1
-    y, _ = AU.read_i16(REF_FLAC)
-    sig = open(REF_FLAC, "rb").read()[8 + 18:8 + 34]
+    assert _lib.lib().ea_audio_verify(flac.encode()) == 1
+    y, _ = AU.read_i16(flac)
+    sig = open(flac, "rb").read()[8 + 18:8 + 34]
     assert hashlib.md5(y.astype("<i2").tobytes()).digest() == sig and np.abs(y).max() > 500
 
 

@@ -1,46 +1,43 @@
 """The argparse presets `speech_transformer_{wsj,librispeech,swbd}` (espresso/models/transformer/speech_transformer_legacy.py)
-against the reference itself: same nested configuration after `base_architecture`, same parameter names and shapes.
-Needs the reference tree (build container only; skipped on the GPU box)."""
-import argparse
+against the reference itself: same nested configuration after `base_architecture`, same parameter names and shapes.  What the
+reference derives and builds is stored in tests/golden/ref_legacy_presets.json (oracle/gen_golden.py legacypresets)."""
+import json
 import os
-import sys
 
 import pytest
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference tree (build container only)")
+ENCODER_FIELDS = ("embed_dim", "ffn_embed_dim", "layers", "attention_heads", "normalize_before", "learned_pos", "relative_positional_embeddings",
+                  "conv_channels", "conv_kernel_sizes", "conv_strides")
+DECODER_FIELDS = ("embed_dim", "ffn_embed_dim", "layers", "attention_heads", "normalize_before", "learned_pos", "input_dim", "output_dim")
+TOP_FIELDS = ("dropout", "attention_dropout", "activation_dropout", "activation_fn", "layernorm_embedding", "no_scale_embedding",
+              "no_token_positional_embeddings", "share_decoder_input_output_embed")
+
+
+def _plain(v):  # the fixture's JSON form of a value (tuples read back as lists)
+    return json.loads(json.dumps(v))
 
 
 @pytest.mark.parametrize("arch,overrides", [("speech_transformer_wsj", {}), ("speech_transformer_librispeech", {"encoder_layers": 2, "decoder_layers": 1}),
                                             ("speech_transformer_swbd", {"encoder_layers": 2, "decoder_layers": 1, "dropout": 0.3})])
-def test_preset_config_and_parameter_names_equal_the_reference(arch, overrides):
-    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, os.path.join(here, "oracle", "ref_stubs"))
-    sys.path.insert(1, REF)
+def test_preset_config_and_parameter_names_equal_the_reference(arch, overrides, golden_dir):
     import torch
-    import fairseq  # noqa: F401
-    import espresso  # noqa: F401
-    from fairseq.models import ARCH_CONFIG_REGISTRY
-    from espresso.models.transformer.speech_transformer_config import SpeechTransformerConfig as RefCfg
 
     import espresso_amd  # noqa: F401
     from espresso_amd.models.transformer.speech_transformer_legacy import SpeechTransformerModel, config_from_flat
 
-    ns = argparse.Namespace(**overrides)
-    ARCH_CONFIG_REGISTRY[arch](ns)  # the reference's preset function fills in every default
-    ref = RefCfg.from_namespace(ns)
+    with open(os.path.join(golden_dir, "ref_legacy_presets.json")) as f:
+        ref = json.load(f)[arch]  # the reference's preset function filled in every default
     mine = config_from_flat(dict(overrides, arch=arch))
-    for f in ("embed_dim", "ffn_embed_dim", "layers", "attention_heads", "normalize_before", "learned_pos", "relative_positional_embeddings",
-              "conv_channels", "conv_kernel_sizes", "conv_strides"):
-        assert getattr(mine.encoder, f) == getattr(ref.encoder, f), ("encoder." + f, getattr(mine.encoder, f), getattr(ref.encoder, f))
-    for f in ("embed_dim", "ffn_embed_dim", "layers", "attention_heads", "normalize_before", "learned_pos", "input_dim", "output_dim"):
-        assert getattr(mine.decoder, f) == getattr(ref.decoder, f), ("decoder." + f, getattr(mine.decoder, f), getattr(ref.decoder, f))
-    for f in ("dropout", "attention_dropout", "activation_dropout", "activation_fn", "layernorm_embedding", "no_scale_embedding",
-              "no_token_positional_embeddings", "share_decoder_input_output_embed"):
-        assert getattr(mine, f) == getattr(ref, f), (f, getattr(mine, f), getattr(ref, f))
+    for f in ENCODER_FIELDS:
+        assert _plain(getattr(mine.encoder, f)) == ref["encoder"][f], ("encoder." + f, getattr(mine.encoder, f), ref["encoder"][f])
+    for f in DECODER_FIELDS:
+        assert _plain(getattr(mine.decoder, f)) == ref["decoder"][f], ("decoder." + f, getattr(mine.decoder, f), ref["decoder"][f])
+    for f in TOP_FIELDS:
+        assert _plain(getattr(mine, f)) == ref["top"][f], (f, getattr(mine, f), ref["top"][f])
 
-    if ref.encoder.layers > 2:
-        return  # parameter-name comparison on the shrunken variants only (a 12-layer 512-wide model is slow to build twice on CPU)
+    if ref["encoder"]["layers"] > 2:
+        assert ref["state_dict"] is None
+        return  # parameter-name comparison on the shrunken variants only (a 12-layer 512-wide model is slow to build on CPU)
 
     class _Task:
         feat_dim, feat_in_channels = 80, 1
@@ -53,19 +50,13 @@ def test_preset_config_and_parameter_names_equal_the_reference(arch, overrides):
 
     task = _Task()
     model = SpeechTransformerModel.build_model(dict(overrides, arch=arch), task)
-    from espresso.models.transformer.speech_transformer_legacy import SpeechTransformerModel as RefModel
 
-    ns2 = argparse.Namespace(**overrides, max_source_positions=3600, max_target_positions=200, scheduled_sampling_probs=[1.0],
-                             start_scheduled_sampling_epoch=1)
-    ARCH_CONFIG_REGISTRY[arch](ns2)
-
-    class _RefTask:
-        feat_dim, feat_in_channels = 80, 1
-        target_dictionary = task.target_dictionary
-        source_dictionary = None
-
-    rmodel = RefModel.build_model(ns2, _RefTask())
-    rsd = {k: v for k, v in rmodel.state_dict().items()}
+    # the reference model's state dict: its own names, shapes, dtypes and buffers; seeded values for its parameters
+    g = torch.Generator().manual_seed(0)
+    rsd = {}
+    for k, shape, dtype, values in ref["state_dict"]:
+        dt = getattr(torch, dtype)
+        rsd[k] = torch.randn(shape, generator=g).to(dt) if values is None else torch.tensor(values, dtype=dt).reshape(shape)
     rsd = model.upgrade_state_dict_named(dict(rsd), "")
     msd = model.state_dict()
     assert set(rsd) == set(msd), (sorted(set(rsd) - set(msd))[:8], sorted(set(msd) - set(rsd))[:8])
