@@ -738,6 +738,26 @@ def gather_rows(src, parent, out=None):
     return out
 
 
+def multilevel_lm_step(word_logits, sub_logits, prev_tok, prev_out, word_lp, cum, nodes, children, prev_subword, word_idx,
+                       subword_weight, log_oov_penalty, open_vocab, word_eos, word_unk, sub_space, sub_eos, root_id):
+    """One multi-level LM fusion step (ea_multilevel_lm_step): updates word_lp [N][Vw] / cum [N] / nodes [N] in place and
+    returns the fused sub-word log-probs fp32 [N][Vs].  prev_out None = the first call (every row refreshes its word
+    distribution and sits at the root)."""
+    N, Vw = word_logits.shape
+    Vs = sub_logits.shape[1]
+    assert word_logits.dtype == sub_logits.dtype == torch.float32 and word_logits.stride(1) == 1 and sub_logits.stride(1) == 1
+    assert prev_tok.dtype == nodes.dtype == torch.int32 and prev_tok.is_contiguous() and nodes.is_contiguous()
+    assert word_lp.shape == (N, Vw) and word_lp.is_contiguous() and cum.shape == (N,) and cum.is_contiguous()
+    assert prev_out is None or (prev_out.shape == (N, Vs) and prev_out.is_contiguous())
+    out = torch.empty(N, Vs, dtype=torch.float32, device=sub_logits.device)
+    check(_lib.lib().ea_multilevel_lm_step(_p(word_logits), word_logits.stride(0), _p(sub_logits), sub_logits.stride(0), _p(prev_tok),
+                                           _p(prev_out), _p(word_lp), _p(cum), _p(nodes), _p(out), _p(children), _p(prev_subword),
+                                           _p(word_idx), N, Vw, Vs, children.shape[1], subword_weight, log_oov_penalty,
+                                           int(prev_out is None), int(open_vocab), word_eos, word_unk, sub_space, sub_eos, root_id,
+                                           _stream()), "ea_multilevel_lm_step")
+    return out
+
+
 def joint_add_relu(E, D, B, T, U1):
     """Z [B*T*U1][J] bf16 = relu(E[b,t] + D[b,u]).  E, D fp32 (the model's path: sum and ReLU in fp32 as in the reference's
     autocast run, only Z is rounded) or both bf16."""

@@ -1,5 +1,5 @@
 """Batched recognition CLI — the decoding loop and output format of espresso/speech_recognize.py:60-360 on the HIP path:
-for every batch run the chosen search (beam search with optional LM / look-ahead word-LM fusion, CTC greedy, transducer
+for every batch run the chosen search (beam search with optional LM / look-ahead word-LM / multi-level LM fusion, CTC greedy, transducer
 greedy / beam), print `T-<utt>` (reference) and `H-<utt>` (hypothesis, score in base 2) lines, accumulate WER / CER with
 `tools.wer.Scorer`, and close with the "Recognized N utterances ..." summary.
 
@@ -151,11 +151,16 @@ def get_parser():
     p.add_argument("--unkpen", type=float, default=0.0)
     p.add_argument("--temperature", type=float, default=1.0)
     p.add_argument("--eos-factor", type=float, default=None)
-    p.add_argument("--lm-path", default=None)
+    p.add_argument("--lm-path", default=None,
+                   help="LSTM LM state_dict; `sub.pt:word.pt` with --word-dict = multi-level fusion (sub-word LM, then word LM)")
     p.add_argument("--lm-arch", default="lstm_lm_librispeech")
+    p.add_argument("--word-lm-arch", default="lstm_lm_wsj", help="architecture of the word LM of a multi-level `--lm-path a:b`")
     p.add_argument("--lm-weight", type=float, default=0.0)
     p.add_argument("--word-dict", default=None, help="enables look-ahead word-LM fusion (the LM at --lm-path is a word LM)")
     p.add_argument("--oov-penalty", type=float, default=1e-4)
+    p.add_argument("--subwordlm-weight", type=float, default=0.8, help="sub-word LM weight of multi-level fusion")
+    p.add_argument("--disable-open-vocab", action="store_true",
+                   help="look-ahead / multi-level fusion: no probability mass for words outside the --word-dict lexicon")
     p.add_argument("--max-num-expansions-per-step", type=int, default=2)
     p.add_argument("--expansion-beta", type=int, default=0)
     p.add_argument("--expansion-gamma", type=float, default=None)
@@ -168,6 +173,23 @@ def get_parser():
     p.add_argument("--shard-id", type=int, default=int(os.environ.get("RANK", "0")), help="this replica (default: RANK)")
     p.add_argument("--device", default=None, help="default: cuda:LOCAL_RANK (cuda:0 outside a launcher)")
     return p
+
+
+def lm_fusion_mode(args):
+    """Which LM the search fuses, from `--lm-path` / `--word-dict` / `--search` (espresso/speech_recognize.py:130-148):
+    None, "subword" (one sub-word LM), "lookahead" (one word LM + --word-dict) or "multilevel" (`sub.pt:word.pt` +
+    --word-dict).  Raises before anything is loaded for combinations that have no implementation."""
+    if not args.lm_path:
+        return None
+    paths = args.lm_path.split(os.pathsep)
+    if len(paths) == 1:
+        return "lookahead" if args.word_dict else "subword"
+    if len(paths) != 2 or not args.word_dict:
+        raise ValueError("--lm-path with two LMs (multi-level fusion) is `sub.pt:word.pt` together with --word-dict")
+    if args.search != "beam":
+        raise NotImplementedError("multi-level (sub-word + word) LM fusion is implemented for the attention decoder's beam search "
+                                  "(--search beam): the transducer decoders fuse one LSTM LM and the CTC decoder none")
+    return "multilevel"
 
 
 def _load_file(path):
@@ -211,10 +233,12 @@ def resolve_model_config(model_name, model_config_path, checkpoint):
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
+    lm_mode = lm_fusion_mode(args)
     import yaml
 
     from . import registry
     from .data.asr_dictionary import AsrDictionary
+    from .models.external_language_model import MultiLevelLanguageModel
     from .models.lstm_lm import LSTMLanguageModelEspresso
     from .models.tensorized_lookahead_language_model import TensorizedLookaheadLanguageModel
     from .tasks.speech_recognition import SpeechRecognitionEspressoConfig, SpeechRecognitionEspressoTask
@@ -256,11 +280,21 @@ def main(argv=None):
             target_dictionary = source_dictionary = task.target_dictionary
         if args.word_dict:
             _LMTask.word_dictionary = AsrDictionary.load(args.word_dict, enable_bos=False)
-        lm = LSTMLanguageModelEspresso.build_model(dict(arch=args.lm_arch, is_wordlm=bool(args.word_dict)), _LMTask)
-        lm.load_state_dict(_load_state(args.lm_path), strict=True)
-        lm = lm.to(dev).eval()
-        if args.word_dict:
-            lm = TensorizedLookaheadLanguageModel(lm, task.target_dictionary, oov_penalty=args.oov_penalty)
+        if lm_mode == "multilevel":
+            sub_path, word_path = args.lm_path.split(os.pathsep)
+            sub_lm = LSTMLanguageModelEspresso.build_model(dict(arch=args.lm_arch, is_wordlm=False), _LMTask)
+            sub_lm.load_state_dict(_load_state(sub_path), strict=True)
+            word_lm = LSTMLanguageModelEspresso.build_model(dict(arch=args.word_lm_arch, is_wordlm=True), _LMTask)
+            word_lm.load_state_dict(_load_state(word_path), strict=True)
+            lm = MultiLevelLanguageModel(word_lm.to(dev).eval(), sub_lm.to(dev).eval(), subwordlm_weight=args.subwordlm_weight,
+                                         oov_penalty=args.oov_penalty, open_vocab=not args.disable_open_vocab)
+        else:
+            lm = LSTMLanguageModelEspresso.build_model(dict(arch=args.lm_arch, is_wordlm=bool(args.word_dict)), _LMTask)
+            lm.load_state_dict(_load_state(args.lm_path), strict=True)
+            lm = lm.to(dev).eval()
+            if args.word_dict:
+                lm = TensorizedLookaheadLanguageModel(lm, task.target_dictionary, oov_penalty=args.oov_penalty,
+                                                      open_vocab=not args.disable_open_vocab)
     gen = build_generator(args, members if len(members) > 1 else model, task.target_dictionary, lm)
     scp = read_scp(args.wav_scp)
     utt_ids = list(scp.keys())

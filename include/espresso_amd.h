@@ -659,6 +659,21 @@ int ea_lookahead_logprobs(const int* nodes, const int* prev_tok, const float* cu
                           ea_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Multi-level (sub-word + word) LM fusion (csrc/multilevel.hip) — espresso/models/external_language_model.py:376-552 over the
+ * same int32 tree tensors as the look-ahead kernels (children [NN][D], prev_subword [NN], word_idx [NN]; node 0 = none).
+ * ea_multilevel_lm_step: one beam step after both LMs' output GEMMs (fp32 logits, rows ldw / lds apart).
+ *   word_lp fp32 [N][Vw] <- log_softmax(word_logits) on the first call and where prev_tok == sub_space, else kept;
+ *   nodes int32 [N] <- tree transition on prev_tok (root on the first call); cum fp32 [N] <- running sub-word score of the
+ *   current word, accumulated from prev_out fp32 [N][Vs] (the previous call's out; NULL on the first call);
+ *   out fp32 [N][Vs] = subword_weight * log_softmax(sub_logits) with the <space> column replaced by the word score and the
+ *   closed-vocabulary / <space> / <eos> masks (logzero = -10). */
+int ea_multilevel_lm_step(const float* word_logits, long ldw, const float* sub_logits, long lds, const int* prev_tok,
+                          const float* prev_out, float* word_lp, float* cum, int* nodes, float* out, const int* children,
+                          const int* prev_subword, const int* word_idx, int N, int Vw, int Vs, int D, float subword_weight,
+                          float log_oov_penalty, int first, int open_vocab, int word_eos, int word_unk, int sub_space, int sub_eos,
+                          int root_id, ea_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * LSTM cell element-wise stages (csrc/lstm.hip) — torch.nn.LSTMCell as driven by espresso/models/speech_lstm.py:846-893
  * (transducer predictor, LSTM LM, attention decoder).  The packed pre-activations gates_pre = x W_ih^T + b_ih + h W_hh^T
  * + b_hh ([B][ldg] fp32, gate order i,f,g,o) come from ea_gemm_bf16 (fp32 output, fp32 residual).
