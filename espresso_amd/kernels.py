@@ -552,6 +552,41 @@ def ctc_greedy_decode(x, in_len, B, T, V, blank, pad, ld=None, want_align=True):
     return tokens, out_len, score, align
 
 
+def ctc_prefix_beam_workspace(B, T, beam, device):
+    """Workspace of the CTC prefix beam search (ea_ctc_prefix_beam_workspace_bytes): the beams and prefix tables of B utterances."""
+    return torch.empty(int(_lib.lib().ea_ctc_prefix_beam_workspace_bytes(B, T, beam)), dtype=torch.uint8, device=device)
+
+
+def ctc_prefix_beam_step(x, in_len, ws, B, T, V, beam, K, blank, t0, t1, lm_rows=None, lm_weight=0.0, ins_bonus=0.0, lm_out=None,
+                         ld=None):
+    """Frames [t0, t1) of the CTC prefix beam search over x [B*T][V] fp32/bf16 log-probs (batch-major).  With an LM: lm_rows
+    fp32 [B*beam][V], t1 = t0 + 1 and lm_out = (parent int32, token int32, keep uint8), each [B*beam], written by the step."""
+    ld = x.stride(0) if ld is None else ld
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.stride(-1) == 1 and x.shape[0] == B * T and x.shape[1] == V
+    assert in_len.dtype == torch.int32 and in_len.numel() == B and ws.numel() >= _lib.lib().ea_ctc_prefix_beam_workspace_bytes(B, T, beam)
+    parent, token, keep = lm_out if lm_out is not None else (None, None, None)
+    if lm_rows is not None:
+        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (B * beam, V) and t1 == t0 + 1
+        assert parent.numel() == token.numel() == keep.numel() == B * beam
+        assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
+    check(_lib.lib().ea_ctc_prefix_beam_step(_p(x), ld, int(x.dtype == torch.bfloat16), _p(in_len), _p(ws), _p(lm_rows),
+                                             lm_rows.stride(0) if lm_rows is not None else 0, _p(parent), _p(token), _p(keep), B, T,
+                                             V, beam, K, blank, lm_weight, ins_bonus, t0, t1, _stream()), "ea_ctc_prefix_beam_step")
+
+
+def ctc_prefix_beam_finish(ws, B, T, beam, nbest, pad, lm_rows=None, lm_weight=0.0, ins_bonus=0.0, eos=-1):
+    """(tokens int32 [B][nbest][T] pad-filled, lengths int32 [B][nbest], scores fp32 [B][nbest], nhyp int32 [B]), best first."""
+    dev = ws.device
+    tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
+    lengths = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
+    nhyp = torch.empty(B, dtype=torch.int32, device=dev)
+    check(_lib.lib().ea_ctc_prefix_beam_finish(_p(ws), _p(lm_rows), lm_rows.stride(0) if lm_rows is not None else 0, lm_weight,
+                                               ins_bonus, eos, B, T, beam, nbest, pad, _p(tokens), _p(lengths), _p(scores),
+                                               _p(nhyp), _stream()), "ea_ctc_prefix_beam_finish")
+    return tokens, lengths, scores, nhyp
+
+
 def embedding_fwd(tokens, positions, W, pos_table, scale):
     M, C = tokens.numel(), W.shape[1]
     out = torch.empty(M, C, dtype=torch.bfloat16, device=W.device)

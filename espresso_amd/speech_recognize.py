@@ -1,7 +1,8 @@
 """Batched recognition CLI — the decoding loop and output format of espresso/speech_recognize.py:60-360 on the HIP path:
-for every batch run the chosen search (beam search with optional LM / look-ahead word-LM / multi-level LM fusion, CTC greedy, transducer
-greedy / beam), print `T-<utt>` (reference) and `H-<utt>` (hypothesis, score in base 2) lines, accumulate WER / CER with
-`tools.wer.Scorer`, and close with the "Recognized N utterances ..." summary.
+for every batch run the chosen search (beam search with optional LM / look-ahead word-LM / multi-level LM fusion, CTC greedy,
+CTC prefix beam search with optional LM fusion, transducer greedy / beam), print `T-<utt>` (reference) and `H-<utt>`
+(hypothesis, score in base 2) lines, accumulate WER / CER with `tools.wer.Scorer`, and close with the "Recognized N utterances
+..." summary.
 
 Checkpoint management is fairseq's and stays out of this framework (SURVEY §2 out of scope): the model is built from a
 config mapping (`--model-config`, the `model:` block of the recipe YAML as JSON/YAML) and a `state_dict` file (`--path`:
@@ -110,11 +111,16 @@ def collate(ids: List[int], utt_ids: List[str], waves: List[np.ndarray], device)
 def build_generator(args, model, dictionary, lm=None):
     from .sequence_generator import SequenceGenerator
     from .tools.ctc_decoder import CTCDecoder
+    from .tools.ctc_prefix_beam_search import CTCPrefixBeamSearchDecoder
     from .tools.transducer_beam_search_decoder import TransducerBeamSearchDecoder
     from .tools.transducer_greedy_decoder import TransducerGreedyDecoder
 
     if args.search == "ctc":
         return CTCDecoder([model], dictionary)
+    if args.search == "ctc_beam":
+        return CTCPrefixBeamSearchDecoder([model], dictionary, beam_size=args.beam, nbest=args.nbest,
+                                          beam_size_token=args.ctc_beam_size_token, lm_model=lm, lm_weight=args.lm_weight,
+                                          insertion_bonus=args.ctc_insertion_bonus)
     if args.search == "transducer_greedy":
         return TransducerGreedyDecoder([model], dictionary, max_num_expansions_per_step=args.max_num_expansions_per_step,
                                        lm_model=lm, lm_weight=args.lm_weight)
@@ -140,7 +146,7 @@ def get_parser():
     p.add_argument("--wav-scp", required=True)
     p.add_argument("--text", default=None, help="reference transcripts (utt_id tokens...)")
     p.add_argument("--global-cmvn-stats-path", default=None)
-    p.add_argument("--search", default="beam", choices=["beam", "ctc", "transducer_greedy", "transducer_beam"])
+    p.add_argument("--search", default="beam", choices=["beam", "ctc", "ctc_beam", "transducer_greedy", "transducer_beam"])
     p.add_argument("--beam", type=int, default=10)
     p.add_argument("--nbest", type=int, default=1)
     p.add_argument("--max-len-a", type=float, default=0.08)
@@ -161,6 +167,9 @@ def get_parser():
     p.add_argument("--subwordlm-weight", type=float, default=0.8, help="sub-word LM weight of multi-level fusion")
     p.add_argument("--disable-open-vocab", action="store_true",
                    help="look-ahead / multi-level fusion: no probability mass for words outside the --word-dict lexicon")
+    p.add_argument("--ctc-beam-size-token", type=int, default=None,
+                   help="ctc_beam: candidate tokens per frame (default: min(--beam, vocabulary size - 1), at most 64)")
+    p.add_argument("--ctc-insertion-bonus", type=float, default=0.0, help="ctc_beam: score added per emitted token")
     p.add_argument("--max-num-expansions-per-step", type=int, default=2)
     p.add_argument("--expansion-beta", type=int, default=0)
     p.add_argument("--expansion-gamma", type=float, default=None)
@@ -179,9 +188,13 @@ def lm_fusion_mode(args):
     """Which LM the search fuses, from `--lm-path` / `--word-dict` / `--search` (espresso/speech_recognize.py:130-148):
     None, "subword" (one sub-word LM), "lookahead" (one word LM + --word-dict) or "multilevel" (`sub.pt:word.pt` +
     --word-dict).  Raises before anything is loaded for combinations that have no implementation."""
+    if args.search == "ctc_beam" and args.word_dict:
+        raise NotImplementedError("--search ctc_beam fuses one sub-word LSTM LM: no look-ahead or multi-level word LM (--word-dict)")
     if not args.lm_path:
         return None
     paths = args.lm_path.split(os.pathsep)
+    if args.search == "ctc_beam" and len(paths) != 1:
+        raise NotImplementedError("--search ctc_beam fuses one sub-word LSTM LM: give one --lm-path")
     if len(paths) == 1:
         return "lookahead" if args.word_dict else "subword"
     if len(paths) != 2 or not args.word_dict:
@@ -234,6 +247,8 @@ def resolve_model_config(model_name, model_config_path, checkpoint):
 def main(argv=None):
     args = get_parser().parse_args(argv)
     lm_mode = lm_fusion_mode(args)
+    if args.search == "ctc_beam" and len(args.path.split(os.pathsep)) > 1:
+        raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
     import yaml
 
     from . import registry
@@ -253,7 +268,7 @@ def main(argv=None):
     model_name, model_cfg = resolve_model_config(args.model, args.model_config, state)
     autoregressive = args.search == "beam"
     # the criterion the checkpoint was trained with decides whether "<s>" is the blank (speech_recognition.py:324, 345-347)
-    crit = {"beam": "label_smoothed_cross_entropy_v2", "ctc": "ctc_loss"}.get(args.search, "transducer_loss")
+    crit = {"beam": "label_smoothed_cross_entropy_v2", "ctc": "ctc_loss", "ctc_beam": "ctc_loss"}.get(args.search, "transducer_loss")
     task = SpeechRecognitionEspressoTask.setup_task(SpeechRecognitionEspressoConfig(
         dict=args.dict, autoregressive=autoregressive, global_cmvn_stats_path=args.global_cmvn_stats_path, criterion_name=crit))
     def load_member(state, name, block):

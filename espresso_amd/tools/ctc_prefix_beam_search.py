@@ -1,0 +1,119 @@
+"""CTCPrefixBeamSearchDecoder — CTC prefix beam search (Hannun et al. 2014) with optional shallow fusion of one sub-word LSTM
+LM, with the generator API of tools/ctc_decoder.CTCDecoder (`generate`, `decode`).  The reference gets a CTC beam only through
+Flashlight's KenLM lexicon decoder (espresso/tools/ctc_decoder.py:55-71, an external C++ library); this search fuses the
+neural LM the project trains instead.
+
+Each hypothesis is a distinct token prefix y with the log-probabilities pb / pnb of ending in blank / non-blank and the LM
+log-probability lm(y) of its tokens after the LM's eos as BOS; its score is logaddexp(pb, pnb) + lm_weight * lm(y) +
+insertion_bonus * |y|, and the final score adds lm_weight * log P_lm(eos | y).  Per frame the K best non-blank tokens are the
+candidates, every hypothesis stays (blank, repeat of its last token) and extends by every candidate, equal prefixes merge,
+and the `beam` best survive (ties: parent slot, stay before extension, token id).
+
+The search is HIP (csrc/ctc_beam.hip): without an LM the whole utterance is one launch; with one, every frame is one step
+launch plus the LM update on the device (reorder the LSTM state by parent, advance the rows that appended a token, output
+layer, log-softmax).  `search` returns device tensors without a host synchronisation."""
+from typing import Dict, List
+
+import torch
+
+from .. import kernels as K
+
+
+class CTCPrefixBeamSearchDecoder:
+    MAX_BEAM = 64
+
+    def __init__(self, models, dictionary, beam_size=10, nbest=1, beam_size_token=None, lm_model=None, lm_weight=0.0,
+                 insertion_bonus=0.0, blank=None, **kwargs):
+        self.model = models[0] if isinstance(models, (list, tuple)) else models
+        self.pad = dictionary.pad()
+        self.eos = dictionary.eos()
+        self.blank = dictionary.bos() if blank is None else blank
+        self.vocab_size = V = len(dictionary)
+        if not 1 <= beam_size <= self.MAX_BEAM:
+            raise ValueError(f"CTC prefix beam search: beam {beam_size} outside [1, {self.MAX_BEAM}]")
+        self.beam_size = beam_size
+        self.beam_size_token = min(beam_size, V - 1) if beam_size_token is None else beam_size_token
+        if not 1 <= self.beam_size_token <= min(self.MAX_BEAM, V - 1):
+            raise ValueError(f"CTC prefix beam search: --ctc-beam-size-token {self.beam_size_token} outside [1, {min(self.MAX_BEAM, V - 1)}]")
+        if not 1 <= nbest <= beam_size:
+            raise ValueError(f"CTC prefix beam search: nbest {nbest} outside [1, beam {beam_size}]")
+        self.nbest = nbest
+        self.lm_model, self.lm_weight, self.insertion_bonus = lm_model, float(lm_weight), float(insertion_bonus)
+        if lm_model is not None:
+            lm_dict = lm_model.decoder.dictionary
+            assert list(lm_dict.symbols) == list(dictionary.symbols), \
+                "CTC prefix beam search fuses an LM over the CTC model's own dictionary (blank <s> included)"
+            lm_model.eval()
+
+    def cuda(self):
+        self.model.cuda()
+        if self.lm_model is not None:
+            self.lm_model.cuda()
+        return self
+
+    # ---------------------------------------------------------------- LM state of the beams
+    def _lm_rows(self, feat):
+        logits = self.lm_model.decoder.output_layer(feat)
+        return K.log_softmax(logits, logits.shape[0], logits.shape[1], logits.stride(0))
+
+    def lm_start(self, N, device):
+        """LSTM state and log-prob rows fp32 [N][V] of N empty hypotheses (the LM's eos as BOS)."""
+        lmd = self.lm_model.decoder
+        state = lmd.init_state(N, device)
+        feat, state = lmd.advance(torch.full((N,), self.eos, dtype=torch.int32, device=device), state)
+        return state, self._lm_rows(feat)
+
+    def lm_update(self, state, parent, token, keep):
+        """After one step: every row continues row `parent` of the previous frame; rows with keep == 0 appended `token`, the
+        others keep their parent's LM state (and so recompute its row)."""
+        lmd = self.lm_model.decoder
+        state = lmd.reorder_state(state, parent)
+        feat, state = lmd.advance(token, state, keep_row=keep)
+        return state, self._lm_rows(feat)
+
+    # ---------------------------------------------------------------- the search
+    @torch.no_grad()
+    def search(self, lprobs, in_len):
+        """lprobs fp32/bf16 [B][T][V] log-probs (row-contiguous), in_len int [B] -> device tensors (tokens int32
+        [B][nbest][T] pad-filled, lengths int32 [B][nbest], scores fp32 [B][nbest] natural log, nhyp int32 [B]), best
+        first.  No host synchronisation."""
+        B, T, V = lprobs.shape
+        assert V == self.vocab_size and lprobs.stride(2) == 1 and lprobs.stride(0) == T * lprobs.stride(1)
+        x = lprobs.view(B * T, V) if lprobs.is_contiguous() else lprobs.reshape(B * T, V)
+        in_len = in_len.to(device=lprobs.device, dtype=torch.int32).contiguous()
+        dev, beam, Kt = lprobs.device, self.beam_size, self.beam_size_token
+        ws = K.ctc_prefix_beam_workspace(B, T, beam, dev)
+        step = dict(B=B, T=T, V=V, beam=beam, K=Kt, blank=self.blank, ins_bonus=self.insertion_bonus)
+        if self.lm_model is None:
+            K.ctc_prefix_beam_step(x, in_len, ws, t0=0, t1=T, **step)
+            return K.ctc_prefix_beam_finish(ws, B, T, beam, self.nbest, self.pad, ins_bonus=self.insertion_bonus)
+        N = B * beam
+        state, rows = self.lm_start(N, dev)
+        lm_out = (torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
+                  torch.empty(N, dtype=torch.uint8, device=dev))
+        if T == 0:
+            K.ctc_prefix_beam_step(x, in_len, ws, t0=0, t1=0, **step)
+        for t in range(T):
+            K.ctc_prefix_beam_step(x, in_len, ws, t0=t, t1=t + 1, lm_rows=rows, lm_weight=self.lm_weight, lm_out=lm_out, **step)
+            state, rows = self.lm_update(state, *lm_out)
+        return K.ctc_prefix_beam_finish(ws, B, T, beam, self.nbest, self.pad, lm_rows=rows, lm_weight=self.lm_weight,
+                                        ins_bonus=self.insertion_bonus, eos=self.eos)
+
+    @torch.no_grad()
+    def _generate(self, sample):
+        net_output = self.model(**sample["net_input"])
+        lprobs = self.model.get_normalized_probs(net_output, log_probs=True)  # T x B x V view of [B][T][V]
+        return self.search(lprobs.transpose(0, 1), net_output["src_lengths"][0])
+
+    @torch.no_grad()
+    def decode(self, models, sample, **kwargs):
+        """(1-best tokens B x U padded with pad, scores B, None) — the validation-time API of CTCDecoder."""
+        tokens, lengths, scores, _ = self._generate(sample)
+        U = max(1, int(lengths[:, 0].max()))
+        return tokens[:, 0, :U].to(torch.long), scores[:, 0], None
+
+    @torch.no_grad()
+    def generate(self, models, sample, **kwargs) -> List[List[Dict[str, torch.Tensor]]]:
+        tokens, lengths, scores, nhyp = (t.cpu() for t in self._generate(sample))
+        return [[{"tokens": tokens[b, i, : int(lengths[b, i])].to(torch.long), "score": scores[b, i], "attention": None,
+                  "alignment": None} for i in range(int(nhyp[b]))] for b in range(tokens.shape[0])]

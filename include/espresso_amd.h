@@ -412,6 +412,26 @@ int ea_ctc_grad(const float* lprobs, const void* workspace, const float* nll, co
 int ea_ctc_greedy_decode(const void* x, long ld, int x_bf16, const int* in_len, int* best, float* bestv, int* tokens,
                          int* align, int* out_len, float* score, int B, int T, int V, int blank, int pad,
                          ea_stream_t stream);
+/* CTC prefix beam search (csrc/ctc_beam.hip; Hannun et al. 2014) with optional shallow fusion of one sub-word LM — the
+ * neural-LM counterpart of the reference's KenLM lexicon decoder (espresso/tools/ctc_decoder.py:55-71).  One workgroup per
+ * utterance; its beam lives in `workspace` (ea_ctc_prefix_beam_workspace_bytes(B, T, beam) bytes, any contents: the
+ * launch with t0 == 0 initialises it).  x: fp32 or bf16 [B][T][ld] log-probs; beam <= 64; K (candidate tokens per frame)
+ * <= min(64, V - 1); V <= 65535.
+ * ea_ctc_prefix_beam_step: frames [t0, t1) (frames >= in_len[b] leave utterance b unchanged).  lm_rows NULL = no LM;
+ *   otherwise fp32 [B*beam][ld_lm] log P_lm(. | hypothesis of that slot), read for the candidate tokens only, and
+ *   t1 == t0 + 1: for every slot the step writes lm_parent int32 [B*beam] (row of the previous frame it continues),
+ *   lm_token int32 [B*beam] (the token it appended; blank where it did not) and lm_keep uint8 [B*beam] (1 = no token
+ *   appended: the LM state of the parent row stays).
+ * ea_ctc_prefix_beam_finish: score = log(p_blank + p_nonblank) + lm_weight * (lm + log P_lm(eos | y)) + ins_bonus * |y|;
+ *   the nbest best per utterance, sorted: tokens int32 [B][nbest][T] (pad after the hypothesis), lengths int32 [B][nbest],
+ *   scores fp32 [B][nbest] (natural log), nhyp int32 [B] (hypotheses returned; the rest: length 0, score -inf). */
+long ea_ctc_prefix_beam_workspace_bytes(int B, int T, int beam);
+int ea_ctc_prefix_beam_step(const void* x, long ld, int x_bf16, const int* in_len, void* workspace, const float* lm_rows,
+                            long ld_lm, int* lm_parent, int* lm_token, void* lm_keep, int B, int T, int V, int beam, int K,
+                            int blank, float lm_weight, float ins_bonus, int t0, int t1, ea_stream_t stream);
+int ea_ctc_prefix_beam_finish(void* workspace, const float* lm_rows, long ld_lm, float lm_weight, float ins_bonus, int eos,
+                              int B, int T, int beam, int nbest, int pad, int* tokens, int* lengths, float* scores, int* nhyp,
+                              ea_stream_t stream);
 /* Label-smoothed CE — espresso/criterions/label_smoothed_cross_entropy_v2.py:49-119.  smoothing 0 = uniform, 1 = unigram
  * (prior fp32 [V], sums to one), 2 = temporal (neighbouring targets of the same sentence, weights 2:5:5:2; rows are
  * b*tgt_len + u).  out_loss[0] += sum loss, out_loss[1] += sum nll (pad rows skipped). */
