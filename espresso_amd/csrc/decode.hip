@@ -11,10 +11,19 @@
 //                        concat(old_cache[parent[n]][0:L], kv_new[n]) — one read + one write of the cache per step.
 //  ea_beam_mask_rows     NaN -> -inf, never-pad, unk penalty, max-len / min-len / eos_factor rules (sequence_generator.py:395-424)
 //  ea_beam_topk          per sentence: top-k over beam*V of (lprobs + cumulative score), k <= 128 — search.py:117-141
+//  ea_decode_attention_probs   ea_decode_attention that also writes the normalised attention rows (alignments)
+//  ea_attn_history_put / ea_attn_backtrace   per-step alignment slabs + one walk back through the parents at finalisation,
+//                        instead of fairseq's per-step index_select of the whole [N][S][step] attention buffer
 #include "common.h"
 #include "espresso_amd.h"
 
 namespace {
+
+// Normalised attention row of one (n, h) for alignments: prow[j] = e_j / sum for j < L, 0 for L <= j < max_len.  The lane
+// strides match the exp pass, so every lane reads back only the LDS entries it wrote itself; the stores are coalesced.
+__device__ __forceinline__ void write_probs(const float* pr, float sum, int L, int max_len, float* __restrict__ prow, int lane) {
+  for (int j = lane; j < max_len; j += 64) prow[j] = j < L ? pr[j] / sum : 0.f;
+}
 
 // q: [N][C] bf16 (already scaled); K,V: row r = kv_row[n] (or n), layout [rows][Lmax][ldkv] with head h at column
 // koff/voff + h*dh; len[r] valid keys.  out: [N][C] bf16.  One wavefront per (n, h); dh == 64 (one lane per channel)
@@ -23,7 +32,7 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(const bf16_t* __r
                                                                const bf16_t* __restrict__ V, const int* __restrict__ kv_row,
                                                                const int* __restrict__ len, bf16_t* __restrict__ out, int N, int H,
                                                                int dh, long ldq, long row_stride, long ldkv, int koff, int voff,
-                                                               int fixed_len) {
+                                                               int fixed_len, float* __restrict__ probs, long ldp) {
   extern __shared__ float sprob[];  // [4 waves][Lpad]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int gw = blockIdx.x * 4 + wave;
@@ -51,6 +60,7 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(const bf16_t* __r
     sum += e;
   }
   sum = wave_sum(sum);
+  if (probs) write_probs(pr, sum, L, fixed_len, probs + ((long)n * H + h) * ldp, lane);
   __builtin_amdgcn_wave_barrier();
   float acc = 0.f;
   if (lane < dh)
@@ -67,7 +77,8 @@ template <int DH>
 __global__ __launch_bounds__(256) void decode_attention_vec_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ K,
                                                                    const bf16_t* __restrict__ V, const int* __restrict__ kv_row,
                                                                    const int* __restrict__ len, bf16_t* __restrict__ out, int N, int H,
-                                                                   long ldq, long row_stride, long ldkv, int koff, int voff, int fixed_len) {
+                                                                   long ldq, long row_stride, long ldkv, int koff, int voff, int fixed_len,
+                                                                   float* __restrict__ probs, long ldp) {
   constexpr int E = DH / 4;  // channels per lane
   extern __shared__ float sprob[];  // [4 waves][Lpad]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -136,6 +147,7 @@ __global__ __launch_bounds__(256) void decode_attention_vec_kernel(const bf16_t*
     sum += e;
   }
   sum = wave_sum(sum);
+  if (probs) write_probs(pr, sum, L, fixed_len, probs + ((long)n * H + h) * ldp, lane);
   __builtin_amdgcn_wave_barrier();
   float acc[E];
 #pragma unroll
@@ -253,12 +265,68 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
   }
 }
 
+// Alignment history (fairseq/sequence_generator.py:349-360, 444-446, 688-692): step k's slab A[k] is [N_k][S] fp32, written once.
+// dst[n][j] = (acc ? dst[n][j] : 0) + (sum_h src[n*s_row + j*s_frame + h*s_head]) / H, then divided by `div` (the ensemble's
+// "sum the members, divide by their number").  Heads are summed in order h = 0..H-1: reproducible, no atomics.
+__global__ __launch_bounds__(256) void attn_history_put_kernel(const float* __restrict__ src, long s_row, long s_frame, long s_head,
+                                                               int N, int H, int S, float* __restrict__ dst, long ldd, int accumulate,
+                                                               float div) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)N * S) return;
+  const int n = (int)(i / S), j = (int)(i % S);
+  const float* p = src + (long)n * s_row + (long)j * s_frame;
+  float v = 0.f;
+  for (int h = 0; h < H; ++h) v += p[(long)h * s_head];
+  v = v / (float)H;
+  float* d = dst + (long)n * ldd + j;
+  if (accumulate) v = *d + v;
+  *d = div == 1.f ? v : v / div;
+}
+
+// One workgroup per finalized hypothesis i: walk its row back through the parents, row_step = bbsz[i],
+// row_{k-1} = P[k][row_k], and write out[i][s][k] = A[k][row_k][s] for k = 0..step (fairseq's [S][step+1] layout).
+// 64 x 64 tiles go through LDS so that the slab reads (along s) and the output stores (along k) are both coalesced.
+constexpr int BT_TILE = 64;
+__global__ __launch_bounds__(256) void attn_backtrace_kernel(const float* __restrict__ A, long slab, long lda, const int* __restrict__ P,
+                                                             long ldp, const long* __restrict__ bbsz, int step, int S,
+                                                             float* __restrict__ out) {
+  extern __shared__ int rows[];  // [step + 1]
+  __shared__ float tile[BT_TILE][BT_TILE + 1];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const int ncol = step + 1;
+  if (tid == 0) {
+    int r = (int)bbsz[i];
+    for (int k = step; k >= 0; --k) {
+      rows[k] = r;
+      if (k > 0) r = P[(long)k * ldp + r];
+    }
+  }
+  __syncthreads();
+  float* o = out + (long)i * S * ncol;
+  const int tx = tid & 63, ty = tid >> 6;  // 64 x 4
+  for (int s0 = 0; s0 < S; s0 += BT_TILE) {
+    for (int k0 = 0; k0 < ncol; k0 += BT_TILE) {
+      for (int kk = ty; kk < BT_TILE; kk += 4) {
+        const int k = k0 + kk, s = s0 + tx;
+        if (k < ncol && s < S) tile[kk][tx] = A[(long)k * slab + (long)rows[k] * lda + s];
+      }
+      __syncthreads();
+      for (int ss = ty; ss < BT_TILE; ss += 4) {
+        const int s = s0 + ss, k = k0 + tx;
+        if (k < ncol && s < S) o[(long)s * ncol + k] = tile[tx][ss];
+      }
+      __syncthreads();
+    }
+  }
+}
+
 }  // namespace
 
-extern "C" int ea_decode_attention(const void* q, const void* K, const void* V, const int* kv_row, const int* len, void* out, int N,
-                                   int H, int dh, long ldq, long row_stride, long ldkv, int koff, int voff, int max_len,
-                                   hipStream_t stream) {
+extern "C" int ea_decode_attention_probs(const void* q, const void* K, const void* V, const int* kv_row, const int* len, void* out,
+                                         int N, int H, int dh, long ldq, long row_stride, long ldkv, int koff, int voff, int max_len,
+                                         float* probs, long ldp, hipStream_t stream) {
   if (N <= 0) return 0;
+  if (probs && ldp < max_len) return -2;
   if (dh > 64 || max_len <= 0) return -2;
   const size_t lds = (size_t)4 * ((max_len + 63) / 64 * 64) * sizeof(float);
   if (lds > 64 * 1024) return -3;
@@ -268,14 +336,20 @@ extern "C" int ea_decode_attention(const void* q, const void* K, const void* V, 
   if (vec_on && aligned && (dh == 64 || dh == 32 || dh == 16)) {
     const dim3 grid((N * H + 3) / 4), block(256);
 #define EA_DA(D) hipLaunchKernelGGL(decode_attention_vec_kernel<D>, grid, block, lds, stream, (const bf16_t*)q, (const bf16_t*)K, (const bf16_t*)V, \
-                                    kv_row, len, (bf16_t*)out, N, H, ldq, row_stride, ldkv, koff, voff, max_len)
+                                    kv_row, len, (bf16_t*)out, N, H, ldq, row_stride, ldkv, koff, voff, max_len, probs, ldp)
     if (dh == 64) EA_DA(64); else if (dh == 32) EA_DA(32); else EA_DA(16);
 #undef EA_DA
     return EA_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(decode_attention_kernel, dim3((N * H + 3) / 4), dim3(256), lds, stream, (const bf16_t*)q, (const bf16_t*)K,
-                     (const bf16_t*)V, kv_row, len, (bf16_t*)out, N, H, dh, ldq, row_stride, ldkv, koff, voff, max_len);
+                     (const bf16_t*)V, kv_row, len, (bf16_t*)out, N, H, dh, ldq, row_stride, ldkv, koff, voff, max_len, probs, ldp);
   return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_decode_attention(const void* q, const void* K, const void* V, const int* kv_row, const int* len, void* out, int N,
+                                   int H, int dh, long ldq, long row_stride, long ldkv, int koff, int voff, int max_len,
+                                   hipStream_t stream) {
+  return ea_decode_attention_probs(q, K, V, kv_row, len, out, N, H, dh, ldq, row_stride, ldkv, koff, voff, max_len, nullptr, 0, stream);
 }
 
 extern "C" int ea_kv_append_reorder(const void* old_cache, void* new_cache, const void* kv_new, const int* parent, int N, int L,
@@ -303,5 +377,25 @@ extern "C" int ea_beam_topk(const float* lprobs, const float* prev_scores, int b
   if (k > KMAXC || k <= 0) return -2;
   hipLaunchKernelGGL(beam_topk_kernel, dim3(bsz), dim3(256), 0, stream, lprobs, prev_scores, V, beam, nbeam_used, k, cand_score,
                      cand_tok, cand_beam);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_attn_history_put(const float* src, long s_row, long s_frame, long s_head, int N, int H, int S, float* dst, long ldd,
+                                   int accumulate, float div, hipStream_t stream) {
+  if (N <= 0 || S <= 0) return 0;
+  if (H <= 0 || ldd < S || !(div > 0.f)) return -2;
+  const long total = (long)N * S;
+  hipLaunchKernelGGL(attn_history_put_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src, s_row, s_frame, s_head, N,
+                     H, S, dst, ldd, accumulate, div);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_attn_backtrace(const float* A, long slab, long lda, const int* P, long ldp, const long* bbsz, int n, int step, int S,
+                                 float* out, hipStream_t stream) {
+  if (n <= 0 || S <= 0) return 0;
+  if (step < 0 || lda < S) return -2;
+  const size_t lds = (size_t)(step + 1) * sizeof(int);
+  if (lds > 32 * 1024) return -3;
+  hipLaunchKernelGGL(attn_backtrace_kernel, dim3(n), dim3(256), lds, stream, A, slab, lda, P, ldp, bbsz, step, S, out);
   return EA_CHECK_LAUNCH();
 }

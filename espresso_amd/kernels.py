@@ -612,6 +612,38 @@ def decode_attention(q, Kc, Vc_off, kv_row, lens, N, H, dh, row_stride, ldkv, ko
     return out
 
 
+def decode_attention_probs(q, Kc, Vc_off, kv_row, lens, N, H, dh, row_stride, ldkv, koff, voff, max_len):
+    """decode_attention that also returns the fp32 attention weights [N][H][max_len] (0 past each row's length); the bf16
+    output is bit-identical to decode_attention's."""
+    out = torch.empty_like(q)
+    probs = torch.empty(N, H, max_len, dtype=torch.float32, device=q.device)
+    check(
+        _lib.lib().ea_decode_attention_probs(_p(q), _p(Kc), _p(Kc), _p(kv_row), _p(lens), _p(out), N, H, dh, q.stride(0), row_stride,
+                                             ldkv, koff, voff, max_len, _p(probs), max_len, _stream()),
+        "ea_decode_attention_probs",
+    )
+    return out, probs
+
+
+def attn_history_put(src, s_row, s_frame, s_head, N, H, S, dst, accumulate=False, div=1.0):
+    """dst [N][>=S] fp32 (a slab of the alignment history) <- mean over the H heads of src (element strides s_row / s_frame /
+    s_head), added to dst if `accumulate`, then divided by `div`."""
+    check(_lib.lib().ea_attn_history_put(_p(src), s_row, s_frame, s_head, N, H, S, _p(dst), dst.stride(0), int(accumulate), float(div),
+                                         _stream()), "ea_attn_history_put")
+    return dst
+
+
+def attn_backtrace(A, P, bbsz_idx, step, S):
+    """A fp32 [steps][rows][S] slabs, P int32 [steps][rows] parents, bbsz_idx int64 [n] rows at `step` ->
+    fp32 [n][S][step+1]: column k is the slab-k row of each hypothesis' ancestor at step k."""
+    n = bbsz_idx.numel()
+    out = torch.empty(n, S, step + 1, dtype=torch.float32, device=A.device)
+    idx = bbsz_idx.contiguous()
+    check(_lib.lib().ea_attn_backtrace(_p(A), A.stride(0), A.stride(1), _p(P), P.stride(0), _p(idx), n, step, S, _p(out), _stream()),
+          "ea_attn_backtrace")
+    return out
+
+
 def kv_append_reorder(old_cache, new_cache, kv_new, parent, N, L, Lmax, W):
     check(_lib.lib().ea_kv_append_reorder(_p(old_cache), _p(new_cache), _p(kv_new), _p(parent), N, L, Lmax, W, _stream()),
           "ea_kv_append_reorder")

@@ -273,8 +273,10 @@ class SpeechLSTMDecoder(nn.Module):
             prev_in = inp[:, :H] if (self.residual and i > 0) else None
             if i == 0:
                 qp = F.linear(h16, self.attention.query_proj.weight, None)
-                _, ctx = K.bahdanau_fwd(qp.contiguous(), st["key"], st["value"], st["nv"], st["bias"], st["len"], st["T"], N,
+                p, ctx = K.bahdanau_fwd(qp.contiguous(), st["key"], st["value"], st["nv"], st["bias"], st["len"], st["T"], N,
                                         kv_col=st["kv_col"], Bkv=st["Bkv"])
+                if st.get("need_attn"):  # alignments: the Bahdanau weights p [T][N] (0 past each utterance's length)
+                    st["attn"] = {"probs": p, "s_row": 1, "s_frame": N, "s_head": 0, "heads": 1, "frames": st["T"]}
             inp = torch.cat((h16, ctx), dim=1)
             if prev_in is not None:
                 inp = torch.cat((inp[:, :H] + prev_in, inp[:, H:]), dim=1)
@@ -463,6 +465,16 @@ class SpeechLSTMModel(nn.Module):
     def forward(self, src_tokens, src_lengths, prev_output_tokens, epoch=1, **kwargs):
         enc = self.encoder(src_tokens, src_lengths)
         return self.decoder(prev_output_tokens, encoder_out=enc, epoch=epoch)
+
+    def make_generation_fast_(self, need_attn=False, **kwargs):
+        """speech_lstm.py SpeechLSTMDecoder.make_generation_fast_: need_attn switches on the decoder's attention output."""
+        self.decoder.need_attn = bool(need_attn)
+
+    def prepare_for_inference_(self, cfg):
+        """fairseq BaseFairseqModel.prepare_for_inference_: need_attn = cfg.generation.print_alignment."""
+        gen = cfg.get("generation", {}) if isinstance(cfg, dict) else getattr(cfg, "generation", None)
+        pa = gen.get("print_alignment", False) if isinstance(gen, dict) else getattr(gen, "print_alignment", False)
+        self.make_generation_fast_(need_attn=bool(pa))
 
     def forward_encoder(self, src_tokens, src_lengths):
         return self.encoder(src_tokens, src_lengths)

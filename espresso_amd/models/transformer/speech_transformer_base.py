@@ -189,7 +189,9 @@ class SpeechTransformerDecoderBase(nn.Module):
     @torch.no_grad()
     def step(self, st, tokens, step, parent):
         """One decoding step for the N live hypotheses.  tokens: [N][step+1] (only the last column is consumed);
-        parent: int64 [N] previous-step hypothesis each row continues (None at step 0).  -> fp32 log-probs [N][V]."""
+        parent: int64 [N] previous-step hypothesis each row continues (None at step 0).  -> fp32 log-probs [N][V].
+        With `st["need_attn"]` set, `st["attn"]` describes the last layer's cross-attention weights of this step (fp32
+        [N][H][S]) for the generator's alignment history."""
         C, H = self.embed_dim, self.layers[0].num_heads
         dh = C // H
         scaling = dh ** -0.5
@@ -207,7 +209,8 @@ class SpeechTransformerDecoderBase(nn.Module):
         x = K.embedding_fwd(tok, pos, self.embed_tokens.weight, tab, self.embed_scale)
         if self.layernorm_embedding is not None:
             x, _, _ = K.layernorm_fwd(x, self.layernorm_embedding.weight, self.layernorm_embedding.bias, save_stats=False)
-        for layer, ls in zip(self.layers, st["layers"]):
+        last = len(self.layers) - 1
+        for li, (layer, ls) in enumerate(zip(self.layers, st["layers"])):
             a = layer.self_attn
             _, bqkv, wqkv16 = a.fused_qkv()
             xn, _, _ = K.layernorm_fwd(x, layer.self_attn_layer_norm.weight, layer.self_attn_layer_norm.bias, save_stats=False)
@@ -229,7 +232,13 @@ class SpeechTransformerDecoderBase(nn.Module):
             K.gemm(xn, F.bf16_weight(e.q_proj.weight), q, N, C, C, lda=C, ldb=C, ldc=C, bias=e.q_proj.bias)
             qs, _ = K.relpos_q_prep(q, C, None, None, N, C, scaling, want_qv=False)
             S = st["S"]
-            att = K.decode_attention(qs, ls["enc_kv"], None, st["kv_row"], st["enc_len"], N, H, dh, S * 2 * C, 2 * C, 0, C, S)
+            if li == last and st.get("need_attn"):
+                # alignments: the last layer's cross-attention (fairseq's alignment_layer), heads averaged by the generator
+                att, probs = K.decode_attention_probs(qs, ls["enc_kv"], None, st["kv_row"], st["enc_len"], N, H, dh, S * 2 * C, 2 * C,
+                                                      0, C, S)
+                st["attn"] = {"probs": probs, "s_row": H * S, "s_frame": 1, "s_head": S, "heads": H, "frames": S}
+            else:
+                att = K.decode_attention(qs, ls["enc_kv"], None, st["kv_row"], st["enc_len"], N, H, dh, S * 2 * C, 2 * C, 0, C, S)
             x2 = torch.empty_like(x)
             K.gemm(att, F.bf16_weight(e.out_proj.weight), x2, N, C, C, lda=C, ldb=C, ldc=C, bias=e.out_proj.bias, resid=x, ldr=C)
             x = x2
@@ -288,6 +297,16 @@ class SpeechTransformerModelBase(nn.Module):
     def forward(self, src_tokens, src_lengths, prev_output_tokens, **kwargs):
         encoder_out = self.encoder(src_tokens, src_lengths)
         return self.decoder(prev_output_tokens, encoder_out=encoder_out, epoch=kwargs.get("epoch", 1))
+
+    def make_generation_fast_(self, need_attn=False, **kwargs):
+        """fairseq's hook: `need_attn` makes the generator collect alignments (the decoder's cross-attention)."""
+        self.decoder.need_attn = bool(need_attn)
+
+    def prepare_for_inference_(self, cfg):
+        """fairseq BaseFairseqModel.prepare_for_inference_: need_attn = cfg.generation.print_alignment."""
+        gen = cfg.get("generation", {}) if isinstance(cfg, dict) else getattr(cfg, "generation", None)
+        pa = gen.get("print_alignment", False) if isinstance(gen, dict) else getattr(gen, "print_alignment", False)
+        self.make_generation_fast_(need_attn=bool(pa))
 
     def forward_encoder(self, src_tokens, src_lengths):
         return self.encoder(src_tokens, src_lengths)

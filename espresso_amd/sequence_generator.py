@@ -36,11 +36,20 @@ class HipBeamSearch:
         cs, ct, cb = K.beam_topk(lprobs, None if step == 0 else prev_scores, bsz, beam, used, k)
         return cs, ct.long(), cb.long()
 
+    def attn_put(self, attn, dst, accumulate, div):
+        """Step slab dst [N][S] <- head-mean of the decoder's attention descriptor (ea_attn_history_put)."""
+        K.attn_history_put(attn["probs"], attn["s_row"], attn["s_frame"], attn["s_head"], dst.shape[0], attn["heads"], attn["frames"],
+                           dst, accumulate, div)
+
+    def attn_backtrace(self, hist, parents, bbsz_idx, step):
+        """-> [n][S][step+1]: the alignment of every finalized hypothesis (ea_attn_backtrace)."""
+        return K.attn_backtrace(hist, parents, bbsz_idx, step, hist.shape[2])
+
 
 class SequenceGenerator:
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, max_len=0, min_len=1, normalize_scores=True,
                  len_penalty=1.0, unk_penalty=0.0, temperature=1.0, match_source_len=False, lm_model=None, lm_weight=1.0,
-                 eos_factor=None, eos=None, search=None, **unused):
+                 eos_factor=None, eos=None, search=None, print_alignment=False, need_attn=False, **unused):
         # an ensemble (`--path a:b`) decodes with the log of the MEAN probability of its members
         # (fairseq/sequence_generator.py:837-939 EnsembleModel.forward_decoder: logsumexp of the log-probabilities - log n)
         self.models = list(models) if isinstance(models, (list, tuple)) else [models]
@@ -61,6 +70,12 @@ class SequenceGenerator:
         self.eos_factor = eos_factor
         assert eos_factor is None or eos_factor >= 1.0, "--eos-factor must be >= 1.0 if set"
         self.search = search if search is not None else HipBeamSearch()
+        # alignments (hypo["attention"]) are collected when asked for here or by a decoder's `need_attn`
+        # (make_generation_fast_ / prepare_for_inference_, as the reference's recognizer switches them on)
+        self.print_alignment = bool(print_alignment or need_attn)
+
+    def _need_attn(self):
+        return self.print_alignment or any(bool(getattr(getattr(m, "decoder", None), "need_attn", False)) for m in self.models)
 
     @torch.no_grad()
     def generate(self, models, sample, **kwargs) -> List[List[Dict[str, torch.Tensor]]]:
@@ -88,6 +103,14 @@ class SequenceGenerator:
         states = [m.decoder.init_incremental(m.forward_encoder(net_input["src_tokens"], net_input.get("src_lengths")), bsz, beam)
                   for m in self.models]
         lm_state = self.lm_model.init_incremental(bsz, beam) if self.lm_model is not None else None
+        need_attn = self._need_attn()
+        if need_attn:
+            for st in states:
+                st["need_attn"] = True
+        # alignment history: slab `hist[k]` [N_k][S] holds step k's attention of the N_k live rows, `parents[k]` the previous-step
+        # row each one continues; allocated on the first step a decoder reports attention (fairseq's `attn` buffer, same size)
+        hist: Optional[torch.Tensor] = None
+        parents: Optional[torch.Tensor] = None
 
         scores = torch.zeros(bsz * beam, max_len + 1, dtype=torch.float32, device=dev)
         tokens = torch.full((bsz * beam, max_len + 2), self.pad, dtype=torch.long, device=dev)
@@ -106,6 +129,8 @@ class SequenceGenerator:
             if len(self.models) > 1:
                 every = [lprobs] + [m.decoder.step(st, tokens[:, : step + 1], step, parent) for m, st in zip(self.models[1:], states[1:])]
                 lprobs = torch.logsumexp(torch.stack(every, 0), dim=0) - math.log(len(every))
+            if need_attn:
+                hist, parents = self._record_attention(states, step, parent, hist, parents, bsz * beam, max_len, dev)
             if self.lm_model is not None:
                 lm_lprobs = self.lm_model.step(lm_state, tokens[:, : step + 1], step, parent)
                 lprobs = lprobs + self.lm_weight * lm_lprobs
@@ -129,7 +154,8 @@ class SequenceGenerator:
             finalized_sents: List[int] = []
             if eos_bbsz_idx.numel() > 0:
                 eos_scores = torch.masked_select(cand_scores[:, :beam], mask=eos_mask[:, :beam])
-                finalized_sents = self._finalize(step, eos_bbsz_idx, eos_scores, tokens, scores, finalized, finished, beam, max_len)
+                finalized_sents = self._finalize(step, eos_bbsz_idx, eos_scores, tokens, scores, finalized, finished, beam, max_len,
+                                                 hist, parents)
                 num_remaining -= len(finalized_sents)
             assert num_remaining >= 0
             if num_remaining == 0:
@@ -178,7 +204,24 @@ class SequenceGenerator:
             finalized[sent] = [finalized[sent][int(i)] for i in order]
         return finalized
 
-    def _finalize(self, step, bbsz_idx, eos_scores, tokens, scores, finalized, finished, beam, max_len):
+    def _record_attention(self, states, step, parent, hist, parents, rows, max_len, dev):
+        """Write step `step`'s slab (the members' head-mean attention, summed and divided by the ensemble size as
+        fairseq's EnsembleModel.forward_decoder does) and the parent vector of this step."""
+        descs = [st.get("attn") for st in states]
+        have = [a for a in descs if a is not None]
+        if not have:
+            return hist, parents
+        if hist is None:
+            hist = torch.empty(max_len + 1, rows, have[0]["frames"], dtype=torch.float32, device=dev)
+            parents = torch.zeros(max_len + 1, rows, dtype=torch.int32, device=dev)
+        n = parent.numel() if parent is not None else rows
+        for i, a in enumerate(have):
+            self.search.attn_put(a, hist[step, :n], accumulate=i > 0, div=float(len(self.models)) if i == len(have) - 1 else 1.0)
+        if parent is not None:
+            parents[step, :n].copy_(parent)
+        return hist, parents
+
+    def _finalize(self, step, bbsz_idx, eos_scores, tokens, scores, finalized, finished, beam, max_len, hist=None, parents=None):
         """Store hypotheses that just produced EOS; return the (current-numbering) sentences that became finished."""
         tokens_clone = tokens.index_select(0, bbsz_idx)[:, 1: step + 2].clone()
         tokens_clone[:, step] = self.eos
@@ -196,10 +239,11 @@ class SequenceGenerator:
                 cum_unfin.append(prev)
         unfin = (bbsz_idx // beam).tolist()
         sents = [u + cum_unfin[u] for u in unfin]
+        attn = self.search.attn_backtrace(hist, parents, bbsz_idx, step) if hist is not None else None  # [n][S][step+1], on the device
         tokens_clone, pos_scores, eos_scores = tokens_clone.cpu(), pos_scores.cpu(), eos_scores.cpu()
         for i, s in enumerate(sents):
             if len(finalized[s]) < beam:
-                finalized[s].append({"tokens": tokens_clone[i], "score": eos_scores[i], "attention": None,
+                finalized[s].append({"tokens": tokens_clone[i], "score": eos_scores[i], "attention": None if attn is None else attn[i],
                                      "alignment": torch.empty(0), "positional_scores": pos_scores[i]})
         newly = []
         for s, u in sorted(set(zip(sents, unfin))):

@@ -61,12 +61,16 @@ def shard_batches(batches: List[List[int]], num_shards: int, shard_id: int) -> L
 
 
 def recognize(task, model, generator, batches: Iterable[dict], dictionary, refs: Optional[Dict[str, str]] = None, out=sys.stdout,
-              nbest: int = 1, quiet: bool = False, bpe_symbol=None):
+              nbest: int = 1, quiet: bool = False, bpe_symbol=None, scorer=None, summary_out=None, attn_plot_dir=None):
     """The loop of espresso/speech_recognize.py:226-330.  `batches` yield dicts with `utt_ids`, `wav`, `wav_offsets`,
-    `num_samples` (device tensors / lists as produced by `collate`).  Returns (scorer, stats)."""
+    `num_samples` (device tensors / lists as produced by `collate`).  `summary_out`: a second stream for the closing summary
+    lines (stdout while `out` is decode.log); `attn_plot_dir`: save the best hypothesis' alignment of every utterance there
+    (plot_attention) when the generator returns one.  Returns (scorer, stats)."""
+    from .tools.utils import plot_attention
     from .tools.wer import Scorer
 
-    scorer = Scorer(dictionary, wer_output_filter=None)
+    if scorer is None:
+        scorer = Scorer(dictionary, wer_output_filter=None)
     num_sent, num_tok, t_gen, audio_s = 0, 0, 0.0, 0.0
     for sample in batches:
         t0 = time.perf_counter()
@@ -76,6 +80,9 @@ def recognize(task, model, generator, batches: Iterable[dict], dictionary, refs:
             torch.cuda.synchronize()
         t_gen += time.perf_counter() - t0
         audio_s += sum(sample["num_samples"]) / 16000.0
+        enc_lens = None
+        if attn_plot_dir is not None:  # valid encoder frames of every utterance (the plot drops the padded rows)
+            enc_lens = model.encoder.output_lengths(s["net_input"]["src_lengths"]).tolist()
         for i, utt in enumerate(sample["utt_ids"]):
             if refs is not None and utt in refs and not quiet:
                 print("T-{}\t{}".format(utt, refs[utt]), file=out)
@@ -86,18 +93,41 @@ def recognize(task, model, generator, batches: Iterable[dict], dictionary, refs:
                 if not quiet:
                     print("H-{}\t{}\t{}".format(utt, hypo_str, float(hypo["score"]) / math.log(2)), file=out)
                 if j == 0:
+                    if enc_lens is not None and hypo.get("attention") is not None:
+                        os.makedirs(attn_plot_dir, exist_ok=True)
+                        plot_attention(hypo["attention"][: int(enc_lens[i])].float().cpu(), hypo_str, utt, attn_plot_dir)
                     scorer.add_prediction(utt, hypo_str)
                     if refs is not None and utt in refs:
                         scorer.add_evaluation(utt, refs[utt], hypo_str)
                     num_tok += len(toks)
         num_sent += len(sample["utt_ids"])
-    print("NOTE: hypothesis and token scores are output in base 2", file=out)
-    print("Recognized {:,} utterances ({} tokens) in {:.1f}s ({:.2f} sentences/s, {:.2f} tokens/s), RTF {:.4f}".format(
-        num_sent, num_tok, t_gen, num_sent / max(t_gen, 1e-9), num_tok / max(t_gen, 1e-9), t_gen / max(audio_s, 1e-9)), file=out)
+    lines = ["NOTE: hypothesis and token scores are output in base 2",
+             "Recognized {:,} utterances ({} tokens) in {:.1f}s ({:.2f} sentences/s, {:.2f} tokens/s), RTF {:.4f}".format(
+                 num_sent, num_tok, t_gen, num_sent / max(t_gen, 1e-9), num_tok / max(t_gen, 1e-9), t_gen / max(audio_s, 1e-9))]
     if refs:
-        for line in scorer.summary_lines():
-            print(line, file=out)
+        lines += scorer.summary_lines()
+    for f in [out] + ([summary_out] if summary_out is not None else []):
+        for line in lines:
+            print(line, file=f)
     return scorer, {"sentences": num_sent, "tokens": num_tok, "seconds": t_gen, "rtf": t_gen / max(audio_s, 1e-9)}
+
+
+def write_results(results_path: str, scorer, has_target: bool):
+    """The result files of espresso/speech_recognize.py:338-389 next to decode.log: decoded_char_results.txt and
+    decoded_results.txt always; with references also `wer`, `cer` (one line each) and aligned_results.txt."""
+    os.makedirs(results_path, exist_ok=True)
+
+    def write(name, text):
+        with open(os.path.join(results_path, name), "w", encoding="utf-8") as f:
+            f.write(text)
+
+    write("decoded_char_results.txt", scorer.print_char_results())
+    write("decoded_results.txt", scorer.print_results())
+    if has_target:
+        wer_line, cer_line = scorer.summary_lines()
+        write("wer", wer_line + "\n")
+        write("cer", cer_line + "\n")
+        write("aligned_results.txt", scorer.print_aligned_results())
 
 
 def collate(ids: List[int], utt_ids: List[str], waves: List[np.ndarray], device):
@@ -132,7 +162,7 @@ def build_generator(args, model, dictionary, lm=None):
     return SequenceGenerator(model if isinstance(model, (list, tuple)) else [model], dictionary, beam_size=args.beam, max_len_a=args.max_len_a, max_len_b=args.max_len_b,
                              min_len=args.min_len, normalize_scores=not args.unnormalized, len_penalty=args.lenpen,
                              unk_penalty=args.unkpen, temperature=args.temperature, lm_model=lm, lm_weight=args.lm_weight,
-                             eos_factor=args.eos_factor)
+                             eos_factor=args.eos_factor, print_alignment=getattr(args, "print_alignment", None) is not None)
 
 
 def get_parser():
@@ -181,6 +211,14 @@ def get_parser():
                    help="decode replicas (default: WORLD_SIZE); each takes every num-shards-th batch")
     p.add_argument("--shard-id", type=int, default=int(os.environ.get("RANK", "0")), help="this replica (default: RANK)")
     p.add_argument("--device", default=None, help="default: cuda:LOCAL_RANK (cuda:0 outside a launcher)")
+    p.add_argument("--results-path", default=None,
+                   help="directory for decode.log, decoded_results.txt, decoded_char_results.txt and, with --text, wer, cer and "
+                        "aligned_results.txt")
+    p.add_argument("--print-alignment", nargs="?", const="hard", default=None, choices=["hard", "soft"],
+                   help="collect the attention alignments; --search beam saves RESULTS_PATH/attn_plots/<utt>.pdf of the best "
+                        "hypothesis (needs --results-path and matplotlib)")
+    p.add_argument("--wer-output-filter", default=None, help="sed-style word filter applied before WER scoring")
+    p.add_argument("--non-lang-syms", default=None, help="non-language symbols (one per line), ignored by WER / CER scoring")
     return p
 
 
@@ -246,6 +284,8 @@ def resolve_model_config(model_name, model_config_path, checkpoint):
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
+    if args.print_alignment is not None and not args.results_path:
+        raise ValueError("--print-alignment saves attention plots under --results-path: give --results-path")
     lm_mode = lm_fusion_mode(args)
     if args.search == "ctc_beam" and len(args.path.split(os.pathsep)) > 1:
         raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
@@ -270,7 +310,8 @@ def main(argv=None):
     # the criterion the checkpoint was trained with decides whether "<s>" is the blank (speech_recognition.py:324, 345-347)
     crit = {"beam": "label_smoothed_cross_entropy_v2", "ctc": "ctc_loss", "ctc_beam": "ctc_loss"}.get(args.search, "transducer_loss")
     task = SpeechRecognitionEspressoTask.setup_task(SpeechRecognitionEspressoConfig(
-        dict=args.dict, autoregressive=autoregressive, global_cmvn_stats_path=args.global_cmvn_stats_path, criterion_name=crit))
+        dict=args.dict, autoregressive=autoregressive, global_cmvn_stats_path=args.global_cmvn_stats_path, criterion_name=crit,
+        non_lang_syms=args.non_lang_syms, wer_output_filter=args.wer_output_filter))
     def load_member(state, name, block):
         cls = registry.MODEL_REGISTRY[name]
         cfg_cls = getattr(cls, "config_class", None)
@@ -320,8 +361,27 @@ def main(argv=None):
     if args.num_shards > 1:  # (the defaults come from WORLD_SIZE / RANK: say that this process decodes — and scores — a part only)
         print(f"| decoding shard {args.shard_id} of {args.num_shards}: {sum(len(b) for b in batches)} of {len(utt_ids)} utterances; "
               "WER / CER below cover this shard only", file=sys.stderr)
-    recognize(task, model, gen, (collate(b, utt_ids, waves, dev) for b in batches), task.target_dictionary, refs, out=sys.stdout,
-              nbest=args.nbest, quiet=args.quiet)
+    from .tools.wer import Scorer
+
+    scorer = Scorer(task.target_dictionary, wer_output_filter=args.wer_output_filter)
+    stream = (collate(b, utt_ids, waves, dev) for b in batches)
+    if not args.results_path:
+        recognize(task, model, gen, stream, task.target_dictionary, refs, out=sys.stdout, nbest=args.nbest, quiet=args.quiet,
+                  scorer=scorer)
+        return scorer
+    os.makedirs(args.results_path, exist_ok=True)
+    # attention plots only for the attention decoder (the reference's is_attention_model: not the CTC / transducer criteria)
+    plot_dir = os.path.join(args.results_path, "attn_plots") if args.print_alignment is not None and args.search == "beam" else None
+    with open(os.path.join(args.results_path, "decode.log"), "w", buffering=1, encoding="utf-8") as log:
+        recognize(task, model, gen, stream, task.target_dictionary, refs, out=log, nbest=args.nbest, quiet=args.quiet, scorer=scorer,
+                  summary_out=sys.stdout, attn_plot_dir=plot_dir)
+    decoded = [u for b in batches for u in (utt_ids[i] for i in b)]
+    has_target = refs is not None and all(u in refs for u in decoded)
+    if has_target:  # wav.scp order of the utterances this process decoded (the reference: dataset.tgt.utt_ids)
+        keep = set(decoded)
+        scorer.add_ordered_utt_list([u for u in utt_ids if u in keep])
+    write_results(args.results_path, scorer, has_target)
+    return scorer
 
 
 if __name__ == "__main__":

@@ -1,7 +1,9 @@
 """Host-side helpers with the reference's names and semantics (espresso/tools/utils.py):
 collate_frames :97-113, sequence_mask :116-129, convert_padding_direction :197-221,
-eval_str_nested_list_or_tuple :224-237, edit_distance :265-331, num_samples_to_num_frames :457-486."""
+eval_str_nested_list_or_tuple :224-237, plot_attention :240-262, edit_distance :265-331, aligned_print :334-420,
+num_samples_to_num_frames :457-486."""
 import ast
+import os
 from typing import List
 
 import numpy as np
@@ -109,6 +111,65 @@ def edit_distance(ref, hyp):
     counter = Counter({"words": R, "corr": 0, "sub": 0, "ins": 0, "del": 0})
     counter.update(steps)
     return dist, steps, counter
+
+
+def aligned_print(ref, hyp, steps):
+    """The REF / HYP / STP lines of one edit-distance alignment plus its WER line and a blank line (the format of the reference's
+    aligned_results.txt).  Every column is as wide as its wider word: a substitution pads the shorter word, an insertion
+    leaves the REF column blank, a deletion the HYP column; STP marks S / I / D (blank when correct)."""
+    assert isinstance(ref, list) and isinstance(hyp, list) and isinstance(steps, list)
+    if not steps:
+        assert not ref and not hyp
+        return "REF: \nHYP: \nSTP: \nWER: {:.2f}%\n\n".format(0.0)
+    r_cols, h_cols, s_cols = [], [], []
+    ri = hi = 0
+    for st in steps:
+        if st == "ins":
+            w = hyp[hi]
+            r_cols.append(" " * len(w))
+            h_cols.append(w)
+            s_cols.append("I".ljust(len(w)))
+            hi += 1
+        elif st == "del":
+            w = ref[ri]
+            r_cols.append(w)
+            h_cols.append(" " * len(w))
+            s_cols.append("D".ljust(len(w)))
+            ri += 1
+        elif st == "sub":
+            rw, hw = ref[ri], hyp[hi]
+            width = max(len(rw), len(hw))
+            r_cols.append(rw.ljust(width))
+            h_cols.append(hw.ljust(width))
+            s_cols.append("S".ljust(width))
+            ri += 1
+            hi += 1
+        else:
+            assert st == "corr"
+            rw = ref[ri]
+            r_cols.append(rw)
+            h_cols.append(hyp[hi])
+            s_cols.append(" " * len(rw))
+            ri += 1
+            hi += 1
+    n_err = sum(st != "corr" for st in steps)
+    wer = float(n_err) / len(ref) * 100 if ref else 0.0
+    return "REF: {}\nHYP: {}\nSTP: {}\nWER: {:.2f}%\n\n".format(" ".join(r_cols), " ".join(h_cols), " ".join(s_cols), wer)
+
+
+def plot_attention(attention, hypo_sent, utt_id, save_dir):
+    """Save `attention` (frames x tokens, a CPU tensor) as `<save_dir>/<utt_id>.pdf`: a matshow titled with the hypothesis."""
+    try:
+        import matplotlib as mpl
+
+        mpl.use("Agg")
+        import matplotlib.pyplot as plt
+    except ImportError:
+        raise ImportError("plot_attention requires matplotlib: install it to write attention plots, or unset --print-alignment.")
+    plt.matshow(attention.detach().cpu().float().numpy())
+    plt.title(hypo_sent, fontsize=8)
+    plt.savefig(os.path.join(save_dir, utt_id + ".pdf"), bbox_inches="tight")
+    plt.close()
 
 
 def tokenize(sent, space="<space>", non_lang_syms=None):

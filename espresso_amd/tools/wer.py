@@ -17,6 +17,7 @@ def wordpiece_decode(x: str, space_word="<space>") -> str:
 class Scorer(object):
     def __init__(self, dictionary, wer_output_filter=None):
         self.dictionary = dictionary
+        self.ordered_utt_list = None
         self.word_filters = []
         if wer_output_filter:
             with open(wer_output_filter, "r", encoding="utf-8") as f:
@@ -34,6 +35,7 @@ class Scorer(object):
         self.word_counter = Counter()
         self.char_results = OrderedDict()
         self.results = OrderedDict()
+        self.aligned_results = OrderedDict()
 
     def _decode(self, s):
         d = self.dictionary
@@ -58,8 +60,11 @@ class Scorer(object):
         ref_words, pred_words = self._decode(ref), self._decode(pred)
         for pattern, repl in self.word_filters:
             ref_words, pred_words = re.sub(pattern, repl, ref_words), re.sub(pattern, repl, pred_words)
-        _, _, counter = speech_utils.edit_distance(ref_words.split(), pred_words.split())
+        ref_list, pred_list = ref_words.split(), pred_words.split()
+        _, steps, counter = speech_utils.edit_distance(ref_list, pred_list)
         self.word_counter += counter
+        assert utt_id not in self.aligned_results, "Duplicated utterance id detected: {}".format(utt_id)
+        self.aligned_results[utt_id] = speech_utils.aligned_print(ref_list, pred_list, steps)
 
     @staticmethod
     def _rates(c):
@@ -98,3 +103,34 @@ class Scorer(object):
         c, w = self.char_counter, self.word_counter
         return ("CER: {:.2f}%, WER: {:.2f}% ({} words: sub {} ins {} del {})".format(
             self.cer()[0], self.wer()[0], w["words"], w["sub"], w["ins"], w["del"]))
+
+    def add_ordered_utt_list(self, *args):
+        """Fix the output order of the print_* methods: one list of utterance ids, or text files whose lines start with one."""
+        if len(args) == 1 and isinstance(args[0], list):
+            self.ordered_utt_list = args[0]
+            return
+        self.ordered_utt_list = []
+        for path in args:
+            with open(path, "r", encoding="utf-8") as f:
+                self.ordered_utt_list.extend(line.strip().split()[0] for line in f)
+        for res in (self.char_results, self.results, self.aligned_results):
+            if len(res):
+                assert set(self.ordered_utt_list) == set(res.keys())
+
+    def _ordered(self, res):
+        if self.ordered_utt_list is None:
+            return list(res.keys())
+        assert set(self.ordered_utt_list) == set(res.keys())
+        return self.ordered_utt_list
+
+    def print_char_results(self):
+        """`<utt> <token string>` lines (decoded_char_results.txt)."""
+        return "".join(u + " " + self.char_results[u] for u in self._ordered(self.char_results))
+
+    def print_results(self):
+        """`<utt> <words>` lines (decoded_results.txt, read by Kaldi scoring)."""
+        return "".join(u + " " + self.results[u] for u in self._ordered(self.results))
+
+    def print_aligned_results(self):
+        """`<utt>` followed by its aligned REF / HYP / STP / WER block (aligned_results.txt)."""
+        return "".join(u + "\n" + self.aligned_results[u] for u in self._ordered(self.aligned_results))

@@ -757,6 +757,18 @@ int ea_decode_attention(const void* q, const void* K, const void* V, const int* 
                         int dh, long ldq, long row_stride, long ldkv, int koff, int voff, int max_len, ea_stream_t stream);
 int ea_kv_append_reorder(const void* old_cache, void* new_cache, const void* kv_new, const int* parent, int N, int L, int Lmax,
                          int W, ea_stream_t stream);
+/* ea_decode_attention_probs: ea_decode_attention (same `out`, bit for bit) that also writes fp32 probs[(n*H + h)*ldp + j]
+ *   = softmax weight of key j for j < len, 0 for len <= j < max_len (ldp >= max_len).
+ * ea_attn_history_put: dst[n*ldd + j] = ((accumulate ? dst : 0) + mean_h src[n*s_row + j*s_frame + h*s_head]) / div, n < N, j < S.
+ * ea_attn_backtrace: for i < n: rows_step = bbsz[i], rows_{k-1} = P[k*ldp + rows_k];
+ *   out[(i*S + s)*(step+1) + k] = A[k*slab + rows_k*lda + s]  (fp32 alignment [S][step+1] of every finalized hypothesis). */
+int ea_decode_attention_probs(const void* q, const void* K, const void* V, const int* kv_row, const int* len, void* out, int N, int H,
+                              int dh, long ldq, long row_stride, long ldkv, int koff, int voff, int max_len, float* probs, long ldp,
+                              ea_stream_t stream);
+int ea_attn_history_put(const float* src, long s_row, long s_frame, long s_head, int N, int H, int S, float* dst, long ldd,
+                        int accumulate, float div, ea_stream_t stream);
+int ea_attn_backtrace(const float* A, long slab, long lda, const int* P, long ldp, const long* bbsz, int n, int step, int S,
+                      float* out, ea_stream_t stream);
 int ea_beam_mask_rows(float* lprobs, int N, int V, int pad, int unk, int eos, float unk_penalty, int only_eos, int forbid_eos,
                       float eos_factor, int use_eos_factor, ea_stream_t stream);
 int ea_beam_topk(const float* lprobs, const float* prev_scores, int bsz, int beam, int nbeam_used, int V, int k,
