@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Hot-path benchmark: LibriSpeech Conformer-12 + CTC training steps on synthetic 16 kHz audio.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = one optimizer update on one per-GPU batch of the recipe
@@ -10,6 +10,11 @@ One "step" = one optimizer update on one per-GPU batch of the recipe
 fbank + CMVN + SpecAugment (HIP) -> Conformer-12 -> CTC -> backward -> overlapped RCCL gradient
 all-reduce -> clip -> Adam.  Weak scaling: every rank processes its own batches.
 Prints ONE JSON line on rank 0 (metric: audio-hours/sec, whole job).
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.  `--full` adds what
+takes runs of its own after the timed steps, on rank 0: the GEMM roofline replay and, on one GPU, the CPU baselines, the beam-10
+decode block and the other BASELINE configurations (each skippable with its --no-* switch).  A block that did not run is null
+(`roofline`, `cpu_baseline`, `decode`) or absent (the other configurations) in the line.
 """
 import argparse
 import json
@@ -334,14 +339,17 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-decode", action="store_true", help="skip the config-5 decode block (beam-10 RTF)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run the roofline replay, the CPU baselines, the decode block and the other configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-decode", action="store_true", help="with --full: skip the config-5 decode block (beam-10 RTF)")
     ap.add_argument("--decode-utts", type=int, default=2864, help="utterances of the 2864-utterance decode workload (SURVEY 8d) to time; default: all of it")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the GEMM roofline replay")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the BASELINE config 2 (Transformer enc-dec) and config 4 (Conformer-16 transducer) training blocks")
+                    help="with --full: skip the BASELINE config 2 (Transformer enc-dec) and config 4 (Conformer-16 transducer) training blocks")
     ap.add_argument("--gemm-nt-bytes", type=int, default=None, help="diagnostic: non-temporal store threshold of the GEMM epilogue (0 = off)")
-    ap.add_argument("--gemm-dump", default=None, help="write the per-launch GEMM records of the roofline replay to this file")
+    ap.add_argument("--gemm-dump", default=None,
+                    help="write the per-launch GEMM records of the roofline replay to this file (runs the replay without --full too)")
     ap.add_argument("--n-utts", type=int, default=20000)
     ap.add_argument("--max-tokens", type=int, default=26000, help="diagnostic only: shrink the batches (host-overhead probes)")
     ap.add_argument("--no-bwd-overlap", action="store_true", help="A/B switch: keep weight-gradient GEMMs on the main stream")
@@ -464,7 +472,7 @@ def main(argv=None):
         dump_outputs(args.dump_outputs, model, trainer, step_out)
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and ((args.full and not args.no_roofline) or args.gemm_dump):
         # Instrumented replay of timed-region steps: the library records one HIP-event pair around every
         # launch of the dominant kernel (the bf16 MFMA GEMM) on its launch stream; flops = 2*M*N*K*batch.
         import ctypes
@@ -502,7 +510,7 @@ def main(argv=None):
                     "gemm_ms_per_step": tot_ms / nrep, "gemm_flop_per_step": tot_fl / nrep}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline()
         # the same CPU port at the recipe's batch size (24 utterances: the host cores are better fed); ~45 s of CPU work
         cpu["at_recipe_batch"] = cpu_baseline(n_utts=24, steps=1)
@@ -512,7 +520,7 @@ def main(argv=None):
         if os.path.exists(ref_file):
             cpu["reference_in_build_container"] = json.load(open(ref_file))
     decode = None
-    if rank == 0 and world == 1 and not args.no_decode:
+    if rank == 0 and world == 1 and args.full and not args.no_decode:
         del trainer, model, criterion, samples  # the decode model gets the GPU to itself
         torch.cuda.empty_cache()
         decode, dmodel, ddict = decode_bench(device, n_utts=args.decode_utts)
@@ -520,7 +528,7 @@ def main(argv=None):
             decode["cpu_baseline"] = decode_cpu_baseline(dmodel, ddict)
         del dmodel
     others = {}
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_other_configs:
         # BASELINE configs 2 and 4 (same machinery, other model families): reported next to the headline, never part of `value`
         # Each block runs in its own interpreter (tools/bench_encdec.py / bench_transducer.py print one JSON line): the transducer
         # step is within 20 % of being host-bound, and inside this process — a heap of ~10^6 objects left by the decode block, the
