@@ -398,6 +398,13 @@ extern "C" long ea_joint_rnnt_workspace_bytes(int B, int T, int U1, int V) {
   return joint_ws(nullptr, n, (V + JBN - 1) / JBN).bytes;
 }
 
+extern "C" long ea_joint_rnnt_lattice_offset(int B, int T, int U1, int V, int which) {
+  if (which < 0 || which > 1) return -1;
+  char* const base = reinterpret_cast<char*>(256);  // (any 256-aligned address: joint_ws only adds offsets to it)
+  const JointWs w = joint_ws(base, (long)B * T * U1, (V + JBN - 1) / JBN);
+  return (which ? reinterpret_cast<char*>(w.lpy) : reinterpret_cast<char*>(w.lpb)) - base;
+}
+
 extern "C" int ea_joint_rnnt_loss(const void* Z, const void* W, const float* bias, const int* targets, const int* logit_lengths,
                                   const int* target_lengths, float* loss, void* workspace, int B, int T, int U1, int V, int J,
                                   int Umax, int blank, hipStream_t stream) {

@@ -425,6 +425,12 @@ extern "C" int ea_joint_reduce_f32(const void* dZ, float* dE, float* dD, int B, 
 
 extern "C" long ea_rnnt_workspace_bytes(int B, int T, int U1) { return 5L * B * T * U1 * (long)sizeof(float); }
 
+// workspace layout of ea_rnnt_loss: lse | lpb | lpy | alpha | beta, n = B*T*U1 floats each
+extern "C" long ea_rnnt_lattice_offset(int B, int T, int U1, int which) {
+  if (which < 0 || which > 1) return -1;
+  return (1L + which) * B * T * U1 * (long)sizeof(float);
+}
+
 // alpha / beta sweep + per-utterance loss from the two log-probabilities per lattice node (shared with csrc/joint_rnnt.hip, whose
 // fused vocabulary projection produces lpb / lpy without materialising the logits)
 extern "C" int ea_rnnt_scan(const float* lpb, const float* lpy, const int* logit_lengths, const int* target_lengths, float* alpha,

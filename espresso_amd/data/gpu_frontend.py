@@ -31,6 +31,7 @@ class GpuFbankFrontend:
                  specaug: Optional[AdaptiveSpecAugmentTransform] = None, seed=1):
         self.device = device
         self.nmel = num_mel_bins
+        self.sample_rate = sample_rate
         self.frame_len = int(sample_rate * 0.025)
         self.frame_shift = int(sample_rate * 0.010)
         self.tables = build_tables(device, num_mel_bins, self.frame_len, 512, float(sample_rate))

@@ -587,6 +587,59 @@ def ctc_prefix_beam_finish(ws, B, T, beam, nbest, pad, lm_rows=None, lm_weight=0
     return tokens, lengths, scores, nhyp
 
 
+def ctc_viterbi_align(x, targets, in_len, tgt_len, B, T, V, blank, ld=None):
+    """Forced alignment of targets int32 [B][Lmax] to x [B*T][V] fp32/bf16 log-probs (batch-major, row pitch ld).  Returns
+    (tok_start int32 [B][Lmax], tok_end int32 [B][Lmax], frame_label int32 [B][T], score fp32 [B]), all on the device."""
+    ld = x.stride(0) if ld is None else ld
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.stride(-1) == 1 and x.shape[0] == B * T and x.shape[1] == V
+    assert targets.dtype == torch.int32 and targets.is_contiguous() and targets.shape[0] == B
+    assert in_len.dtype == tgt_len.dtype == torch.int32 and in_len.numel() == tgt_len.numel() == B
+    Lmax = targets.shape[1]
+    dev = x.device
+    ws = torch.empty(max(1, int(_lib.lib().ea_ctc_viterbi_workspace_bytes(B, T, Lmax))), dtype=torch.uint8, device=dev)
+    tok_start = torch.empty(B, Lmax, dtype=torch.int32, device=dev)
+    tok_end = torch.empty(B, Lmax, dtype=torch.int32, device=dev)
+    frame_label = torch.empty(B, T, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    check(_lib.lib().ea_ctc_viterbi_align(_p(x), ld, int(x.dtype == torch.bfloat16), _p(targets), _p(in_len), _p(tgt_len), _p(ws),
+                                          _p(tok_start), _p(tok_end), _p(frame_label), _p(score), B, T, V, Lmax, blank, _stream()),
+          "ea_ctc_viterbi_align")
+    return tok_start, tok_end, frame_label, score
+
+
+def rnnt_viterbi_align(lpb, lpy, logit_lengths, target_lengths):
+    """Forced alignment over a transducer lattice lpb / lpy fp32 [B][T][U1] (ea_rnnt_scan's meaning).  Returns (emit_frame int32
+    [B][U1 - 1], score fp32 [B]) on the device."""
+    B, T, U1 = lpb.shape
+    assert lpb.dtype == lpy.dtype == torch.float32 and lpb.is_contiguous() and lpy.is_contiguous() and lpy.shape == lpb.shape
+    assert logit_lengths.dtype == target_lengths.dtype == torch.int32 and logit_lengths.numel() == target_lengths.numel() == B
+    dev = lpb.device
+    ws = torch.empty(max(1, int(_lib.lib().ea_rnnt_viterbi_workspace_bytes(B, T, U1))), dtype=torch.uint8, device=dev)
+    emit_frame = torch.empty(B, U1 - 1, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    check(_lib.lib().ea_rnnt_viterbi_align(_p(lpb), _p(lpy), _p(logit_lengths), _p(target_lengths), _p(ws), _p(emit_frame),
+                                           _p(score), B, T, U1, _stream()), "ea_rnnt_viterbi_align")
+    return emit_frame, score
+
+
+def _lattice_views(ws, off_b, off_y, B, T, U1):
+    n = B * T * U1
+    return (ws[off_b:off_b + 4 * n].view(torch.float32).view(B, T, U1), ws[off_y:off_y + 4 * n].view(torch.float32).view(B, T, U1))
+
+
+def joint_rnnt_lattice(ws, B, T, U1, V):
+    """(lpb, lpy) fp32 [B][T][U1]: views of the lattice `joint_rnnt_loss_fwd` left in its workspace."""
+    lib = _lib.lib()
+    return _lattice_views(ws, lib.ea_joint_rnnt_lattice_offset(B, T, U1, V, 0), lib.ea_joint_rnnt_lattice_offset(B, T, U1, V, 1),
+                          B, T, U1)
+
+
+def rnnt_lattice(ws, B, T, U1):
+    """(lpb, lpy) fp32 [B][T][U1]: views of the lattice `rnnt_loss_fwd` left in its workspace."""
+    lib = _lib.lib()
+    return _lattice_views(ws, lib.ea_rnnt_lattice_offset(B, T, U1, 0), lib.ea_rnnt_lattice_offset(B, T, U1, 1), B, T, U1)
+
+
 def embedding_fwd(tokens, positions, W, pos_table, scale):
     M, C = tokens.numel(), W.shape[1]
     out = torch.empty(M, C, dtype=torch.bfloat16, device=W.device)

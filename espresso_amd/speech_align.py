@@ -1,0 +1,154 @@
+"""Forced-alignment CLI: time every token (or word) of known transcripts with a trained CTC or transducer model and write a
+CTM (`utt 1 start dur unit conf`).
+
+Model, dictionary, audio and batching options mean what they mean in `speech_recognize`.  Transcripts (`--text`, `utt_id
+text...`) are tokenised as the task tokenises training targets (the dictionary's `--bpe` encoder, else the text is taken as
+space-separated tokens).  The model kind decides the aligner: an encoder-only CTC model -> `CTCForcedAligner`, a transducer
+-> `TransducerForcedAligner` (tools/forced_aligner.py); attention encoder-decoder models are refused.  Seconds per encoder
+frame = the front-end's frame shift x the model's sub-sampling factor.  `--scores` gets one line per utterance (id, encoder
+frames, tokens, Viterbi log-prob, log-prob per frame); utterances whose transcript cannot be aligned (too few frames) are
+marked `infeasible` there and left out of the CTM."""
+import argparse
+import math
+import os
+import sys
+import time
+from typing import Dict, List
+
+import torch
+
+from .speech_recognize import _load_file, collate, load_member, make_batches, read_scp, read_wav, resolve_model_config, shard_batches
+
+
+def get_parser():
+    p = argparse.ArgumentParser("espresso_amd.speech_align", description=__doc__.split("\n")[0])
+    p.add_argument("--path", required=True, help="state_dict (or fairseq checkpoint dict with a 'model' entry)")
+    p.add_argument("--model", default=None, help="registered model name (default: the checkpoint's cfg.model._name)")
+    p.add_argument("--model-config", default=None, help="JSON/YAML file with the recipe's `model:` block (default: the checkpoint's)")
+    p.add_argument("--dict", required=True)
+    p.add_argument("--wav-scp", required=True)
+    p.add_argument("--text", required=True, help="transcripts to align (utt_id text...)")
+    p.add_argument("--global-cmvn-stats-path", default=None)
+    p.add_argument("--bpe", default=None, choices=["characters_asr", "sentencepiece"],
+                   help="tokenise the transcripts with this encoder (as the task does for training targets)")
+    p.add_argument("--sentencepiece-model", default=None)
+    p.add_argument("--non-lang-syms", default=None, help="non-language symbols (one per line), kept whole by characters_asr")
+    p.add_argument("--max-tokens", type=int, default=15000)
+    p.add_argument("--batch-size", type=int, default=24)
+    p.add_argument("--num-shards", type=int, default=int(os.environ.get("WORLD_SIZE", "1")))
+    p.add_argument("--shard-id", type=int, default=int(os.environ.get("RANK", "0")))
+    p.add_argument("--device", default=None, help="default: cuda:LOCAL_RANK (cuda:0 outside a launcher)")
+    p.add_argument("--output", default="-", help="CTM file (default: stdout)")
+    p.add_argument("--unit", default="token", choices=["token", "word"],
+                   help="CTM units: tokens, or words (<space> tokens / pieces that begin with the sentencepiece mark separate words)")
+    p.add_argument("--scores", default=None, help="per-utterance alignment scores file")
+    return p
+
+
+def model_kind(name: str) -> str:
+    """"ctc" (encoder-only CTC) or "transducer" for a registered model name; attention encoder-decoders raise."""
+    from . import registry
+    from .models.transformer.speech_transformer_encoder_model import SpeechTransformerEncoderModel
+    from .models.transformer.speech_transformer_transducer_base import SpeechTransformerTransducerModelBase
+
+    cls = registry.MODEL_REGISTRY.get(name)
+    if cls is None:
+        raise ValueError(f"unknown model '{name}'")
+    if issubclass(cls, SpeechTransformerTransducerModelBase):
+        return "transducer"
+    if issubclass(cls, SpeechTransformerEncoderModel):
+        return "ctc"
+    raise NotImplementedError(f"forced alignment is implemented for CTC and transducer models, not for the attention model '{name}': "
+                              "its attention alignments of the hypothesis come from `python -m espresso_amd.speech_recognize "
+                              "--print-alignment`")
+
+
+def read_text(path: str) -> Dict[str, str]:
+    out = {}
+    for line in open(path, encoding="utf-8"):
+        parts = line.strip().split(None, 1)
+        if parts:
+            out[parts[0]] = parts[1] if len(parts) > 1 else ""
+    return out
+
+
+def tokenize(dictionary, text: str, blank: int) -> List[int]:
+    """Target ids of a transcript, as the task builds training targets (asr_dataset: encode_line(wordpiece_encode(text)))."""
+    ids = dictionary.encode_line(dictionary.wordpiece_encode(text), append_eos=False).tolist()
+    if blank in ids:
+        raise ValueError(f"transcript {text!r} contains the blank symbol {dictionary[blank]!r}")
+    return ids
+
+
+def main(argv=None):
+    args = get_parser().parse_args(argv)
+    if args.model:  # refuse attention models before anything is loaded
+        model_kind(args.model)
+    from .tasks.speech_recognition import SpeechRecognitionEspressoConfig, SpeechRecognitionEspressoTask
+    from .tools.forced_aligner import CTCForcedAligner, TransducerForcedAligner, ctm_lines, frame_seconds, utterance_units
+
+    state = _load_file(args.path)
+    model_name, model_cfg = resolve_model_config(args.model, args.model_config, state)
+    kind = model_kind(model_name)
+    dev = torch.device(args.device or "cuda:{}".format(int(os.environ.get("LOCAL_RANK", "0"))))
+    if dev.type == "cuda":
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        torch.cuda.set_device(dev)
+    task = SpeechRecognitionEspressoTask.setup_task(SpeechRecognitionEspressoConfig(
+        dict=args.dict, autoregressive=False, global_cmvn_stats_path=args.global_cmvn_stats_path,
+        criterion_name="ctc_loss" if kind == "ctc" else "transducer_loss", non_lang_syms=args.non_lang_syms, bpe=args.bpe,
+        sentencepiece_model=args.sentencepiece_model))
+    d = task.target_dictionary
+    model = load_member(state, model_name, model_cfg, task, dev)
+    aligner = (CTCForcedAligner if kind == "ctc" else TransducerForcedAligner)([model], d)
+
+    scp = read_scp(args.wav_scp)
+    texts = read_text(args.text)
+    utt_ids = list(scp.keys())
+    missing = [u for u in utt_ids if u not in texts]
+    if missing:
+        raise ValueError(f"--text has no transcript for {len(missing)} utterance(s), e.g. {missing[0]}")
+    targets = {u: tokenize(d, texts[u], aligner.blank) for u in utt_ids}
+    waves = [read_wav(scp[u]) for u in utt_ids]
+    task.build_frontend(dev)
+    spf = frame_seconds(model, task.frontend.frame_shift / task.frontend.sample_rate)
+    batches = shard_batches(make_batches(utt_ids, [len(w) for w in waves], args.max_tokens, args.batch_size), args.num_shards,
+                            args.shard_id)
+
+    results, t_align, audio_s = {}, 0.0, 0.0
+    for ids in batches:
+        sample = collate(ids, utt_ids, waves, dev)
+        t0 = time.perf_counter()
+        s = task.prepare_sample(sample, train=False)
+        out = aligner.align(s, [targets[u] for u in sample["utt_ids"]])  # (one host copy per batch)
+        t_align += time.perf_counter() - t0
+        audio_s += sum(sample["num_samples"]) / float(task.frontend.sample_rate)
+        results.update(zip(sample["utt_ids"], out))
+
+    order = [u for u in utt_ids if u in results]  # wav.scp order
+    ctm = sys.stdout if args.output == "-" else open(args.output, "w", encoding="utf-8")
+    try:
+        for u in order:
+            r = results[u]
+            if r["feasible"]:
+                for line in ctm_lines(u, utterance_units(r, d, args.unit), spf):
+                    print(line, file=ctm)
+    finally:
+        if ctm is not sys.stdout:
+            ctm.close()
+    if args.scores:
+        with open(args.scores, "w", encoding="utf-8") as f:
+            for u in order:
+                r = results[u]
+                per = r["score"] / r["frames"] if r["feasible"] and r["frames"] > 0 else (0.0 if r["feasible"] else -math.inf)
+                print("{} {} {} {:.4f} {:.4f}{}".format(u, r["frames"], len(r["tokens"]), r["score"], per,
+                                                       "" if r["feasible"] else " infeasible"), file=f)
+    n_bad = sum(not results[u]["feasible"] for u in order)
+    print("| aligned {} utterances ({} infeasible) in {:.1f}s, RTF {:.4f}".format(len(order), n_bad, t_align,
+                                                                               t_align / max(audio_s, 1e-9)), file=sys.stderr)
+    return results
+
+
+if __name__ == "__main__":
+    main()

@@ -282,6 +282,21 @@ def resolve_model_config(model_name, model_config_path, checkpoint):
     return name, block
 
 
+def load_member(state, name, block, task, dev):
+    """The model `name` built from its `model:` block for `task`, with the checkpoint's weights, on `dev`, in eval mode."""
+    from . import registry
+
+    cls = registry.MODEL_REGISTRY[name]
+    cfg_cls = getattr(cls, "config_class", None)
+    cfg = cfg_cls.from_dict(block) if cfg_cls is not None else block
+    m = cls.build_model(cfg, task)
+    sd = state["model"] if isinstance(state, dict) and isinstance(state.get("model"), dict) else state
+    if hasattr(m, "upgrade_state_dict_named"):
+        sd = m.upgrade_state_dict_named(dict(sd), "")
+    m.load_state_dict(sd, strict=True)
+    return m.to(dev).eval()
+
+
 def main(argv=None):
     args = get_parser().parse_args(argv)
     if args.print_alignment is not None and not args.results_path:
@@ -291,7 +306,6 @@ def main(argv=None):
         raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
     import yaml
 
-    from . import registry
     from .data.asr_dictionary import AsrDictionary
     from .models.external_language_model import MultiLevelLanguageModel
     from .models.lstm_lm import LSTMLanguageModelEspresso
@@ -312,22 +326,11 @@ def main(argv=None):
     task = SpeechRecognitionEspressoTask.setup_task(SpeechRecognitionEspressoConfig(
         dict=args.dict, autoregressive=autoregressive, global_cmvn_stats_path=args.global_cmvn_stats_path, criterion_name=crit,
         non_lang_syms=args.non_lang_syms, wer_output_filter=args.wer_output_filter))
-    def load_member(state, name, block):
-        cls = registry.MODEL_REGISTRY[name]
-        cfg_cls = getattr(cls, "config_class", None)
-        cfg = cfg_cls.from_dict(block) if cfg_cls is not None else block
-        m = cls.build_model(cfg, task)
-        sd = state["model"] if isinstance(state, dict) and isinstance(state.get("model"), dict) else state
-        if hasattr(m, "upgrade_state_dict_named"):
-            sd = m.upgrade_state_dict_named(dict(sd), "")
-        m.load_state_dict(sd, strict=True)
-        return m.to(dev).eval()
-
-    model = load_member(state, model_name, model_cfg)
+    model = load_member(state, model_name, model_cfg, task, dev)
     members = [model]
     for extra in paths[1:]:  # every member is rebuilt from ITS OWN checkpoint's configuration (checkpoint_utils.load_model_ensemble)
         st = _load_file(extra)
-        members.append(load_member(st, *resolve_model_config(args.model, args.model_config, st)))
+        members.append(load_member(st, *resolve_model_config(args.model, args.model_config, st), task, dev))
     if len(members) > 1 and args.search != "beam":
         raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
     lm = None

@@ -1,0 +1,187 @@
+"""Forced alignment of known transcripts with a trained CTC or transducer model: when was each token (and word) spoken.
+
+The reference aligns only through Kaldi (espresso/tools/estimate_initial_state_prior_from_alignments.py); its greedy CTC
+timesteps (espresso/tools/ctc_decoder.py:171-186) belong to the hypothesis, not to the transcript.  Here the model runs its
+ordinary HIP forward pass and the Viterbi search over the transcript's lattice is HIP too (csrc/align.hip):
+  - CTC: encoder + log-softmax, then `ea_ctc_viterbi_align` over the extended label sequence blank y1 blank ... yU blank;
+  - transducer: encoder, predictor teacher-forced on <eos> y1 ... yU, the joint network's lattice log p(blank | t,u) and
+    log p(y_{u+1} | t,u) from the fused output layer + log-sum-exp pass of the RNN-T loss (the logits are not written; shapes
+    the fused kernels do not take go through the materialised logits), then `ea_rnnt_viterbi_align`.
+Everything stays on the device until one copy per batch brings the spans, scores and lengths to the host.
+
+A token's span is [start, end) in encoder frames: for CTC the frames of its non-blank run, for a transducer the frame that
+emits it (one frame).  `frame_seconds` converts frames to seconds; `word_spans` and `ctm_lines` build the CTM."""
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from .. import kernels as K
+
+SP_SPACE = "▁"  # sentencepiece's word-boundary mark
+
+
+def _pad_targets(targets, target_lengths, pad_value: int, device):
+    """int32 [B][max(1, Lmax)] targets (columns past a target's length = pad_value) and int32 lengths on `device`."""
+    if isinstance(targets, (list, tuple)):
+        target_lengths = [len(t) for t in targets]
+        L = max([1] + target_lengths)
+        tg = torch.full((len(targets), L), pad_value, dtype=torch.int32)
+        for b, t in enumerate(targets):
+            if len(t):
+                tg[b, : len(t)] = torch.as_tensor(list(t), dtype=torch.int32)
+    else:
+        tg = targets.to(torch.int32)
+        if tg.shape[1] == 0:
+            tg = torch.full((tg.shape[0], 1), pad_value, dtype=torch.int32, device=tg.device)
+    tl = torch.as_tensor(target_lengths, dtype=torch.int32)
+    tg = tg.to(device)
+    tl = tl.to(device)
+    cols = torch.arange(tg.shape[1], device=device).unsqueeze(0)
+    tg = torch.where(cols < tl.unsqueeze(1), tg, torch.full_like(tg, pad_value)).contiguous()
+    return tg, tl.contiguous()
+
+
+def _results(host: np.ndarray, B: int, L: int, end_offset: Optional[int] = None) -> List[Dict]:
+    """Unpack the one int32 host copy [tokens | start | end | lengths | frames | score bits] of a batch."""
+    tok = host[: B * L].reshape(B, L)
+    st = host[B * L: 2 * B * L].reshape(B, L)
+    en = host[2 * B * L: 3 * B * L].reshape(B, L)
+    tl = host[3 * B * L: 3 * B * L + B]
+    fr = host[3 * B * L + B: 3 * B * L + 2 * B]
+    sc = host[3 * B * L + 2 * B:].view(np.float32)
+    out = []
+    for b in range(B):
+        n = int(tl[b])
+        feasible = bool(np.isfinite(sc[b]))
+        s = st[b, :n].astype(np.int64)
+        e = (s + end_offset) if end_offset is not None else en[b, :n].astype(np.int64)
+        out.append({"tokens": tok[b, :n].astype(np.int64), "start": s if feasible else np.full(n, -1),
+                    "end": e if feasible else np.full(n, -1), "score": float(sc[b]), "frames": int(fr[b]), "feasible": feasible})
+    return out
+
+
+class CTCForcedAligner:
+    """Viterbi alignment of transcripts with an encoder-only CTC model (blank = "<s>", as in the `ctc_loss` criterion)."""
+
+    def __init__(self, models, dictionary, blank=None):
+        self.model = models[0] if isinstance(models, (list, tuple)) else models
+        self.dictionary = dictionary
+        self.blank = dictionary.bos() if blank is None else blank
+
+    @torch.no_grad()
+    def align(self, sample, targets, target_lengths=None) -> List[Dict]:
+        """targets: [B][Lmax] token ids (tensor, host or device) with target_lengths, or a list of B id lists.  Returns per
+        utterance: tokens, start / end (encoder frames, [start, end)), score (Viterbi log-prob), frames (valid encoder frames),
+        feasible."""
+        net_output = self.model(**sample["net_input"])
+        lprobs = self.model.get_normalized_probs(net_output, log_probs=True)  # T x B x V view of [B][T][V]
+        Tp, B, V = lprobs.shape
+        enc_len = net_output["src_lengths"][0].to(torch.int32).contiguous()
+        flat = lprobs.transpose(0, 1).reshape(B * Tp, V)
+        tg, tl = _pad_targets(targets, target_lengths, 0, flat.device)
+        ts, te, _, score = K.ctc_viterbi_align(flat, tg, enc_len, tl, B, Tp, V, self.blank)
+        host = torch.cat([tg.flatten(), ts.flatten(), te.flatten(), tl, enc_len, score.view(torch.int32)]).cpu().numpy()
+        return _results(host, B, tg.shape[1])
+
+
+class TransducerForcedAligner:
+    """Viterbi alignment of transcripts with a transducer model (blank = "<s>", predictor start symbol = </s>, as in training
+    with the `transducer_loss` criterion).  `fused=False` forces the materialised-logits lattice (what shapes the fused joint
+    does not take use anyway)."""
+
+    def __init__(self, models, dictionary, blank=None, bos=None, fused=True):
+        self.model = models[0] if isinstance(models, (list, tuple)) else models
+        self.dictionary = dictionary
+        self.blank = dictionary.bos() if blank is None else blank
+        self.bos = dictionary.eos() if bos is None else bos
+        self.pad = dictionary.pad()
+        self.fused = fused
+
+    @torch.no_grad()
+    def lattice(self, sample, tg, tl):
+        """(lpb, lpy fp32 [B][T'][U+1], encoder lengths int32 [B], loss fp32 [B]) of targets tg int32 [B][U]."""
+        m = self.model
+        ni = sample["net_input"]
+        enc = m.encoder(ni["src_tokens"], ni["src_lengths"])
+        x = enc["_x_bt"][0]
+        enc_len = enc["src_lengths"][0].to(torch.int32).contiguous()
+        B = enc_len.numel()
+        T = x.shape[0] // B
+        U1 = tg.shape[1] + 1
+        prev = torch.full((B, U1), self.pad, dtype=torch.long, device=tg.device)
+        prev[:, 0] = self.bos
+        cols = torch.arange(U1 - 1, device=tg.device).unsqueeze(0)
+        prev[:, 1:] = torch.where(cols < tl.unsqueeze(1), tg.long(), torch.full_like(prev[:, 1:], self.pad))
+        dec, _ = m.decoder.extract_features(prev)
+        D = m._joint_decoder_branch(dec.reshape(B * U1, -1)).contiguous()
+        E = m.joint_encoder_branch(x).contiguous()
+        w, b = m.fc_out_params()
+        V = w.shape[0]
+        w16 = K.cast_f32_to_bf16(w.detach().contiguous())
+        Z = K.joint_add_relu(E, D, B, T, U1) if self.fused else None
+        if self.fused and U1 <= 512 and E.dtype == D.dtype == torch.float32 and K.joint_rnnt_supported(Z, w16):
+            loss, ws = K.joint_rnnt_loss_fwd(Z, w16, b, tg, enc_len, tl, B, T, U1, self.blank)
+            lpb, lpy = K.joint_rnnt_lattice(ws, B, T, U1, V)
+        else:
+            from .. import functional as F
+
+            logits = F.transducer_joint(E, D, w, b, B, T, U1)
+            loss, ws = K.rnnt_loss_fwd(logits, tg, enc_len, tl, self.blank)
+            lpb, lpy = K.rnnt_lattice(ws, B, T, U1)
+        return lpb, lpy, enc_len, loss
+
+    @torch.no_grad()
+    def align(self, sample, targets, target_lengths=None) -> List[Dict]:
+        """As CTCForcedAligner.align; a token's span is the one frame that emits it."""
+        dev = sample["net_input"]["src_tokens"].device
+        tg, tl = _pad_targets(targets, target_lengths, 0, dev)
+        lpb, lpy, enc_len, _ = self.lattice(sample, tg, tl)
+        emit, score = K.rnnt_viterbi_align(lpb, lpy, enc_len, tl)
+        host = torch.cat([tg.flatten(), emit.flatten(), emit.flatten(), tl, enc_len, score.view(torch.int32)]).cpu().numpy()
+        return _results(host, tg.shape[0], tg.shape[1], end_offset=1)
+
+
+# ------------------------------------------------------------------------------------------------ frames, words, CTM
+def subsampling_factor(encoder) -> int:
+    """Input frames per encoder frame, from the encoder's own length arithmetic (the sub-sampler's time strides)."""
+    probe = 720720 ** 2  # divisible by every product of two strides up to 16
+    return int(round(probe / int(encoder.output_lengths(probe))))
+
+
+def frame_seconds(model, frame_shift_seconds: float) -> float:
+    """Seconds per encoder frame = the front-end's frame shift x the model's sub-sampling factor."""
+    return frame_shift_seconds * subsampling_factor(model.encoder)
+
+
+def word_spans(symbols: Sequence[str], starts: Sequence[int], ends: Sequence[int], space: str = "<space>"):
+    """Group token spans into words: `space` tokens separate words (character dictionaries) and a piece that begins with
+    "▁" begins one (sentencepiece).  A word spans from its first token's start to its last token's end.
+    Returns [(word, start, end)]."""
+    words, cur = [], None
+    for sym, s, e in zip(symbols, starts, ends):
+        if sym == space:
+            cur = None
+            continue
+        if sym.startswith(SP_SPACE) or cur is None:
+            cur = [sym.lstrip(SP_SPACE), int(s), int(e)]
+            words.append(cur)
+        else:
+            cur[0] += sym
+            cur[2] = int(e)
+    return [(w, s, e) for w, s, e in words if w]
+
+
+def ctm_lines(utt: str, units, seconds_per_frame: float) -> List[str]:
+    """`utt 1 start dur unit conf` lines (seconds, 3 decimals); units = [(text, start_frame, end_frame)].  The transcript is
+    given, not recognised: the confidence column is 1.00."""
+    return ["{} 1 {:.3f} {:.3f} {} 1.00".format(utt, s * seconds_per_frame, (e - s) * seconds_per_frame, text)
+            for text, s, e in units]
+
+
+def utterance_units(result: Dict, dictionary, unit: str = "token"):
+    """[(text, start_frame, end_frame)] of one feasible alignment result: its tokens, or its words (`word_spans`)."""
+    syms = [dictionary[int(t)] for t in result["tokens"]]
+    if unit == "word":
+        return word_spans(syms, result["start"], result["end"], space=getattr(dictionary, "space_word", "<space>"))
+    return [(s, int(a), int(b)) for s, a, b in zip(syms, result["start"], result["end"])]

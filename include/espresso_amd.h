@@ -808,6 +808,44 @@ int ea_joint_rnnt_loss(const void* Z, const void* W, const float* bias, const in
 int ea_joint_rnnt_grad(const void* Z, const void* W, const float* bias, const int* targets, const int* logit_lengths,
                        const int* target_lengths, const float* loss, void* workspace, void* dl, long ld, int B, int T, int U1,
                        int V, int J, int Umax, int blank, float grad_scale, const float* grad_scale_dev, ea_stream_t stream);
+/* Where the transducer lattice sits after a loss call: byte offset of lpb (which = 0) or lpy (which = 1), fp32 [B][T][U1] with
+ * the meaning of ea_rnnt_scan's, inside the workspace of ea_joint_rnnt_loss (..._joint_...) or of ea_rnnt_loss; -1 for another
+ * `which`.  The forced aligner reads the lattice there (no change to what the loss calls compute). */
+long ea_joint_rnnt_lattice_offset(int B, int T, int U1, int V, int which);
+long ea_rnnt_lattice_offset(int B, int T, int U1, int which);
+
+/* ------------------------------------------------------------------------------------------
+ * Forced alignment (csrc/align.hip): the Viterbi (max-plus) twins of the CTC and RNN-T scans plus a backtrace, for a known
+ * transcript.  The reference aligns only through Kaldi (estimate_initial_state_prior_from_alignments.py); the greedy CTC
+ * timesteps of espresso/tools/ctc_decoder.py:171-186 belong to the hypothesis.  One workgroup per utterance; outputs stay on
+ * the device (no host synchronisation).
+ *
+ * ea_ctc_viterbi_align: x fp32 or bf16 (x_bf16) [B][T][ld] log-probs (ld >= V), targets int32 [B][Lmax], in_len / tgt_len int32
+ *   [B] (clamped to T / Lmax), workspace: ea_ctc_viterbi_workspace_bytes(B, T, Lmax) bytes, any contents.
+ *   Lattice: blank y1 blank ... yU blank (S = 2U + 1 states); moves stay, +1, +2 (+2 only into a non-blank state whose label
+ *   differs from the label two states earlier); a path starts in state 0 or 1 and ends in state S-1 or S-2.
+ *   TIE RULE: stay over +1 over +2 (from the predecessor's side: the backtrace takes the first of s, s-1, s-2 with the maximum);
+ *   at the end S-1 over S-2.
+ *   Outputs: tok_start / tok_end int32 [B][Lmax] = first frame of token u's non-blank run and one past its last frame (trailing
+ *   blanks are not part of a token; -1 for u >= U); frame_label int32 [B][T] = u on a frame of token u, -1 on blank frames, -2
+ *   from in_len on; score fp32 [B] = sum of the chosen log-probs (U == 0: the all-blank path; in_len == U == 0: 0).
+ *   Infeasible utterances (in_len < U + number of equal adjacent targets, or a lattice with no finite path): score = -inf,
+ *   tok_start = tok_end = -1, frame_label = -2.  A target id outside [0, V) or equal to blank cannot be returned as an error
+ *   without reading device memory on the host: that utterance gets score = NaN and the -1 / -2 fill, and is not aligned.
+ *   Returns -2 for S > 2048 (Lmax > 1023), Lmax < 1, ld < V or blank outside [0, V).
+ * ea_rnnt_viterbi_align: lpb / lpy fp32 [B][T][U1] as in ea_rnnt_scan (log p(blank | t,u), log p(y_{u+1} | t,u)),
+ *   logit_lengths / target_lengths int32 [B], workspace: ea_rnnt_viterbi_workspace_bytes(B, T, U1) bytes, any contents.
+ *   From node (t,u) the path takes blank to (t+1,u) or emits y_{u+1} to (t,u+1); it ends with the blank out of (T_b-1, U_b).
+ *   TIE RULE: emit over blank at the node where the choice is made (the earlier emission).
+ *   Outputs: emit_frame int32 [B][U1-1] = the frame at which token u is emitted (-1 for u >= U_b); score fp32 [B] = sum of
+ *   the chosen log-probs (-inf and emit_frame -1 when T_b == 0 or no path is finite).  Returns -2 for U1 > 1024. */
+long ea_ctc_viterbi_workspace_bytes(int B, int T, int Lmax);
+int ea_ctc_viterbi_align(const void* x, long ld, int x_bf16, const int* targets, const int* in_len, const int* tgt_len,
+                         void* workspace, int* tok_start, int* tok_end, int* frame_label, float* score, int B, int T, int V,
+                         int Lmax, int blank, ea_stream_t stream);
+long ea_rnnt_viterbi_workspace_bytes(int B, int T, int U1);
+int ea_rnnt_viterbi_align(const float* lpb, const float* lpy, const int* logit_lengths, const int* target_lengths,
+                          void* workspace, int* emit_frame, float* score, int B, int T, int U1, ea_stream_t stream);
 /* Joint network element-wise stages (espresso/models/transformer/speech_transformer_transducer_base.py:276-299):
  * Z[b][t][u] = relu(E[b][t] + D[b][u]) (bf16, E [B*T][J], D [B*U1][J], Z [B*T*U1][J], J % 8 == 0) and its backward
  * reductions dE[b][t] = sum_u dZ[b][t][u], dD[b][u] = sum_t dZ[b][t][u] (either output may be NULL). */
