@@ -1,0 +1,752 @@
+// Lexicon-constrained CTC prefix beam search with shallow fusion of a word n-gram LM (ARPA), for gfx950 — the search the
+// reference gets from Flashlight's KenLM lexicon decoder (espresso/tools/ctc_decoder.py:24-71), built here on the prefix
+// beam of ctc_beam.hip: the same candidates (K best non-blank tokens per frame), stays and extensions of every hypothesis,
+// merging of equal token sequences only, and the same tie rules.
+//
+// Scoring contract.  A hypothesis y is completed words w_1..w_m and a partial word p (a node of the lexicon trie):
+//   score(y) = log(p_b + p_nb) + alpha * (L(y) + S(p)) + beta * m + gamma * |y|
+// with L(y) = sum ln P(w_i | w_{i-n+1..i-1}) (<s> as the sentence-start context) and S(p) = max ln P_1(w) over the lexicon
+// words below p (S(root) = 0).  The LM part is kept as a running sum of increments:
+//   a token moves p down the trie:  alpha * (S(child) - S(node));
+//   a word is completed:            alpha * (ln P(w | ctx) - S(node)) + beta;
+//   at the end:                     the pending word is completed, then alpha * ln P(</s> | ctx).
+// A word ends on <space> (space mode, `space` >= 0) or before a token that starts a word (word-start mode, `word_start`
+// flags).  Closed vocabulary: leaving the trie, ending a word on a node that is no word, an empty word, and a pending
+// non-word at the end score -inf.  Prefixes merge only when their token sequences are equal, so the LM state is a function
+// of the prefix.
+//
+// ARPA tables (host loader below): a sorted-array trie.  Order 1 is indexed by word
+// id; every order k >= 2 holds its records sorted by (record of the (k-1)-gram context, word id).  A record of order k < n
+// carries a child range into order k + 1.  ln P(w | h) is the standard backoff: the longest suffix h' of h with (h', w)
+// present, plus the backoff weights of the longer suffixes (0 where a suffix is absent).  Every lookup is a chain of binary
+// searches over these arrays: dependent, latency-bound loads.
+//
+// The search (ctc_lexicon_beam_kernel): one 256-thread workgroup per utterance walks every frame in one launch and
+// finishes in the same launch.  The beam state (with trie node, word context and LM sum per slot) lives in LDS; the
+// per-utterance prefix table and its (parent, token) hash are in the workspace, as in ctc_beam.hip.  Per frame the n-gram
+// lookup of a slot's pending word is done once, by one lane per slot, and only if a candidate token ends a word; the trie
+// step of every extension runs on its own lane.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "common.h"
+#include "ctc_beam_common.h"
+#include "espresso_amd.h"
+
+namespace {
+
+constexpr int kMaxOrder = 6;
+constexpr int kMaxCtx = kMaxOrder - 1;
+constexpr int kLexMaxBeam = 64;
+constexpr int kLexMaxK = 64;
+constexpr int kLexMaxCand = kLexMaxBeam * (kLexMaxK + 1);
+constexpr int kLexRowLds = 5120;
+
+// ------------------------------------------------------------------------------------------------ n-gram tables
+struct NgramDev {  // device pointers of the tables, passed by value
+  int order, n1, unk, bos, eos;
+  const float* logp[kMaxOrder + 1];  // [k]: records of order k (natural log)
+  const float* bow[kMaxOrder + 1];   // [k], k < order (0 where the ARPA line has none)
+  const int* word[kMaxOrder + 1];    // [k], k >= 2: last word of the record (order 1: record i is word i)
+  const int* child[kMaxOrder + 1];   // [k], k < order: records [child[i], child[i + 1]) of order k + 1 extend record i
+};
+
+struct NgramLM {
+  int order = 0, unk = -1, bos = -1, eos = -1;
+  long counts[kMaxOrder + 1] = {};
+  std::vector<std::string> vocab;
+  std::vector<float> logp[kMaxOrder + 1], bow[kMaxOrder + 1];
+  std::vector<int> word[kMaxOrder + 1], child[kMaxOrder + 1], parent[kMaxOrder + 1];
+  void* dev_buf = nullptr;
+  NgramDev dev{}, host{};  // the same tables: device copy, host vectors
+};
+
+// the record of order k + 1 that extends record r of order k by word w (order 0: the root), -1 if none
+__host__ __device__ __forceinline__ int ng_find(const int* const* child, const int* const* word, int n1, int k, int r, int w) {
+  if (k == 0) return (w >= 0 && w < n1) ? w : -1;
+  const int* wd = word[k + 1];
+  int lo = child[k][r];
+  const int end = child[k][r + 1];
+  int hi = end;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (wd[mid] < w) lo = mid + 1; else hi = mid;
+  }
+  return (lo < end && wd[lo] == w) ? lo : -1;
+}
+
+// ln P(w | h[0..L)), h oldest first; w outside the vocabulary scores as <unk> (-inf without one)
+__host__ __device__ inline float ng_logp(const NgramDev& m, const int* h, int L, int w) {
+  if (w < 0 || w >= m.n1) w = m.unk;
+  if (w < 0) return -INFINITY;
+  if (L > m.order - 1) { h += L - (m.order - 1); L = m.order - 1; }
+  float acc = 0.f;
+  for (int l = L; l >= 0; --l) {
+    int r = 0, k = 0;
+    for (; k < l; ++k) {
+      r = ng_find(m.child, m.word, m.n1, k, r, h[L - l + k]);
+      if (r < 0) break;
+    }
+    if (k < l) continue;  // the context h[L-l..L) is absent: its backoff weight counts as 0
+    const int rw = ng_find(m.child, m.word, m.n1, l, r, w);
+    if (rw >= 0) return acc + m.logp[l + 1][rw];
+    if (l > 0) acc += m.bow[l][r];
+  }
+  return -INFINITY;  // not reached: every w in [0, n1) is a unigram
+}
+
+// contexts: fixed width W = order - 1, oldest first, front-padded with -1; the valid words are those after the last -1
+__host__ __device__ __forceinline__ int ctx_len(const int* h, int W) {
+  int L = 0;
+  while (L < W && h[W - 1 - L] >= 0) ++L;
+  return L;
+}
+
+__global__ __launch_bounds__(256) void ngram_score_kernel(const NgramDev m, const int* ctx, const int* words, int N, float* out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  const int W = m.order - 1;
+  const int* h = ctx + (long)i * W;
+  const int L = ctx_len(h, W);
+  out[i] = ng_logp(m, h + W - L, L, words[i]);
+}
+
+// ------------------------------------------------------------------------------------------------ ARPA parser (host)
+struct ArpaError {
+  std::string msg;
+};
+
+[[noreturn]] void arpa_fail(long line, const std::string& what) {
+  char buf[64];
+  snprintf(buf, sizeof(buf), "line %ld: ", line);
+  throw ArpaError{line > 0 ? buf + what : what};
+}
+
+bool is_space(char c) { return c == ' ' || c == '\t' || c == '\r'; }
+
+void split_fields(const char* s, const char* e, std::vector<std::pair<const char*, const char*>>& out) {
+  out.clear();
+  while (s < e) {
+    while (s < e && is_space(*s)) ++s;
+    const char* b = s;
+    while (s < e && !is_space(*s)) ++s;
+    if (s > b) out.emplace_back(b, s);
+  }
+}
+
+double parse_num(std::pair<const char*, const char*> f, long line) {
+  std::string t(f.first, f.second);
+  char* end = nullptr;
+  const double v = strtod(t.c_str(), &end);
+  if (t.empty() || *end) arpa_fail(line, "'" + t + "' is not a number");
+  return v;
+}
+
+void arpa_parse(const std::string& text, NgramLM& lm) {
+  constexpr double kLn10 = 2.302585092994045684;
+  std::vector<std::pair<const char*, const char*>> f;
+  std::unordered_map<std::string, int> ids;
+  const char* p = text.data();
+  const char* const end = p + text.size();
+  long line = 0;
+  auto next_line = [&](const char*& b, const char*& e) {
+    if (p >= end) return false;
+    b = p;
+    e = (const char*)memchr(p, '\n', end - p);
+    if (!e) e = end;
+    p = e < end ? e + 1 : end;
+    ++line;
+    while (e > b && is_space(e[-1])) --e;
+    while (b < e && is_space(*b)) ++b;
+    return true;
+  };
+  const char *b, *e;
+  bool found = false;
+  while (next_line(b, e))
+    if (std::string(b, e) == "\\data\\") { found = true; break; }
+  if (!found) arpa_fail(0, "no \\data\\ header");
+  // ngram k=count lines
+  long data_line = line;
+  while (next_line(b, e)) {
+    if (b == e) continue;
+    std::string s(b, e);
+    if (s.rfind("ngram ", 0) != 0) { p = b; --line; break; }
+    const size_t eq = s.find('=');
+    if (eq == std::string::npos) arpa_fail(line, "expected 'ngram N=count'");
+    const int k = atoi(s.c_str() + 6);
+    const long c = atol(s.c_str() + eq + 1);
+    if (k < 1) arpa_fail(line, "bad n-gram order in '" + s + "'");
+    if (k > kMaxOrder) arpa_fail(line, "order " + std::to_string(k) + " exceeds the supported maximum of 6");
+    if (k != lm.order + 1) arpa_fail(line, "n-gram counts must be listed for orders 1, 2, ... in turn");
+    if (c < 1 || c >= (1L << 31) - 1) arpa_fail(line, "bad count in '" + s + "'");
+    lm.order = k;
+    lm.counts[k] = c;
+  }
+  if (lm.order == 0) arpa_fail(data_line, "\\data\\ lists no n-gram counts");
+  for (int k = 1; k <= lm.order; ++k) {
+    const std::string head = "\\" + std::to_string(k) + "-grams:";
+    while (next_line(b, e) && b == e) {}
+    if (std::string(b, e) != head) arpa_fail(line, "expected '" + head + "'");
+    const long head_line = line, n = lm.counts[k];
+    std::vector<int> words;  // k per record, in file order
+    std::vector<int> lines;
+    std::vector<float> lp, bw;
+    words.reserve(n * k);
+    lp.reserve(n);
+    bw.reserve(n);
+    if (k > 1) lines.reserve(n);
+    while (p < end) {
+      const char* save = p;
+      const long save_line = line;
+      next_line(b, e);
+      if (b == e) break;
+      if (*b == '\\') { p = save; line = save_line; break; }
+      split_fields(b, e, f);
+      const int nf = (int)f.size();
+      if (nf != k + 1 && !(nf == k + 2 && k < lm.order))
+        arpa_fail(line, "a " + std::to_string(k) + "-gram line has " + std::to_string(nf) + " fields, expected " +
+                            std::to_string(k + 1) + (k < lm.order ? " or " + std::to_string(k + 2) : std::string()));
+      if ((long)lp.size() >= n) arpa_fail(line, "more " + std::to_string(k) + "-grams than the " + std::to_string(n) + " \\data\\ declares");
+      lp.push_back((float)(parse_num(f[0], line) * kLn10));
+      bw.push_back(nf == k + 2 ? (float)(parse_num(f[k + 1], line) * kLn10) : 0.f);
+      for (int i = 0; i < k; ++i) {
+        std::string wd(f[1 + i].first, f[1 + i].second);
+        if (k == 1) {
+          if (!ids.emplace(wd, (int)lm.vocab.size()).second) arpa_fail(line, "unigram '" + wd + "' listed twice");
+          lm.vocab.push_back(wd);
+          words.push_back((int)lm.vocab.size() - 1);
+        } else {
+          auto it = ids.find(wd);
+          if (it == ids.end()) arpa_fail(line, "word '" + wd + "' is not a unigram");
+          words.push_back(it->second);
+        }
+      }
+      if (k > 1) lines.push_back((int)line);
+    }
+    if ((long)lp.size() != n)
+      arpa_fail(head_line, head + " has " + std::to_string(lp.size()) + " entries, \\data\\ declares " + std::to_string(n));
+    if (k == 1) {
+      lm.logp[1] = std::move(lp);
+      lm.bow[1] = std::move(bw);
+      continue;
+    }
+    // parent record (the (k-1)-gram context) of every k-gram, then sort by (parent, word)
+    const int n1 = (int)lm.counts[1];
+    const int* cp[kMaxOrder + 1] = {};
+    const int* wp[kMaxOrder + 1] = {};
+    for (int j = 1; j < k; ++j) { cp[j] = lm.child[j].data(); wp[j] = lm.word[j].data(); }
+    std::vector<std::pair<unsigned long long, int>> key(n);
+    for (long i = 0; i < n; ++i) {
+      const int* t = &words[i * k];
+      int r = 0;
+      for (int j = 0; j < k - 1 && r >= 0; ++j) r = ng_find(cp, wp, n1, j, r, t[j]);
+      if (r < 0) {
+        std::string ctx;
+        for (int j = 0; j < k - 1; ++j) ctx += (j ? " " : "") + lm.vocab[t[j]];
+        arpa_fail(lines[i], std::to_string(k) + "-gram context '" + ctx + "' is not a " + std::to_string(k - 1) + "-gram");
+      }
+      key[i] = {((unsigned long long)r << 32) | (unsigned)t[k - 1], (int)i};
+    }
+    std::sort(key.begin(), key.end());
+    for (long i = 1; i < n; ++i)
+      if (key[i].first == key[i - 1].first)
+        arpa_fail(lines[key[i].second], std::to_string(k) + "-gram listed twice (first on line " +
+                                           std::to_string(lines[key[i - 1].second]) + ")");
+    lm.logp[k].resize(n);
+    lm.bow[k].resize(n);
+    lm.word[k].resize(n);
+    lm.parent[k].resize(n);
+    for (long i = 0; i < n; ++i) {
+      const int src = key[i].second;
+      lm.logp[k][i] = lp[src];
+      lm.bow[k][i] = bw[src];
+      lm.word[k][i] = words[(long)src * k + k - 1];
+      lm.parent[k][i] = (int)(key[i].first >> 32);
+    }
+    std::vector<int>& ch = lm.child[k - 1];
+    ch.assign(lm.counts[k - 1] + 1, 0);
+    for (long i = 0; i < n; ++i) ch[lm.parent[k][i] + 1]++;
+    for (long i = 0; i < lm.counts[k - 1]; ++i) ch[i + 1] += ch[i];
+  }
+  while (next_line(b, e) && b == e) {}
+  if (std::string(b, e) != "\\end\\") arpa_fail(line, "expected '\\end\\'");
+  auto id = [&](const char* w) { auto it = ids.find(w); return it == ids.end() ? -1 : it->second; };
+  lm.unk = id("<unk>");
+  lm.bos = id("<s>");
+  lm.eos = id("</s>");
+  if (lm.bos < 0 || lm.eos < 0) arpa_fail(0, "the ARPA file has no <s> or no </s> unigram");
+}
+
+}  // namespace
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------ the search
+struct LexDev {  // the lexicon trie in CSR form (node 0 = root): children of n are tok/child[off[n] .. off[n + 1]), tok sorted
+  const int *off, *tok, *child, *word;  // word: LM word id of the node, -1 if no word ends there
+  const float* smear;                   // S(node), S(root) = 0
+  const uint8_t* word_start;            // [V] word-start mode: 1 = the token starts a word; NULL in space mode
+  int space;                            // space mode: the <space> token, else -1
+};
+
+__device__ __forceinline__ int lex_child(const LexDev& x, int node, int c) {
+  int lo = x.off[node];
+  const int end = x.off[node + 1];
+  int hi = end;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (x.tok[mid] < c) lo = mid + 1; else hi = mid;
+  }
+  return (lo < end && x.tok[lo] == c) ? x.child[lo] : -1;
+}
+
+// per utterance: hash table (parent node, token) -> node and the prefix table of 1 + T * beam nodes, as in ctc_beam.hip
+struct LexWs {
+  unsigned long long* tab_key;
+  int *tab_val, *node_par, *node_tok;
+  int cap, tsize;
+};
+__host__ __device__ __forceinline__ long lex_ws_cap(int T, int beam) { return 1L + (long)T * beam; }
+__host__ __device__ __forceinline__ long lex_ws_tsize(int T, int beam) {
+  long n = 64;
+  while (n < 2 * lex_ws_cap(T, beam)) n <<= 1;
+  return n;
+}
+__host__ __device__ __forceinline__ long lex_ws_words(int T, int beam) {
+  return (3 * lex_ws_tsize(T, beam) + 2 * lex_ws_cap(T, beam) + 1) & ~1L;
+}
+__device__ __forceinline__ LexWs lex_ws(void* ws, int b, int T, int beam) {
+  LexWs w;
+  w.cap = (int)lex_ws_cap(T, beam);
+  w.tsize = (int)lex_ws_tsize(T, beam);
+  int* base = (int*)ws + (long)b * lex_ws_words(T, beam);
+  w.tab_key = (unsigned long long*)base;
+  w.tab_val = base + 2L * w.tsize;
+  w.node_par = w.tab_val + w.tsize;
+  w.node_tok = w.node_par + w.cap;
+  return w;
+}
+
+struct LexArgs {
+  const void* x; long ld; const int* in_len; void* ws;
+  NgramDev lm; LexDev lex;
+  int T, V, beam, K, blank, nbest, pad, W /* context width = order - 1 */;
+  float alpha, beta, gamma;
+  int *tokens, *lengths; float* scores; int* nhyp;
+};
+
+// the increment of completing the word at trie node `node` after context h (W words, front-padded with -1); -inf when
+// the node is the root (an empty word) or no word
+__device__ float word_end(const LexArgs& a, int node, const int* h, int& w) {
+  w = node > 0 ? a.lex.word[node] : -1;
+  if (w < 0) return -INFINITY;
+  const int L = ctx_len(h, a.W);
+  return a.alpha * (ng_logp(a.lm, h + a.W - L, L, w) - a.lex.smear[node]) + a.beta;
+}
+
+template <typename TX>
+__global__ __launch_bounds__(256) void ctc_lexicon_beam_kernel(const LexArgs a) {
+  __shared__ uint64_t s_key[kLexMaxCand];
+  __shared__ float s_nlm[kLexMaxCand];  // LM sum of extension i
+  __shared__ int s_ntn[kLexMaxCand];    // trie node of extension i
+  __shared__ SelectScratch s_sel;
+  __shared__ float s_pb[kLexMaxBeam], s_pnb[kLexMaxBeam], s_lm[kLexMaxBeam];
+  __shared__ int s_len[kLexMaxBeam], s_last[kLexMaxBeam], s_node[kLexMaxBeam], s_pnode[kLexMaxBeam], s_tn[kLexMaxBeam];
+  __shared__ int s_ctx[kLexMaxBeam][kMaxCtx];
+  __shared__ float s_wend[kLexMaxBeam];  // increment of ending the slot's pending word this frame
+  __shared__ int s_wid[kLexMaxBeam];     // that word (-1: none / nothing pending)
+  __shared__ int s_lrank[kLexMaxBeam], s_msrc[kLexMaxBeam];
+  __shared__ unsigned long long s_merged[kLexMaxBeam];
+  __shared__ int s_ctok[kLexMaxK], s_cunsorted[kLexMaxK], s_cbound[kLexMaxK];
+  __shared__ float s_cx[kLexMaxK];
+  __shared__ int s_sel_idx[kLexMaxBeam];
+  __shared__ float s_row[kLexRowLds];
+  __shared__ float s_fin[kLexMaxBeam];
+  __shared__ int s_nhyp, s_nnodes, s_ncand, s_nsel, s_nfresh, s_anybound;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int beam = a.beam, K = a.K, K1 = a.K + 1, W = a.W;
+  const LexWs w = lex_ws(a.ws, b, a.T, beam);
+  const int L = min(a.in_len[b], a.T);
+  const bool space_mode = a.lex.space >= 0;
+
+  for (int i = tid; i < w.tsize; i += 256) w.tab_key[i] = 0ull;
+  if (tid == 0) {
+    s_pb[0] = 0.f; s_pnb[0] = -INFINITY; s_lm[0] = 0.f;
+    s_len[0] = 0; s_last[0] = -1; s_node[0] = 0; s_pnode[0] = -1; s_tn[0] = 0;
+    for (int i = 0; i < W; ++i) s_ctx[0][i] = i == W - 1 ? a.lm.bos : -1;
+    s_nhyp = 1; s_nnodes = 1;
+    w.node_par[0] = -1; w.node_tok[0] = -1;
+  }
+  __threadfence();
+  __syncthreads();
+
+  for (int t = 0; t < L; ++t) {
+    const TX* xr = (const TX*)a.x + ((long)b * a.T + t) * a.ld;
+    for (int v = tid; v < min(a.V, kLexRowLds); v += 256) s_row[v] = ldx(xr, v);
+    __syncthreads();
+    auto xv = [&](int v) { return v < kLexRowLds ? s_row[v] : ldx(xr, v); };
+    const int nh = s_nhyp;
+    const int V = a.V, blank = a.blank;
+
+    // 1. top-K non-blank tokens of the frame, in token-id order; which of them end a word
+    auto tok_key = [&](int v) -> uint64_t { return v == blank ? 0ull : mk_key(xv(v), v); };
+    const uint64_t kth = select_nth(tok_key, V, K, s_sel);
+    if (tid == 0) { s_ncand = 0; s_anybound = 0; }
+    __syncthreads();
+    for (int v = tid; v < V; v += 256) {
+      const uint64_t k = tok_key(v);
+      if (k && k >= kth) s_cunsorted[atomicAdd(&s_ncand, 1)] = v;
+    }
+    __syncthreads();
+    if (tid < K) {
+      const int v = s_cunsorted[tid];
+      int r = 0;
+      for (int i = 0; i < K; ++i) r += s_cunsorted[i] < v;
+      const int bound = a.lex.space >= 0 ? v == a.lex.space : (int)a.lex.word_start[v];
+      s_ctok[r] = v;
+      s_cx[r] = xv(v);
+      s_cbound[r] = bound;
+      if (bound) s_anybound = 1;
+    }
+    if (tid < kLexMaxBeam) s_merged[tid] = 0ull;
+    __syncthreads();
+
+    // 2a. stays that absorb an extension (as ctc_beam.hip); the word-end increment of every slot, if a candidate ends words
+    if (tid < nh) {
+      const int l = s_last[tid];
+      int r = -1;
+      if (s_len[tid] > 0)
+        for (int i = 0; i < K; ++i) r = s_ctok[i] == l ? i : r;
+      int src = -1;
+      if (r >= 0)
+        for (int j = 0; j < nh; ++j) src = s_node[j] == s_pnode[tid] ? j : src;
+      s_lrank[tid] = r;
+      s_msrc[tid] = src;
+      if (src >= 0) atomicOr(&s_merged[src], 1ull << r);
+      float inc = -INFINITY;
+      int wd = -1;
+      if (s_anybound) {
+        if (!space_mode && s_tn[tid] == 0) inc = 0.f;  // word-start mode, nothing pending: nothing to end
+        else inc = word_end(a, s_tn[tid], s_ctx[tid], wd);
+      }
+      s_wend[tid] = inc;
+      s_wid[tid] = wd;
+    }
+    __syncthreads();
+
+    // 2b. candidate scores; index i = slot * (K + 1) + (0: stay, 1 + r: extension by the r-th candidate token)
+    const float xb = xv(blank);
+    auto stay_pnb = [&](int j) {
+      const int r = s_lrank[j];
+      float pnb = r >= 0 ? s_pnb[j] + s_cx[r] : -INFINITY;
+      const int src = s_msrc[j];
+      if (src >= 0) pnb = lae(pnb, (s_last[src] == s_last[j] ? s_pb[src] : lae(s_pb[src], s_pnb[src])) + s_cx[r]);
+      return pnb;
+    };
+    auto ext_pnb = [&](int j, int r) { return (s_ctok[r] == s_last[j] ? s_pb[j] : lae(s_pb[j], s_pnb[j])) + s_cx[r]; };
+    const int N = nh * K1;
+    for (int i = tid; i < N; i += 256) {
+      const int j = i / K1, q = i - j * K1;
+      uint64_t key = 0ull;
+      if (q == 0) {
+        key = mk_key(lae(lae(s_pb[j], s_pnb[j]) + xb, stay_pnb(j)) + s_lm[j] + a.gamma * (float)s_len[j], i);
+      } else if (!((s_merged[j] >> (q - 1)) & 1ull)) {
+        const int r = q - 1, c = s_ctok[r];
+        float lm = s_lm[j];  // -inf exactly when the slot's trie node is -1
+        int tn = 0;
+        if (space_mode && s_cbound[r]) {  // <space>: end the pending word
+          lm += s_wend[j];
+        } else {
+          int node = s_tn[j];
+          if (s_cbound[r]) { lm += s_wend[j]; node = 0; }  // word-start mode: end the pending word, c starts one
+          tn = lm == -INFINITY ? -1 : lex_child(a.lex, node, c);
+          lm = tn < 0 ? -INFINITY : lm + a.alpha * (a.lex.smear[tn] - a.lex.smear[node]);
+        }
+        s_nlm[i] = lm;
+        s_ntn[i] = tn;
+        key = mk_key(ext_pnb(j, r) + lm + a.gamma * (float)(s_len[j] + 1), i);
+      }
+      s_key[i] = key;
+    }
+    __syncthreads();
+
+    // 3. the `beam` best candidates
+    const uint64_t cth = select_nth([&](int i) { return s_key[i]; }, N, beam, s_sel);
+    if (tid == 0) s_nsel = 0;
+    __syncthreads();
+    for (int i = tid; i < N; i += 256) {
+      const uint64_t k = s_key[i];
+      if (k && k >= cth) s_sel_idx[atomicAdd(&s_nsel, 1)] = i;
+    }
+    __syncthreads();
+    const int ns = s_nsel;
+
+    // 4. new state (wave 0: lane = one selected candidate, written to slot = its rank)
+    float n_pb = 0.f, n_pnb = 0.f, n_lm = 0.f;
+    int n_len = 0, n_last = -1, n_node = 0, n_pnode = -1, n_tn = 0, slot = 0, fresh = 0, tslot = -1, n_done = -1;
+    int n_ctx[kMaxCtx];
+    if (tid < ns) {
+      const int i = s_sel_idx[tid];
+      const uint64_t k = s_key[i];
+      for (int m = 0; m < ns; ++m) slot += s_key[s_sel_idx[m]] > k;
+      const int j = i / K1, q = i - j * K1;
+      for (int m = 0; m < W; ++m) n_ctx[m] = s_ctx[j][m];
+      if (q == 0) {
+        n_pb = lae(s_pb[j], s_pnb[j]) + xb; n_pnb = stay_pnb(j); n_lm = s_lm[j];
+        n_len = s_len[j]; n_last = s_last[j]; n_node = s_node[j]; n_pnode = s_pnode[j]; n_tn = s_tn[j];
+      } else {
+        const int r = q - 1;
+        n_pb = -INFINITY; n_pnb = ext_pnb(j, r); n_lm = s_nlm[i]; n_tn = s_ntn[i];
+        n_len = s_len[j] + 1; n_last = s_ctok[r]; n_pnode = s_node[j];
+        if (s_cbound[r]) n_done = s_wid[j];
+        const unsigned long long key = ((unsigned long long)(n_pnode + 1) << 32) | (uint32_t)n_last;
+        const uint32_t mask = (uint32_t)w.tsize - 1u;
+        for (uint32_t h = tab_hash(key) & mask;; h = (h + 1) & mask) {
+          const unsigned long long cur = ld_l2(w.tab_key + h);
+          if (cur == key) { n_node = ld_l2(w.tab_val + h); break; }
+          if (cur == 0ull && atomicCAS(w.tab_key + h, 0ull, key) == 0ull) { fresh = 1; tslot = (int)h; break; }
+        }
+      }
+      if (n_done >= 0 && W > 0) {
+        for (int m = 0; m + 1 < W; ++m) n_ctx[m] = n_ctx[m + 1];
+        n_ctx[W - 1] = n_done;
+      }
+    }
+    if (tid < 64) {  // fresh nodes numbered in lane order (deterministic)
+      const unsigned long long fm = __ballot(fresh);
+      if (fresh) {
+        const int id = s_nnodes + __popcll(fm & ((1ull << tid) - 1ull));
+        n_node = id;
+        w.tab_val[tslot] = id;
+        if (id < w.cap) { w.node_par[id] = n_pnode; w.node_tok[id] = n_last; }
+      }
+      if (tid == 0) s_nfresh = __popcll(fm);
+    }
+    __syncthreads();
+    if (tid < ns) {
+      s_pb[slot] = n_pb; s_pnb[slot] = n_pnb; s_lm[slot] = n_lm;
+      s_len[slot] = n_len; s_last[slot] = n_last; s_node[slot] = n_node; s_pnode[slot] = n_pnode; s_tn[slot] = n_tn;
+      for (int m = 0; m < W; ++m) s_ctx[slot][m] = n_ctx[m];
+    }
+    if (tid == 0) { s_nhyp = ns; s_nnodes += s_nfresh; }
+    __threadfence();  // this frame's table entries, before the next frame's L2 reads
+    __syncthreads();
+  }
+
+  // finish: end the pending word, add ln P(</s> | ctx); the nbest best finite hypotheses, sorted, backtracked
+  const int nh = s_nhyp;
+  if (tid < nh) {
+    float s = lae(s_pb[tid], s_pnb[tid]) + s_lm[tid] + a.gamma * (float)s_len[tid];
+    int h[kMaxCtx];
+    for (int m = 0; m < W; ++m) h[m] = s_ctx[tid][m];
+    if (s_tn[tid] > 0) {
+      int wd;
+      s += word_end(a, s_tn[tid], h, wd);
+      if (wd >= 0 && W > 0) {
+        for (int m = 0; m + 1 < W; ++m) h[m] = h[m + 1];
+        h[W - 1] = wd;
+      }
+    }
+    if (s != -INFINITY) {
+      const int Lh = ctx_len(h, W);
+      s += a.alpha * ng_logp(a.lm, h + W - Lh, Lh, a.lm.eos);
+    }
+    s_fin[tid] = L > 0 ? s : -INFINITY;  // an empty utterance returns no hypothesis
+  }
+  __syncthreads();
+  if (tid < 64) {
+    const bool ok = tid < nh && s_fin[tid] != -INFINITY && s_fin[tid] == s_fin[tid];
+    const int nfin = __popcll(__ballot(ok));
+    if (tid == 0) a.nhyp[b] = min(nfin, a.nbest);
+    int rank = a.nbest;
+    if (ok) {
+      const float s = s_fin[tid];
+      rank = 0;
+      for (int m = 0; m < nh; ++m) rank += s_fin[m] > s || (s_fin[m] == s && m < tid);
+    }
+    if (rank < a.nbest) {
+      int* out = a.tokens + ((long)b * a.nbest + rank) * a.T;
+      const int n = s_len[tid];
+      for (int u = n; u < a.T; ++u) out[u] = a.pad;
+      int node = s_node[tid];
+      for (int u = n - 1; u >= 0 && node > 0; --u) { out[u] = ld_l2(w.node_tok + node); node = ld_l2(w.node_par + node); }
+      a.lengths[b * a.nbest + rank] = n;
+      a.scores[b * a.nbest + rank] = s_fin[tid];
+    }
+    for (int r = min(nfin, a.nbest) + tid; r < a.nbest; r += 64) {
+      int* out = a.tokens + ((long)b * a.nbest + r) * a.T;
+      for (int u = 0; u < a.T; ++u) out[u] = a.pad;
+      a.lengths[b * a.nbest + r] = 0;
+      a.scores[b * a.nbest + r] = -INFINITY;
+    }
+  }
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------ C ABI: the n-gram LM
+extern "C" int ea_ngram_create(const char* path, void* handle_host, char* err_host, long err_cap) {
+  auto err = [&](const std::string& m) {
+    if (err_host && err_cap > 0) snprintf(err_host, err_cap, "%s", m.c_str());
+  };
+  *(void**)handle_host = nullptr;
+  FILE* fp = fopen(path, "rb");
+  if (!fp) { err(std::string("cannot open ") + path); return -1; }
+  std::string text;
+  char buf[1 << 16];
+  for (size_t n; (n = fread(buf, 1, sizeof(buf), fp)) > 0;) text.append(buf, n);
+  fclose(fp);
+  auto* lm = new NgramLM();
+  try {
+    arpa_parse(text, *lm);
+  } catch (const ArpaError& e) {
+    err(std::string(path) + ": " + e.msg);
+    delete lm;
+    return -3;
+  }
+  NgramDev& h = lm->host;
+  h.order = lm->order; h.n1 = (int)lm->counts[1]; h.unk = lm->unk; h.bos = lm->bos; h.eos = lm->eos;
+  for (int k = 1; k <= lm->order; ++k) {
+    h.logp[k] = lm->logp[k].data(); h.bow[k] = lm->bow[k].data(); h.word[k] = lm->word[k].data(); h.child[k] = lm->child[k].data();
+  }
+  lm->dev = h;
+  *(void**)handle_host = lm;
+  return 0;
+}
+
+extern "C" int ea_ngram_destroy(void* handle) {
+  auto* lm = (NgramLM*)handle;
+  if (!lm) return 0;
+  if (lm->dev_buf) hipFree(lm->dev_buf);
+  delete lm;
+  return 0;
+}
+
+extern "C" int ea_ngram_info(const void* handle, int* meta_host, long* counts_host) {
+  const auto* lm = (const NgramLM*)handle;
+  if (!lm) return -2;
+  meta_host[0] = lm->order; meta_host[1] = lm->unk; meta_host[2] = lm->bos; meta_host[3] = lm->eos;
+  for (int k = 1; k <= kMaxOrder; ++k) counts_host[k - 1] = lm->counts[k];
+  return 0;
+}
+
+extern "C" long ea_ngram_vocab(const void* handle, char* buf_host, long cap) {
+  const auto* lm = (const NgramLM*)handle;
+  if (!lm) return -2;
+  long need = 0;
+  for (const auto& w : lm->vocab) need += (long)w.size() + 1;
+  if (buf_host && cap >= need) {
+    char* o = buf_host;
+    for (const auto& w : lm->vocab) { memcpy(o, w.data(), w.size()); o += w.size(); *o++ = '\n'; }
+  }
+  return need;
+}
+
+extern "C" long ea_ngram_records(const void* handle, int order, int* ngrams_host, float* logp_host, float* bow_host) {
+  const auto* lm = (const NgramLM*)handle;
+  if (!lm || order < 1 || order > lm->order) return -2;
+  const long n = lm->counts[order];
+  for (long i = 0; i < n; ++i) {
+    int r = (int)i;
+    for (int k = order; k >= 1; --k) {
+      ngrams_host[i * order + k - 1] = k == 1 ? r : lm->word[k][r];
+      if (k > 1) r = lm->parent[k][r];
+    }
+    logp_host[i] = lm->logp[order][i];
+    bow_host[i] = lm->bow[order][i];
+  }
+  return n;
+}
+
+extern "C" int ea_ngram_upload(void* handle) {
+  auto* lm = (NgramLM*)handle;
+  if (!lm) return -2;
+  if (lm->dev_buf) return 0;
+  std::vector<std::pair<const void*, size_t>> parts;
+  for (int k = 1; k <= lm->order; ++k) {
+    parts.emplace_back(lm->logp[k].data(), lm->logp[k].size() * 4);
+    parts.emplace_back(lm->bow[k].data(), lm->bow[k].size() * 4);
+    parts.emplace_back(lm->word[k].data(), lm->word[k].size() * 4);
+    parts.emplace_back(lm->child[k].data(), lm->child[k].size() * 4);
+  }
+  size_t total = 0;
+  for (auto& q : parts) total += (q.second + 255) & ~(size_t)255;
+  char* base = nullptr;
+  if (hipMalloc(&base, total ? total : 256) != hipSuccess) return -1;
+  size_t off = 0;
+  std::vector<char*> at;
+  for (auto& q : parts) {
+    at.push_back(base + off);
+    if (q.second && hipMemcpy(base + off, q.first, q.second, hipMemcpyHostToDevice) != hipSuccess) { hipFree(base); return -1; }
+    off += (q.second + 255) & ~(size_t)255;
+  }
+  for (int k = 1; k <= lm->order; ++k) {
+    lm->dev.logp[k] = (const float*)at[4 * (k - 1)];
+    lm->dev.bow[k] = (const float*)at[4 * (k - 1) + 1];
+    lm->dev.word[k] = (const int*)at[4 * (k - 1) + 2];
+    lm->dev.child[k] = (const int*)at[4 * (k - 1) + 3];
+  }
+  lm->dev_buf = base;
+  return 0;
+}
+
+extern "C" int ea_ngram_score_host(const void* handle, const int* ctx_host, const int* words_host, int N, float* out_host) {
+  const auto* lm = (const NgramLM*)handle;
+  if (!lm || N < 0) return -2;
+  const int W = lm->order - 1;
+  for (int i = 0; i < N; ++i) {
+    const int* h = ctx_host + (long)i * W;
+    const int L = ctx_len(h, W);
+    out_host[i] = ng_logp(lm->host, h + W - L, L, words_host[i]);
+  }
+  return 0;
+}
+
+extern "C" int ea_ngram_score(const void* handle, const int* ctx, const int* words, int N, float* out, ea_stream_t stream) {
+  const auto* lm = (const NgramLM*)handle;
+  if (!lm || !lm->dev_buf || N < 0) return -2;
+  if (N == 0) return 0;
+  hipLaunchKernelGGL(ngram_score_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, lm->dev, ctx, words, N, out);
+  return EA_CHECK_LAUNCH();
+}
+
+// ------------------------------------------------------------------------------------------------ C ABI: the search
+extern "C" long ea_ctc_lexicon_beam_workspace_bytes(int B, int T, int beam) {
+  if (B <= 0 || T < 0 || beam < 1 || beam > kLexMaxBeam) return 0;
+  return (long)B * lex_ws_words(T, beam) * 4L;
+}
+
+extern "C" int ea_ctc_lexicon_beam_search(const void* x, long ld, int x_bf16, const int* in_len, void* workspace, const void* ngram,
+                                          const int* trie_off, const int* trie_tok, const int* trie_child, const int* trie_word,
+                                          const float* trie_smear, const void* word_start, int space, int B, int T, int V, int beam,
+                                          int K, int blank, float lm_weight, float word_score, float ins_bonus, int nbest, int pad,
+                                          int* tokens, int* lengths, float* scores, int* nhyp, ea_stream_t stream) {
+  const auto* lm = (const NgramLM*)ngram;
+  if (!lm || !lm->dev_buf) return -2;
+  if (B <= 0) return 0;
+  if (T < 0 || V < 2 || V > 65535 || ld < V || beam < 1 || beam > kLexMaxBeam || K < 1 || K > kLexMaxK || K > V - 1 || blank < 0 ||
+      blank >= V || nbest < 1 || nbest > beam || space >= V || (space < 0 && !word_start) || lm->order < 1 ||
+      lm->order > kMaxOrder || !trie_off || !trie_word || !trie_smear)
+    return -2;
+  LexArgs a;
+  a.x = x; a.ld = ld; a.in_len = in_len; a.ws = workspace;
+  a.lm = lm->dev;
+  a.lex.off = trie_off; a.lex.tok = trie_tok; a.lex.child = trie_child; a.lex.word = trie_word; a.lex.smear = trie_smear;
+  a.lex.word_start = space >= 0 ? nullptr : (const uint8_t*)word_start;
+  a.lex.space = space;
+  a.T = T; a.V = V; a.beam = beam; a.K = K; a.blank = blank; a.nbest = nbest; a.pad = pad; a.W = lm->order - 1;
+  a.alpha = lm_weight; a.beta = word_score; a.gamma = ins_bonus;
+  a.tokens = tokens; a.lengths = lengths; a.scores = scores; a.nhyp = nhyp;
+  if (x_bf16)
+    hipLaunchKernelGGL(ctc_lexicon_beam_kernel<bf16_t>, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(ctc_lexicon_beam_kernel<float>, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+  return EA_CHECK_LAUNCH();
+}

@@ -640,6 +640,46 @@ def rnnt_lattice(ws, B, T, U1):
     return _lattice_views(ws, lib.ea_rnnt_lattice_offset(B, T, U1, 0), lib.ea_rnnt_lattice_offset(B, T, U1, 1), B, T, U1)
 
 
+def ngram_score(handle, ctx, words):
+    """ln P(words[i] | ctx[i]) fp32 [N] from an uploaded n-gram handle (ea_ngram_score): ctx int32 [N][order - 1] oldest
+    first, front-padded with -1; words int32 [N]."""
+    N = words.numel()
+    assert words.dtype == ctx.dtype == torch.int32 and ctx.is_contiguous() and words.is_contiguous() and ctx.shape[0] == N
+    out = torch.empty(N, dtype=torch.float32, device=words.device)
+    check(_lib.lib().ea_ngram_score(handle, _p(ctx) if ctx.numel() else None, _p(words), N, _p(out), _stream()), "ea_ngram_score")
+    return out
+
+
+def ctc_lexicon_beam_workspace(B, T, beam, device):
+    """Workspace of the lexicon beam search (ea_ctc_lexicon_beam_workspace_bytes): the prefix tables of B utterances."""
+    return torch.empty(int(_lib.lib().ea_ctc_lexicon_beam_workspace_bytes(B, T, beam)), dtype=torch.uint8, device=device)
+
+
+def ctc_lexicon_beam_search(x, in_len, ws, ngram, trie, word_start, space, B, T, V, beam, K, blank, nbest, pad, lm_weight,
+                            word_score, ins_bonus, ld=None):
+    """The whole lexicon-constrained CTC prefix beam search with n-gram fusion over x [B*T][V] fp32/bf16 log-probs
+    (batch-major), one call.  trie = (off, tok, child, word int32, smear fp32) device tensors; word_start uint8 [V] (space
+    mode: None).  Returns (tokens int32 [B][nbest][T] pad-filled, lengths int32 [B][nbest], scores fp32 [B][nbest], nhyp
+    int32 [B]), best first."""
+    ld = x.stride(0) if ld is None else ld
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.stride(-1) == 1 and x.shape[0] == B * T and x.shape[1] == V
+    assert in_len.dtype == torch.int32 and in_len.numel() == B
+    assert ws.numel() >= _lib.lib().ea_ctc_lexicon_beam_workspace_bytes(B, T, beam)
+    off, tok, child, word, smear = trie
+    assert off.dtype == tok.dtype == child.dtype == word.dtype == torch.int32 and smear.dtype == torch.float32
+    assert word_start is None or (word_start.dtype == torch.uint8 and word_start.numel() == V)
+    dev = x.device
+    tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
+    lengths = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
+    nhyp = torch.empty(B, dtype=torch.int32, device=dev)
+    check(_lib.lib().ea_ctc_lexicon_beam_search(_p(x), ld, int(x.dtype == torch.bfloat16), _p(in_len), _p(ws), ngram, _p(off),
+                                                _p(tok), _p(child), _p(word), _p(smear), _p(word_start), space, B, T, V, beam, K,
+                                                blank, lm_weight, word_score, ins_bonus, nbest, pad, _p(tokens), _p(lengths),
+                                                _p(scores), _p(nhyp), _stream()), "ea_ctc_lexicon_beam_search")
+    return tokens, lengths, scores, nhyp
+
+
 def embedding_fwd(tokens, positions, W, pos_table, scale):
     M, C = tokens.numel(), W.shape[1]
     out = torch.empty(M, C, dtype=torch.bfloat16, device=W.device)

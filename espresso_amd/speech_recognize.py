@@ -1,6 +1,6 @@
 """Batched recognition CLI — the decoding loop and output format of espresso/speech_recognize.py:60-360 on the HIP path:
 for every batch run the chosen search (beam search with optional LM / look-ahead word-LM / multi-level LM fusion, CTC greedy,
-CTC prefix beam search with optional LM fusion, transducer greedy / beam), print `T-<utt>` (reference) and `H-<utt>`
+CTC prefix beam search with optional LSTM-LM or lexicon + n-gram LM fusion, transducer greedy / beam), print `T-<utt>` (reference) and `H-<utt>`
 (hypothesis, score in base 2) lines, accumulate WER / CER with `tools.wer.Scorer`, and close with the "Recognized N utterances
 ..." summary.
 
@@ -138,15 +138,21 @@ def collate(ids: List[int], utt_ids: List[str], waves: List[np.ndarray], device)
             "wav_offsets": torch.from_numpy(offs).to(device), "num_samples": lens, "net_input": {}}
 
 
-def build_generator(args, model, dictionary, lm=None):
+def build_generator(args, model, dictionary, lm=None, ngram=None):
+    """ngram: (NGramLanguageModel, LexiconTrie) for --search ctc_beam --ngram-lm."""
     from .sequence_generator import SequenceGenerator
     from .tools.ctc_decoder import CTCDecoder
+    from .tools.ctc_lexicon_beam_search import CTCLexiconBeamSearchDecoder
     from .tools.ctc_prefix_beam_search import CTCPrefixBeamSearchDecoder
     from .tools.transducer_beam_search_decoder import TransducerBeamSearchDecoder
     from .tools.transducer_greedy_decoder import TransducerGreedyDecoder
 
     if args.search == "ctc":
         return CTCDecoder([model], dictionary)
+    if args.search == "ctc_beam" and ngram is not None:
+        return CTCLexiconBeamSearchDecoder([model], dictionary, *ngram, beam_size=args.beam, nbest=args.nbest,
+                                           beam_size_token=args.ctc_beam_size_token, lm_weight=args.lm_weight,
+                                           word_score=args.word_score, insertion_bonus=args.ctc_insertion_bonus)
     if args.search == "ctc_beam":
         return CTCPrefixBeamSearchDecoder([model], dictionary, beam_size=args.beam, nbest=args.nbest,
                                           beam_size_token=args.ctc_beam_size_token, lm_model=lm, lm_weight=args.lm_weight,
@@ -200,6 +206,12 @@ def get_parser():
     p.add_argument("--ctc-beam-size-token", type=int, default=None,
                    help="ctc_beam: candidate tokens per frame (default: min(--beam, vocabulary size - 1), at most 64)")
     p.add_argument("--ctc-insertion-bonus", type=float, default=0.0, help="ctc_beam: score added per emitted token")
+    p.add_argument("--ngram-lm", default=None,
+                   help="ctc_beam: word n-gram LM (plain-text ARPA) fused with --lm-weight under a closed-vocabulary lexicon")
+    p.add_argument("--lexicon", default=None,
+                   help="ctc_beam --ngram-lm: `word tok1 tok2 ...` lines (default with a <space> dictionary: the ARPA words spelled "
+                        "by characters)")
+    p.add_argument("--word-score", type=float, default=-1.0, help="ctc_beam --ngram-lm: score added per completed word")
     p.add_argument("--max-num-expansions-per-step", type=int, default=2)
     p.add_argument("--expansion-beta", type=int, default=0)
     p.add_argument("--expansion-gamma", type=float, default=None)
@@ -220,6 +232,21 @@ def get_parser():
     p.add_argument("--wer-output-filter", default=None, help="sed-style word filter applied before WER scoring")
     p.add_argument("--non-lang-syms", default=None, help="non-language symbols (one per line), ignored by WER / CER scoring")
     return p
+
+
+def check_ngram_args(args):
+    """--ngram-lm is the lexicon + n-gram fusion of --search ctc_beam alone: refused, before anything is loaded, with other
+    searches, with an LSTM LM (--lm-path / --word-dict) and with ensembles."""
+    if not args.ngram_lm:
+        if args.lexicon:
+            raise ValueError("--lexicon constrains the n-gram fusion of --search ctc_beam: give --ngram-lm too")
+        return
+    if args.search != "ctc_beam":
+        raise NotImplementedError("--ngram-lm (lexicon + n-gram LM fusion) is implemented for --search ctc_beam only")
+    if args.lm_path or args.word_dict:
+        raise NotImplementedError("--ngram-lm fuses the n-gram LM alone: no --lm-path or --word-dict with it")
+    if len(args.path.split(os.pathsep)) > 1:
+        raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
 
 
 def lm_fusion_mode(args):
@@ -301,6 +328,7 @@ def main(argv=None):
     args = get_parser().parse_args(argv)
     if args.print_alignment is not None and not args.results_path:
         raise ValueError("--print-alignment saves attention plots under --results-path: give --results-path")
+    check_ngram_args(args)
     lm_mode = lm_fusion_mode(args)
     if args.search == "ctc_beam" and len(args.path.split(os.pathsep)) > 1:
         raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
@@ -326,6 +354,14 @@ def main(argv=None):
     task = SpeechRecognitionEspressoTask.setup_task(SpeechRecognitionEspressoConfig(
         dict=args.dict, autoregressive=autoregressive, global_cmvn_stats_path=args.global_cmvn_stats_path, criterion_name=crit,
         non_lang_syms=args.non_lang_syms, wer_output_filter=args.wer_output_filter))
+    ngram = None
+    if args.ngram_lm:  # before the model: a malformed ARPA or lexicon file fails fast
+        from .models.ngram_lm import NGramLanguageModel
+        from .tools.lexicon import build_lexicon
+
+        ngram_lm = NGramLanguageModel(args.ngram_lm)
+        ngram = (ngram_lm, build_lexicon(task.target_dictionary, ngram_lm, args.lexicon))
+        ngram_lm.to(dev)
     model = load_member(state, model_name, model_cfg, task, dev)
     members = [model]
     for extra in paths[1:]:  # every member is rebuilt from ITS OWN checkpoint's configuration (checkpoint_utils.load_model_ensemble)
@@ -354,7 +390,7 @@ def main(argv=None):
             if args.word_dict:
                 lm = TensorizedLookaheadLanguageModel(lm, task.target_dictionary, oov_penalty=args.oov_penalty,
                                                       open_vocab=not args.disable_open_vocab)
-    gen = build_generator(args, members if len(members) > 1 else model, task.target_dictionary, lm)
+    gen = build_generator(args, members if len(members) > 1 else model, task.target_dictionary, lm, ngram)
     scp = read_scp(args.wav_scp)
     utt_ids = list(scp.keys())
     waves = [read_wav(scp[u]) for u in utt_ids]

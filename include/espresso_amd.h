@@ -432,6 +432,47 @@ int ea_ctc_prefix_beam_step(const void* x, long ld, int x_bf16, const int* in_le
 int ea_ctc_prefix_beam_finish(void* workspace, const float* lm_rows, long ld_lm, float lm_weight, float ins_bonus, int eos,
                               int B, int T, int beam, int nbest, int pad, int* tokens, int* lengths, float* scores, int* nhyp,
                               ea_stream_t stream);
+/* Word n-gram LM (ARPA) and lexicon-constrained CTC prefix beam search with its fusion (csrc/ctc_lexicon_beam.hip) — the
+ * search the reference takes from Flashlight's KenLM lexicon decoder (espresso/tools/ctc_decoder.py:24-71).
+ * ea_ngram_create: parses a plain-text ARPA file of order <= 6 at `path` into host tables and writes an opaque handle to
+ *   *(void**)handle_host; 0 = success, -1 = the file cannot be read, -3 = malformed (err_host, err_cap bytes, then names the
+ *   line).  Log10 values become natural logs.  Word ids are the unigrams in file order (ea_ngram_vocab: the words, each
+ *   followed by '\n'; returns the bytes needed and writes them when cap suffices).  ea_ngram_info: meta_host int[4] =
+ *   order, <unk>, <s>, </s> ids (-1 where absent; <s> and </s> are required), counts_host long[6] = n-grams per order.
+ *   ea_ngram_records: the records of one order, in table order: ngrams_host int [count][order] word ids, logp_host and
+ *   bow_host fp32 [count].  ea_ngram_upload copies the tables to the current device once (later calls return 0); the
+ *   `ngram` / `handle` arguments below are such handles (not device pointers).  ea_ngram_destroy frees both copies.
+ * ea_ngram_score: out fp32 [N] = ln P(words[i] | ctx[i]) with ARPA backoff; ctx int32 [N][order - 1] oldest first,
+ *   front-padded with -1 (<s> is an ordinary context word); a word outside the vocabulary scores as <unk> (-inf without).
+ *   ea_ngram_score_host: the same on the host tables and host arrays (no device needed).
+ * ea_ctc_lexicon_beam_search: the prefix beam search of ea_ctc_prefix_beam_step (K best non-blank tokens per frame, stay and
+ *   extend, merging of equal token sequences, the same tie rules) with a closed-vocabulary lexicon and n-gram fusion, the
+ *   whole batch in one launch (one workgroup per utterance).  Score of a hypothesis with completed words w_1..w_m and a
+ *   partial word p:  log(p_b + p_nb) + lm_weight * (L(y) + S(p)) + word_score * m + ins_bonus * |y|,  L(y) = sum of
+ *   ln P(w_i | history) with <s> as the start, S(p) = the trie node's smear (max unigram ln P below it, 0 at the root); the
+ *   final score completes the pending word and adds lm_weight * ln P(</s> | history).  Leaving the trie, ending a word on a
+ *   node that is no word, an empty word and a pending non-word at the end score -inf.  Lexicon trie in CSR form (device,
+ *   node 0 = root): children of node n are trie_tok / trie_child [trie_off[n] .. trie_off[n + 1]) with trie_tok ascending;
+ *   trie_word int32 [nodes] = LM word id ending at the node or -1; trie_smear fp32 [nodes].  A word ends on token `space`
+ *   (space mode, space >= 0) or, with space < 0, before every token v with word_start uint8 [V] set.  x: fp32 or bf16
+ *   [B][T][ld] log-probs; beam <= 64, K <= min(64, V - 1), V <= 65535, nbest <= beam.  workspace:
+ *   ea_ctc_lexicon_beam_workspace_bytes(B, T, beam) bytes, any contents.  Outputs as ea_ctc_prefix_beam_finish: tokens
+ *   int32 [B][nbest][T], lengths, scores (natural log), nhyp = the number of finite hypotheses returned (0 for an empty
+ *   utterance or when none is finite). */
+int ea_ngram_create(const char* path, void* handle_host, char* err_host, long err_cap);
+int ea_ngram_destroy(void* handle);
+int ea_ngram_info(const void* handle, int* meta_host, long* counts_host);
+long ea_ngram_vocab(const void* handle, char* buf_host, long cap);
+long ea_ngram_records(const void* handle, int order, int* ngrams_host, float* logp_host, float* bow_host);
+int ea_ngram_upload(void* handle);
+int ea_ngram_score_host(const void* handle, const int* ctx_host, const int* words_host, int N, float* out_host);
+int ea_ngram_score(const void* handle, const int* ctx, const int* words, int N, float* out, ea_stream_t stream);
+long ea_ctc_lexicon_beam_workspace_bytes(int B, int T, int beam);
+int ea_ctc_lexicon_beam_search(const void* x, long ld, int x_bf16, const int* in_len, void* workspace, const void* ngram,
+                               const int* trie_off, const int* trie_tok, const int* trie_child, const int* trie_word,
+                               const float* trie_smear, const void* word_start, int space, int B, int T, int V, int beam, int K,
+                               int blank, float lm_weight, float word_score, float ins_bonus, int nbest, int pad, int* tokens,
+                               int* lengths, float* scores, int* nhyp, ea_stream_t stream);
 /* Label-smoothed CE — espresso/criterions/label_smoothed_cross_entropy_v2.py:49-119.  smoothing 0 = uniform, 1 = unigram
  * (prior fp32 [V], sums to one), 2 = temporal (neighbouring targets of the same sentence, weights 2:5:5:2; rows are
  * b*tgt_len + u).  out_loss[0] += sum loss, out_loss[1] += sum nll (pad rows skipped). */
