@@ -937,3 +937,40 @@ def joint_reduce(dZ, B, T, U1, out_f32=False):
     fn = _lib.lib().ea_joint_reduce_f32 if out_f32 else _lib.lib().ea_joint_reduce
     check(fn(_p(dZ), _p(dE), _p(dD), B, T, U1, J, _stream()), "ea_joint_reduce")
     return dE, dD
+
+
+def stream_attention_supported(dh, chunk_size, left_chunks, C) -> bool:
+    return bool(_lib.lib().ea_stream_attention_supported(dh, chunk_size, left_chunks, C))
+
+
+def stream_kv_append(kv, ldkv, cache, meta, frames, B, C, chunk_size, left_chunks, total_rows):
+    """cache bf16 [max_streams][(L+1)*cs][2C] <- rows of kv (k, v adjacent); meta int32 [3][B] = (slot_idx, n_new, row_off)."""
+    assert meta.dtype == torch.int32 and meta.shape == (3, B) and meta.is_contiguous() and frames.dtype == torch.int32
+    max_streams = cache.shape[0]
+    assert cache.dtype == torch.bfloat16 and cache.is_contiguous() and cache.shape[1:] == ((left_chunks + 1) * chunk_size, 2 * C)
+    check(_lib.lib().ea_stream_kv_append(_p(kv), ldkv, _p(cache), _p(meta[0]), _p(meta[1]), _p(meta[2]), _p(frames), B, C,
+                                         chunk_size, left_chunks, max_streams, total_rows, _stream()), "ea_stream_kv_append")
+
+
+def stream_attention(qu, qv, cache, pp, pp_center, meta, frames, B, H, dh, chunk_size, left_chunks, out=None):
+    """Chunk attention over the ring cache (include/espresso_amd.h).  qu / qv bf16 [rows][C]; pp bf16 [R][C] or None."""
+    rows, C = qu.shape
+    assert C == H * dh and qu.dtype == torch.bfloat16 and qu.is_contiguous()
+    assert meta.dtype == torch.int32 and meta.shape == (3, B) and meta.is_contiguous() and frames.dtype == torch.int32
+    max_streams = cache.shape[0]
+    assert cache.dtype == torch.bfloat16 and cache.is_contiguous() and cache.shape[1:] == ((left_chunks + 1) * chunk_size, 2 * C)
+    assert frames.numel() >= max_streams
+    if pp is not None:
+        assert pp.dtype == torch.bfloat16 and pp.stride(1) == 1 and qv is not None and qv.shape == qu.shape and qv.is_contiguous()
+    if out is None:
+        out = torch.empty(rows, C, dtype=torch.bfloat16, device=qu.device)
+    check(_lib.lib().ea_stream_attention(_p(qu), _p(qv) if pp is not None else None, C, _p(cache), _p(pp),
+                                         pp.stride(0) if pp is not None else 0, pp_center, pp.shape[0] if pp is not None else 0,
+                                         _p(meta[0]), _p(meta[1]), _p(meta[2]), _p(frames), _p(out), out.stride(0), B, H, dh,
+                                         chunk_size, left_chunks, max_streams, rows, _stream()), "ea_stream_attention")
+    return out
+
+
+def stream_advance(frames, meta, B, chunk_size):
+    check(_lib.lib().ea_stream_advance(_p(frames), _p(meta[0]), _p(meta[1]), B, chunk_size, frames.numel(), _stream()),
+          "ea_stream_advance")

@@ -229,6 +229,12 @@ def get_parser():
     p.add_argument("--print-alignment", nargs="?", const="hard", default=None, choices=["hard", "soft"],
                    help="collect the attention alignments; --search beam saves RESULTS_PATH/attn_plots/<utt>.pdf of the best "
                         "hypothesis (needs --results-path and matplotlib)")
+    p.add_argument("--streaming", action="store_true",
+                   help="chunk-by-chunk recognition of a chunk-streaming transformer encoder (--search ctc or transducer_greedy): audio is "
+                        "fed in "
+                        "pieces of --stream-chunk-ms with --streams utterances in flight")
+    p.add_argument("--stream-chunk-ms", type=int, default=None, help="--streaming: audio per piece (default 400)")
+    p.add_argument("--streams", type=int, default=None, help="--streaming: concurrent utterances (default 16)")
     p.add_argument("--wer-output-filter", default=None, help="sed-style word filter applied before WER scoring")
     p.add_argument("--non-lang-syms", default=None, help="non-language symbols (one per line), ignored by WER / CER scoring")
     return p
@@ -247,6 +253,100 @@ def check_ngram_args(args):
         raise NotImplementedError("--ngram-lm fuses the n-gram LM alone: no --lm-path or --word-dict with it")
     if len(args.path.split(os.pathsep)) > 1:
         raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
+
+
+def check_streaming_args(args):
+    """--streaming is greedy decoding (CTC or transducer) of one chunk-streaming model: refused, before anything is loaded, with
+    every other search, with LM fusion, ensembles and alignment output."""
+    if not args.streaming:
+        for opt, v in (("--stream-chunk-ms", args.stream_chunk_ms), ("--streams", args.streams)):
+            if v is not None:
+                raise ValueError(f"{opt} configures --streaming: give --streaming too")
+        return
+    if args.search not in ("ctc", "transducer_greedy"):
+        raise NotImplementedError("--streaming is implemented for greedy decoding (--search ctc, --search transducer_greedy), "
+                                  f"not --search {args.search}")
+    for opt, v in (("--lm-path", args.lm_path), ("--word-dict", args.word_dict), ("--ngram-lm", args.ngram_lm),
+                   ("--print-alignment", args.print_alignment)):
+        if v:
+            raise NotImplementedError(f"--streaming decodes greedily without LM fusion or alignments: no {opt} with it")
+    if len(args.path.split(os.pathsep)) > 1:
+        raise NotImplementedError("--streaming takes one model: ensembles (--path a.pt:b.pt) are not streamed")
+    if (args.stream_chunk_ms is not None and args.stream_chunk_ms <= 0) or (args.streams is not None and args.streams <= 0):
+        raise ValueError("--stream-chunk-ms and --streams must be positive")
+
+
+def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=400, streams=16, refs=None, out=sys.stdout,
+                        quiet=False, scorer=None, summary_out=None, search="ctc", max_num_expansions_per_step=2):
+    """The output of `recognize` from a streamed pass: every utterance is read in pieces of `chunk_ms`, `streams` of them in
+    flight; a finished utterance frees its slot for the next one (wav.scp order)."""
+    from .models.transformer.streaming_encoder import StreamingEncoder
+    from .tools.streaming_ctc_decoder import StreamingCTCDecoder
+    from .tools.streaming_transducer_greedy_decoder import StreamingTransducerGreedyDecoder
+    from .tools.wer import Scorer
+
+    if scorer is None:
+        scorer = Scorer(dictionary, wer_output_filter=None)
+    se = StreamingEncoder(model, streams, frontend=task.frontend)
+    if search == "ctc":
+        dec = StreamingCTCDecoder(dictionary)
+        strip = {dictionary.eos(), dictionary.pad()}
+    else:
+        dec = StreamingTransducerGreedyDecoder(model, dictionary, max_num_expansions_per_step=max_num_expansions_per_step)
+        strip = dec.symbols_to_strip_from_output
+    piece = max(1, int(16000 * chunk_ms / 1000))
+    pending = list(range(len(utt_ids)))
+    live = {}  # utterance index -> samples consumed
+    hyps = {}
+    num_tok, audio_s = 0, 0.0
+    t0 = time.perf_counter()
+    while pending or live:
+        while pending and len(live) < streams:
+            i = pending.pop(0)
+            live[i] = 0
+            se.open([i])
+            dec.open([i])
+        ids = list(live)
+        pieces, final = [], []
+        for i in ids:
+            a = live[i]
+            b = min(len(waves[i]), a + piece)
+            pieces.append(torch.from_numpy(np.ascontiguousarray(waves[i][a:b])).float())
+            live[i] = b
+            final.append(b >= len(waves[i]))
+        logits, counts = se.accept_waveform(ids, pieces, final)
+        if logits is not None:
+            dec.accept(ids, logits, counts)
+        for i, f in zip(ids, final):
+            if f:
+                se.close([i])
+                hyps[i] = dec.close(i)
+                del live[i]
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    t_gen = time.perf_counter() - t0
+    for i, utt in enumerate(utt_ids):
+        hypo = hyps[i]
+        if refs is not None and utt in refs and not quiet:
+            print("T-{}\t{}".format(utt, refs[utt]), file=out)
+        hypo_str = dictionary.string(torch.tensor([t for t in hypo["tokens"].tolist() if t not in strip]), bpe_symbol=None)
+        if not quiet:
+            print("H-{}\t{}\t{}".format(utt, hypo_str, float(hypo["score"]) / math.log(2)), file=out)
+        scorer.add_prediction(utt, hypo_str)
+        if refs is not None and utt in refs:
+            scorer.add_evaluation(utt, refs[utt], hypo_str)
+        num_tok += len(hypo["tokens"])
+        audio_s += len(waves[i]) / 16000.0
+    n = len(utt_ids)
+    lines = ["NOTE: hypothesis and token scores are output in base 2",
+             "Recognized {:,} utterances ({} tokens) in {:.1f}s ({:.2f} sentences/s, {:.2f} tokens/s), RTF {:.4f}".format(
+                 n, num_tok, t_gen, n / max(t_gen, 1e-9), num_tok / max(t_gen, 1e-9), t_gen / max(audio_s, 1e-9))]
+    if refs:
+        lines += scorer.summary_lines()
+    for f in [out] + ([summary_out] if summary_out is not None else []):
+        for line in lines:
+            print(line, file=f)
+    return scorer
 
 
 def lm_fusion_mode(args):
@@ -329,6 +429,7 @@ def main(argv=None):
     if args.print_alignment is not None and not args.results_path:
         raise ValueError("--print-alignment saves attention plots under --results-path: give --results-path")
     check_ngram_args(args)
+    check_streaming_args(args)
     lm_mode = lm_fusion_mode(args)
     if args.search == "ctc_beam" and len(args.path.split(os.pathsep)) > 1:
         raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
@@ -362,6 +463,15 @@ def main(argv=None):
         ngram_lm = NGramLanguageModel(args.ngram_lm)
         ngram = (ngram_lm, build_lexicon(task.target_dictionary, ngram_lm, args.lexicon))
         ngram_lm.to(dev)
+    if args.streaming:  # the encoder options streaming cannot reproduce exactly: refused before the model is built or audio is read
+        from . import registry
+        from .models.transformer.streaming_encoder import check_streamable
+
+        cfg_cls = getattr(registry.MODEL_REGISTRY[model_name], "config_class", None)
+        cfg0 = cfg_cls.from_dict(model_cfg) if cfg_cls is not None else None
+        if cfg0 is None or not hasattr(cfg0, "encoder") or not hasattr(cfg0.encoder, "chunk_size"):
+            raise NotImplementedError(f"--streaming needs a chunk-streaming transformer encoder model, not {model_name}")
+        check_streamable(cfg0)
     model = load_member(state, model_name, model_cfg, task, dev)
     members = [model]
     for extra in paths[1:]:  # every member is rebuilt from ITS OWN checkpoint's configuration (checkpoint_utils.load_model_ensemble)
@@ -404,6 +514,23 @@ def main(argv=None):
 
     scorer = Scorer(task.target_dictionary, wer_output_filter=args.wer_output_filter)
     stream = (collate(b, utt_ids, waves, dev) for b in batches)
+    if args.streaming:
+        mine = [i for b in batches for i in b]
+        mine.sort()
+        s_ids, s_waves = [utt_ids[i] for i in mine], [waves[i] for i in mine]
+        kw = dict(chunk_ms=args.stream_chunk_ms or 400, streams=args.streams or 16, refs=refs, quiet=args.quiet, scorer=scorer,
+                  search=args.search, max_num_expansions_per_step=args.max_num_expansions_per_step)
+        if not args.results_path:
+            recognize_streaming(task, model, task.target_dictionary, s_ids, s_waves, dev, out=sys.stdout, **kw)
+            return scorer
+        os.makedirs(args.results_path, exist_ok=True)
+        with open(os.path.join(args.results_path, "decode.log"), "w", buffering=1, encoding="utf-8") as log:
+            recognize_streaming(task, model, task.target_dictionary, s_ids, s_waves, dev, out=log, summary_out=sys.stdout, **kw)
+        has_target = refs is not None and all(u in refs for u in s_ids)
+        if has_target:
+            scorer.add_ordered_utt_list(s_ids)
+        write_results(args.results_path, scorer, has_target)
+        return scorer
     if not args.results_path:
         recognize(task, model, gen, stream, task.target_dictionary, refs, out=sys.stdout, nbest=args.nbest, quiet=args.quiet,
                   scorer=scorer)

@@ -898,6 +898,37 @@ int ea_joint_reduce(const void* dZ, void* dE, void* dD, int B, int T, int U1, in
 int ea_joint_add_relu_f32(const float* E, const float* D, void* Z, int B, int T, int U1, int J, ea_stream_t stream);
 int ea_joint_reduce_f32(const void* dZ, float* dE, float* dD, int B, int T, int U1, int J, ea_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Chunk-streaming encoder attention (csrc/stream_attention.hip): incremental inference of encoders trained with
+ * `encoder.chunk_size = cs > 0`, `chunk_left_window = L`, `chunk_right_window = 0` — the visibility of
+ * espresso/tools/utils.py chunk_streaming_mask(always_partial_in_last=True), one chunk at a time for many streams.
+ *   cache   : one layer's ring, bf16 [max_streams][W][2C], W = (L+1)*cs slots, K in columns [0,C), V in [C,2C); chunk c of a
+ *             stream occupies slots (c % (L+1))*cs .. +cs.
+ *   frames  : int [max_streams], device: frames appended to a stream before the chunk in flight (a multiple of cs; the
+ *             host never reads it).  The chunk index, the validity of every slot and its absolute position follow from it.
+ *   slot_idx, n_new, row_off : int [B]: batch entry b is stream slot_idx[b] with n_new[b] <= cs new rows at rows
+ *             row_off[b] .. of the packed [total_rows][*] activations.  n_new[b] == 0: idle, nothing read or written.
+ *             Entries with out-of-range values are skipped.
+ * ea_stream_kv_append : ring <- the 2C contiguous bf16 (k, v) of rows row_off[b]+i of `kv` (ldkv elements per row).
+ * ea_stream_attention : out[row_off[b]+i][h*dh+d] = softmax_j(qu_i . k_j + qv_i . pp[pp_center + pos_j - pos_i]) v_j over the
+ *             valid slots j (previous <= L chunks + the n_new[b] rows of the current one; append first).  qu / qv bf16
+ *             [total_rows][ldq] from ea_relpos_q_prep (pre-scaled); pp bf16 [pp_rows][ldpp] projected relative table, row
+ *             pp_center <-> distance 0, rows pp_center-(W-1) .. pp_center+cs-1 are read; pp == NULL: plain attention (qv
+ *             ignored).  fp32 softmax; P is normalised, then rounded to bf16 before P.V (ea_relpos_softmax_fwd's rounding).
+ * ea_stream_advance   : frames[slot_idx[b]] += n_new[b], once per chunk after the last layer.
+ * ea_stream_attention_supported: dh in {16, 32, 64}, cs <= 128, (L+1)*cs <= 512, C % dh == 0, C % 8 == 0; the launchers
+ *             return -2 otherwise. */
+int ea_stream_attention_supported(int dh, int chunk_size, int left_chunks, int C);
+int ea_stream_kv_append(const void* kv, long ldkv, void* cache, const int* slot_idx, const int* n_new, const int* row_off,
+                        const int* frames, int B, int C, int chunk_size, int left_chunks, int max_streams, int total_rows,
+                        ea_stream_t stream);
+int ea_stream_attention(const void* qu, const void* qv, long ldq, const void* cache, const void* pp, long ldpp, int pp_center,
+                        int pp_rows, const int* slot_idx, const int* n_new, const int* row_off, const int* frames, void* out,
+                        long ldo, int B, int H, int dh, int chunk_size, int left_chunks, int max_streams, int total_rows,
+                        ea_stream_t stream);
+int ea_stream_advance(int* frames, const int* slot_idx, const int* n_new, int B, int chunk_size, int max_streams,
+                      ea_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
