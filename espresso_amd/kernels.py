@@ -680,6 +680,79 @@ def ctc_lexicon_beam_search(x, in_len, ws, ngram, trie, word_start, space, B, T,
     return tokens, lengths, scores, nhyp
 
 
+def ctc_lexicon_stream_state(max_streams, max_frames, beam, device):
+    """(state uint8 [max_streams][bytes per slot], zero-filled; bytes per slot) of the streamed lexicon beam search
+    (ea_ctc_lexicon_stream_state_bytes)."""
+    nbytes = int(_lib.lib().ea_ctc_lexicon_stream_state_bytes(max_frames, beam))
+    assert nbytes > 0 and max_streams >= 1
+    return torch.zeros(max_streams, nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def _check_stream_state(state, max_frames, beam):
+    assert state.dtype == torch.uint8 and state.is_contiguous() and state.dim() == 2
+    assert state.shape[1] == _lib.lib().ea_ctc_lexicon_stream_state_bytes(max_frames, beam)
+
+
+def ctc_lexicon_stream_reset(state, slots, ngram, max_frames, beam):
+    """The slots int32 [n] (device) of `state` get the search state before frame 0 (ea_ctc_lexicon_stream_reset)."""
+    _check_stream_state(state, max_frames, beam)
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
+    check(_lib.lib().ea_ctc_lexicon_stream_reset(_p(state), _p(slots), slots.numel(), ngram, state.shape[0], max_frames, beam,
+                                                 _stream()), "ea_ctc_lexicon_stream_reset")
+
+
+def ctc_lexicon_stream_step(x, meta, state, ngram, trie, word_start, space, max_frames, V, beam, K, blank, lm_weight, word_score,
+                            ins_bonus, ld=None):
+    """The new frames of every ready stream through the lexicon beam search, one launch (ea_ctc_lexicon_stream_step).  x
+    [rows][V] fp32/bf16 log-probs packed stream by stream; meta int32 [3][n] = (slot, n_new, row_off) on the device."""
+    ld = x.stride(0) if ld is None else ld
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.stride(-1) == 1 and x.shape[1] == V
+    assert meta.dtype == torch.int32 and meta.dim() == 2 and meta.shape[0] == 3 and meta.is_contiguous()
+    _check_stream_state(state, max_frames, beam)
+    off, tok, child, word, smear = trie
+    assert off.dtype == tok.dtype == child.dtype == word.dtype == torch.int32 and smear.dtype == torch.float32
+    assert word_start is None or (word_start.dtype == torch.uint8 and word_start.numel() == V)
+    check(_lib.lib().ea_ctc_lexicon_stream_step(_p(x), ld, int(x.dtype == torch.bfloat16), x.shape[0], _p(meta[0]), _p(meta[1]),
+                                                _p(meta[2]), meta.shape[1], _p(state), ngram, _p(off), _p(tok), _p(child),
+                                                _p(word), _p(smear), _p(word_start), space, state.shape[0], max_frames, V, beam, K,
+                                                blank, lm_weight, word_score, ins_bonus, _stream()), "ea_ctc_lexicon_stream_step")
+
+
+def ctc_lexicon_stream_finish(state, slots, ngram, trie, max_frames, beam, nbest, pad, max_u, lm_weight, word_score, ins_bonus):
+    """The finished hypotheses of the slots int32 [n] (device), the state left as it is (ea_ctc_lexicon_stream_finish).
+    Returns (tokens int32 [n][nbest][max_u] pad-filled, lengths int32 [n][nbest], scores fp32 [n][nbest], nhyp int32 [n])."""
+    _check_stream_state(state, max_frames, beam)
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and 1 <= nbest <= beam
+    word, smear = trie[3], trie[4]
+    assert word.dtype == torch.int32 and smear.dtype == torch.float32
+    n, dev = slots.numel(), state.device
+    tokens = torch.empty(n, nbest, max_u, dtype=torch.int32, device=dev)
+    lengths = torch.empty(n, nbest, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, nbest, dtype=torch.float32, device=dev)
+    nhyp = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.lib().ea_ctc_lexicon_stream_finish(_p(state), _p(slots), n, ngram, _p(word), _p(smear), state.shape[0], max_frames,
+                                                  beam, lm_weight, word_score, ins_bonus, nbest, pad, max_u, _p(tokens),
+                                                  _p(lengths), _p(scores), _p(nhyp), _stream()), "ea_ctc_lexicon_stream_finish")
+    return tokens, lengths, scores, nhyp
+
+
+def ctc_lexicon_stream_partial(state, slots, max_frames, beam, pad, max_u, ins_bonus):
+    """The best live hypothesis of the slots int32 [n] (device) and the length of the beam's common prefix
+    (ea_ctc_lexicon_stream_partial).  Returns (tokens int32 [n][max_u] pad-filled, lengths int32 [n], scores fp32 [n],
+    stable_len int32 [n])."""
+    _check_stream_state(state, max_frames, beam)
+    assert slots.dtype == torch.int32 and slots.is_contiguous()
+    n, dev = slots.numel(), state.device
+    tokens = torch.empty(n, max_u, dtype=torch.int32, device=dev)
+    lengths = torch.empty(n, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, dtype=torch.float32, device=dev)
+    stable = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.lib().ea_ctc_lexicon_stream_partial(_p(state), _p(slots), n, state.shape[0], max_frames, beam, ins_bonus, pad, max_u,
+                                                   _p(tokens), _p(lengths), _p(scores), _p(stable), _stream()),
+          "ea_ctc_lexicon_stream_partial")
+    return tokens, lengths, scores, stable
+
+
 def embedding_fwd(tokens, positions, W, pos_table, scale):
     M, C = tokens.numel(), W.shape[1]
     out = torch.empty(M, C, dtype=torch.bfloat16, device=W.device)

@@ -230,11 +230,13 @@ def get_parser():
                    help="collect the attention alignments; --search beam saves RESULTS_PATH/attn_plots/<utt>.pdf of the best "
                         "hypothesis (needs --results-path and matplotlib)")
     p.add_argument("--streaming", action="store_true",
-                   help="chunk-by-chunk recognition of a chunk-streaming transformer encoder (--search ctc or transducer_greedy): audio is "
-                        "fed in "
-                        "pieces of --stream-chunk-ms with --streams utterances in flight")
+                   help="chunk-by-chunk recognition of a chunk-streaming transformer encoder (--search ctc, transducer_greedy, or "
+                        "ctc_beam with --ngram-lm): audio is fed in pieces of --stream-chunk-ms with --streams utterances in flight")
     p.add_argument("--stream-chunk-ms", type=int, default=None, help="--streaming: audio per piece (default 400)")
     p.add_argument("--streams", type=int, default=None, help="--streaming: concurrent utterances (default 16)")
+    p.add_argument("--stream-partials", action="store_true",
+                   help="--streaming --search ctc_beam --ngram-lm: after every piece print `P-<utt>`, the seconds consumed, the stable "
+                        "text and the rest of the currently best hypothesis, whenever the text changed")
     p.add_argument("--wer-output-filter", default=None, help="sed-style word filter applied before WER scoring")
     p.add_argument("--non-lang-syms", default=None, help="non-language symbols (one per line), ignored by WER / CER scoring")
     return p
@@ -256,20 +258,28 @@ def check_ngram_args(args):
 
 
 def check_streaming_args(args):
-    """--streaming is greedy decoding (CTC or transducer) of one chunk-streaming model: refused, before anything is loaded, with
-    every other search, with LM fusion, ensembles and alignment output."""
+    """--streaming is greedy decoding (CTC or transducer), or the lexicon + n-gram beam search (--search ctc_beam --ngram-lm),
+    of one chunk-streaming model: refused, before anything is loaded, with every other search, with LSTM-LM fusion, ensembles
+    and alignment output."""
     if not args.streaming:
-        for opt, v in (("--stream-chunk-ms", args.stream_chunk_ms), ("--streams", args.streams)):
+        for opt, v in (("--stream-chunk-ms", args.stream_chunk_ms), ("--streams", args.streams),
+                       ("--stream-partials", args.stream_partials or None)):
             if v is not None:
                 raise ValueError(f"{opt} configures --streaming: give --streaming too")
         return
-    if args.search not in ("ctc", "transducer_greedy"):
-        raise NotImplementedError("--streaming is implemented for greedy decoding (--search ctc, --search transducer_greedy), "
-                                  f"not --search {args.search}")
-    for opt, v in (("--lm-path", args.lm_path), ("--word-dict", args.word_dict), ("--ngram-lm", args.ngram_lm),
+    lexicon_beam = args.search == "ctc_beam" and bool(args.ngram_lm)
+    if args.search == "ctc_beam" and not lexicon_beam:
+        raise NotImplementedError("--streaming --search ctc_beam needs --ngram-lm: the lexicon + n-gram search is the prefix beam "
+                                  "search that is streamed, not the one without LM or with an LSTM LM")
+    if args.search not in ("ctc", "transducer_greedy", "ctc_beam"):
+        raise NotImplementedError("--streaming is implemented for greedy decoding (--search ctc, --search transducer_greedy) and for "
+                                  f"--search ctc_beam with --ngram-lm, not --search {args.search}")
+    for opt, v in (("--lm-path", args.lm_path), ("--word-dict", args.word_dict), ("--ngram-lm", args.ngram_lm and not lexicon_beam),
                    ("--print-alignment", args.print_alignment)):
         if v:
-            raise NotImplementedError(f"--streaming decodes greedily without LM fusion or alignments: no {opt} with it")
+            raise NotImplementedError(f"--streaming decodes without LSTM-LM fusion or alignments: no {opt} with it")
+    if args.stream_partials and not lexicon_beam:
+        raise NotImplementedError("--stream-partials prints the partial results of --search ctc_beam --ngram-lm")
     if len(args.path.split(os.pathsep)) > 1:
         raise NotImplementedError("--streaming takes one model: ensembles (--path a.pt:b.pt) are not streamed")
     if (args.stream_chunk_ms is not None and args.stream_chunk_ms <= 0) or (args.streams is not None and args.streams <= 0):
@@ -277,11 +287,15 @@ def check_streaming_args(args):
 
 
 def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=400, streams=16, refs=None, out=sys.stdout,
-                        quiet=False, scorer=None, summary_out=None, search="ctc", max_num_expansions_per_step=2):
+                        quiet=False, scorer=None, summary_out=None, search="ctc", max_num_expansions_per_step=2, lexicon_beam=None,
+                        partials=False):
     """The output of `recognize` from a streamed pass: every utterance is read in pieces of `chunk_ms`, `streams` of them in
-    flight; a finished utterance frees its slot for the next one (wav.scp order)."""
+    flight; a finished utterance frees its slot for the next one (wav.scp order).  search "ctc_beam": lexicon_beam holds the
+    arguments of StreamingCTCLexiconBeamDecoder after `dictionary` (n-gram LM, lexicon) and its options; its prefix tables are
+    sized for the longest utterance given.  partials: a `P-` line per stream whenever its partial text changed."""
     from .models.transformer.streaming_encoder import StreamingEncoder
     from .tools.streaming_ctc_decoder import StreamingCTCDecoder
+    from .tools.streaming_ctc_lexicon_beam_decoder import StreamingCTCLexiconBeamDecoder
     from .tools.streaming_transducer_greedy_decoder import StreamingTransducerGreedyDecoder
     from .tools.wer import Scorer
 
@@ -291,6 +305,11 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
     if search == "ctc":
         dec = StreamingCTCDecoder(dictionary)
         strip = {dictionary.eos(), dictionary.pad()}
+    elif search == "ctc_beam":
+        (ngram_lm, lexicon), opts = lexicon_beam
+        max_frames = max([1] + [-(-task.frontend.num_frames(len(w)) // se.stride) for w in waves])
+        dec = StreamingCTCLexiconBeamDecoder(dictionary, ngram_lm, lexicon, streams, max_frames, **opts)
+        strip = {dictionary.eos(), dictionary.pad()}
     else:
         dec = StreamingTransducerGreedyDecoder(model, dictionary, max_num_expansions_per_step=max_num_expansions_per_step)
         strip = dec.symbols_to_strip_from_output
@@ -298,7 +317,12 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
     pending = list(range(len(utt_ids)))
     live = {}  # utterance index -> samples consumed
     hyps = {}
+    shown = {}  # utterance index -> the partial text last printed
     num_tok, audio_s = 0, 0.0
+
+    def text_of(toks):
+        return dictionary.string(torch.tensor([t for t in toks if t not in strip], dtype=torch.long), bpe_symbol=None)
+
     t0 = time.perf_counter()
     while pending or live:
         while pending and len(live) < streams:
@@ -317,25 +341,34 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
         logits, counts = se.accept_waveform(ids, pieces, final)
         if logits is not None:
             dec.accept(ids, logits, counts)
+        if partials:
+            for i, part in zip(ids, dec.partial(ids)):
+                k = len(part["stable"])
+                texts = (text_of(part["tokens"][:k]), text_of(part["tokens"][k:]))
+                if shown.get(i) != texts:
+                    shown[i] = texts
+                    print("P-{}\t{:.2f}\t{}\t{}".format(utt_ids[i], live[i] / 16000.0, *texts), file=out)
         for i, f in zip(ids, final):
             if f:
                 se.close([i])
-                hyps[i] = dec.close(i)
+                h = dec.close(i)
+                hyps[i] = h if isinstance(h, list) else [h]
                 del live[i]
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     t_gen = time.perf_counter() - t0
     for i, utt in enumerate(utt_ids):
-        hypo = hyps[i]
         if refs is not None and utt in refs and not quiet:
             print("T-{}\t{}".format(utt, refs[utt]), file=out)
-        hypo_str = dictionary.string(torch.tensor([t for t in hypo["tokens"].tolist() if t not in strip]), bpe_symbol=None)
-        if not quiet:
-            print("H-{}\t{}\t{}".format(utt, hypo_str, float(hypo["score"]) / math.log(2)), file=out)
-        scorer.add_prediction(utt, hypo_str)
-        if refs is not None and utt in refs:
-            scorer.add_evaluation(utt, refs[utt], hypo_str)
-        num_tok += len(hypo["tokens"])
+        for j, hypo in enumerate(hyps[i]):  # best first (one, but for the nbest of --search ctc_beam)
+            hypo_str = dictionary.string(torch.tensor([t for t in hypo["tokens"].tolist() if t not in strip]), bpe_symbol=None)
+            if not quiet:
+                print("H-{}\t{}\t{}".format(utt, hypo_str, float(hypo["score"]) / math.log(2)), file=out)
+            if j == 0:
+                scorer.add_prediction(utt, hypo_str)
+                if refs is not None and utt in refs:
+                    scorer.add_evaluation(utt, refs[utt], hypo_str)
+                num_tok += len(hypo["tokens"])
         audio_s += len(waves[i]) / 16000.0
     n = len(utt_ids)
     lines = ["NOTE: hypothesis and token scores are output in base 2",
@@ -519,7 +552,11 @@ def main(argv=None):
         mine.sort()
         s_ids, s_waves = [utt_ids[i] for i in mine], [waves[i] for i in mine]
         kw = dict(chunk_ms=args.stream_chunk_ms or 400, streams=args.streams or 16, refs=refs, quiet=args.quiet, scorer=scorer,
-                  search=args.search, max_num_expansions_per_step=args.max_num_expansions_per_step)
+                  search=args.search, max_num_expansions_per_step=args.max_num_expansions_per_step, partials=args.stream_partials)
+        if args.search == "ctc_beam":
+            kw["lexicon_beam"] = (ngram, dict(beam_size=args.beam, nbest=args.nbest, beam_size_token=args.ctc_beam_size_token,
+                                              lm_weight=args.lm_weight, word_score=args.word_score,
+                                              insertion_bonus=args.ctc_insertion_bonus))
         if not args.results_path:
             recognize_streaming(task, model, task.target_dictionary, s_ids, s_waves, dev, out=sys.stdout, **kw)
             return scorer

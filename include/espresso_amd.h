@@ -473,6 +473,46 @@ int ea_ctc_lexicon_beam_search(const void* x, long ld, int x_bf16, const int* in
                                const float* trie_smear, const void* word_start, int space, int B, int T, int V, int beam, int K,
                                int blank, float lm_weight, float word_score, float ins_bonus, int nbest, int pad, int* tokens,
                                int* lengths, float* scores, int* nhyp, ea_stream_t stream);
+/* The same search, resumable per stream slot (streaming recognition): the frames of an utterance arrive in pieces, and the
+ * results are those of ea_ctc_lexicon_beam_search over all of them, bit for bit — the per-frame code is the same.
+ *   state   : caller-allocated device buffer [max_streams][ea_ctc_lexicon_stream_state_bytes(max_frames, beam)], 8-byte
+ *             aligned.  A slot holds what the offline kernel has live between two frames: the beam (hypothesis count, and per
+ *             hypothesis p_b, p_nb, LM sum, length, last token, prefix node, its parent, trie node, word context), the
+ *             prefix table with its hash, sized for max_frames frames, and the number of frames consumed.  max_frames, beam
+ *             and the n-gram order are fixed for the life of the buffer.
+ *   slots   : int [n], device: the stream slots a call handles; entries outside [0, max_streams) are skipped.
+ * ea_ctc_lexicon_stream_reset  : the given slots get the state before frame 0 (empty prefix, <s> context, cleared hash).
+ *             A kernel on `stream`, no host synchronisation.  A slot must be reset before its first step.
+ * ea_ctc_lexicon_stream_step   : slot_idx, n_new, row_off int [n] (device), as ea_stream_attention takes them: entry b is
+ *             stream slot_idx[b] with n_new[b] new frames at rows row_off[b] .. of x, fp32 or bf16 [total_rows][ld]
+ *             log-probs.  One launch, one workgroup per entry: the slot's beam is loaded into LDS, the frames are searched,
+ *             the beam is stored.  n_new[b] == 0, out-of-range entries and an entry that would take its slot past max_frames
+ *             leave the slot untouched.  A slot may appear once per call.  The other arguments are those of
+ *             ea_ctc_lexicon_beam_search and must not change between the steps of a stream.
+ * ea_ctc_lexicon_stream_finish : the finish of the offline search for the given slots (pending word, ln P(</s> | history), the
+ *             nbest best finite hypotheses, sorted): tokens int32 [n][nbest][max_u] (pad after the hypothesis; tokens beyond
+ *             max_u are dropped and the length is clipped: give max_u >= the frames consumed), lengths, scores [n][nbest],
+ *             nhyp [n] (0 for a slot without frames).  The state is not modified: it is a readout, valid mid-stream.
+ * ea_ctc_lexicon_stream_partial: per given slot, the live hypothesis with the best in-beam score
+ *             log(p_b + p_nb) + lm + ins_bonus * length (the smeared LM sum the search prunes by; ties: the lower beam slot):
+ *             tokens int32 [n][max_u], lengths, scores [n], and stable_len [n] = the length of the longest common prefix of
+ *             the live hypotheses whose in-beam score is finite (of all live ones when none is).  Every hypothesis a later
+ *             finish can return starts with those tokens.  The state is not modified. */
+long ea_ctc_lexicon_stream_state_bytes(int max_frames, int beam);
+int ea_ctc_lexicon_stream_reset(void* state, const int* slots, int n, const void* ngram, int max_streams, int max_frames,
+                                int beam, ea_stream_t stream);
+int ea_ctc_lexicon_stream_step(const void* x, long ld, int x_bf16, long total_rows, const int* slot_idx, const int* n_new,
+                               const int* row_off, int n, void* state, const void* ngram, const int* trie_off,
+                               const int* trie_tok, const int* trie_child, const int* trie_word, const float* trie_smear,
+                               const void* word_start, int space, int max_streams, int max_frames, int V, int beam, int K,
+                               int blank, float lm_weight, float word_score, float ins_bonus, ea_stream_t stream);
+int ea_ctc_lexicon_stream_finish(const void* state, const int* slots, int n, const void* ngram, const int* trie_word,
+                                 const float* trie_smear, int max_streams, int max_frames, int beam, float lm_weight,
+                                 float word_score, float ins_bonus, int nbest, int pad, int max_u, int* tokens, int* lengths,
+                                 float* scores, int* nhyp, ea_stream_t stream);
+int ea_ctc_lexicon_stream_partial(const void* state, const int* slots, int n, int max_streams, int max_frames, int beam,
+                                  float ins_bonus, int pad, int max_u, int* tokens, int* lengths, float* scores, int* stable_len,
+                                  ea_stream_t stream);
 /* Label-smoothed CE — espresso/criterions/label_smoothed_cross_entropy_v2.py:49-119.  smoothing 0 = uniform, 1 = unigram
  * (prior fp32 [V], sums to one), 2 = temporal (neighbouring targets of the same sentence, weights 2:5:5:2; rows are
  * b*tgt_len + u).  out_loss[0] += sum loss, out_loss[1] += sum nll (pad rows skipped). */
