@@ -15,6 +15,12 @@
 // sequence exactly one node, so y' + c == y  <=>  node(y') == pnode(y) && last(y) == c: prefixes merge iff their token
 // sequences are equal.
 // ctc_beam_finish_kernel adds the LM's end-of-sentence term, sorts and walks the backpointers into token rows.
+//
+// Hotword biasing (BIAS instantiations, ea_ctc_prefix_beam_bias_*): every hypothesis also carries a state q of the context
+// graph (ctc_beam_common.h) and its running bias b, both functions of the token sequence alone, so merging is untouched.  Per
+// frame the root's edges of the K candidate tokens go to LDS; every extension (slot, candidate) takes one automaton step on
+// its own lane (slots in the root, the usual case, read LDS only), b' joins its ranking key, and (q', b') wait in LDS for the
+// selected ones.  The finish takes the pending phi(q) back.  LDS: 92 968 bytes (the unbiased instantiation: 58 664).
 #include "common.h"
 #include "ctc_beam_common.h"
 #include "espresso_amd.h"
@@ -75,9 +81,25 @@ struct StepArgs {
   float lm_weight, ins_bonus;
   int t0, t1;
 };
+struct BiasStepArgs : StepArgs { CgTables g; };
 
-template <typename TX>
-__global__ __launch_bounds__(256) void ctc_beam_step_kernel(const StepArgs a) {
+// the biased search's own per-slot state (q, b): behind the B unbiased workspaces, whose layout stays what it is
+struct BiasWs { int* q; float* b; };
+__device__ __forceinline__ BiasWs bias_ws(void* ws, int B, int b, int T, int beam) {
+  int* base = (int*)ws + (long)B * beam_ws_words(T, beam) + 2L * b * beam;
+  return {base, (float*)(base + beam)};
+}
+
+template <bool BIAS> struct BiasLds {};
+template <> struct BiasLds<true> {
+  int q[kMaxBeam]; float b[kMaxBeam];       // per slot
+  int cq[kMaxCand]; float cb[kMaxCand];     // per extension: the state and the running bias after it
+  int rchild[kMaxK]; float rboost[kMaxK];   // the root's edge by each candidate token of the frame
+};
+
+template <typename TX, bool BIAS>
+__global__ __launch_bounds__(256) void ctc_beam_step_kernel(const std::conditional_t<BIAS, BiasStepArgs, StepArgs> a) {
+  __shared__ BiasLds<BIAS> s_bias;
   __shared__ uint64_t s_key[kMaxCand];
   __shared__ SelectScratch s_sel;
   __shared__ float s_pb[kMaxBeam], s_pnb[kMaxBeam], s_lm[kMaxBeam];  // beam state of the previous frame, slot-indexed
@@ -103,6 +125,10 @@ __global__ __launch_bounds__(256) void ctc_beam_step_kernel(const StepArgs a) {
       w.len[0] = 0; w.last[0] = -1; w.node[0] = 0; w.pnode[0] = -1;
       w.cnt[0] = 1; w.cnt[1] = 1;
       w.node_par[0] = -1; w.node_tok[0] = -1;
+      if constexpr (BIAS) {
+        const BiasWs bw = bias_ws(a.ws, gridDim.x, b, a.T, beam);
+        bw.q[0] = 0; bw.b[0] = 0.f;
+      }
     }
     __threadfence_block();
     __syncthreads();
@@ -111,6 +137,10 @@ __global__ __launch_bounds__(256) void ctc_beam_step_kernel(const StepArgs a) {
   if (tid < beam) {
     s_pb[tid] = w.pb[tid]; s_pnb[tid] = w.pnb[tid]; s_lm[tid] = w.lm[tid];
     s_len[tid] = w.len[tid]; s_last[tid] = w.last[tid]; s_node[tid] = w.node[tid]; s_pnode[tid] = w.pnode[tid];
+    if constexpr (BIAS) {
+      const BiasWs bw = bias_ws(a.ws, gridDim.x, b, a.T, beam);
+      s_bias.q[tid] = bw.q[tid]; s_bias.b[tid] = bw.b[tid];
+    }
   }
   __syncthreads();
 
@@ -144,6 +174,10 @@ __global__ __launch_bounds__(256) void ctc_beam_step_kernel(const StepArgs a) {
       for (int i = 0; i < K; ++i) r += s_cunsorted[i] < v;
       s_ctok[r] = v;
       s_cx[r] = xv(v);
+      if constexpr (BIAS) {
+        const CgRoot rt = cg_root(a.g, v);
+        s_bias.rchild[r] = rt.child; s_bias.rboost[r] = rt.boost;
+      }
     }
     if (tid < kMaxBeam) s_merged[tid] = 0ull;
     __syncthreads();
@@ -178,10 +212,20 @@ __global__ __launch_bounds__(256) void ctc_beam_step_kernel(const StepArgs a) {
     for (int i = tid; i < N; i += 256) {
       const int j = i / K1, q = i - j * K1;
       uint64_t key = 0ull;
-      if (q == 0)
-        key = mk_key(lae(lae(s_pb[j], s_pnb[j]) + xb, stay_pnb(j)) + lw * s_lm[j] + a.ins_bonus * (float)s_len[j], i);
-      else if (!((s_merged[j] >> (q - 1)) & 1ull))
-        key = mk_key(ext_pnb(j, q - 1) + lw * ext_lm(j, q - 1) + a.ins_bonus * (float)(s_len[j] + 1), i);
+      if (q == 0) {
+        float s = lae(lae(s_pb[j], s_pnb[j]) + xb, stay_pnb(j)) + lw * s_lm[j] + a.ins_bonus * (float)s_len[j];
+        if constexpr (BIAS) s += s_bias.b[j];
+        key = mk_key(s, i);
+      } else if (!((s_merged[j] >> (q - 1)) & 1ull)) {
+        float s = ext_pnb(j, q - 1) + lw * ext_lm(j, q - 1) + a.ins_bonus * (float)(s_len[j] + 1);
+        if constexpr (BIAS) {  // one automaton step per live extension, each on its own lane
+          const CgStep st = cg_step(a.g, s_bias.q[j], s_ctok[q - 1], CgRoot{s_bias.rchild[q - 1], s_bias.rboost[q - 1]});
+          const float nb = s_bias.b[j] + st.inc;
+          s_bias.cq[i] = st.q; s_bias.cb[i] = nb;
+          s += nb;
+        }
+        key = mk_key(s, i);
+      }
       s_key[i] = key;
     }
     __syncthreads();
@@ -200,6 +244,8 @@ __global__ __launch_bounds__(256) void ctc_beam_step_kernel(const StepArgs a) {
     // 4. new state (wave 0: lane = one selected candidate, written to slot = its rank)
     float n_pb = 0.f, n_pnb = 0.f, n_lm = 0.f;
     int n_len = 0, n_last = -1, n_node = 0, n_pnode = -1, slot = 0, par = 0, ext = 0, fresh = 0, tslot = -1;
+    int n_q = 0;
+    float n_b = 0.f;
     if (tid < ns) {
       const int i = s_sel_idx[tid];
       const uint64_t k = s_key[i];
@@ -209,8 +255,10 @@ __global__ __launch_bounds__(256) void ctc_beam_step_kernel(const StepArgs a) {
       if (q == 0) {
         n_pb = lae(s_pb[j], s_pnb[j]) + xb; n_pnb = stay_pnb(j); n_lm = s_lm[j];
         n_len = s_len[j]; n_last = s_last[j]; n_node = s_node[j]; n_pnode = s_pnode[j];
+        if constexpr (BIAS) { n_q = s_bias.q[j]; n_b = s_bias.b[j]; }
       } else {
         ext = 1;
+        if constexpr (BIAS) { n_q = s_bias.cq[i]; n_b = s_bias.cb[i]; }
         const int r = q - 1;
         n_pb = -INFINITY; n_pnb = ext_pnb(j, r); n_lm = ext_lm(j, r);
         n_len = s_len[j] + 1; n_last = s_ctok[r]; n_pnode = s_node[j];
@@ -238,6 +286,7 @@ __global__ __launch_bounds__(256) void ctc_beam_step_kernel(const StepArgs a) {
     if (tid < ns) {
       s_pb[slot] = n_pb; s_pnb[slot] = n_pnb; s_lm[slot] = n_lm;
       s_len[slot] = n_len; s_last[slot] = n_last; s_node[slot] = n_node; s_pnode[slot] = n_pnode;
+      if constexpr (BIAS) { s_bias.q[slot] = n_q; s_bias.b[slot] = n_b; }
       if (a.lm_parent) {
         a.lm_parent[row0 + slot] = (int)(row0 + par);
         a.lm_token[row0 + slot] = ext ? n_last : a.blank;
@@ -255,13 +304,21 @@ __global__ __launch_bounds__(256) void ctc_beam_step_kernel(const StepArgs a) {
   if (tid < beam) {
     w.pb[tid] = s_pb[tid]; w.pnb[tid] = s_pnb[tid]; w.lm[tid] = s_lm[tid];
     w.len[tid] = s_len[tid]; w.last[tid] = s_last[tid]; w.node[tid] = s_node[tid]; w.pnode[tid] = s_pnode[tid];
+    if constexpr (BIAS) {
+      const BiasWs bw = bias_ws(a.ws, gridDim.x, b, a.T, beam);
+      bw.q[tid] = s_bias.q[tid]; bw.b[tid] = s_bias.b[tid];
+    }
   }
 }
 
-// final score = s(y) + lm_weight * log P_lm(eos | y); the nbest best, sorted, backtracked into tokens [B][nbest][T]
+struct NoBias {};
+
+// final score = s(y) + lm_weight * log P_lm(eos | y) [+ b - phi(q)]; the nbest best, sorted, backtracked into tokens [B][nbest][T]
+template <bool BIAS>
 __global__ __launch_bounds__(64) void ctc_beam_finish_kernel(void* ws, const float* lm_rows, long ld_lm, float lm_weight,
                                                              float ins_bonus, int eos, int T, int beam, int nbest, int pad,
-                                                             int* tokens, int* lengths, float* scores, int* nhyp) {
+                                                             int* tokens, int* lengths, float* scores, int* nhyp,
+                                                             const std::conditional_t<BIAS, CgTables, NoBias> g) {
   __shared__ float s_fin[kMaxBeam];
   const int b = blockIdx.x, j = threadIdx.x;
   const BeamWs w = beam_ws(ws, b, T, beam);
@@ -270,6 +327,10 @@ __global__ __launch_bounds__(64) void ctc_beam_finish_kernel(void* ws, const flo
   if (j < nh) {
     float s = lae(w.pb[j], w.pnb[j]) + ins_bonus * (float)w.len[j];
     if (lm_rows) s += lm_weight * (w.lm[j] + lm_rows[(row0 + j) * ld_lm + eos]);
+    if constexpr (BIAS) {
+      const BiasWs bw = bias_ws(ws, gridDim.x, b, T, beam);
+      s += bw.b[j] - cg_phi(g, bw.q[j]);
+    }
     s_fin[j] = s;
   }
   __syncthreads();
@@ -296,6 +357,15 @@ __global__ __launch_bounds__(64) void ctc_beam_finish_kernel(void* ws, const flo
   }
 }
 
+// replay of token rows through the context graph: one lane per row
+__global__ __launch_bounds__(256) void context_graph_score_kernel(const CgTables g, const int* tokens, const int* lens, int N,
+                                                                   int L, float* running, float* final_bias, int* q_out) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  cg_replay(g, tokens + (long)n * L, min(max(lens[n], 0), L), running ? running + (long)n * L : nullptr, final_bias + n,
+            q_out + n);
+}
+
 }  // namespace
 
 extern "C" long ea_ctc_prefix_beam_workspace_bytes(int B, int T, int beam) {
@@ -303,25 +373,36 @@ extern "C" long ea_ctc_prefix_beam_workspace_bytes(int B, int T, int beam) {
   return (long)B * beam_ws_words(T, beam) * 4L;
 }
 
-extern "C" int ea_ctc_prefix_beam_step(const void* x, long ld, int x_bf16, const int* in_len, void* workspace,
-                                       const float* lm_rows, long ld_lm, int* lm_parent, int* lm_token, void* lm_keep, int B,
-                                       int T, int V, int beam, int K, int blank, float lm_weight, float ins_bonus, int t0, int t1,
-                                       hipStream_t stream) {
-  if (B <= 0) return 0;
-  if (T < 0 || V < 2 || V > 65535 || ld < V || beam < 1 || beam > kMaxBeam || K < 1 || K > kMaxK || K > V - 1 || blank < 0 ||
-      blank >= V || t0 < 0 || t1 < t0 || t1 > T || (lm_rows && (ld_lm < V || !lm_parent || !lm_token || !lm_keep)))
-    return -2;
-  StepArgs a;
+static int step_args_ok(long ld, const float* lm_rows, long ld_lm, const int* lm_parent, const int* lm_token, const void* lm_keep,
+                        int T, int V, int beam, int K, int blank, int t0, int t1) {
+  return !(T < 0 || V < 2 || V > 65535 || ld < V || beam < 1 || beam > kMaxBeam || K < 1 || K > kMaxK || K > V - 1 || blank < 0 ||
+           blank >= V || t0 < 0 || t1 < t0 || t1 > T || (lm_rows && (ld_lm < V || !lm_parent || !lm_token || !lm_keep)));
+}
+
+static void fill_step_args(StepArgs& a, const void* x, long ld, const int* in_len, void* workspace, const float* lm_rows, long ld_lm,
+                           int* lm_parent, int* lm_token, void* lm_keep, int T, int V, int beam, int K, int blank, float lm_weight,
+                           float ins_bonus, int t0, int t1) {
   a.x = x; a.ld = ld; a.in_len = in_len; a.ws = workspace;
   a.lm_rows = lm_rows; a.ld_lm = ld_lm;
   a.lm_parent = lm_parent; a.lm_token = lm_token; a.lm_keep = (uint8_t*)lm_keep;
   a.T = T; a.V = V; a.beam = beam; a.K = K; a.blank = blank;
   a.lm_weight = lm_weight; a.ins_bonus = ins_bonus;
   a.t0 = t0; a.t1 = t1;
+}
+
+extern "C" int ea_ctc_prefix_beam_step(const void* x, long ld, int x_bf16, const int* in_len, void* workspace,
+                                       const float* lm_rows, long ld_lm, int* lm_parent, int* lm_token, void* lm_keep, int B,
+                                       int T, int V, int beam, int K, int blank, float lm_weight, float ins_bonus, int t0, int t1,
+                                       hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (!step_args_ok(ld, lm_rows, ld_lm, lm_parent, lm_token, lm_keep, T, V, beam, K, blank, t0, t1)) return -2;
+  StepArgs a;
+  fill_step_args(a, x, ld, in_len, workspace, lm_rows, ld_lm, lm_parent, lm_token, lm_keep, T, V, beam, K, blank, lm_weight,
+                 ins_bonus, t0, t1);
   if (x_bf16)
-    hipLaunchKernelGGL(ctc_beam_step_kernel<bf16_t>, dim3(B), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((ctc_beam_step_kernel<bf16_t, false>), dim3(B), dim3(256), 0, stream, a);
   else
-    hipLaunchKernelGGL(ctc_beam_step_kernel<float>, dim3(B), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((ctc_beam_step_kernel<float, false>), dim3(B), dim3(256), 0, stream, a);
   return EA_CHECK_LAUNCH();
 }
 
@@ -330,7 +411,86 @@ extern "C" int ea_ctc_prefix_beam_finish(void* workspace, const float* lm_rows, 
                                          float* scores, int* nhyp, hipStream_t stream) {
   if (B <= 0) return 0;
   if (T < 0 || beam < 1 || beam > kMaxBeam || nbest < 1 || nbest > beam || (lm_rows && eos < 0)) return -2;
-  hipLaunchKernelGGL(ctc_beam_finish_kernel, dim3(B), dim3(64), 0, stream, workspace, lm_rows, ld_lm, lm_weight, ins_bonus,
-                     eos, T, beam, nbest, pad, tokens, lengths, scores, nhyp);
+  hipLaunchKernelGGL(ctc_beam_finish_kernel<false>, dim3(B), dim3(64), 0, stream, workspace, lm_rows, ld_lm, lm_weight,
+                     ins_bonus, eos, T, beam, nbest, pad, tokens, lengths, scores, nhyp, NoBias{});
+  return EA_CHECK_LAUNCH();
+}
+
+// ------------------------------------------------------------------------------------------------ hotword biasing
+static int cg_tables(CgTables& g, const int* nodes, const int* edges, const int* root, int n_nodes, int n_edges, int V) {
+  // a trie: one edge into every node but the root; an empty graph is the root alone, and then the edge table may be NULL
+  if (!nodes || !root || n_nodes < 1 || n_edges < 0 || (n_edges > 0 && !edges) || n_edges != n_nodes - 1 || V < 1) return 0;
+  g.nodes = nodes; g.edges = edges; g.root = root;
+  g.n_nodes = n_nodes; g.n_edges = n_edges; g.V = V;
+  return 1;
+}
+
+extern "C" long ea_ctc_prefix_beam_bias_workspace_bytes(int B, int T, int beam) {
+  const long base = ea_ctc_prefix_beam_workspace_bytes(B, T, beam);
+  return base ? base + (long)B * 2L * beam * 4L : 0;
+}
+
+extern "C" int ea_ctc_prefix_beam_bias_step(const void* x, long ld, int x_bf16, const int* in_len, void* workspace,
+                                            const float* lm_rows, long ld_lm, int* lm_parent, int* lm_token, void* lm_keep,
+                                            const int* cg_nodes, const int* cg_edges, const int* cg_root, int cg_n_nodes,
+                                            int cg_n_edges, int B, int T, int V, int beam, int K, int blank, float lm_weight,
+                                            float ins_bonus, int t0, int t1, hipStream_t stream) {
+  if (B <= 0) return 0;
+  BiasStepArgs a;
+  if (!step_args_ok(ld, lm_rows, ld_lm, lm_parent, lm_token, lm_keep, T, V, beam, K, blank, t0, t1) ||
+      !cg_tables(a.g, cg_nodes, cg_edges, cg_root, cg_n_nodes, cg_n_edges, V))
+    return -2;
+  fill_step_args(a, x, ld, in_len, workspace, lm_rows, ld_lm, lm_parent, lm_token, lm_keep, T, V, beam, K, blank, lm_weight,
+                 ins_bonus, t0, t1);
+  if (x_bf16)
+    hipLaunchKernelGGL((ctc_beam_step_kernel<bf16_t, true>), dim3(B), dim3(256), 0, stream, a);
+  else
+    hipLaunchKernelGGL((ctc_beam_step_kernel<float, true>), dim3(B), dim3(256), 0, stream, a);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_ctc_prefix_beam_bias_finish(void* workspace, const float* lm_rows, long ld_lm, float lm_weight, float ins_bonus,
+                                              int eos, const int* cg_nodes, int cg_n_nodes, int B, int T, int beam, int nbest,
+                                              int pad, int* tokens, int* lengths, float* scores, int* nhyp, hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (T < 0 || beam < 1 || beam > kMaxBeam || nbest < 1 || nbest > beam || (lm_rows && eos < 0) || !cg_nodes || cg_n_nodes < 1)
+    return -2;
+  CgTables g;
+  g.nodes = cg_nodes; g.edges = nullptr; g.root = nullptr;
+  g.n_nodes = cg_n_nodes; g.n_edges = 0; g.V = 0;
+  hipLaunchKernelGGL(ctc_beam_finish_kernel<true>, dim3(B), dim3(64), 0, stream, workspace, lm_rows, ld_lm, lm_weight, ins_bonus,
+                     eos, T, beam, nbest, pad, tokens, lengths, scores, nhyp, g);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_context_graph_score_host(const int* nodes_host, const int* edges_host, const int* root_host, int n_nodes,
+                                           int n_edges, int V, const int* tokens_host, const int* lens_host, int N, int L,
+                                           float* running_host, float* final_host, int* q_host) {
+  CgTables g;
+  if (N < 0 || L < 0 || !cg_tables(g, nodes_host, edges_host, root_host, n_nodes, n_edges, V)) return -2;
+  // host tables are checked in full: every index in range, fail links strictly towards the root in node order
+  for (int n = 0; n < n_nodes; ++n) {
+    const int* r = nodes_host + 4L * n;
+    if (r[0] < 0 || r[1] < r[0] || r[1] > n_edges || r[2] < 0 || r[2] >= n_nodes) return -2;
+  }
+  for (int e = 0; e < n_edges; ++e)
+    if (edges_host[4L * e + 1] < 1 || edges_host[4L * e + 1] >= n_nodes) return -2;
+  for (int v = 0; v < V; ++v)
+    if (root_host[2L * v] < -1 || root_host[2L * v] >= n_nodes) return -2;
+  for (int n = 0; n < N; ++n) {
+    const int len = lens_host[n] < 0 ? 0 : (lens_host[n] > L ? L : lens_host[n]);
+    cg_replay(g, tokens_host + (long)n * L, len, running_host ? running_host + (long)n * L : nullptr, final_host + n, q_host + n);
+  }
+  return 0;
+}
+
+extern "C" int ea_context_graph_score(const int* nodes, const int* edges, const int* root, int n_nodes, int n_edges, int V,
+                                      const int* tokens, const int* lens, int N, int L, float* running, float* final_bias,
+                                      int* q_out, hipStream_t stream) {
+  CgTables g;
+  if (N < 0 || L < 0 || !cg_tables(g, nodes, edges, root, n_nodes, n_edges, V)) return -2;
+  if (N == 0) return 0;
+  hipLaunchKernelGGL(context_graph_score_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, g, tokens, lens, N, L, running,
+                     final_bias, q_out);
   return EA_CHECK_LAUNCH();
 }

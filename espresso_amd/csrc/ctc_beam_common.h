@@ -1,5 +1,7 @@
 // Device helpers shared by the CTC prefix beam searches (ctc_beam.hip, ctc_lexicon_beam.hip): 48-bit ordering keys,
-// the workgroup-wide radix select over them, log-add-exp, the prefix hash and L2 loads of the workgroup's own writes.
+// the workgroup-wide radix select over them, log-add-exp, the prefix hash and L2 loads of the workgroup's own writes; and the
+// one step of the hotword context graph (an Aho-Corasick automaton over the phrase trie) that the biased search, the replay
+// kernel and its host twin share.
 #pragma once
 #include "common.h"
 
@@ -84,6 +86,70 @@ __device__ uint64_t select_nth(KeyFn key, int N, int n, SelectScratch& s) {
     if (s.done) return 1;
   }
   return s.prefix;
+}
+
+// Context graph (tools/context_graph.py), packed for one 16-byte load per visited node and per probed edge:
+//   nodes int32 [n_nodes][4] = (first edge, end edge, fail node, bits of phi);  node 0 = root
+//   edges int32 [n_edges][4] = (token, child node, bits of the edge boost, 0), the edges of a node ascending by token
+//   root  int32 [V][2]       = (child of the root by token or -1, bits of its edge boost): the first level, direct-indexed
+struct CgTables {
+  const int* nodes; const int* edges; const int* root;
+  int n_nodes, n_edges, V;
+};
+struct CgStep { int q; float inc; };  // the state after the token, and b' - b
+struct CgRoot { int child; float boost; };
+
+__host__ __device__ __forceinline__ float cg_bits(int i) {
+  float f;
+  __builtin_memcpy(&f, &i, 4);
+  return f;
+}
+__host__ __device__ __forceinline__ CgRoot cg_root(const CgTables& g, int v) {
+  if ((unsigned)v >= (unsigned)g.V) return {-1, 0.f};
+  const int2 r = *(const int2*)(g.root + 2L * v);
+  return {r.x, cg_bits(r.y)};
+}
+// Appending token v in state q: down the failure links from q until a node has the edge v (the root's edge comes from
+// `root_of_v`, which the search keeps in LDS for the frame's candidates).  inc = phi(m) + e(q') - phi(q), or -phi(q) when the
+// automaton falls back to the root.  Out-of-range table entries end the walk at the root (malformed tables cannot hang it).
+__host__ __device__ __forceinline__ CgStep cg_step(const CgTables& g, int q, int v, CgRoot root_of_v) {
+  float phi_q = 0.f;
+  if (q > 0 && q < g.n_nodes) {
+    int4 nm = *(const int4*)(g.nodes + 4L * q);
+    phi_q = cg_bits(nm.w);
+    for (int hops = 0; hops < g.n_nodes; ++hops) {
+      int lo = nm.x > 0 ? nm.x : 0, hi = nm.y < g.n_edges ? nm.y : g.n_edges;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const int4 e = *(const int4*)(g.edges + 4L * mid);
+        if (e.x == v) return {e.y, cg_bits(nm.w) + cg_bits(e.z) - phi_q};
+        if (e.x < v) lo = mid + 1; else hi = mid;
+      }
+      const int m = nm.z;
+      if (m <= 0 || m >= g.n_nodes) break;
+      nm = *(const int4*)(g.nodes + 4L * m);
+    }
+  }
+  if (root_of_v.child >= 0) return {root_of_v.child, root_of_v.boost - phi_q};
+  return {0, -phi_q};
+}
+__host__ __device__ __forceinline__ float cg_phi(const CgTables& g, int q) {
+  return q > 0 && q < g.n_nodes ? cg_bits(g.nodes[4L * q + 3]) : 0.f;
+}
+
+// one token row through the graph: running[u] = b after token u (may be NULL), *final_bias = b - phi(q) = B(y), *q_out = q
+__host__ __device__ __forceinline__ void cg_replay(const CgTables& g, const int* tokens, int len, float* running, float* final_bias,
+                                                   int* q_out) {
+  int q = 0;
+  float b = 0.f;
+  for (int u = 0; u < len; ++u) {
+    const CgStep st = cg_step(g, q, tokens[u], cg_root(g, tokens[u]));
+    q = st.q;
+    b += st.inc;
+    if (running) running[u] = b;
+  }
+  *final_bias = b - cg_phi(g, q);
+  *q_out = q;
 }
 
 template <typename TX>

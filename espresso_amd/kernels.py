@@ -587,6 +587,66 @@ def ctc_prefix_beam_finish(ws, B, T, beam, nbest, pad, lm_rows=None, lm_weight=0
     return tokens, lengths, scores, nhyp
 
 
+def _cg(graph, V=None):
+    """(nodes, edges, root) device tables of a context graph -> the five table arguments of the bias calls."""
+    nodes, edges, root = graph
+    assert nodes.dtype == edges.dtype == root.dtype == torch.int32 and nodes.is_contiguous() and edges.is_contiguous() and root.is_contiguous()
+    assert nodes.dim() == 2 and nodes.shape[1] == 4 and nodes.shape[0] >= 1 and tuple(edges.shape) == (nodes.shape[0] - 1, 4)
+    assert root.dim() == 2 and root.shape[1] == 2 and (V is None or root.shape[0] == V), "context graph built for another vocabulary"
+    return _p(nodes), (_p(edges) if edges.numel() else None), _p(root), nodes.shape[0], edges.shape[0]
+
+
+def ctc_prefix_beam_bias_workspace(B, T, beam, device):
+    """Workspace of the hotword-biased CTC prefix beam search (ea_ctc_prefix_beam_bias_workspace_bytes)."""
+    return torch.empty(int(_lib.lib().ea_ctc_prefix_beam_bias_workspace_bytes(B, T, beam)), dtype=torch.uint8, device=device)
+
+
+def ctc_prefix_beam_bias_step(x, in_len, ws, graph, B, T, V, beam, K, blank, t0, t1, lm_rows=None, lm_weight=0.0, ins_bonus=0.0,
+                              lm_out=None, ld=None):
+    """ctc_prefix_beam_step with a context graph (nodes, edges, root device tables of tools.context_graph.ContextGraph.cuda())."""
+    ld = x.stride(0) if ld is None else ld
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.stride(-1) == 1 and x.shape[0] == B * T and x.shape[1] == V
+    assert in_len.dtype == torch.int32 and in_len.numel() == B
+    assert ws.numel() >= _lib.lib().ea_ctc_prefix_beam_bias_workspace_bytes(B, T, beam)
+    parent, token, keep = lm_out if lm_out is not None else (None, None, None)
+    if lm_rows is not None:
+        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (B * beam, V) and t1 == t0 + 1
+        assert parent.numel() == token.numel() == keep.numel() == B * beam
+        assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
+    check(_lib.lib().ea_ctc_prefix_beam_bias_step(_p(x), ld, int(x.dtype == torch.bfloat16), _p(in_len), _p(ws), _p(lm_rows),
+                                                  lm_rows.stride(0) if lm_rows is not None else 0, _p(parent), _p(token), _p(keep),
+                                                  *_cg(graph, V), B, T, V, beam, K, blank, lm_weight, ins_bonus, t0, t1, _stream()),
+          "ea_ctc_prefix_beam_bias_step")
+
+
+def ctc_prefix_beam_bias_finish(ws, graph, B, T, beam, nbest, pad, lm_rows=None, lm_weight=0.0, ins_bonus=0.0, eos=-1):
+    """ctc_prefix_beam_finish of a biased search: the scores include the boosts of the completed phrases."""
+    dev = ws.device
+    tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
+    lengths = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
+    nhyp = torch.empty(B, dtype=torch.int32, device=dev)
+    nodes, _, _, n_nodes, _ = _cg(graph)
+    check(_lib.lib().ea_ctc_prefix_beam_bias_finish(_p(ws), _p(lm_rows), lm_rows.stride(0) if lm_rows is not None else 0, lm_weight,
+                                                    ins_bonus, eos, nodes, n_nodes, B, T, beam, nbest, pad, _p(tokens), _p(lengths),
+                                                    _p(scores), _p(nhyp), _stream()), "ea_ctc_prefix_beam_bias_finish")
+    return tokens, lengths, scores, nhyp
+
+
+def context_graph_score(graph, tokens, lens):
+    """Token rows int32 [N][L] (lens int32 [N]) replayed through a context graph on the device (ea_context_graph_score):
+    (running bias fp32 [N][L], final bias fp32 [N], node int32 [N])."""
+    assert tokens.dtype == lens.dtype == torch.int32 and tokens.is_contiguous() and tokens.dim() == 2 and lens.numel() == tokens.shape[0]
+    N, L = tokens.shape
+    running = torch.zeros(N, L, dtype=torch.float32, device=tokens.device)
+    final = torch.empty(N, dtype=torch.float32, device=tokens.device)
+    q = torch.empty(N, dtype=torch.int32, device=tokens.device)
+    nodes, edges, root, n_nodes, n_edges = _cg(graph)
+    check(_lib.lib().ea_context_graph_score(nodes, edges, root, n_nodes, n_edges, graph[2].shape[0], _p(tokens), _p(lens), N, L,
+                                            _p(running), _p(final), _p(q), _stream()), "ea_context_graph_score")
+    return running, final, q
+
+
 def ctc_viterbi_align(x, targets, in_len, tgt_len, B, T, V, blank, ld=None):
     """Forced alignment of targets int32 [B][Lmax] to x [B*T][V] fp32/bf16 log-probs (batch-major, row pitch ld).  Returns
     (tok_start int32 [B][Lmax], tok_end int32 [B][Lmax], frame_label int32 [B][T], score fp32 [B]), all on the device."""

@@ -138,8 +138,8 @@ def collate(ids: List[int], utt_ids: List[str], waves: List[np.ndarray], device)
             "wav_offsets": torch.from_numpy(offs).to(device), "num_samples": lens, "net_input": {}}
 
 
-def build_generator(args, model, dictionary, lm=None, ngram=None):
-    """ngram: (NGramLanguageModel, LexiconTrie) for --search ctc_beam --ngram-lm."""
+def build_generator(args, model, dictionary, lm=None, ngram=None, context_graph=None):
+    """ngram: (NGramLanguageModel, LexiconTrie) for --search ctc_beam --ngram-lm; context_graph: the ContextGraph of --hotwords."""
     from .sequence_generator import SequenceGenerator
     from .tools.ctc_decoder import CTCDecoder
     from .tools.ctc_lexicon_beam_search import CTCLexiconBeamSearchDecoder
@@ -156,7 +156,7 @@ def build_generator(args, model, dictionary, lm=None, ngram=None):
     if args.search == "ctc_beam":
         return CTCPrefixBeamSearchDecoder([model], dictionary, beam_size=args.beam, nbest=args.nbest,
                                           beam_size_token=args.ctc_beam_size_token, lm_model=lm, lm_weight=args.lm_weight,
-                                          insertion_bonus=args.ctc_insertion_bonus)
+                                          insertion_bonus=args.ctc_insertion_bonus, context_graph=context_graph)
     if args.search == "transducer_greedy":
         return TransducerGreedyDecoder([model], dictionary, max_num_expansions_per_step=args.max_num_expansions_per_step,
                                        lm_model=lm, lm_weight=args.lm_weight)
@@ -212,6 +212,16 @@ def get_parser():
                    help="ctc_beam --ngram-lm: `word tok1 tok2 ...` lines (default with a <space> dictionary: the ARPA words spelled "
                         "by characters)")
     p.add_argument("--word-score", type=float, default=-1.0, help="ctc_beam --ngram-lm: score added per completed word")
+    p.add_argument("--hotwords", default=None,
+                   help="ctc_beam (without --ngram-lm): phrases to bias the search towards, one per line, optionally `<TAB>boost`; "
+                        "`#` comments.  A hypothesis gains the boost for every token of a phrase it completes (natural log, not "
+                        "scaled by --lm-weight; H- scores include it).  The candidate tokens of a frame stay the "
+                        "--ctc-beam-size-token best by acoustic score: biasing re-ranks hypotheses, it does not bring back a token "
+                        "outside them")
+    p.add_argument("--hotword-score", type=float, default=None,
+                   help="--hotwords: boost per token of the phrases that give none of their own (default 1.5)")
+    p.add_argument("--bpe", default=None, choices=["characters_asr", "sentencepiece"], help="--hotwords: sub-word tokeniser of the phrases (as speech_align --bpe)")
+    p.add_argument("--sentencepiece-model", default=None, help="--bpe sentencepiece: the model file")
     p.add_argument("--max-num-expansions-per-step", type=int, default=2)
     p.add_argument("--expansion-beta", type=int, default=0)
     p.add_argument("--expansion-gamma", type=float, default=None)
@@ -255,6 +265,28 @@ def check_ngram_args(args):
         raise NotImplementedError("--ngram-lm fuses the n-gram LM alone: no --lm-path or --word-dict with it")
     if len(args.path.split(os.pathsep)) > 1:
         raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
+
+
+DEFAULT_HOTWORD_SCORE = 1.5
+
+
+def check_hotword_args(args):
+    """--hotwords biases the prefix beam search of --search ctc_beam (alone or with an LSTM LM): refused, before anything is
+    loaded, with every other search, with the lexicon + n-gram search and with --streaming."""
+    if not args.hotwords:
+        for opt, v in (("--hotword-score", args.hotword_score), ("--bpe", args.bpe), ("--sentencepiece-model", args.sentencepiece_model)):
+            if v is not None:
+                raise ValueError(f"{opt} configures --hotwords: give --hotwords too")
+        return
+    if args.search != "ctc_beam":
+        raise NotImplementedError("--hotwords (phrase biasing) is implemented for --search ctc_beam only, not --search "
+                                  f"{args.search}")
+    if args.ngram_lm:
+        raise NotImplementedError("--hotwords biases the prefix beam search without a lexicon: no --ngram-lm with it")
+    if args.streaming:
+        raise NotImplementedError("--hotwords is not streamed: no --streaming with it")
+    if args.hotword_score is not None and not args.hotword_score > 0:
+        raise ValueError("--hotword-score must be positive")
 
 
 def check_streaming_args(args):
@@ -461,6 +493,7 @@ def main(argv=None):
     args = get_parser().parse_args(argv)
     if args.print_alignment is not None and not args.results_path:
         raise ValueError("--print-alignment saves attention plots under --results-path: give --results-path")
+    check_hotword_args(args)
     check_ngram_args(args)
     check_streaming_args(args)
     lm_mode = lm_fusion_mode(args)
@@ -487,7 +520,15 @@ def main(argv=None):
     crit = {"beam": "label_smoothed_cross_entropy_v2", "ctc": "ctc_loss", "ctc_beam": "ctc_loss"}.get(args.search, "transducer_loss")
     task = SpeechRecognitionEspressoTask.setup_task(SpeechRecognitionEspressoConfig(
         dict=args.dict, autoregressive=autoregressive, global_cmvn_stats_path=args.global_cmvn_stats_path, criterion_name=crit,
-        non_lang_syms=args.non_lang_syms, wer_output_filter=args.wer_output_filter))
+        non_lang_syms=args.non_lang_syms, wer_output_filter=args.wer_output_filter, bpe=args.bpe,
+        sentencepiece_model=args.sentencepiece_model))
+    context_graph = None
+    if args.hotwords:  # before the model: a malformed phrase file fails fast
+        from .tools.context_graph import load_context_graph
+
+        d = task.target_dictionary
+        context_graph = load_context_graph(args.hotwords, d, d.bos(), DEFAULT_HOTWORD_SCORE if args.hotword_score is None
+                                           else args.hotword_score)
     ngram = None
     if args.ngram_lm:  # before the model: a malformed ARPA or lexicon file fails fast
         from .models.ngram_lm import NGramLanguageModel
@@ -533,7 +574,7 @@ def main(argv=None):
             if args.word_dict:
                 lm = TensorizedLookaheadLanguageModel(lm, task.target_dictionary, oov_penalty=args.oov_penalty,
                                                       open_vocab=not args.disable_open_vocab)
-    gen = build_generator(args, members if len(members) > 1 else model, task.target_dictionary, lm, ngram)
+    gen = build_generator(args, members if len(members) > 1 else model, task.target_dictionary, lm, ngram, context_graph)
     scp = read_scp(args.wav_scp)
     utt_ids = list(scp.keys())
     waves = [read_wav(scp[u]) for u in utt_ids]

@@ -11,7 +11,12 @@ and the `beam` best survive (ties: parent slot, stay before extension, token id)
 
 The search is HIP (csrc/ctc_beam.hip): without an LM the whole utterance is one launch; with one, every frame is one step
 launch plus the LM update on the device (reorder the LSTM state by parent, advance the rows that appended a token, output
-layer, log-softmax).  `search` returns device tensors without a host synchronisation."""
+layer, log-softmax).  `search` returns device tensors without a host synchronisation.
+
+Hotword biasing: with `context_graph` (tools/context_graph.ContextGraph) every hypothesis also carries its state in the phrase
+automaton and a running bias that joins the score unweighted; the final score is the unbiased score of the same tokens plus
+the boosts of the phrases it completed.  The candidate tokens of a frame stay the K best by acoustic score: biasing re-ranks
+hypotheses, it does not bring back a token outside the top K.  Without a graph the search calls what it always called."""
 from typing import Dict, List
 
 import torch
@@ -23,7 +28,7 @@ class CTCPrefixBeamSearchDecoder:
     MAX_BEAM = 64
 
     def __init__(self, models, dictionary, beam_size=10, nbest=1, beam_size_token=None, lm_model=None, lm_weight=0.0,
-                 insertion_bonus=0.0, blank=None, **kwargs):
+                 insertion_bonus=0.0, blank=None, context_graph=None, **kwargs):
         self.model = models[0] if isinstance(models, (list, tuple)) else models
         self.pad = dictionary.pad()
         self.eos = dictionary.eos()
@@ -44,11 +49,17 @@ class CTCPrefixBeamSearchDecoder:
             assert list(lm_dict.symbols) == list(dictionary.symbols), \
                 "CTC prefix beam search fuses an LM over the CTC model's own dictionary (blank <s> included)"
             lm_model.eval()
+        if context_graph is not None and context_graph.vocab_size != V:
+            raise ValueError(f"CTC prefix beam search: context graph built for {context_graph.vocab_size} tokens, dictionary has {V}")
+        self.context_graph = context_graph
+        self._graph_dev = None
 
     def cuda(self):
         self.model.cuda()
         if self.lm_model is not None:
             self.lm_model.cuda()
+        if self.context_graph is not None:
+            self._graph_dev = self.context_graph.cuda()
         return self
 
     # ---------------------------------------------------------------- LM state of the beams
@@ -82,22 +93,35 @@ class CTCPrefixBeamSearchDecoder:
         x = lprobs.view(B * T, V) if lprobs.is_contiguous() else lprobs.reshape(B * T, V)
         in_len = in_len.to(device=lprobs.device, dtype=torch.int32).contiguous()
         dev, beam, Kt = lprobs.device, self.beam_size, self.beam_size_token
-        ws = K.ctc_prefix_beam_workspace(B, T, beam, dev)
         step = dict(B=B, T=T, V=V, beam=beam, K=Kt, blank=self.blank, ins_bonus=self.insertion_bonus)
+        if self.context_graph is None:
+            ws = K.ctc_prefix_beam_workspace(B, T, beam, dev)
+            beam_step, beam_finish = K.ctc_prefix_beam_step, K.ctc_prefix_beam_finish
+        else:
+            if self._graph_dev is None or self._graph_dev[0].device != dev:  # uploaded once (here when `cuda()` was not called)
+                self._graph_dev = self.context_graph.cuda(dev)
+            graph = self._graph_dev
+            ws = K.ctc_prefix_beam_bias_workspace(B, T, beam, dev)
+
+            def beam_step(x, in_len, ws, **kw):
+                K.ctc_prefix_beam_bias_step(x, in_len, ws, graph, **kw)
+
+            def beam_finish(ws, *a, **kw):
+                return K.ctc_prefix_beam_bias_finish(ws, graph, *a, **kw)
         if self.lm_model is None:
-            K.ctc_prefix_beam_step(x, in_len, ws, t0=0, t1=T, **step)
-            return K.ctc_prefix_beam_finish(ws, B, T, beam, self.nbest, self.pad, ins_bonus=self.insertion_bonus)
+            beam_step(x, in_len, ws, t0=0, t1=T, **step)
+            return beam_finish(ws, B, T, beam, self.nbest, self.pad, ins_bonus=self.insertion_bonus)
         N = B * beam
         state, rows = self.lm_start(N, dev)
         lm_out = (torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
                   torch.empty(N, dtype=torch.uint8, device=dev))
         if T == 0:
-            K.ctc_prefix_beam_step(x, in_len, ws, t0=0, t1=0, **step)
+            beam_step(x, in_len, ws, t0=0, t1=0, **step)
         for t in range(T):
-            K.ctc_prefix_beam_step(x, in_len, ws, t0=t, t1=t + 1, lm_rows=rows, lm_weight=self.lm_weight, lm_out=lm_out, **step)
+            beam_step(x, in_len, ws, t0=t, t1=t + 1, lm_rows=rows, lm_weight=self.lm_weight, lm_out=lm_out, **step)
             state, rows = self.lm_update(state, *lm_out)
-        return K.ctc_prefix_beam_finish(ws, B, T, beam, self.nbest, self.pad, lm_rows=rows, lm_weight=self.lm_weight,
-                                        ins_bonus=self.insertion_bonus, eos=self.eos)
+        return beam_finish(ws, B, T, beam, self.nbest, self.pad, lm_rows=rows, lm_weight=self.lm_weight,
+                           ins_bonus=self.insertion_bonus, eos=self.eos)
 
     @torch.no_grad()
     def _generate(self, sample):

@@ -432,6 +432,39 @@ int ea_ctc_prefix_beam_step(const void* x, long ld, int x_bf16, const int* in_le
 int ea_ctc_prefix_beam_finish(void* workspace, const float* lm_rows, long ld_lm, float lm_weight, float ins_bonus, int eos,
                               int B, int T, int beam, int nbest, int pad, int* tokens, int* lengths, float* scores, int* nhyp,
                               ea_stream_t stream);
+/* Hotword (contextual phrase) biasing of the CTC prefix beam search (csrc/ctc_beam.hip).  A context graph is the trie of the
+ * phrases with Aho-Corasick failure links (tools/context_graph.py), node 0 = root, packed as
+ *   cg_nodes int32 [cg_n_nodes][4] = (first edge, end edge, fail node, bits of phi fp32),
+ *   cg_edges int32 [cg_n_edges][4] = (token, child node, bits of the edge boost fp32, 0), a node's edges ascending by token,
+ *   cg_root  int32 [V][2]          = (the root's child by token or -1, bits of its edge boost): the first level by direct index;
+ * cg_n_edges == cg_n_nodes - 1 (< 2^31 nodes).  An empty graph (the root alone, cg_edges NULL) is legal and gives the unbiased
+ * results.  Every hypothesis carries a node q and a running bias b (root, 0 for the empty prefix).  Appending token v:
+ * m = q; while m is not the root and has no edge v: m = fail(m); with an edge m -v-> q': b += phi(m) + boost(q') - phi(q),
+ * else q' = root, b -= phi(q).  Stays change neither.  b joins the ranking score unweighted; the finish adds b - phi(q), so
+ * a final score is the unbiased score of the same token sequence plus the boosts of the phrases completed along trie edges.
+ * The candidate tokens of a frame stay the K best by acoustic score.  A phrase reached only through a failure link is not
+ * credited.
+ * ea_ctc_prefix_beam_bias_workspace_bytes / _bias_step / _bias_finish: as the three calls above (same arguments, limits and
+ *   outputs) with the graph; the workspace is that of the unbiased search followed by (q, b) per slot, and one search uses
+ *   the bias calls for all of its steps and its finish.
+ * ea_context_graph_score: token rows int32 [N][L] with lens int32 [N] replayed through the graph: running fp32 [N][L] (b after
+ *   every token; may be NULL), final_bias fp32 [N] (b - phi(q)), q_out int32 [N].  Tokens outside [0, V) match nothing.
+ *   ea_context_graph_score_host: the same on host tables and host arrays (no device needed); it also checks every table
+ *   index and returns -2 for a malformed graph. */
+long ea_ctc_prefix_beam_bias_workspace_bytes(int B, int T, int beam);
+int ea_ctc_prefix_beam_bias_step(const void* x, long ld, int x_bf16, const int* in_len, void* workspace, const float* lm_rows,
+                                 long ld_lm, int* lm_parent, int* lm_token, void* lm_keep, const int* cg_nodes,
+                                 const int* cg_edges, const int* cg_root, int cg_n_nodes, int cg_n_edges, int B, int T, int V,
+                                 int beam, int K, int blank, float lm_weight, float ins_bonus, int t0, int t1, ea_stream_t stream);
+int ea_ctc_prefix_beam_bias_finish(void* workspace, const float* lm_rows, long ld_lm, float lm_weight, float ins_bonus, int eos,
+                                   const int* cg_nodes, int cg_n_nodes, int B, int T, int beam, int nbest, int pad, int* tokens,
+                                   int* lengths, float* scores, int* nhyp, ea_stream_t stream);
+int ea_context_graph_score_host(const int* nodes_host, const int* edges_host, const int* root_host, int n_nodes, int n_edges,
+                                int V, const int* tokens_host, const int* lens_host, int N, int L, float* running_host,
+                                float* final_host, int* q_host);
+int ea_context_graph_score(const int* nodes, const int* edges, const int* root, int n_nodes, int n_edges, int V,
+                           const int* tokens, const int* lens, int N, int L, float* running, float* final_bias, int* q_out,
+                           ea_stream_t stream);
 /* Word n-gram LM (ARPA) and lexicon-constrained CTC prefix beam search with its fusion (csrc/ctc_lexicon_beam.hip) — the
  * search the reference takes from Flashlight's KenLM lexicon decoder (espresso/tools/ctc_decoder.py:24-71).
  * ea_ngram_create: parses a plain-text ARPA file of order <= 6 at `path` into host tables and writes an opaque handle to
