@@ -633,6 +633,41 @@ def ctc_prefix_beam_bias_finish(ws, graph, B, T, beam, nbest, pad, lm_rows=None,
     return tokens, lengths, scores, nhyp
 
 
+def rnnt_frame_beam_workspace(B, T, beam, device):
+    """Workspace of the frame-synchronous transducer beam search (ea_rnnt_frame_beam_workspace_bytes): the beams, prefix tables
+    and per-row candidates of B utterances of at most T frames."""
+    return torch.empty(int(_lib.lib().ea_rnnt_frame_beam_workspace_bytes(B, T, beam)), dtype=torch.uint8, device=device)
+
+
+def rnnt_frame_beam_step(logits, in_len, ws, out, B, T, V, beam, K, blank, t, eos=-1, temperature=1.0, lm_rows=None, lm_weight=0.0,
+                         lm_no_blank=False):
+    """Frame t of the frame-synchronous transducer beam search: logits fp32 [B*beam][>= V] (the joint's output for this frame, row
+    b * beam + slot), in_len int32 [B], out = (parent int32, token int32, keep uint8), each [B*beam], written by the step.
+    lm_rows fp32 [B*beam][V or V - 1 (lm_no_blank)]; eos >= 0: the model's eos is folded into blank."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == B * beam and logits.shape[1] >= V
+    assert in_len.dtype == torch.int32 and in_len.numel() == B  # (ws: rnnt_frame_beam_workspace(B, T, beam), checked by its owner)
+    parent, token, keep = out
+    assert parent.numel() == token.numel() == keep.numel() == B * beam
+    assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
+    if lm_rows is not None:
+        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (B * beam, V - 1 if lm_no_blank else V)
+    check(_lib.lib().ea_rnnt_frame_beam_step(_p(logits), logits.stride(0), _p(lm_rows), lm_rows.stride(0) if lm_rows is not None else 0,
+                                             int(lm_no_blank), _p(in_len), _p(ws), _p(parent), _p(token), _p(keep), B, T, V, beam, K,
+                                             blank, eos, temperature, lm_weight, t, _stream()), "ea_rnnt_frame_beam_step")
+
+
+def rnnt_frame_beam_finish(ws, B, T, beam, nbest, pad, normalize=True):
+    """(tokens int32 [B][nbest][T] pad-filled, lengths int32 [B][nbest], scores fp32 [B][nbest], nhyp int32 [B]), best first."""
+    dev = ws.device
+    tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
+    lengths = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
+    nhyp = torch.empty(B, dtype=torch.int32, device=dev)
+    check(_lib.lib().ea_rnnt_frame_beam_finish(_p(ws), B, T, beam, nbest, pad, int(bool(normalize)), _p(tokens), _p(lengths),
+                                               _p(scores), _p(nhyp), _stream()), "ea_rnnt_frame_beam_finish")
+    return tokens, lengths, scores, nhyp
+
+
 def context_graph_score(graph, tokens, lens):
     """Token rows int32 [N][L] (lens int32 [N]) replayed through a context graph on the device (ea_context_graph_score):
     (running bias fp32 [N][L], final bias fp32 [N], node int32 [N])."""

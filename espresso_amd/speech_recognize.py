@@ -1,6 +1,6 @@
 """Batched recognition CLI — the decoding loop and output format of espresso/speech_recognize.py:60-360 on the HIP path:
 for every batch run the chosen search (beam search with optional LM / look-ahead word-LM / multi-level LM fusion, CTC greedy,
-CTC prefix beam search with optional LSTM-LM or lexicon + n-gram LM fusion, transducer greedy / beam), print `T-<utt>` (reference) and `H-<utt>`
+CTC prefix beam search with optional LSTM-LM or lexicon + n-gram LM fusion, transducer greedy / beam / frame-synchronous beam), print `T-<utt>` (reference) and `H-<utt>`
 (hypothesis, score in base 2) lines, accumulate WER / CER with `tools.wer.Scorer`, and close with the "Recognized N utterances
 ..." summary.
 
@@ -145,6 +145,7 @@ def build_generator(args, model, dictionary, lm=None, ngram=None, context_graph=
     from .tools.ctc_lexicon_beam_search import CTCLexiconBeamSearchDecoder
     from .tools.ctc_prefix_beam_search import CTCPrefixBeamSearchDecoder
     from .tools.transducer_beam_search_decoder import TransducerBeamSearchDecoder
+    from .tools.transducer_frame_beam_decoder import TransducerFrameBeamDecoder
     from .tools.transducer_greedy_decoder import TransducerGreedyDecoder
 
     if args.search == "ctc":
@@ -165,6 +166,10 @@ def build_generator(args, model, dictionary, lm=None, ngram=None, context_graph=
                                            max_num_expansions_per_step=args.max_num_expansions_per_step, expansion_beta=args.expansion_beta,
                                            expansion_gamma=args.expansion_gamma, prefix_alpha=args.prefix_alpha, lm_model=lm,
                                            lm_weight=args.lm_weight)
+    if args.search == "transducer_frame_beam":
+        return TransducerFrameBeamDecoder([model], dictionary, beam_size=args.beam, nbest=args.nbest,
+                                          beam_size_token=args.transducer_beam_size_token, temperature=args.temperature,
+                                          normalize_scores=not args.unnormalized, lm_model=lm, lm_weight=args.lm_weight)
     return SequenceGenerator(model if isinstance(model, (list, tuple)) else [model], dictionary, beam_size=args.beam, max_len_a=args.max_len_a, max_len_b=args.max_len_b,
                              min_len=args.min_len, normalize_scores=not args.unnormalized, len_penalty=args.lenpen,
                              unk_penalty=args.unkpen, temperature=args.temperature, lm_model=lm, lm_weight=args.lm_weight,
@@ -182,7 +187,7 @@ def get_parser():
     p.add_argument("--wav-scp", required=True)
     p.add_argument("--text", default=None, help="reference transcripts (utt_id tokens...)")
     p.add_argument("--global-cmvn-stats-path", default=None)
-    p.add_argument("--search", default="beam", choices=["beam", "ctc", "ctc_beam", "transducer_greedy", "transducer_beam"])
+    p.add_argument("--search", default="beam", choices=["beam", "ctc", "ctc_beam", "transducer_greedy", "transducer_beam", "transducer_frame_beam"])
     p.add_argument("--beam", type=int, default=10)
     p.add_argument("--nbest", type=int, default=1)
     p.add_argument("--max-len-a", type=float, default=0.08)
@@ -206,6 +211,9 @@ def get_parser():
     p.add_argument("--ctc-beam-size-token", type=int, default=None,
                    help="ctc_beam: candidate tokens per frame (default: min(--beam, vocabulary size - 1), at most 64)")
     p.add_argument("--ctc-insertion-bonus", type=float, default=0.0, help="ctc_beam: score added per emitted token")
+    p.add_argument("--transducer-beam-size-token", type=int, default=None,
+                   help="transducer_frame_beam: extensions per hypothesis and frame (default: min(--beam, vocabulary size - 1), at "
+                        "most 64)")
     p.add_argument("--ngram-lm", default=None,
                    help="ctc_beam: word n-gram LM (plain-text ARPA) fused with --lm-weight under a closed-vocabulary lexicon")
     p.add_argument("--lexicon", default=None,
@@ -265,6 +273,24 @@ def check_ngram_args(args):
         raise NotImplementedError("--ngram-lm fuses the n-gram LM alone: no --lm-path or --word-dict with it")
     if len(args.path.split(os.pathsep)) > 1:
         raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
+
+
+def check_frame_beam_args(args):
+    """--search transducer_frame_beam is the device-resident frame-synchronous beam search of one transducer model, alone or with
+    one sub-word LSTM LM: refused, before anything is loaded, with streaming, hotwords, n-gram / word-level LMs, alignments and
+    ensembles."""
+    if args.search != "transducer_frame_beam":
+        if args.transducer_beam_size_token is not None:
+            raise ValueError("--transducer-beam-size-token configures --search transducer_frame_beam")
+        return
+    for opt, v in (("--streaming", args.streaming), ("--hotwords", args.hotwords), ("--ngram-lm", args.ngram_lm),
+                   ("--word-dict", args.word_dict), ("--print-alignment", args.print_alignment is not None)):
+        if v:
+            raise NotImplementedError(f"--search transducer_frame_beam is not implemented with {opt}")
+    if args.lm_path and len(args.lm_path.split(os.pathsep)) != 1:
+        raise NotImplementedError("--search transducer_frame_beam fuses one sub-word LSTM LM: no multi-level --lm-path a:b")
+    if len(args.path.split(os.pathsep)) > 1:
+        raise NotImplementedError("--search transducer_frame_beam takes one model: ensembles (--path a.pt:b.pt) are not implemented")
 
 
 DEFAULT_HOTWORD_SCORE = 1.5
@@ -491,6 +517,7 @@ def load_member(state, name, block, task, dev):
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
+    check_frame_beam_args(args)
     if args.print_alignment is not None and not args.results_path:
         raise ValueError("--print-alignment saves attention plots under --results-path: give --results-path")
     check_hotword_args(args)
@@ -546,6 +573,11 @@ def main(argv=None):
         if cfg0 is None or not hasattr(cfg0, "encoder") or not hasattr(cfg0.encoder, "chunk_size"):
             raise NotImplementedError(f"--streaming needs a chunk-streaming transformer encoder model, not {model_name}")
         check_streamable(cfg0)
+    if args.search == "transducer_frame_beam":  # before the weights are loaded: the model class must be a transducer
+        from . import registry
+
+        if not hasattr(registry.MODEL_REGISTRY[model_name], "joint_step"):
+            raise NotImplementedError(f"--search transducer_frame_beam needs a transducer model (predictor + joint), not {model_name}")
     model = load_member(state, model_name, model_cfg, task, dev)
     members = [model]
     for extra in paths[1:]:  # every member is rebuilt from ITS OWN checkpoint's configuration (checkpoint_utils.load_model_ensemble)

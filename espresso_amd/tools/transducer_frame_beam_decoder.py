@@ -1,0 +1,157 @@
+"""TransducerFrameBeamDecoder — frame-synchronous transducer beam search (at most one symbol per encoder frame and hypothesis,
+equal token sequences merged: the "modified beam search" of other toolkits) with optional shallow fusion of one sub-word LSTM
+LM, with the `generate` / `decode` API of the other transducer decoders.  The reference has no such search: its beam search
+is the modified Adaptive Expansion Search (tools/transducer_beam_search_decoder.py, kept as it is), whose bookkeeping lives on
+the host.  The contract is DESIGN.md section 3.5 and the header of csrc/rnnt_beam.hip.
+
+One encoder pass and one `joint_encoder_branch`; then per frame: gather this frame's rows of the encoder branch for the
+B * beam slots, `joint_step`, the step kernels (log-softmax, fusion, per-row top K, merge, selection: csrc/rnnt_beam.hip), and
+`reorder_state` + `advance(token, state, keep_row)` for the predictor (and the LM, its output layer and log-softmax).  Beam,
+prefix table and selection live in a device workspace; the loop runs over the padded frame count (frames past an
+utterance's length are no-ops in the kernel) and never synchronises with the host.
+
+The LM fusion is the mass-preserving one of the two other transducer decoders (transducer_greedy_decoder.py): non-blank
+log-probs get lm_weight * log P_lm and are renormalised to the non-blank mass they had; blank is untouched."""
+from typing import Dict, List
+
+import torch
+
+from .. import kernels as K
+
+
+class TransducerFrameBeamDecoder:
+    MAX_BEAM = 64
+
+    def __init__(self, models, dictionary, beam_size=5, nbest=1, beam_size_token=None, temperature=1.0, normalize_scores=True,
+                 lm_model=None, lm_weight=0.0, model_predicts_eos=False, bos=None, blank=None, eos=None, pad=None,
+                 symbols_to_strip_from_output=None, print_alignment=False, **kwargs):
+        if isinstance(models, (list, tuple)):
+            if len(models) != 1:
+                raise NotImplementedError("the frame-synchronous transducer beam search takes one model: ensembles are not implemented")
+            models = models[0]
+        if print_alignment:
+            raise NotImplementedError("the frame-synchronous transducer beam search produces no alignments (print_alignment)")
+        self.model = models
+        self.eos = dictionary.eos() if eos is None else eos
+        self.bos = dictionary.eos() if bos is None else bos
+        self.blank = dictionary.bos() if blank is None else blank
+        self.pad = dictionary.pad() if pad is None else pad
+        self.model_predicts_eos = model_predicts_eos
+        strip = {self.eos, self.bos, self.blank}
+        self.symbols_to_strip_from_output = strip.union(symbols_to_strip_from_output) if symbols_to_strip_from_output else strip
+        self.vocab_size = V = len(dictionary)
+        if not 1 <= beam_size <= self.MAX_BEAM:
+            raise ValueError(f"transducer frame beam search: beam {beam_size} outside [1, {self.MAX_BEAM}]")
+        self.beam_size = beam_size
+        self.beam_size_token = min(beam_size, V - 1) if beam_size_token is None else beam_size_token
+        if not 1 <= self.beam_size_token <= min(self.MAX_BEAM, V - 1):
+            raise ValueError(f"transducer frame beam search: --transducer-beam-size-token {self.beam_size_token} outside "
+                             f"[1, {min(self.MAX_BEAM, V - 1)}]")
+        if not 1 <= nbest <= beam_size:
+            raise ValueError(f"transducer frame beam search: nbest {nbest} outside [1, beam {beam_size}]")
+        self.nbest = nbest
+        if not temperature > 0:
+            raise ValueError("--temperature must be greater than 0")
+        self.temperature = float(temperature)
+        self.normalize_scores = bool(normalize_scores)
+        if self.model is not None:
+            self.model.eval()
+        self.lm_model, self.lm_weight = lm_model, float(lm_weight)
+        self.no_blank_in_lm = False
+        if lm_model is not None:
+            nlm = len(lm_model.decoder.dictionary)
+            if nlm not in (V, V - 1):
+                raise ValueError(f"transducer frame beam search: the LM's dictionary has {nlm} entries, the model's {V}: it must "
+                                 "be the same dictionary, or that dictionary without the blank")
+            self.no_blank_in_lm = nlm == V - 1
+            lm_model.eval()
+
+    def cuda(self):
+        self.model.cuda()
+        if self.lm_model is not None:
+            self.lm_model.cuda()
+        return self
+
+    # ---------------------------------------------------------------- LM state of the beams
+    def _lm_tokens(self, tokens):
+        return torch.where(tokens > self.blank, tokens - 1, tokens) if self.no_blank_in_lm else tokens
+
+    def _lm_rows(self, feat):
+        logits = self.lm_model.decoder.output_layer(feat)
+        return K.log_softmax(logits, logits.shape[0], logits.shape[1], logits.stride(0))
+
+    def lm_start(self, N, device):
+        """LSTM state and log-prob rows fp32 [N][V or V - 1] of N empty hypotheses (the LM's eos as BOS)."""
+        lmd = self.lm_model.decoder
+        state = lmd.init_state(N, device)
+        feat, state = lmd.advance(self._lm_tokens(torch.full((N,), self.eos, dtype=torch.int32, device=device)), state)
+        return state, self._lm_rows(feat)
+
+    def lm_update(self, state, parent, token, keep):
+        """After one step: every row continues row `parent` of the previous frame; rows with keep == 0 appended `token`, the
+        others keep their parent's LM state (and so recompute its row)."""
+        lmd = self.lm_model.decoder
+        state = lmd.reorder_state(state, parent)
+        feat, state = lmd.advance(self._lm_tokens(token), state, keep_row=keep)
+        return state, self._lm_rows(feat)
+
+    # ---------------------------------------------------------------- the search
+    @torch.no_grad()
+    def search(self, E, enc_len, bos_token=None):
+        """E fp32 [B][T'][J] (the joint's encoder branch, `joint_encoder_branch`), enc_len int [B] on the device -> device
+        tensors (tokens int32 [B][nbest][T'] pad-filled, lengths int32 [B][nbest], scores fp32 [B][nbest] natural log, nhyp
+        int32 [B]), best first.  No host synchronisation."""
+        model, dec = self.model, self.model.decoder
+        B, Tp, J = E.shape
+        dev, beam, V = E.device, self.beam_size, self.vocab_size
+        N = B * beam
+        E = E.contiguous().view(B * Tp, J)
+        in_len = enc_len.to(device=dev, dtype=torch.int32).contiguous()
+        # everything the loop needs, allocated before it: the encoder rows of every (frame, slot), the triples, the workspace
+        rows = (torch.arange(B, device=dev, dtype=torch.int32) * Tp).repeat_interleave(beam)
+        frame_rows = (rows.unsqueeze(0) + torch.arange(Tp, device=dev, dtype=torch.int32).unsqueeze(1)).contiguous()  # [T'][N]
+        out = (torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
+               torch.empty(N, dtype=torch.uint8, device=dev))
+        ws = K.rnnt_frame_beam_workspace(B, Tp, beam, dev)
+        state = dec.init_state(N, dev)
+        dec_out, state = dec.advance(torch.full((N,), self.bos if bos_token is None else bos_token, dtype=torch.int32, device=dev), state)
+        lm_state = lm_rows = None
+        if self.lm_model is not None:
+            lm_state, lm_rows = self.lm_start(N, dev)
+        step = dict(B=B, T=Tp, V=V, beam=beam, K=self.beam_size_token, blank=self.blank, eos=self.eos if self.model_predicts_eos else -1,
+                    temperature=self.temperature, lm_weight=self.lm_weight, lm_no_blank=self.no_blank_in_lm)
+        for t in range(Tp):
+            logits = model.joint_step(K.gather_rows(E, frame_rows[t]), dec_out)
+            K.rnnt_frame_beam_step(logits, in_len, ws, out, t=t, lm_rows=lm_rows, **step)
+            state = dec.reorder_state(state, out[0])
+            dec_out, state = dec.advance(out[1], state, keep_row=out[2])
+            if self.lm_model is not None:
+                lm_state, lm_rows = self.lm_update(lm_state, *out)
+        return K.rnnt_frame_beam_finish(ws, B, Tp, beam, self.nbest, self.pad, normalize=self.normalize_scores)
+
+    @torch.no_grad()
+    def encode(self, sample):
+        """(E fp32 [B][T'][J], encoder output lengths [B]) of a sample: the encoder and the joint's encoder branch, once."""
+        net_input = sample["net_input"]
+        enc = self.model.encoder(net_input["src_tokens"], net_input["src_lengths"])
+        x = enc["_x_bt"][0]
+        enc_len = enc["src_lengths"][0]
+        B = enc_len.shape[0]
+        return self.model.joint_encoder_branch(x).view(B, x.shape[0] // B, -1), enc_len
+
+    @torch.no_grad()
+    def _generate(self, sample, bos_token=None):
+        return self.search(*self.encode(sample), bos_token=bos_token)
+
+    @torch.no_grad()
+    def decode(self, models, sample, **kwargs):
+        """(1-best tokens B x U padded with pad, scores B, None) — the validation-time API of the transducer decoders."""
+        tokens, lengths, scores, _ = self._generate(sample)
+        U = max(1, int(lengths[:, 0].max()))
+        return tokens[:, 0, :U].to(torch.long), scores[:, 0], None
+
+    @torch.no_grad()
+    def generate(self, models, sample, **kwargs) -> List[List[Dict[str, torch.Tensor]]]:
+        tokens, lengths, scores, nhyp = (t.cpu() for t in self._generate(sample, bos_token=kwargs.get("bos_token", None)))
+        return [[{"tokens": tokens[b, i, : int(lengths[b, i])].to(torch.long), "score": scores[b, i], "attention": None,
+                  "alignment": None} for i in range(int(nhyp[b]))] for b in range(tokens.shape[0])]

@@ -465,6 +465,33 @@ int ea_context_graph_score_host(const int* nodes_host, const int* edges_host, co
 int ea_context_graph_score(const int* nodes, const int* edges, const int* root, int n_nodes, int n_edges, int V,
                            const int* tokens, const int* lens, int N, int L, float* running, float* final_bias, int* q_out,
                            ea_stream_t stream);
+/* Frame-synchronous transducer beam search (csrc/rnnt_beam.hip; at most one symbol per encoder frame and hypothesis, equal
+ * token sequences merged — "modified beam search") with optional mass-preserving shallow fusion of one sub-word LM: the
+ * transducer counterpart of ea_ctc_prefix_beam_*.  Hypotheses are distinct token sequences with a score (natural log), at most
+ * `beam` per utterance, best first; they live in `workspace` (ea_rnnt_frame_beam_workspace_bytes(B, T, beam) bytes, any
+ * contents: the step with t == 0 initialises it).  beam <= 64; K (extensions per hypothesis and frame) <= min(64, V - 1);
+ * V <= 65535; bad arguments return -2 and launch nothing.
+ * ea_rnnt_frame_beam_step: frame t (0 <= t < T; frames >= in_len[b] leave utterance b unchanged).  logits: the joint's fp32
+ *   logits of THIS frame, [B*beam][ld], row b * beam + slot — the step never sees the encoder, so the state between two calls
+ *   is exactly the workspace (a streamed search can feed it frame by frame).  Rows of dead slots (slot >= number of
+ *   hypotheses) are not read.  Per live row: r = log_softmax(logits[:V] / temperature); with lm_rows (fp32 [B*beam][ld_lm],
+ *   log P_lm(. | hypothesis of that slot), finite entries; NULL or lm_weight == 0 = no LM, the rows are not read)
+ *   f_v = r_v + lm_weight * lm_v for v != blank, renormalised so that the
+ *   non-blank mass of r is kept, r_blank untouched (lm_no_blank != 0: the LM has V - 1 entries and token v > blank reads
+ *   column v - 1); with eos >= 0 (-1 = none) r_blank = logaddexp(r_blank, r_eos) and r_eos = -inf.  Candidates: the stay
+ *   (score + r_blank) and the extensions by the K non-blank tokens with the largest finite r_v (ties: lower id); an extension
+ *   equal to a hypothesis of the beam merges into that hypothesis' stay (log-add-exp); the `beam` best finite candidates
+ *   survive (ties: parent slot, stay before extension, token id).  For every slot the step writes parent int32 [B*beam] (row
+ *   of the previous frame it continues), token int32 [B*beam] (the token it appended; blank for a stay) and keep uint8
+ *   [B*beam] (1 = stay: the predictor / LM state of the parent row stands).
+ * ea_rnnt_frame_beam_finish: final score = the score, or with normalize != 0 score / max(1, length); the nbest best per
+ *   utterance, sorted (ties: slot); outputs as ea_ctc_prefix_beam_finish. */
+long ea_rnnt_frame_beam_workspace_bytes(int B, int T, int beam);
+int ea_rnnt_frame_beam_step(const float* logits, long ld, const float* lm_rows, long ld_lm, int lm_no_blank, const int* in_len,
+                            void* workspace, int* parent, int* token, void* keep, int B, int T, int V, int beam, int K, int blank,
+                            int eos, float temperature, float lm_weight, int t, ea_stream_t stream);
+int ea_rnnt_frame_beam_finish(void* workspace, int B, int T, int beam, int nbest, int pad, int normalize, int* tokens,
+                              int* lengths, float* scores, int* nhyp, ea_stream_t stream);
 /* Word n-gram LM (ARPA) and lexicon-constrained CTC prefix beam search with its fusion (csrc/ctc_lexicon_beam.hip) — the
  * search the reference takes from Flashlight's KenLM lexicon decoder (espresso/tools/ctc_decoder.py:24-71).
  * ea_ngram_create: parses a plain-text ARPA file of order <= 6 at `path` into host tables and writes an opaque handle to
