@@ -27,6 +27,30 @@
 // would run the 7-pass select over V serially for `beam` rows on 24 of 256 CUs.
 // Prefix table as ctc_beam.hip: a canonical node per token sequence (hash of (parent node, token)), node ids in creation
 // order, cap = 1 + T * beam; sequence equality is node equality: y_j + v == y_i  <=>  node(y_j) == pnode(y_i) && last(y_i) == v.
+//
+// The streamed search (ea_rnnt_frame_beam_stream_*): the same frames, one per call, for streams that come and go.  What the
+// offline workspace holds per utterance is kept per stream SLOT in a caller-allocated buffer, behind a two-word head (frames
+// consumed, 0); the frame number comes from that counter instead of `t` and `in_len`.  State of one slot, int32 words:
+//   words(max_frames, beam) = 2 + even(3 * tsize + 5 * beam + 2 + 2 * cap + 2 * beam + 2 * beam * 64)
+//   cap = 1 + max_frames * beam,  tsize = the smallest power of two >= max(64, 2 * cap),  even(w) = w rounded up to even
+// (hash keys 2 * tsize, hash values tsize; score / len / last / node / pnode; the two counters; node_par and node_tok; and the
+// row-to-select hand-over rblank, rnc, ctok, cval, which lives in the slot as it lives in the offline workspace).  Row phase,
+// select phase, the state before frame 0 and the finish are __device__ functions over a view of that state (RnntWs), which
+// the streamed kernels run.  They restate the offline kernels' bodies line by line; the offline kernels keep their own bodies
+// (calling the shared functions from them cost 1.9 % of the offline step), and the tests hold the two to
+// each other with torch.equal: a stream fed in any pieces gives, bit for bit, what the offline search gives for the whole
+// utterance, and a state sized for max_frames
+// what a workspace sized for T gives (node ids are creation order; no rule looks at the table size).  Within one frame the
+// order in which the fresh nodes get their ids is arbitrary (the selected candidates reach their lanes through an atomic
+// counter); no result depends on it, only parent id < child id does.  "Bit for bit" is a statement about results (triples,
+// finish, partial), not about the bytes of a state buffer: do not compare those across runs.  Table entries are
+// published by atomics and read through L1-bypassing loads; everything else is ordered by the kernel boundaries.
+//
+// Kernels of the streamed search, LDS and occupancy (gfx950: 160 KB LDS per CU), equal to their offline twins:
+//   rnnt_beam_stream_row_kernel     256 threads, 21848 B LDS (RowLds), 46 VGPRs -> 7 workgroups per CU by LDS
+//   rnnt_beam_stream_select_kernel  256 threads, 69912 B LDS (SelLds), 39 VGPRs -> 2 workgroups per CU by LDS
+//   rnnt_beam_stream_reset_kernel   256 threads, no LDS;  rnnt_beam_stream_finish_kernel 64 threads, 256 B;
+//   rnnt_beam_stream_partial_kernel 64 threads (one wave per slot), no LDS
 #include "common.h"
 #include "ctc_beam_common.h"
 #include "espresso_amd.h"
@@ -63,6 +87,26 @@ __host__ __device__ __forceinline__ long rnnt_ws_words(int T, int beam) {  // 4-
   return (w + 1) & ~1L;
 }
 
+__device__ __forceinline__ RnntWs rnnt_ws_at(int* base, int T, int beam) {
+  RnntWs w;
+  w.cap = (int)rnnt_ws_cap(T, beam);
+  w.tsize = (int)rnnt_ws_tsize(T, beam);
+  w.tab_key = (unsigned long long*)base;
+  w.tab_val = base + 2L * w.tsize;
+  w.score = (float*)(w.tab_val + w.tsize);
+  w.len = (int*)(w.score + beam);
+  w.last = w.len + beam;
+  w.node = w.last + beam;
+  w.pnode = w.node + beam;
+  w.cnt = w.pnode + beam;
+  w.node_par = w.cnt + 2;
+  w.node_tok = w.node_par + w.cap;
+  w.rblank = (float*)(w.node_tok + w.cap);
+  w.rnc = (int*)(w.rblank + beam);
+  w.ctok = w.rnc + beam;
+  w.cval = (float*)(w.ctok + (long)beam * kMaxK);
+  return w;
+}
 __device__ __forceinline__ RnntWs rnnt_ws(void* ws, int b, int T, int beam) {
   RnntWs w;
   w.cap = (int)rnnt_ws_cap(T, beam);
@@ -85,6 +129,273 @@ __device__ __forceinline__ RnntWs rnnt_ws(void* ws, int b, int T, int beam) {
   return w;
 }
 
+// ------------------------------------------------------------------------------------------------ the shared phases
+struct RowParams {  // what the row phase needs besides its row, the same for the offline and the streamed search
+  int V, K, blank, eos, lm_no_blank;
+  float temperature, lm_weight;
+};
+
+struct RowLds {
+  float row[kRowLds];
+  SelectScratch sel;
+  float red[16];
+  int cunsorted[kMaxK];
+  int nc;
+};
+
+// steps 1 - 3 of the contract and the top K of the row x (LM row m or null) of live slot j; leaves the hand-over in w
+__device__ __forceinline__ void rnnt_row_phase(RowLds& s, const RowParams& a, const RnntWs& w, const float* x, const float* m, int j) {
+  const int tid = threadIdx.x;
+  const int V = a.V, blank = a.blank, eos = a.eos;
+  const float temp = a.temperature, lw = a.lm_weight;
+  auto lm_col = [&](int v) { return a.lm_no_blank && v > blank ? v - 1 : v; };
+
+  // 1. z = logits / temperature to LDS; max, log-sum-exp, and the non-blank part of the sum
+  float mx = -INFINITY;
+  for (int v = tid; v < V; v += 256) {
+    const float z = x[v] / temp;
+    if (v < kRowLds) s.row[v] = z;
+    mx = fmaxf(mx, z);
+  }
+  mx = block_max(mx, s.red);
+  auto z_of = [&](int v) { return v < kRowLds ? s.row[v] : x[v] / temp; };
+  float sa = 0.f, snb = 0.f;
+  for (int v = tid; v < V; v += 256) {
+    const float e = expf(z_of(v) - mx);
+    sa += e;
+    snb += v == blank ? 0.f : e;
+  }
+  sa = block_sum(sa, s.red);
+  snb = block_sum(snb, s.red);
+  const float lse = mx + logf(sa);
+  float rb = z_of(blank) - lse;
+  float shift = -lse;  // r_v = (what LDS holds for v) + shift
+
+  // 2. fusion: f_v replaces z_v for v != blank; the shift gives the fused row the non-blank mass of the unfused one
+  if (m) {
+    float fm = -INFINITY;
+    for (int v = tid; v < V; v += 256) {
+      if (v == blank) continue;
+      const float f = z_of(v) - lse + lw * m[lm_col(v)];
+      if (v < kRowLds) s.row[v] = f;
+      fm = fmaxf(fm, f);
+    }
+    fm = block_max(fm, s.red);
+    auto f_of = [&](int v) { return v < kRowLds ? s.row[v] : x[v] / temp - lse + lw * m[lm_col(v)]; };
+    float sf = 0.f;
+    for (int v = tid; v < V; v += 256) sf += v == blank ? 0.f : expf(f_of(v) - fm);
+    sf = block_sum(sf, s.red);
+    shift = logf(snb) - logf(sa) - (fm + logf(sf));
+  }
+  auto r_of = [&](int v) {
+    if (v < kRowLds) return s.row[v] + shift;
+    return (m ? x[v] / temp - lse + lw * m[lm_col(v)] : x[v] / temp) + shift;
+  };
+  // 3. the model's eos counts as blank
+  if (eos >= 0) rb = lae(rb, r_of(eos));
+
+  // 4. the K non-blank tokens with the largest finite r, listed in token-id order
+  auto tok_key = [&](int v) -> uint64_t {
+    if (v == blank || v == eos) return 0ull;
+    const float r = r_of(v);
+    return isfinite(r) ? mk_key(r, v) : 0ull;
+  };
+  const uint64_t kth = select_nth(tok_key, V, a.K, s.sel);
+  if (tid == 0) s.nc = 0;
+  __syncthreads();
+  for (int v = tid; v < V; v += 256) {
+    const uint64_t k = tok_key(v);
+    if (k && k >= kth) s.cunsorted[atomicAdd(&s.nc, 1)] = v;
+  }
+  __syncthreads();
+  const int nc = s.nc;  // <= K: the keys are unique
+  if (tid < nc) {
+    const int v = s.cunsorted[tid];
+    int r = 0;
+    for (int i = 0; i < nc; ++i) r += s.cunsorted[i] < v;
+    w.ctok[(long)j * kMaxK + r] = v;
+    w.cval[(long)j * kMaxK + r] = r_of(v);
+  }
+  if (tid == 0) { w.rblank[j] = rb; w.rnc[j] = nc; }
+}
+
+// the state before frame 0: the empty hypothesis with score 0 in slot 0, node 0 in an empty table (blockDim 256; the caller
+// synchronises)
+__device__ __forceinline__ void rnnt_init(const RnntWs& w) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < w.tsize; i += 256) w.tab_key[i] = 0ull;
+  if (tid == 0) {
+    w.score[0] = 0.f; w.len[0] = 0; w.last[0] = -1; w.node[0] = 0; w.pnode[0] = -1;
+    w.cnt[0] = 1; w.cnt[1] = 1;
+    w.node_par[0] = -1; w.node_tok[0] = -1;
+  }
+}
+
+// the triple of a beam that stands still: parent = identity, no token, every state kept
+__device__ __forceinline__ void rnnt_identity(int* parent, int* token, uint8_t* keep, long row0, int beam, int blank) {
+  const int tid = threadIdx.x;
+  if (tid < beam) { parent[row0 + tid] = (int)(row0 + tid); token[row0 + tid] = blank; keep[row0 + tid] = 1; }
+}
+
+struct SelLds {
+  uint64_t key[kMaxCand];
+  SelectScratch sel;
+  int ctok[kMaxBeam * kMaxK];  // [slot][K]
+  float cval[kMaxBeam * kMaxK];
+  float score[kMaxBeam], rb[kMaxBeam], stay[kMaxBeam];
+  int len[kMaxBeam], last[kMaxBeam], node[kMaxBeam], pnode[kMaxBeam], nc[kMaxBeam];
+  unsigned long long merged[kMaxBeam];  // bit r of slot j: extension (j, r) merged into a stay
+  int sel_idx[kMaxBeam];
+  int nsel, nfresh;
+};
+
+// merge, selection and the new state of one beam with nh hypotheses and nnodes table nodes; the triples go to rows row0 ...
+__device__ __forceinline__ void rnnt_select_phase(SelLds& s, const RnntWs& w, int beam, int K, int blank, int nh, int nnodes,
+                                                  int* parent, int* token, uint8_t* keep, long row0) {
+  const int tid = threadIdx.x;
+  const int K1 = K + 1;
+  if (tid < nh) {
+    s.score[tid] = w.score[tid]; s.len[tid] = w.len[tid]; s.last[tid] = w.last[tid]; s.node[tid] = w.node[tid];
+    s.pnode[tid] = w.pnode[tid]; s.rb[tid] = w.rblank[tid]; s.nc[tid] = w.rnc[tid];
+    s.merged[tid] = 0ull;
+  }
+  for (int i = tid; i < nh * K; i += 256) {  // (entries at or beyond a row's count are never used)
+    const int j = i / K, r = i - j * K;
+    s.ctok[i] = w.ctok[(long)j * kMaxK + r];
+    s.cval[i] = w.cval[(long)j * kMaxK + r];
+  }
+  __syncthreads();
+
+  // stays; a stay absorbs the extension y' + v == y (y' in the beam, v among its candidates)
+  if (tid < nh) {
+    float st = s.score[tid] + s.rb[tid];
+    if (s.len[tid] > 0) {
+      int src = -1;
+      for (int j = 0; j < nh; ++j) src = s.node[j] == s.pnode[tid] ? j : src;
+      if (src >= 0) {
+        const int nc = min(s.nc[src], K);
+        for (int r = 0; r < nc; ++r)
+          if (s.ctok[src * K + r] == s.last[tid]) {
+            atomicOr(&s.merged[src], 1ull << r);
+            st = lae(st, s.score[src] + s.cval[src * K + r]);
+          }
+      }
+    }
+    s.stay[tid] = st;
+  }
+  __syncthreads();
+
+  // candidates; index i = slot * (K + 1) + (0: stay, 1 + r: extension by the slot's r-th candidate token)
+  const int N = nh * K1;
+  for (int i = tid; i < N; i += 256) {
+    const int j = i / K1, q = i - j * K1;
+    float sc = NAN;
+    if (q == 0) sc = s.stay[j];
+    else if (q - 1 < s.nc[j] && !((s.merged[j] >> (q - 1)) & 1ull)) sc = s.score[j] + s.cval[j * K + q - 1];
+    s.key[i] = isfinite(sc) ? mk_key(sc, i) : 0ull;
+  }
+  __syncthreads();
+  const uint64_t cth = select_nth([&](int i) { return s.key[i]; }, N, beam, s.sel);
+  if (tid == 0) s.nsel = 0;
+  __syncthreads();
+  for (int i = tid; i < N; i += 256) {
+    const uint64_t k = s.key[i];
+    if (k && k >= cth) s.sel_idx[atomicAdd(&s.nsel, 1)] = i;
+  }
+  __syncthreads();
+  const int ns = s.nsel;
+
+  // the new state (wave 0: lane = one selected candidate, written to slot = its rank)
+  float n_score = 0.f;
+  int n_len = 0, n_last = -1, n_node = 0, n_pnode = -1, slot = 0, par = 0, ext = 0, fresh = 0, tslot = -1;
+  if (tid < ns) {
+    const int i = s.sel_idx[tid];
+    const uint64_t k = s.key[i];
+    for (int m = 0; m < ns; ++m) slot += s.key[s.sel_idx[m]] > k;
+    const int j = i / K1, q = i - j * K1;
+    par = j;
+    if (q == 0) {
+      n_score = s.stay[j]; n_len = s.len[j]; n_last = s.last[j]; n_node = s.node[j]; n_pnode = s.pnode[j];
+    } else {
+      ext = 1;
+      n_score = s.score[j] + s.cval[j * K + q - 1];
+      n_len = s.len[j] + 1; n_last = s.ctok[j * K + q - 1]; n_pnode = s.node[j];
+      // the node of y_j + v: found in the hash table, or claimed there (distinct keys within one frame)
+      const unsigned long long key = ((unsigned long long)(n_pnode + 1) << 32) | (uint32_t)n_last;
+      const uint32_t mask = (uint32_t)w.tsize - 1u;
+      for (uint32_t h = tab_hash(key) & mask;; h = (h + 1) & mask) {
+        const unsigned long long cur = ld_l2(w.tab_key + h);
+        if (cur == key) { n_node = ld_l2(w.tab_val + h); break; }
+        if (cur == 0ull && atomicCAS(w.tab_key + h, 0ull, key) == 0ull) { fresh = 1; tslot = (int)h; break; }
+      }
+    }
+  }
+  if (tid < 64) {  // fresh nodes numbered in lane order (which candidate a lane holds is arbitrary: see the header)
+    const unsigned long long fm = __ballot(fresh);
+    if (fresh) {
+      const int id = nnodes + __popcll(fm & ((1ull << tid) - 1ull));
+      n_node = id;
+      w.tab_val[tslot] = id;
+      if (id < w.cap) { w.node_par[id] = n_pnode; w.node_tok[id] = n_last; }
+    }
+    if (tid == 0) s.nfresh = __popcll(fm);
+  }
+  __syncthreads();
+  if (tid < ns) {
+    w.score[slot] = n_score; w.len[slot] = n_len; w.last[slot] = n_last; w.node[slot] = n_node; w.pnode[slot] = n_pnode;
+    parent[row0 + slot] = (int)(row0 + par);
+    token[row0 + slot] = ext ? n_last : blank;
+    keep[row0 + slot] = (uint8_t)!ext;
+  } else if (tid < beam) {  // empty slot: any valid row
+    parent[row0 + tid] = (int)row0; token[row0 + tid] = blank; keep[row0 + tid] = 1;
+  }
+  if (tid == 0) { w.cnt[0] = ns; w.cnt[1] = nnodes + s.nfresh; }
+}
+
+// final score = s, or s / max(1, |y|); the nbest best of the nh hypotheses by (-final, slot), backtracked into tokens
+// [nbest][max_u] (pad-filled), lengths / scores [nbest] and *nhyp.  fresh: no step has run, the beam is the empty hypothesis
+// and w is not read.  Reads the state only (blockDim 64).
+__device__ __forceinline__ void rnnt_finish(float* s_fin, const RnntWs& w, int nh, bool fresh, int nbest, int pad, int normalize,
+                                            int max_u, int* tokens, int* lengths, float* scores, int* nhyp) {
+  const int j = threadIdx.x;
+  if (j < nh) {
+    const float s = fresh ? 0.f : w.score[j];
+    const int n = fresh ? 0 : w.len[j];
+    s_fin[j] = normalize ? s / (float)max(1, n) : s;
+  }
+  __syncthreads();
+  if (j == 0) *nhyp = min(nh, nbest);
+  if (j < nh) {
+    const float s = s_fin[j];
+    int rank = 0;
+    for (int m = 0; m < nh; ++m) rank += s_fin[m] > s || (s_fin[m] == s && m < j);
+    if (rank < nbest) {
+      int* out = tokens + (long)rank * max_u;
+      const int len = fresh ? 0 : w.len[j];
+      const int n = min(len, max_u);
+      for (int u = n; u < max_u; ++u) out[u] = pad;
+      int node = fresh ? 0 : w.node[j];
+      for (int u = len - 1; u >= 0 && node > 0 && node < w.cap; --u) {
+        if (u < max_u) out[u] = w.node_tok[node];
+        node = w.node_par[node];
+      }
+      lengths[rank] = n;
+      scores[rank] = s;
+    }
+  }
+  for (int r = nh + j; r < nbest; r += 64) {
+    int* out = tokens + (long)r * max_u;
+    for (int u = 0; u < max_u; ++u) out[u] = pad;
+    lengths[r] = 0;
+    scores[r] = -INFINITY;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ the offline search
+// The offline kernels keep their own bodies, as they were before the search was streamed: their machine code is that of the
+// earlier build, instruction for instruction (checked by disassembly), so their time cannot have changed.  The streamed kernels
+// below run the shared phases above, which restate these bodies line by line; tests/test_streaming_transducer_beam.py holds the
+// two to each other with torch.equal.  A change to a tie rule, the merge or a select has to be made in both places.
 struct RowArgs {
   const float* logits; long ld;
   const float* lm_rows; long ld_lm; int lm_no_blank;
@@ -353,7 +664,157 @@ __global__ __launch_bounds__(64) void rnnt_beam_finish_kernel(void* ws, int T, i
   }
 }
 
+// ------------------------------------------------------------------------------------------------ the streamed search
+// State of one stream slot, int32 words: [0] frames consumed, [1] 0, then the offline workspace of one utterance of max_frames
+// frames (RnntWs: the row-to-select hand-over included).
+__host__ __device__ __forceinline__ long rnnt_state_words(int max_frames, int beam) { return 2 + rnnt_ws_words(max_frames, beam); }
+
+struct RnntSlot {
+  int* head;
+  RnntWs w;
+};
+__device__ __forceinline__ RnntSlot rnnt_slot(void* state, int slot, int max_frames, int beam) {
+  RnntSlot q;
+  q.head = (int*)state + (long)slot * rnnt_state_words(max_frames, beam);
+  q.w = rnnt_ws_at(q.head + 2, max_frames, beam);
+  return q;
+}
+
+__global__ __launch_bounds__(256) void rnnt_beam_stream_reset_kernel(void* state, const int* slots, int max_streams, int max_frames,
+                                                                     int beam) {
+  const int slot = slots[blockIdx.x];
+  if (slot < 0 || slot >= max_streams) return;
+  const RnntSlot q = rnnt_slot(state, slot, max_frames, beam);
+  rnnt_init(q.w);
+  if (threadIdx.x == 0) { q.head[0] = 0; q.head[1] = 0; }
+}
+
+struct StreamRowArgs {
+  const float* logits; long ld;
+  const float* lm_rows; long ld_lm;
+  const int *slot_idx, *n_new; void* state;
+  RowParams p;
+  int max_streams, max_frames, beam, j;
+};
+
+// the row phase of the streamed search, one workgroup per (listed stream, slot of its beam)
+__global__ __launch_bounds__(256) void rnnt_beam_stream_row_kernel(const StreamRowArgs a) {
+  __shared__ RowLds s;
+  const int n = blockIdx.x, b = n / a.beam, j = n - b * a.beam;
+  const int slot = a.slot_idx[b];
+  if (slot < 0 || slot >= a.max_streams || a.j >= a.n_new[b]) return;
+  const RnntSlot q = rnnt_slot(a.state, slot, a.max_frames, a.beam);
+  const int frames = q.head[0];
+  if (frames < 0 || frames >= a.max_frames) return;  // a full slot
+  if (j >= q.w.cnt[0]) return;                       // dead slot: the row is not read
+  rnnt_row_phase(s, a.p, q.w, a.logits + (long)n * a.ld, a.lm_rows ? a.lm_rows + (long)n * a.ld_lm : nullptr, j);
+}
+
+struct StreamSelArgs {
+  const int *slot_idx, *n_new; void* state;
+  int* parent; int* token; uint8_t* keep;
+  int max_streams, max_frames, beam, K, blank, j;
+};
+
+// the select phase of the streamed search, one workgroup per listed stream; counts the frame
+__global__ __launch_bounds__(256) void rnnt_beam_stream_select_kernel(const StreamSelArgs a) {
+  __shared__ SelLds s;
+  const int b = blockIdx.x;
+  const long row0 = (long)b * a.beam;
+  const int slot = a.slot_idx[b];
+  bool due = slot >= 0 && slot < a.max_streams && a.j < a.n_new[b];
+  const RnntSlot q = rnnt_slot(a.state, due ? slot : 0, a.max_frames, a.beam);
+  const int frames = due ? q.head[0] : -1;
+  due = due && frames >= 0 && frames < a.max_frames;
+  if (!due) {  // idle, no such slot, or a full slot: the slot is untouched
+    rnnt_identity(a.parent, a.token, a.keep, row0, a.beam, a.blank);
+    return;
+  }
+  const int nh = min(max(q.w.cnt[0], 0), a.beam);
+  rnnt_select_phase(s, q.w, a.beam, a.K, a.blank, nh, q.w.cnt[1], a.parent, a.token, a.keep, row0);
+  if (threadIdx.x == 0) q.head[0] = frames + 1;
+}
+
+struct StreamReadArgs {
+  const void* state; const int* slots;
+  int max_streams, max_frames, beam, nbest, pad, normalize, max_u;
+  int *tokens, *lengths; float* scores; int* aux;  // aux: nhyp (finish) / stable_len (partial)
+};
+
+// readout of the given slots, as the offline kernel finishes; the state is read only
+__global__ __launch_bounds__(64) void rnnt_beam_stream_finish_kernel(const StreamReadArgs a) {
+  __shared__ float s_fin[kMaxBeam];
+  const int b = blockIdx.x, slot = a.slots[b];
+  const bool valid = slot >= 0 && slot < a.max_streams;  // no such slot: no hypothesis
+  const RnntSlot q = rnnt_slot((void*)a.state, valid ? slot : 0, a.max_frames, a.beam);
+  rnnt_finish(s_fin, q.w, valid ? min(max(q.w.cnt[0], 0), a.beam) : 0, false, a.nbest, a.pad, a.normalize, a.max_u,
+              a.tokens + (long)b * a.nbest * a.max_u, a.lengths + b * a.nbest, a.scores + b * a.nbest, a.aux + b);
+}
+
+// The live hypothesis with the best score s (what the search prunes by; ties: the lower slot) and the length of the longest
+// common prefix of all live hypotheses: the depth of their lowest common ancestor in node_par.  Nodes are numbered in creation
+// order, so a parent's id is below its child's: lifting the highest node until all are equal ends at that ancestor.  One wave
+// per slot; the state is read only.
+__global__ __launch_bounds__(64) void rnnt_beam_stream_partial_kernel(const StreamReadArgs a) {
+  const int b = blockIdx.x, lane = threadIdx.x, slot = a.slots[b];
+  int* out = a.tokens + (long)b * a.max_u;
+  const bool valid = slot >= 0 && slot < a.max_streams;
+  const RnntSlot q = rnnt_slot((void*)a.state, valid ? slot : 0, a.max_frames, a.beam);
+  const int nh = valid ? min(max(q.w.cnt[0], 0), a.beam) : 0;
+  float sc = -INFINITY;
+  int len = 0, node = 0;
+  if (lane < nh) { sc = q.w.score[lane]; len = q.w.len[lane]; node = q.w.node[lane]; }
+  const bool in_set = lane < nh;
+  // best: the highest score, then the lower slot (a nan score ranks below everything)
+  const uint64_t key = in_set ? mk_key(sc == sc ? sc : -INFINITY, lane) : 0ull;
+  uint64_t best = key;
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint64_t other = __shfl_xor(best, o, 64);
+    best = other > best ? other : best;
+  }
+  const bool is_best = nh > 0 && key == best;
+  if (is_best) {
+    const int n = min(len, a.max_u);
+    for (int u = n; u < a.max_u; ++u) out[u] = a.pad;
+    int nd = node;
+    for (int u = len - 1; u >= 0 && nd > 0 && nd < q.w.cap; --u) {
+      if (u < a.max_u) out[u] = q.w.node_tok[nd];
+      nd = q.w.node_par[nd];
+    }
+    a.lengths[b] = n;
+    a.scores[b] = sc;
+  }
+  int depth = len, cur = in_set ? node : -1;
+  for (int it = 0; it < q.w.cap; ++it) {  // every pass lowers the highest node: fewer than `cap` passes
+    int hi = cur;
+    for (int o = 32; o > 0; o >>= 1) hi = max(hi, __shfl_xor(hi, o, 64));
+    if (hi <= 0 || !__ballot(in_set && cur != hi)) break;  // the root, or every member at the same node
+    if (in_set && cur == hi) { cur = cur < q.w.cap ? q.w.node_par[cur] : 0; --depth; }
+  }
+  if (is_best) a.aux[b] = depth;  // the best hypothesis is a member: its depth after the lifts is the ancestor's
+  if (nh == 0 && lane == 0) {
+    for (int u = 0; u < a.max_u; ++u) out[u] = a.pad;
+    a.lengths[b] = 0; a.scores[b] = -INFINITY; a.aux[b] = 0;
+  }
+}
+
 }  // namespace
+
+// weight 0 is no fusion: the LM rows are not read (an entry of -inf times 0 would be NaN)
+static RowParams rnnt_row_params(const float*& lm_rows, int lm_no_blank, int V, int K, int blank, int eos, float temperature,
+                                 float lm_weight) {
+  RowParams p;
+  p.V = V; p.K = K; p.blank = blank; p.eos = eos; p.lm_no_blank = lm_no_blank;
+  p.temperature = temperature; p.lm_weight = lm_rows ? lm_weight : 0.f;
+  if (lm_weight == 0.f) lm_rows = nullptr;
+  return p;
+}
+
+static bool rnnt_step_args_bad(long ld, const float* lm_rows, long ld_lm, int lm_no_blank, int V, int beam, int K, int blank, int eos,
+                               float temperature) {
+  return V < 2 || V > 65535 || ld < V || beam < 1 || beam > kMaxBeam || K < 1 || K > kMaxK || K > V - 1 || blank < 0 || blank >= V ||
+         eos < -1 || eos >= V || eos == blank || !(temperature > 0.f) || (lm_rows && ld_lm < (lm_no_blank ? V - 1 : V));
+}
 
 extern "C" long ea_rnnt_frame_beam_workspace_bytes(int B, int T, int beam) {
   if (B <= 0 || T < 0 || beam < 1 || beam > kMaxBeam) return 0;
@@ -391,5 +852,74 @@ extern "C" int ea_rnnt_frame_beam_finish(void* workspace, int B, int T, int beam
     return -2;
   hipLaunchKernelGGL(rnnt_beam_finish_kernel, dim3(B), dim3(64), 0, stream, workspace, T, beam, nbest, pad, normalize, tokens,
                      lengths, scores, nhyp);
+  return EA_CHECK_LAUNCH();
+}
+
+// ------------------------------------------------------------------------------------------------ C ABI: the streamed search
+extern "C" long ea_rnnt_frame_beam_stream_state_bytes(int max_frames, int beam) {
+  if (max_frames < 1 || beam < 1 || beam > kMaxBeam) return 0;
+  return rnnt_state_words(max_frames, beam) * 4L;
+}
+
+extern "C" int ea_rnnt_frame_beam_stream_reset(void* state, const int* slots, int n, int max_streams, int max_frames, int beam,
+                                               hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!state || !slots || max_streams < 1 || max_frames < 1 || beam < 1 || beam > kMaxBeam) return -2;
+  hipLaunchKernelGGL(rnnt_beam_stream_reset_kernel, dim3(n), dim3(256), 0, stream, state, slots, max_streams, max_frames, beam);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_rnnt_frame_beam_stream_step(const float* logits, long ld, const float* lm_rows, long ld_lm, int lm_no_blank,
+                                              const int* slot_idx, const int* n_new, int j, int n, void* state, int* parent,
+                                              int* token, void* keep, int max_streams, int max_frames, int V, int beam, int K,
+                                              int blank, int eos, float temperature, float lm_weight, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!logits || !slot_idx || !n_new || !state || !parent || !token || !keep || j < 0 || max_streams < 1 || max_frames < 1 ||
+      rnnt_step_args_bad(ld, lm_rows, ld_lm, lm_no_blank, V, beam, K, blank, eos, temperature))
+    return -2;
+  StreamRowArgs r;
+  r.p = rnnt_row_params(lm_rows, lm_no_blank, V, K, blank, eos, temperature, lm_weight);
+  r.logits = logits; r.ld = ld; r.lm_rows = lm_rows; r.ld_lm = ld_lm;
+  r.slot_idx = slot_idx; r.n_new = n_new; r.state = state;
+  r.max_streams = max_streams; r.max_frames = max_frames; r.beam = beam; r.j = j;
+  hipLaunchKernelGGL(rnnt_beam_stream_row_kernel, dim3(n * beam), dim3(256), 0, stream, r);
+  StreamSelArgs s;
+  s.slot_idx = slot_idx; s.n_new = n_new; s.state = state; s.parent = parent; s.token = token; s.keep = (uint8_t*)keep;
+  s.max_streams = max_streams; s.max_frames = max_frames; s.beam = beam; s.K = K; s.blank = blank; s.j = j;
+  hipLaunchKernelGGL(rnnt_beam_stream_select_kernel, dim3(n), dim3(256), 0, stream, s);
+  return EA_CHECK_LAUNCH();
+}
+
+static bool rnnt_read_args_bad(const void* state, const int* slots, int max_streams, int max_frames, int beam, int max_u,
+                               const int* tokens, const int* lengths, const float* scores, const int* aux) {
+  return !state || !slots || !tokens || !lengths || !scores || !aux || max_streams < 1 || max_frames < 1 || beam < 1 ||
+         beam > kMaxBeam || max_u < 0;
+}
+
+extern "C" int ea_rnnt_frame_beam_stream_finish(const void* state, const int* slots, int n, int max_streams, int max_frames,
+                                                int beam, int nbest, int pad, int normalize, int max_u, int* tokens, int* lengths,
+                                                float* scores, int* nhyp, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (rnnt_read_args_bad(state, slots, max_streams, max_frames, beam, max_u, tokens, lengths, scores, nhyp) || nbest < 1 || nbest > beam)
+    return -2;
+  StreamReadArgs a;
+  a.state = state; a.slots = slots;
+  a.max_streams = max_streams; a.max_frames = max_frames; a.beam = beam; a.nbest = nbest; a.pad = pad; a.normalize = normalize;
+  a.max_u = max_u;
+  a.tokens = tokens; a.lengths = lengths; a.scores = scores; a.aux = nhyp;
+  hipLaunchKernelGGL(rnnt_beam_stream_finish_kernel, dim3(n), dim3(64), 0, stream, a);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_rnnt_frame_beam_stream_partial(const void* state, const int* slots, int n, int max_streams, int max_frames,
+                                                 int beam, int pad, int max_u, int* tokens, int* lengths, float* scores,
+                                                 int* stable_len, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (rnnt_read_args_bad(state, slots, max_streams, max_frames, beam, max_u, tokens, lengths, scores, stable_len)) return -2;
+  StreamReadArgs a;
+  a.state = state; a.slots = slots;
+  a.max_streams = max_streams; a.max_frames = max_frames; a.beam = beam; a.nbest = 1; a.pad = pad; a.normalize = 0; a.max_u = max_u;
+  a.tokens = tokens; a.lengths = lengths; a.scores = scores; a.aux = stable_len;
+  hipLaunchKernelGGL(rnnt_beam_stream_partial_kernel, dim3(n), dim3(64), 0, stream, a);
   return EA_CHECK_LAUNCH();
 }

@@ -668,6 +668,83 @@ def rnnt_frame_beam_finish(ws, B, T, beam, nbest, pad, normalize=True):
     return tokens, lengths, scores, nhyp
 
 
+def rnnt_frame_beam_stream_state(max_streams, max_frames, beam, device):
+    """(state uint8 [max_streams][bytes per slot], zero-filled; bytes per slot) of the streamed frame-synchronous transducer
+    beam search (ea_rnnt_frame_beam_stream_state_bytes)."""
+    nbytes = int(_lib.lib().ea_rnnt_frame_beam_stream_state_bytes(max_frames, beam))
+    assert nbytes > 0 and max_streams >= 1
+    return torch.zeros(max_streams, nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def _check_rnnt_stream_state(state, max_frames, beam):
+    assert state.dtype == torch.uint8 and state.is_contiguous() and state.dim() == 2
+    assert state.shape[1] == _lib.lib().ea_rnnt_frame_beam_stream_state_bytes(max_frames, beam)
+
+
+def rnnt_frame_beam_stream_reset(state, slots, max_frames, beam):
+    """The slots int32 [n] (device) of `state` get the search state before frame 0 (ea_rnnt_frame_beam_stream_reset)."""
+    _check_rnnt_stream_state(state, max_frames, beam)
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
+    check(_lib.lib().ea_rnnt_frame_beam_stream_reset(_p(state), _p(slots), slots.numel(), state.shape[0], max_frames, beam, _stream()),
+          "ea_rnnt_frame_beam_stream_reset")
+
+
+def rnnt_frame_beam_stream_step(logits, slot_idx, n_new, j, state, out, max_frames, V, beam, K, blank, eos=-1, temperature=1.0,
+                                lm_rows=None, lm_weight=0.0, lm_no_blank=False):
+    """The j-th new frame of the n listed streams through the frame-synchronous transducer beam search
+    (ea_rnnt_frame_beam_stream_step): logits fp32 [n*beam][>= V], row b * beam + beam slot; slot_idx / n_new int32 [n] on the
+    device; out = (parent int32, token int32, keep uint8), each [n*beam], written by the step (identity / blank / 1 for an entry
+    with j >= n_new, a slot out of range or a full slot, whose state is left as it is)."""
+    n = slot_idx.numel()
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == n * beam and logits.shape[1] >= V
+    assert slot_idx.dtype == n_new.dtype == torch.int32 and n_new.numel() == n and slot_idx.is_contiguous() and n_new.is_contiguous()
+    _check_rnnt_stream_state(state, max_frames, beam)
+    parent, token, keep = out
+    assert parent.numel() == token.numel() == keep.numel() == n * beam
+    assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
+    if lm_rows is not None:
+        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (n * beam, V - 1 if lm_no_blank else V)
+    check(_lib.lib().ea_rnnt_frame_beam_stream_step(_p(logits), logits.stride(0), _p(lm_rows),
+                                                    lm_rows.stride(0) if lm_rows is not None else 0, int(lm_no_blank), _p(slot_idx),
+                                                    _p(n_new), j, n, _p(state), _p(parent), _p(token), _p(keep), state.shape[0],
+                                                    max_frames, V, beam, K, blank, eos, temperature, lm_weight, _stream()),
+          "ea_rnnt_frame_beam_stream_step")
+
+
+def rnnt_frame_beam_stream_finish(state, slots, max_frames, beam, nbest, pad, max_u, normalize=True):
+    """The hypotheses of the slots int32 [n] (device) as if their streams ended now, the state left as it is
+    (ea_rnnt_frame_beam_stream_finish).  Returns (tokens int32 [n][nbest][max_u] pad-filled, lengths int32 [n][nbest], scores
+    fp32 [n][nbest], nhyp int32 [n]), best first."""
+    _check_rnnt_stream_state(state, max_frames, beam)
+    assert slots.dtype == torch.int32 and slots.is_contiguous()
+    n, dev = slots.numel(), state.device
+    tokens = torch.empty(n, nbest, max_u, dtype=torch.int32, device=dev)
+    lengths = torch.empty(n, nbest, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, nbest, dtype=torch.float32, device=dev)
+    nhyp = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.lib().ea_rnnt_frame_beam_stream_finish(_p(state), _p(slots), n, state.shape[0], max_frames, beam, nbest, pad,
+                                                      int(bool(normalize)), max_u, _p(tokens), _p(lengths), _p(scores), _p(nhyp),
+                                                      _stream()), "ea_rnnt_frame_beam_stream_finish")
+    return tokens, lengths, scores, nhyp
+
+
+def rnnt_frame_beam_stream_partial(state, slots, max_frames, beam, pad, max_u):
+    """The best live hypothesis (by the raw score the search prunes by) of the slots int32 [n] (device) and the length of the
+    beam's common prefix (ea_rnnt_frame_beam_stream_partial).  Returns (tokens int32 [n][max_u] pad-filled, lengths int32 [n],
+    scores fp32 [n], stable_len int32 [n])."""
+    _check_rnnt_stream_state(state, max_frames, beam)
+    assert slots.dtype == torch.int32 and slots.is_contiguous()
+    n, dev = slots.numel(), state.device
+    tokens = torch.empty(n, max_u, dtype=torch.int32, device=dev)
+    lengths = torch.empty(n, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, dtype=torch.float32, device=dev)
+    stable = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.lib().ea_rnnt_frame_beam_stream_partial(_p(state), _p(slots), n, state.shape[0], max_frames, beam, pad, max_u,
+                                                       _p(tokens), _p(lengths), _p(scores), _p(stable), _stream()),
+          "ea_rnnt_frame_beam_stream_partial")
+    return tokens, lengths, scores, stable
+
+
 def context_graph_score(graph, tokens, lens):
     """Token rows int32 [N][L] (lens int32 [N]) replayed through a context graph on the device (ea_context_graph_score):
     (running bias fp32 [N][L], final bias fp32 [N], node int32 [N])."""

@@ -1,6 +1,7 @@
 """Batched recognition CLI — the decoding loop and output format of espresso/speech_recognize.py:60-360 on the HIP path:
 for every batch run the chosen search (beam search with optional LM / look-ahead word-LM / multi-level LM fusion, CTC greedy,
-CTC prefix beam search with optional LSTM-LM or lexicon + n-gram LM fusion, transducer greedy / beam / frame-synchronous beam), print `T-<utt>` (reference) and `H-<utt>`
+CTC prefix beam search with optional LSTM-LM or lexicon + n-gram LM fusion, transducer greedy / beam / frame-synchronous beam,
+the latter also streamed), print `T-<utt>` (reference) and `H-<utt>`
 (hypothesis, score in base 2) lines, accumulate WER / CER with `tools.wer.Scorer`, and close with the "Recognized N utterances
 ..." summary.
 
@@ -139,7 +140,8 @@ def collate(ids: List[int], utt_ids: List[str], waves: List[np.ndarray], device)
 
 
 def build_generator(args, model, dictionary, lm=None, ngram=None, context_graph=None):
-    """ngram: (NGramLanguageModel, LexiconTrie) for --search ctc_beam --ngram-lm; context_graph: the ContextGraph of --hotwords."""
+    """ngram: (NGramLanguageModel, LexiconTrie) for --search ctc_beam --ngram-lm; context_graph: the ContextGraph of --hotwords.
+    (--search transducer_stream_beam has no generator: recognize_streaming builds its decoder from stream_beam_options.)"""
     from .sequence_generator import SequenceGenerator
     from .tools.ctc_decoder import CTCDecoder
     from .tools.ctc_lexicon_beam_search import CTCLexiconBeamSearchDecoder
@@ -176,6 +178,13 @@ def build_generator(args, model, dictionary, lm=None, ngram=None, context_graph=
                              eos_factor=args.eos_factor, print_alignment=getattr(args, "print_alignment", None) is not None)
 
 
+def stream_beam_options(args, lm=None):
+    """The options of StreamingTransducerFrameBeamDecoder (after model, dictionary, max_streams, max_frames) from the command
+    line of --search transducer_stream_beam."""
+    return dict(beam_size=args.beam, nbest=args.nbest, beam_size_token=args.transducer_beam_size_token, temperature=args.temperature,
+                normalize_scores=not args.unnormalized, lm_model=lm, lm_weight=args.lm_weight)
+
+
 def get_parser():
     p = argparse.ArgumentParser("espresso_amd.speech_recognize", description=__doc__.split("\n")[0])
     p.add_argument("--path", required=True, help="state_dict (or fairseq checkpoint dict with a 'model' entry)")
@@ -187,7 +196,9 @@ def get_parser():
     p.add_argument("--wav-scp", required=True)
     p.add_argument("--text", default=None, help="reference transcripts (utt_id tokens...)")
     p.add_argument("--global-cmvn-stats-path", default=None)
-    p.add_argument("--search", default="beam", choices=["beam", "ctc", "ctc_beam", "transducer_greedy", "transducer_beam", "transducer_frame_beam"])
+    p.add_argument("--search", default="beam", choices=["beam", "ctc", "ctc_beam", "transducer_greedy", "transducer_beam", "transducer_frame_beam", "transducer_stream_beam"],
+                   help="transducer_stream_beam is the frame-synchronous transducer beam search under --streaming (a search name of "
+                        "its own: --search transducer_frame_beam is the offline search and refuses --streaming)")
     p.add_argument("--beam", type=int, default=10)
     p.add_argument("--nbest", type=int, default=1)
     p.add_argument("--max-len-a", type=float, default=0.08)
@@ -212,7 +223,7 @@ def get_parser():
                    help="ctc_beam: candidate tokens per frame (default: min(--beam, vocabulary size - 1), at most 64)")
     p.add_argument("--ctc-insertion-bonus", type=float, default=0.0, help="ctc_beam: score added per emitted token")
     p.add_argument("--transducer-beam-size-token", type=int, default=None,
-                   help="transducer_frame_beam: extensions per hypothesis and frame (default: min(--beam, vocabulary size - 1), at "
+                   help="transducer_frame_beam / transducer_stream_beam: extensions per hypothesis and frame (default: min(--beam, vocabulary size - 1), at "
                         "most 64)")
     p.add_argument("--ngram-lm", default=None,
                    help="ctc_beam: word n-gram LM (plain-text ARPA) fused with --lm-weight under a closed-vocabulary lexicon")
@@ -248,12 +259,12 @@ def get_parser():
                    help="collect the attention alignments; --search beam saves RESULTS_PATH/attn_plots/<utt>.pdf of the best "
                         "hypothesis (needs --results-path and matplotlib)")
     p.add_argument("--streaming", action="store_true",
-                   help="chunk-by-chunk recognition of a chunk-streaming transformer encoder (--search ctc, transducer_greedy, or "
-                        "ctc_beam with --ngram-lm): audio is fed in pieces of --stream-chunk-ms with --streams utterances in flight")
+                   help="chunk-by-chunk recognition of a chunk-streaming transformer encoder (--search ctc, transducer_greedy, "
+                        "transducer_stream_beam, or ctc_beam with --ngram-lm): audio is fed in pieces of --stream-chunk-ms with --streams utterances in flight")
     p.add_argument("--stream-chunk-ms", type=int, default=None, help="--streaming: audio per piece (default 400)")
     p.add_argument("--streams", type=int, default=None, help="--streaming: concurrent utterances (default 16)")
     p.add_argument("--stream-partials", action="store_true",
-                   help="--streaming --search ctc_beam --ngram-lm: after every piece print `P-<utt>`, the seconds consumed, the stable "
+                   help="--streaming --search ctc_beam --ngram-lm or --search transducer_stream_beam: after every piece print `P-<utt>`, the seconds consumed, the stable "
                         "text and the rest of the currently best hypothesis, whenever the text changed")
     p.add_argument("--wer-output-filter", default=None, help="sed-style word filter applied before WER scoring")
     p.add_argument("--non-lang-syms", default=None, help="non-language symbols (one per line), ignored by WER / CER scoring")
@@ -280,8 +291,8 @@ def check_frame_beam_args(args):
     one sub-word LSTM LM: refused, before anything is loaded, with streaming, hotwords, n-gram / word-level LMs, alignments and
     ensembles."""
     if args.search != "transducer_frame_beam":
-        if args.transducer_beam_size_token is not None:
-            raise ValueError("--transducer-beam-size-token configures --search transducer_frame_beam")
+        if args.transducer_beam_size_token is not None and args.search != "transducer_stream_beam":
+            raise ValueError("--transducer-beam-size-token configures --search transducer_frame_beam / transducer_stream_beam")
         return
     for opt, v in (("--streaming", args.streaming), ("--hotwords", args.hotwords), ("--ngram-lm", args.ngram_lm),
                    ("--word-dict", args.word_dict), ("--print-alignment", args.print_alignment is not None)):
@@ -291,6 +302,26 @@ def check_frame_beam_args(args):
         raise NotImplementedError("--search transducer_frame_beam fuses one sub-word LSTM LM: no multi-level --lm-path a:b")
     if len(args.path.split(os.pathsep)) > 1:
         raise NotImplementedError("--search transducer_frame_beam takes one model: ensembles (--path a.pt:b.pt) are not implemented")
+
+
+def check_stream_beam_args(args):
+    """--search transducer_stream_beam is the frame-synchronous transducer beam search of one chunk-streaming transducer model
+    under --streaming, alone or with one sub-word LSTM LM (a name of its own: --search transducer_frame_beam --streaming stays
+    refused).  Refused, before anything is loaded: without --streaming, and with hotwords, n-gram / word-level LMs, multi-level
+    LMs, alignments and ensembles."""
+    if args.search != "transducer_stream_beam":
+        return
+    if not args.streaming:
+        raise ValueError("--search transducer_stream_beam is the streamed search: give --streaming too (offline: --search "
+                         "transducer_frame_beam)")
+    for opt, v in (("--hotwords", args.hotwords), ("--ngram-lm", args.ngram_lm), ("--word-dict", args.word_dict),
+                   ("--print-alignment", args.print_alignment is not None)):
+        if v:
+            raise NotImplementedError(f"--search transducer_stream_beam is not implemented with {opt}")
+    if args.lm_path and len(args.lm_path.split(os.pathsep)) != 1:
+        raise NotImplementedError("--search transducer_stream_beam fuses one sub-word LSTM LM: no multi-level --lm-path a:b")
+    if len(args.path.split(os.pathsep)) > 1:
+        raise NotImplementedError("--search transducer_stream_beam takes one model: ensembles (--path a.pt:b.pt) are not implemented")
 
 
 DEFAULT_HOTWORD_SCORE = 1.5
@@ -316,9 +347,10 @@ def check_hotword_args(args):
 
 
 def check_streaming_args(args):
-    """--streaming is greedy decoding (CTC or transducer), or the lexicon + n-gram beam search (--search ctc_beam --ngram-lm),
-    of one chunk-streaming model: refused, before anything is loaded, with every other search, with LSTM-LM fusion, ensembles
-    and alignment output."""
+    """--streaming is greedy decoding (CTC or transducer), the lexicon + n-gram beam search (--search ctc_beam --ngram-lm) or
+    the frame-synchronous transducer beam search (--search transducer_stream_beam, the one search that fuses an LSTM LM under
+    streaming) of one chunk-streaming model: refused, before anything is loaded, with every other search, with LSTM-LM fusion
+    elsewhere, ensembles and alignment output."""
     if not args.streaming:
         for opt, v in (("--stream-chunk-ms", args.stream_chunk_ms), ("--streams", args.streams),
                        ("--stream-partials", args.stream_partials or None)):
@@ -329,15 +361,18 @@ def check_streaming_args(args):
     if args.search == "ctc_beam" and not lexicon_beam:
         raise NotImplementedError("--streaming --search ctc_beam needs --ngram-lm: the lexicon + n-gram search is the prefix beam "
                                   "search that is streamed, not the one without LM or with an LSTM LM")
-    if args.search not in ("ctc", "transducer_greedy", "ctc_beam"):
-        raise NotImplementedError("--streaming is implemented for greedy decoding (--search ctc, --search transducer_greedy) and for "
-                                  f"--search ctc_beam with --ngram-lm, not --search {args.search}")
-    for opt, v in (("--lm-path", args.lm_path), ("--word-dict", args.word_dict), ("--ngram-lm", args.ngram_lm and not lexicon_beam),
+    stream_beam = args.search == "transducer_stream_beam"
+    if args.search not in ("ctc", "transducer_greedy", "ctc_beam", "transducer_stream_beam"):
+        raise NotImplementedError("--streaming is implemented for greedy decoding (--search ctc, --search transducer_greedy), for "
+                                  "--search ctc_beam with --ngram-lm and for --search transducer_stream_beam, not --search "
+                                  f"{args.search}")
+    for opt, v in (("--lm-path", args.lm_path and not stream_beam), ("--word-dict", args.word_dict), ("--ngram-lm", args.ngram_lm and not lexicon_beam),
                    ("--print-alignment", args.print_alignment)):
         if v:
             raise NotImplementedError(f"--streaming decodes without LSTM-LM fusion or alignments: no {opt} with it")
-    if args.stream_partials and not lexicon_beam:
-        raise NotImplementedError("--stream-partials prints the partial results of --search ctc_beam --ngram-lm")
+    if args.stream_partials and not (lexicon_beam or stream_beam):
+        raise NotImplementedError("--stream-partials prints the partial results of --search ctc_beam --ngram-lm and of --search "
+                                  "transducer_stream_beam")
     if len(args.path.split(os.pathsep)) > 1:
         raise NotImplementedError("--streaming takes one model: ensembles (--path a.pt:b.pt) are not streamed")
     if (args.stream_chunk_ms is not None and args.stream_chunk_ms <= 0) or (args.streams is not None and args.streams <= 0):
@@ -346,20 +381,24 @@ def check_streaming_args(args):
 
 def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=400, streams=16, refs=None, out=sys.stdout,
                         quiet=False, scorer=None, summary_out=None, search="ctc", max_num_expansions_per_step=2, lexicon_beam=None,
-                        partials=False):
+                        partials=False, stream_beam=None):
     """The output of `recognize` from a streamed pass: every utterance is read in pieces of `chunk_ms`, `streams` of them in
     flight; a finished utterance frees its slot for the next one (wav.scp order).  search "ctc_beam": lexicon_beam holds the
     arguments of StreamingCTCLexiconBeamDecoder after `dictionary` (n-gram LM, lexicon) and its options; its prefix tables are
-    sized for the longest utterance given.  partials: a `P-` line per stream whenever its partial text changed."""
+    sized for the longest utterance given.  search "transducer_stream_beam": stream_beam holds the options of
+    StreamingTransducerFrameBeamDecoder (beam, n-best, LM, ...); its prefix tables are sized the same way.  partials: a `P-` line
+    per stream whenever its partial text changed."""
     from .models.transformer.streaming_encoder import StreamingEncoder
     from .tools.streaming_ctc_decoder import StreamingCTCDecoder
     from .tools.streaming_ctc_lexicon_beam_decoder import StreamingCTCLexiconBeamDecoder
+    from .tools.streaming_transducer_frame_beam_decoder import StreamingTransducerFrameBeamDecoder
     from .tools.streaming_transducer_greedy_decoder import StreamingTransducerGreedyDecoder
     from .tools.wer import Scorer
 
     if scorer is None:
         scorer = Scorer(dictionary, wer_output_filter=None)
     se = StreamingEncoder(model, streams, frontend=task.frontend)
+    partial_of = None  # a decoder's partial -> (tokens of the best hypothesis, how many of them are stable)
     if search == "ctc":
         dec = StreamingCTCDecoder(dictionary)
         strip = {dictionary.eos(), dictionary.pad()}
@@ -367,7 +406,13 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
         (ngram_lm, lexicon), opts = lexicon_beam
         max_frames = max([1] + [-(-task.frontend.num_frames(len(w)) // se.stride) for w in waves])
         dec = StreamingCTCLexiconBeamDecoder(dictionary, ngram_lm, lexicon, streams, max_frames, **opts)
+        partial_of = lambda part: (part["tokens"], len(part["stable"]))  # noqa: E731
         strip = {dictionary.eos(), dictionary.pad()}
+    elif search == "transducer_stream_beam":
+        max_frames = max([1] + [-(-task.frontend.num_frames(len(w)) // se.stride) for w in waves])
+        dec = StreamingTransducerFrameBeamDecoder(model, dictionary, max_streams=streams, max_frames=max_frames, **stream_beam)
+        strip = dec.symbols_to_strip_from_output
+        partial_of = lambda part: part[:2]  # noqa: E731
     else:
         dec = StreamingTransducerGreedyDecoder(model, dictionary, max_num_expansions_per_step=max_num_expansions_per_step)
         strip = dec.symbols_to_strip_from_output
@@ -401,8 +446,8 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
             dec.accept(ids, logits, counts)
         if partials:
             for i, part in zip(ids, dec.partial(ids)):
-                k = len(part["stable"])
-                texts = (text_of(part["tokens"][:k]), text_of(part["tokens"][k:]))
+                toks, k = partial_of(part)
+                texts = (text_of(toks[:k]), text_of(toks[k:]))
                 if shown.get(i) != texts:
                     shown[i] = texts
                     print("P-{}\t{:.2f}\t{}\t{}".format(utt_ids[i], live[i] / 16000.0, *texts), file=out)
@@ -518,6 +563,7 @@ def load_member(state, name, block, task, dev):
 def main(argv=None):
     args = get_parser().parse_args(argv)
     check_frame_beam_args(args)
+    check_stream_beam_args(args)
     if args.print_alignment is not None and not args.results_path:
         raise ValueError("--print-alignment saves attention plots under --results-path: give --results-path")
     check_hotword_args(args)
@@ -573,11 +619,11 @@ def main(argv=None):
         if cfg0 is None or not hasattr(cfg0, "encoder") or not hasattr(cfg0.encoder, "chunk_size"):
             raise NotImplementedError(f"--streaming needs a chunk-streaming transformer encoder model, not {model_name}")
         check_streamable(cfg0)
-    if args.search == "transducer_frame_beam":  # before the weights are loaded: the model class must be a transducer
+    if args.search in ("transducer_frame_beam", "transducer_stream_beam"):  # before the weights are loaded: a transducer model
         from . import registry
 
         if not hasattr(registry.MODEL_REGISTRY[model_name], "joint_step"):
-            raise NotImplementedError(f"--search transducer_frame_beam needs a transducer model (predictor + joint), not {model_name}")
+            raise NotImplementedError(f"--search {args.search} needs a transducer model (predictor + joint), not {model_name}")
     model = load_member(state, model_name, model_cfg, task, dev)
     members = [model]
     for extra in paths[1:]:  # every member is rebuilt from ITS OWN checkpoint's configuration (checkpoint_utils.load_model_ensemble)
@@ -606,7 +652,9 @@ def main(argv=None):
             if args.word_dict:
                 lm = TensorizedLookaheadLanguageModel(lm, task.target_dictionary, oov_penalty=args.oov_penalty,
                                                       open_vocab=not args.disable_open_vocab)
-    gen = build_generator(args, members if len(members) > 1 else model, task.target_dictionary, lm, ngram, context_graph)
+    gen = None  # (the streamed transducer beam builds its own decoder in recognize_streaming, which validates the same options)
+    if args.search != "transducer_stream_beam":
+        gen = build_generator(args, members if len(members) > 1 else model, task.target_dictionary, lm, ngram, context_graph)
     scp = read_scp(args.wav_scp)
     utt_ids = list(scp.keys())
     waves = [read_wav(scp[u]) for u in utt_ids]
@@ -630,6 +678,8 @@ def main(argv=None):
             kw["lexicon_beam"] = (ngram, dict(beam_size=args.beam, nbest=args.nbest, beam_size_token=args.ctc_beam_size_token,
                                               lm_weight=args.lm_weight, word_score=args.word_score,
                                               insertion_bonus=args.ctc_insertion_bonus))
+        if args.search == "transducer_stream_beam":
+            kw["stream_beam"] = stream_beam_options(args, lm)
         if not args.results_path:
             recognize_streaming(task, model, task.target_dictionary, s_ids, s_waves, dev, out=sys.stdout, **kw)
             return scorer

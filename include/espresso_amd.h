@@ -492,6 +492,43 @@ int ea_rnnt_frame_beam_step(const float* logits, long ld, const float* lm_rows, 
                             int eos, float temperature, float lm_weight, int t, ea_stream_t stream);
 int ea_rnnt_frame_beam_finish(void* workspace, int B, int T, int beam, int nbest, int pad, int normalize, int* tokens,
                               int* lengths, float* scores, int* nhyp, ea_stream_t stream);
+/* The streamed frame-synchronous transducer beam search: the same frames, one per call, over streams that come and go
+ * (csrc/rnnt_beam.hip; the per-frame code restates the offline step's and is tested against it, so a stream fed in any pieces gives bit for bit the offline
+ * results of the whole utterance, whatever max_frames >= its length).  The search state of a stream lives in one of max_streams
+ * slots of `state` (max_streams * ea_rnnt_frame_beam_stream_state_bytes(max_frames, beam) bytes, slot-major).  Per slot, int32
+ * words: words = 2 + even(3 * tsize + 5 * beam + 2 + 2 * cap + 2 * beam + 2 * beam * 64) with cap = 1 + max_frames * beam, tsize
+ * the smallest power of two >= max(64, 2 * cap) and even() rounding up to an even count: [0] frames consumed, [1] 0, then the
+ * offline workspace of one utterance of max_frames frames — hash table, beam, counters, node_par / node_tok and the
+ * row-to-select hand-over (rblank, rnc, ctok, cval), which lives in the slot, not in a per-call scratch.  ..._state_bytes
+ * returns 0 for max_frames < 1 or beam outside [1, 64].  Conventions of ea_stream_attention / ea_ctc_lexicon_stream_*: slots /
+ * slot_idx / n_new are device int32 [n]; an entry whose slot is outside [0, max_streams) is skipped; no call synchronises with
+ * the host; bad arguments return -2 and launch nothing; n <= 0 returns 0.
+ * ..._reset: the listed slots get the state before frame 0 (the empty hypothesis with score 0, a cleared hash, frames = 0).
+ * ..._step: ONE encoder frame for each of the n listed streams: logits fp32 [n*beam][ld], row b * beam + beam slot (lm_rows
+ *   likewise), the j-th new frame of this round.  Entry b is active iff its slot is in range, j < n_new[b] and the slot has
+ *   consumed fewer than max_frames frames; an active entry does one frame of the contract of ea_rnnt_frame_beam_step and
+ *   increments the slot's frame counter; an inactive one leaves its slot untouched and writes parent = identity, token =
+ *   blank, keep = 1 (what the offline step writes for t >= in_len).  parent / token / keep are [n*beam], parent in rows of
+ *   THIS call (b * beam + slot of the previous frame).  Rows of dead beam slots are not read.  A slot may be listed once.
+ * ..._finish: ea_rnnt_frame_beam_finish per listed slot into tokens int32 [n][nbest][max_u] (pad-filled; longer hypotheses
+ *   are cut at max_u), lengths / scores [n][nbest], nhyp [n]; the state is read only, so the call is valid mid-stream.
+ * ..._partial: per listed slot the live hypothesis with the best score s (the quantity the search prunes by; ties: the lower
+ *   beam slot) into tokens int32 [n][max_u], lengths / scores [n], and stable_len [n]: the length of the longest common prefix
+ *   of all live hypotheses (the depth of their lowest common ancestor in the prefix table).  Every hypothesis a later finish
+ *   can return starts with those tokens.  The state is read only. */
+long ea_rnnt_frame_beam_stream_state_bytes(int max_frames, int beam);
+int ea_rnnt_frame_beam_stream_reset(void* state, const int* slots, int n, int max_streams, int max_frames, int beam,
+                                    ea_stream_t stream);
+int ea_rnnt_frame_beam_stream_step(const float* logits, long ld, const float* lm_rows, long ld_lm, int lm_no_blank,
+                                   const int* slot_idx, const int* n_new, int j, int n, void* state, int* parent, int* token,
+                                   void* keep, int max_streams, int max_frames, int V, int beam, int K, int blank, int eos,
+                                   float temperature, float lm_weight, ea_stream_t stream);
+int ea_rnnt_frame_beam_stream_finish(const void* state, const int* slots, int n, int max_streams, int max_frames, int beam,
+                                     int nbest, int pad, int normalize, int max_u, int* tokens, int* lengths, float* scores,
+                                     int* nhyp, ea_stream_t stream);
+int ea_rnnt_frame_beam_stream_partial(const void* state, const int* slots, int n, int max_streams, int max_frames, int beam,
+                                      int pad, int max_u, int* tokens, int* lengths, float* scores, int* stable_len,
+                                      ea_stream_t stream);
 /* Word n-gram LM (ARPA) and lexicon-constrained CTC prefix beam search with its fusion (csrc/ctc_lexicon_beam.hip) — the
  * search the reference takes from Flashlight's KenLM lexicon decoder (espresso/tools/ctc_decoder.py:24-71).
  * ea_ngram_create: parses a plain-text ARPA file of order <= 6 at `path` into host tables and writes an opaque handle to
