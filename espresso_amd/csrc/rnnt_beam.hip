@@ -34,23 +34,33 @@
 //   words(max_frames, beam) = 2 + even(3 * tsize + 5 * beam + 2 + 2 * cap + 2 * beam + 2 * beam * 64)
 //   cap = 1 + max_frames * beam,  tsize = the smallest power of two >= max(64, 2 * cap),  even(w) = w rounded up to even
 // (hash keys 2 * tsize, hash values tsize; score / len / last / node / pnode; the two counters; node_par and node_tok; and the
-// row-to-select hand-over rblank, rnc, ctok, cval, which lives in the slot as it lives in the offline workspace).  Row phase,
-// select phase, the state before frame 0 and the finish are __device__ functions over a view of that state (RnntWs), which
-// the streamed kernels run.  They restate the offline kernels' bodies line by line; the offline kernels keep their own bodies
-// (calling the shared functions from them cost 1.9 % of the offline step), and the tests hold the two to
-// each other with torch.equal: a stream fed in any pieces gives, bit for bit, what the offline search gives for the whole
-// utterance, and a state sized for max_frames
+// row-to-select hand-over rblank, rnc, ctok, cval, which lives in the slot as it lives in the offline workspace).
+//
+// One body, two wrappers.  Row phase, select phase, the state before frame 0 and the finish each exist once, as __device__
+// functions over a view of that state (RnntWs) and structs of the LDS arrays: rnnt_row_phase, rnnt_select_phase, rnnt_init,
+// rnnt_finish.  The offline and the streamed kernels only decide where the view points and whether a frame is due (offline:
+// workspace b, t < min(in_len[b], T), frame 0 initialises; streamed: slot in range, j < n_new[b], fewer than max_frames frames
+// in the slot head), then call the phase.  The phases are templates on <kStreamed> so that each wrapper gets an instantiation
+// of its own: select_nth (ctc_beam_common.h) is not __forceinline__ and is inlined only while every instantiation of it has a
+// single caller, and the flag drops from the offline finish the two guards only a caller-sized streamed readout needs.  An
+// earlier build whose offline kernels shared the streamed kernels' instantiation was 1.9 % slower per offline step; this one
+// is not slower than the separate bodies it replaces (measured).  The tests still hold the two searches to
+// each other with torch.equal, which now checks the wrappers: a stream fed in any pieces gives, bit for bit, what the offline
+// search gives for the whole utterance, and a state sized for max_frames
 // what a workspace sized for T gives (node ids are creation order; no rule looks at the table size).  Within one frame the
 // order in which the fresh nodes get their ids is arbitrary (the selected candidates reach their lanes through an atomic
 // counter); no result depends on it, only parent id < child id does.  "Bit for bit" is a statement about results (triples,
 // finish, partial), not about the bytes of a state buffer: do not compare those across runs.  Table entries are
 // published by atomics and read through L1-bypassing loads; everything else is ordered by the kernel boundaries.
 //
-// Kernels of the streamed search, LDS and occupancy (gfx950: 160 KB LDS per CU), equal to their offline twins:
-//   rnnt_beam_stream_row_kernel     256 threads, 21848 B LDS (RowLds), 46 VGPRs -> 7 workgroups per CU by LDS
-//   rnnt_beam_stream_select_kernel  256 threads, 69912 B LDS (SelLds), 39 VGPRs -> 2 workgroups per CU by LDS
-//   rnnt_beam_stream_reset_kernel   256 threads, no LDS;  rnnt_beam_stream_finish_kernel 64 threads, 256 B;
-//   rnnt_beam_stream_partial_kernel 64 threads (one wave per slot), no LDS
+// Kernels, LDS and occupancy (gfx950: 160 KB LDS per CU); no kernel uses scratch:
+//   rnnt_beam_row_kernel, rnnt_beam_stream_row_kernel        256 threads, 21848 B LDS (RowLds), 46 VGPRs -> 7 workgroups per CU by LDS
+//   rnnt_beam_select_kernel, rnnt_beam_stream_select_kernel  256 threads, 69912 B LDS (SelLds), 39 VGPRs -> 2 workgroups per CU by LDS
+//   rnnt_beam_finish_kernel, rnnt_beam_stream_finish_kernel  64 threads, 256 B LDS, 18 VGPRs
+//   rnnt_beam_stream_reset_kernel    256 threads, no LDS, 6 VGPRs
+//   rnnt_beam_stream_partial_kernel  64 threads (one wave per slot), no LDS, 22 VGPRs
+// RowLds and SelLds are left at their natural alignment of 8: aligning the row to 16 turns the radix passes' ds_read2_b64 into
+// ds_read_b128, which measured 0.1 - 0.2 us per frame slower, not faster.
 #include "common.h"
 #include "ctc_beam_common.h"
 #include "espresso_amd.h"
@@ -107,29 +117,9 @@ __device__ __forceinline__ RnntWs rnnt_ws_at(int* base, int T, int beam) {
   w.cval = (float*)(w.ctok + (long)beam * kMaxK);
   return w;
 }
-__device__ __forceinline__ RnntWs rnnt_ws(void* ws, int b, int T, int beam) {
-  RnntWs w;
-  w.cap = (int)rnnt_ws_cap(T, beam);
-  w.tsize = (int)rnnt_ws_tsize(T, beam);
-  int* base = (int*)ws + (long)b * rnnt_ws_words(T, beam);
-  w.tab_key = (unsigned long long*)base;
-  w.tab_val = base + 2L * w.tsize;
-  w.score = (float*)(w.tab_val + w.tsize);
-  w.len = (int*)(w.score + beam);
-  w.last = w.len + beam;
-  w.node = w.last + beam;
-  w.pnode = w.node + beam;
-  w.cnt = w.pnode + beam;
-  w.node_par = w.cnt + 2;
-  w.node_tok = w.node_par + w.cap;
-  w.rblank = (float*)(w.node_tok + w.cap);
-  w.rnc = (int*)(w.rblank + beam);
-  w.ctok = w.rnc + beam;
-  w.cval = (float*)(w.ctok + (long)beam * kMaxK);
-  return w;
-}
 
-// ------------------------------------------------------------------------------------------------ the shared phases
+// ------------------------------------------------------------------------------------------------ the phases
+// (templates on <kStreamed>: one instantiation per wrapper, see the header)
 struct RowParams {  // what the row phase needs besides its row, the same for the offline and the streamed search
   int V, K, blank, eos, lm_no_blank;
   float temperature, lm_weight;
@@ -144,6 +134,7 @@ struct RowLds {
 };
 
 // steps 1 - 3 of the contract and the top K of the row x (LM row m or null) of live slot j; leaves the hand-over in w
+template <bool kStreamed>
 __device__ __forceinline__ void rnnt_row_phase(RowLds& s, const RowParams& a, const RnntWs& w, const float* x, const float* m, int j) {
   const int tid = threadIdx.x;
   const int V = a.V, blank = a.blank, eos = a.eos;
@@ -250,6 +241,7 @@ struct SelLds {
 };
 
 // merge, selection and the new state of one beam with nh hypotheses and nnodes table nodes; the triples go to rows row0 ...
+template <bool kStreamed>
 __device__ __forceinline__ void rnnt_select_phase(SelLds& s, const RnntWs& w, int beam, int K, int blank, int nh, int nnodes,
                                                   int* parent, int* token, uint8_t* keep, long row0) {
   const int tid = threadIdx.x;
@@ -355,6 +347,7 @@ __device__ __forceinline__ void rnnt_select_phase(SelLds& s, const RnntWs& w, in
 // final score = s, or s / max(1, |y|); the nbest best of the nh hypotheses by (-final, slot), backtracked into tokens
 // [nbest][max_u] (pad-filled), lengths / scores [nbest] and *nhyp.  fresh: no step has run, the beam is the empty hypothesis
 // and w is not read.  Reads the state only (blockDim 64).
+template <bool kStreamed>
 __device__ __forceinline__ void rnnt_finish(float* s_fin, const RnntWs& w, int nh, bool fresh, int nbest, int pad, int normalize,
                                             int max_u, int* tokens, int* lengths, float* scores, int* nhyp) {
   const int j = threadIdx.x;
@@ -372,11 +365,11 @@ __device__ __forceinline__ void rnnt_finish(float* s_fin, const RnntWs& w, int n
     if (rank < nbest) {
       int* out = tokens + (long)rank * max_u;
       const int len = fresh ? 0 : w.len[j];
-      const int n = min(len, max_u);
+      const int n = kStreamed ? min(len, max_u) : len;
       for (int u = n; u < max_u; ++u) out[u] = pad;
       int node = fresh ? 0 : w.node[j];
-      for (int u = len - 1; u >= 0 && node > 0 && node < w.cap; --u) {
-        if (u < max_u) out[u] = w.node_tok[node];
+      for (int u = len - 1; u >= 0 && node > 0 && (!kStreamed || node < w.cap); --u) {
+        if (!kStreamed || u < max_u) out[u] = w.node_tok[node];
         node = w.node_par[node];
       }
       lengths[rank] = n;
@@ -392,104 +385,28 @@ __device__ __forceinline__ void rnnt_finish(float* s_fin, const RnntWs& w, int n
 }
 
 // ------------------------------------------------------------------------------------------------ the offline search
-// The offline kernels keep their own bodies, as they were before the search was streamed: their machine code is that of the
-// earlier build, instruction for instruction (checked by disassembly), so their time cannot have changed.  The streamed kernels
-// below run the shared phases above, which restate these bodies line by line; tests/test_streaming_transducer_beam.py holds the
-// two to each other with torch.equal.  A change to a tie rule, the merge or a select has to be made in both places.
+// One workspace per utterance b; a frame is due while t < min(in_len[b], T); frame 0 starts from the empty hypothesis, which
+// the select kernel writes before it runs the phase (the row kernel of frame 0 only needs the count, 1).
+__device__ __forceinline__ RnntWs rnnt_ws_of(void* ws, int b, int T, int beam) {
+  return rnnt_ws_at((int*)ws + (long)b * rnnt_ws_words(T, beam), T, beam);
+}
+
 struct RowArgs {
   const float* logits; long ld;
-  const float* lm_rows; long ld_lm; int lm_no_blank;
+  const float* lm_rows; long ld_lm;
   const int* in_len; void* ws;
-  int T, V, beam, K, blank, eos;
-  float temperature, lm_weight;
-  int t;
+  RowParams p;
+  int T, beam, t;
 };
 
-// steps 1 - 3 of the contract and the row's top K, one workgroup per (utterance, slot)
+// the row phase, one workgroup per (utterance, slot)
 __global__ __launch_bounds__(256) void rnnt_beam_row_kernel(const RowArgs a) {
-  __shared__ float s_row[kRowLds];
-  __shared__ SelectScratch s_sel;
-  __shared__ float s_red[16];
-  __shared__ int s_cunsorted[kMaxK];
-  __shared__ int s_nc;
-  const int n = blockIdx.x, b = n / a.beam, j = n - b * a.beam, tid = threadIdx.x;
-  const RnntWs w = rnnt_ws(a.ws, b, a.T, a.beam);
+  __shared__ RowLds s;
+  const int n = blockIdx.x, b = n / a.beam, j = n - b * a.beam;
+  const RnntWs w = rnnt_ws_of(a.ws, b, a.T, a.beam);
   if (a.t >= min(a.in_len[b], a.T)) return;  // past the end of this utterance
-  const int nh = a.t == 0 ? 1 : w.cnt[0];    // (frame 0 starts from the empty hypothesis: the select phase initialises)
-  if (j >= nh) return;                       // dead slot: the row is not read
-  const float* x = a.logits + (long)n * a.ld;
-  const float* m = a.lm_rows ? a.lm_rows + (long)n * a.ld_lm : nullptr;
-  const int V = a.V, blank = a.blank, eos = a.eos;
-  const float temp = a.temperature, lw = a.lm_weight;
-  auto lm_col = [&](int v) { return a.lm_no_blank && v > blank ? v - 1 : v; };
-
-  // 1. z = logits / temperature to LDS; max, log-sum-exp, and the non-blank part of the sum
-  float mx = -INFINITY;
-  for (int v = tid; v < V; v += 256) {
-    const float z = x[v] / temp;
-    if (v < kRowLds) s_row[v] = z;
-    mx = fmaxf(mx, z);
-  }
-  mx = block_max(mx, s_red);
-  auto z_of = [&](int v) { return v < kRowLds ? s_row[v] : x[v] / temp; };
-  float sa = 0.f, snb = 0.f;
-  for (int v = tid; v < V; v += 256) {
-    const float e = expf(z_of(v) - mx);
-    sa += e;
-    snb += v == blank ? 0.f : e;
-  }
-  sa = block_sum(sa, s_red);
-  snb = block_sum(snb, s_red);
-  const float lse = mx + logf(sa);
-  float rb = z_of(blank) - lse;
-  float shift = -lse;  // r_v = (what LDS holds for v) + shift
-
-  // 2. fusion: f_v replaces z_v for v != blank; the shift gives the fused row the non-blank mass of the unfused one
-  if (m) {
-    float fm = -INFINITY;
-    for (int v = tid; v < V; v += 256) {
-      if (v == blank) continue;
-      const float f = z_of(v) - lse + lw * m[lm_col(v)];
-      if (v < kRowLds) s_row[v] = f;
-      fm = fmaxf(fm, f);
-    }
-    fm = block_max(fm, s_red);
-    auto f_of = [&](int v) { return v < kRowLds ? s_row[v] : x[v] / temp - lse + lw * m[lm_col(v)]; };
-    float sf = 0.f;
-    for (int v = tid; v < V; v += 256) sf += v == blank ? 0.f : expf(f_of(v) - fm);
-    sf = block_sum(sf, s_red);
-    shift = logf(snb) - logf(sa) - (fm + logf(sf));
-  }
-  auto r_of = [&](int v) {
-    if (v < kRowLds) return s_row[v] + shift;
-    return (m ? x[v] / temp - lse + lw * m[lm_col(v)] : x[v] / temp) + shift;
-  };
-  // 3. the model's eos counts as blank
-  if (eos >= 0) rb = lae(rb, r_of(eos));
-
-  // 4. the K non-blank tokens with the largest finite r, listed in token-id order
-  auto tok_key = [&](int v) -> uint64_t {
-    if (v == blank || v == eos) return 0ull;
-    const float r = r_of(v);
-    return isfinite(r) ? mk_key(r, v) : 0ull;
-  };
-  const uint64_t kth = select_nth(tok_key, V, a.K, s_sel);
-  if (tid == 0) s_nc = 0;
-  __syncthreads();
-  for (int v = tid; v < V; v += 256) {
-    const uint64_t k = tok_key(v);
-    if (k && k >= kth) s_cunsorted[atomicAdd(&s_nc, 1)] = v;
-  }
-  __syncthreads();
-  const int nc = s_nc;  // <= K: the keys are unique
-  if (tid < nc) {
-    const int v = s_cunsorted[tid];
-    int r = 0;
-    for (int i = 0; i < nc; ++i) r += s_cunsorted[i] < v;
-    w.ctok[(long)j * kMaxK + r] = v;
-    w.cval[(long)j * kMaxK + r] = r_of(v);
-  }
-  if (tid == 0) { w.rblank[j] = rb; w.rnc[j] = nc; }
+  if (j >= (a.t == 0 ? 1 : w.cnt[0])) return;  // dead slot: the row is not read
+  rnnt_row_phase<false>(s, a.p, w, a.logits + (long)n * a.ld, a.lm_rows ? a.lm_rows + (long)n * a.ld_lm : nullptr, j);
 }
 
 struct SelArgs {
@@ -498,170 +415,33 @@ struct SelArgs {
   int T, beam, K, blank, t;
 };
 
-// merge, selection and the new state of one utterance
+// the select phase, one workgroup per utterance
 __global__ __launch_bounds__(256) void rnnt_beam_select_kernel(const SelArgs a) {
-  __shared__ uint64_t s_key[kMaxCand];
-  __shared__ SelectScratch s_sel;
-  __shared__ int s_ctok[kMaxBeam * kMaxK];   // [slot][K]
-  __shared__ float s_cval[kMaxBeam * kMaxK];
-  __shared__ float s_score[kMaxBeam], s_rb[kMaxBeam], s_stay[kMaxBeam];
-  __shared__ int s_len[kMaxBeam], s_last[kMaxBeam], s_node[kMaxBeam], s_pnode[kMaxBeam], s_nc[kMaxBeam];
-  __shared__ unsigned long long s_merged[kMaxBeam];  // bit r of slot j: extension (j, r) merged into a stay
-  __shared__ int s_sel_idx[kMaxBeam];
-  __shared__ int s_nsel, s_nfresh;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int beam = a.beam, K = a.K, K1 = a.K + 1;
-  const RnntWs w = rnnt_ws(a.ws, b, a.T, beam);
-  const long row0 = (long)b * beam;
-
-  if (a.t == 0) {  // the empty hypothesis, an empty node table
-    for (int i = tid; i < w.tsize; i += 256) w.tab_key[i] = 0ull;
-    if (tid == 0) {
-      w.score[0] = 0.f; w.len[0] = 0; w.last[0] = -1; w.node[0] = 0; w.pnode[0] = -1;
-      w.cnt[0] = 1; w.cnt[1] = 1;
-      w.node_par[0] = -1; w.node_tok[0] = -1;
-    }
+  __shared__ SelLds s;
+  const int b = blockIdx.x;
+  const RnntWs w = rnnt_ws_of(a.ws, b, a.T, a.beam);
+  const long row0 = (long)b * a.beam;
+  if (a.t == 0) {
+    rnnt_init(w);
     __threadfence_block();
     __syncthreads();
   }
   if (a.t >= min(a.in_len[b], a.T)) {  // past the end of this utterance: the beam stands still
-    if (tid < beam) { a.parent[row0 + tid] = (int)(row0 + tid); a.token[row0 + tid] = a.blank; a.keep[row0 + tid] = 1; }
+    rnnt_identity(a.parent, a.token, a.keep, row0, a.beam, a.blank);
     return;
   }
-  const int nh = a.t == 0 ? 1 : w.cnt[0];
-  const int nnodes = a.t == 0 ? 1 : w.cnt[1];
-  if (tid < nh) {
-    s_score[tid] = w.score[tid]; s_len[tid] = w.len[tid]; s_last[tid] = w.last[tid]; s_node[tid] = w.node[tid];
-    s_pnode[tid] = w.pnode[tid]; s_rb[tid] = w.rblank[tid]; s_nc[tid] = w.rnc[tid];
-    s_merged[tid] = 0ull;
-  }
-  for (int i = tid; i < nh * K; i += 256) {  // (entries at or beyond a row's count are never used)
-    const int j = i / K, r = i - j * K;
-    s_ctok[i] = w.ctok[(long)j * kMaxK + r];
-    s_cval[i] = w.cval[(long)j * kMaxK + r];
-  }
-  __syncthreads();
-
-  // stays; a stay absorbs the extension y' + v == y (y' in the beam, v among its candidates)
-  if (tid < nh) {
-    float st = s_score[tid] + s_rb[tid];
-    if (s_len[tid] > 0) {
-      int src = -1;
-      for (int j = 0; j < nh; ++j) src = s_node[j] == s_pnode[tid] ? j : src;
-      if (src >= 0) {
-        const int nc = min(s_nc[src], K);
-        for (int r = 0; r < nc; ++r)
-          if (s_ctok[src * K + r] == s_last[tid]) {
-            atomicOr(&s_merged[src], 1ull << r);
-            st = lae(st, s_score[src] + s_cval[src * K + r]);
-          }
-      }
-    }
-    s_stay[tid] = st;
-  }
-  __syncthreads();
-
-  // candidates; index i = slot * (K + 1) + (0: stay, 1 + r: extension by the slot's r-th candidate token)
-  const int N = nh * K1;
-  for (int i = tid; i < N; i += 256) {
-    const int j = i / K1, q = i - j * K1;
-    float s = NAN;
-    if (q == 0) s = s_stay[j];
-    else if (q - 1 < s_nc[j] && !((s_merged[j] >> (q - 1)) & 1ull)) s = s_score[j] + s_cval[j * K + q - 1];
-    s_key[i] = isfinite(s) ? mk_key(s, i) : 0ull;
-  }
-  __syncthreads();
-  const uint64_t cth = select_nth([&](int i) { return s_key[i]; }, N, beam, s_sel);
-  if (tid == 0) s_nsel = 0;
-  __syncthreads();
-  for (int i = tid; i < N; i += 256) {
-    const uint64_t k = s_key[i];
-    if (k && k >= cth) s_sel_idx[atomicAdd(&s_nsel, 1)] = i;
-  }
-  __syncthreads();
-  const int ns = s_nsel;
-
-  // the new state (wave 0: lane = one selected candidate, written to slot = its rank)
-  float n_score = 0.f;
-  int n_len = 0, n_last = -1, n_node = 0, n_pnode = -1, slot = 0, par = 0, ext = 0, fresh = 0, tslot = -1;
-  if (tid < ns) {
-    const int i = s_sel_idx[tid];
-    const uint64_t k = s_key[i];
-    for (int m = 0; m < ns; ++m) slot += s_key[s_sel_idx[m]] > k;
-    const int j = i / K1, q = i - j * K1;
-    par = j;
-    if (q == 0) {
-      n_score = s_stay[j]; n_len = s_len[j]; n_last = s_last[j]; n_node = s_node[j]; n_pnode = s_pnode[j];
-    } else {
-      ext = 1;
-      n_score = s_score[j] + s_cval[j * K + q - 1];
-      n_len = s_len[j] + 1; n_last = s_ctok[j * K + q - 1]; n_pnode = s_node[j];
-      // the node of y_j + v: found in the hash table, or claimed there (distinct keys within one frame)
-      const unsigned long long key = ((unsigned long long)(n_pnode + 1) << 32) | (uint32_t)n_last;
-      const uint32_t mask = (uint32_t)w.tsize - 1u;
-      for (uint32_t h = tab_hash(key) & mask;; h = (h + 1) & mask) {
-        const unsigned long long cur = ld_l2(w.tab_key + h);
-        if (cur == key) { n_node = ld_l2(w.tab_val + h); break; }
-        if (cur == 0ull && atomicCAS(w.tab_key + h, 0ull, key) == 0ull) { fresh = 1; tslot = (int)h; break; }
-      }
-    }
-  }
-  if (tid < 64) {  // fresh nodes numbered in lane order (deterministic)
-    const unsigned long long fm = __ballot(fresh);
-    if (fresh) {
-      const int id = nnodes + __popcll(fm & ((1ull << tid) - 1ull));
-      n_node = id;
-      w.tab_val[tslot] = id;
-      if (id < w.cap) { w.node_par[id] = n_pnode; w.node_tok[id] = n_last; }
-    }
-    if (tid == 0) s_nfresh = __popcll(fm);
-  }
-  __syncthreads();
-  if (tid < ns) {
-    w.score[slot] = n_score; w.len[slot] = n_len; w.last[slot] = n_last; w.node[slot] = n_node; w.pnode[slot] = n_pnode;
-    a.parent[row0 + slot] = (int)(row0 + par);
-    a.token[row0 + slot] = ext ? n_last : a.blank;
-    a.keep[row0 + slot] = (uint8_t)!ext;
-  } else if (tid < beam) {  // empty slot: any valid row
-    a.parent[row0 + tid] = (int)row0; a.token[row0 + tid] = a.blank; a.keep[row0 + tid] = 1;
-  }
-  if (tid == 0) { w.cnt[0] = ns; w.cnt[1] = nnodes + s_nfresh; }
+  rnnt_select_phase<false>(s, w, a.beam, a.K, a.blank, a.t == 0 ? 1 : w.cnt[0], a.t == 0 ? 1 : w.cnt[1], a.parent, a.token, a.keep,
+                           row0);
 }
 
-// final score = s, or s / max(1, |y|); the nbest best by (-final, slot), backtracked into tokens [B][nbest][T]
+// the finish of every utterance into tokens [B][nbest][T]; T == 0: no step has run
 __global__ __launch_bounds__(64) void rnnt_beam_finish_kernel(void* ws, int T, int beam, int nbest, int pad, int normalize,
                                                               int* tokens, int* lengths, float* scores, int* nhyp) {
   __shared__ float s_fin[kMaxBeam];
-  const int b = blockIdx.x, j = threadIdx.x;
-  const RnntWs w = rnnt_ws(ws, b, T, beam);
-  const int nh = T == 0 ? 1 : w.cnt[0];  // (no frame at all: no step ran; the empty hypothesis)
-  if (j < nh) {
-    const float s = T == 0 ? 0.f : w.score[j];
-    const int n = T == 0 ? 0 : w.len[j];
-    s_fin[j] = normalize ? s / (float)max(1, n) : s;
-  }
-  __syncthreads();
-  if (j == 0) nhyp[b] = min(nh, nbest);
-  if (j < nh) {
-    const float s = s_fin[j];
-    int rank = 0;
-    for (int m = 0; m < nh; ++m) rank += s_fin[m] > s || (s_fin[m] == s && m < j);
-    if (rank < nbest) {
-      int* out = tokens + ((long)b * nbest + rank) * T;
-      const int n = T == 0 ? 0 : w.len[j];
-      for (int u = n; u < T; ++u) out[u] = pad;
-      int node = T == 0 ? 0 : w.node[j];
-      for (int u = n - 1; u >= 0 && node > 0; --u) { out[u] = w.node_tok[node]; node = w.node_par[node]; }
-      lengths[b * nbest + rank] = n;
-      scores[b * nbest + rank] = s;
-    }
-  }
-  for (int r = nh + j; r < nbest; r += 64) {
-    int* out = tokens + ((long)b * nbest + r) * T;
-    for (int u = 0; u < T; ++u) out[u] = pad;
-    lengths[b * nbest + r] = 0;
-    scores[b * nbest + r] = -INFINITY;
-  }
+  const int b = blockIdx.x;
+  const RnntWs w = rnnt_ws_of(ws, b, T, beam);
+  rnnt_finish<false>(s_fin, w, T == 0 ? 1 : w.cnt[0], T == 0, nbest, pad, normalize, T, tokens + (long)b * nbest * T,
+                     lengths + b * nbest, scores + b * nbest, nhyp + b);
 }
 
 // ------------------------------------------------------------------------------------------------ the streamed search
@@ -707,7 +487,7 @@ __global__ __launch_bounds__(256) void rnnt_beam_stream_row_kernel(const StreamR
   const int frames = q.head[0];
   if (frames < 0 || frames >= a.max_frames) return;  // a full slot
   if (j >= q.w.cnt[0]) return;                       // dead slot: the row is not read
-  rnnt_row_phase(s, a.p, q.w, a.logits + (long)n * a.ld, a.lm_rows ? a.lm_rows + (long)n * a.ld_lm : nullptr, j);
+  rnnt_row_phase<true>(s, a.p, q.w, a.logits + (long)n * a.ld, a.lm_rows ? a.lm_rows + (long)n * a.ld_lm : nullptr, j);
 }
 
 struct StreamSelArgs {
@@ -731,7 +511,7 @@ __global__ __launch_bounds__(256) void rnnt_beam_stream_select_kernel(const Stre
     return;
   }
   const int nh = min(max(q.w.cnt[0], 0), a.beam);
-  rnnt_select_phase(s, q.w, a.beam, a.K, a.blank, nh, q.w.cnt[1], a.parent, a.token, a.keep, row0);
+  rnnt_select_phase<true>(s, q.w, a.beam, a.K, a.blank, nh, q.w.cnt[1], a.parent, a.token, a.keep, row0);
   if (threadIdx.x == 0) q.head[0] = frames + 1;
 }
 
@@ -747,7 +527,7 @@ __global__ __launch_bounds__(64) void rnnt_beam_stream_finish_kernel(const Strea
   const int b = blockIdx.x, slot = a.slots[b];
   const bool valid = slot >= 0 && slot < a.max_streams;  // no such slot: no hypothesis
   const RnntSlot q = rnnt_slot((void*)a.state, valid ? slot : 0, a.max_frames, a.beam);
-  rnnt_finish(s_fin, q.w, valid ? min(max(q.w.cnt[0], 0), a.beam) : 0, false, a.nbest, a.pad, a.normalize, a.max_u,
+  rnnt_finish<true>(s_fin, q.w, valid ? min(max(q.w.cnt[0], 0), a.beam) : 0, false, a.nbest, a.pad, a.normalize, a.max_u,
               a.tokens + (long)b * a.nbest * a.max_u, a.lengths + b * a.nbest, a.scores + b * a.nbest, a.aux + b);
 }
 
@@ -826,17 +606,14 @@ extern "C" int ea_rnnt_frame_beam_step(const float* logits, long ld, const float
                                        int beam, int K, int blank, int eos, float temperature, float lm_weight, int t,
                                        hipStream_t stream) {
   if (B <= 0) return 0;
-  if (!logits || !in_len || !workspace || !parent || !token || !keep || T < 1 || t < 0 || t >= T || V < 2 || V > 65535 || ld < V ||
-      beam < 1 || beam > kMaxBeam || K < 1 || K > kMaxK || K > V - 1 || blank < 0 || blank >= V || eos < -1 || eos >= V ||
-      eos == blank || !(temperature > 0.f) || (lm_rows && ld_lm < (lm_no_blank ? V - 1 : V)))
+  if (!logits || !in_len || !workspace || !parent || !token || !keep || T < 1 || t < 0 || t >= T ||
+      rnnt_step_args_bad(ld, lm_rows, ld_lm, lm_no_blank, V, beam, K, blank, eos, temperature))
     return -2;
   RowArgs r;
-  // weight 0 is no fusion: the LM rows are not read (an entry of -inf times 0 would be NaN)
-  r.logits = logits; r.ld = ld; r.lm_rows = lm_weight != 0.f ? lm_rows : nullptr; r.ld_lm = ld_lm; r.lm_no_blank = lm_no_blank;
+  r.p = rnnt_row_params(lm_rows, lm_no_blank, V, K, blank, eos, temperature, lm_weight);
+  r.logits = logits; r.ld = ld; r.lm_rows = lm_rows; r.ld_lm = ld_lm;
   r.in_len = in_len; r.ws = workspace;
-  r.T = T; r.V = V; r.beam = beam; r.K = K; r.blank = blank; r.eos = eos;
-  r.temperature = temperature; r.lm_weight = lm_rows ? lm_weight : 0.f;
-  r.t = t;
+  r.T = T; r.beam = beam; r.t = t;
   hipLaunchKernelGGL(rnnt_beam_row_kernel, dim3(B * beam), dim3(256), 0, stream, r);
   SelArgs s;
   s.in_len = in_len; s.ws = workspace; s.parent = parent; s.token = token; s.keep = (uint8_t*)keep;

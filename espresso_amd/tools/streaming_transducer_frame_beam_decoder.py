@@ -14,8 +14,9 @@ listed streams' predictor (and LM) rows into [n * beam]-row tensors, and then pe
 frame's encoder rows (ea_gather_rows), `joint_step`, the step (ea_rnnt_frame_beam_stream_step), `reorder_state` +
 `advance(token, state, keep_row)` for the predictor (and the LM) — the loop of the offline decoder; the rows go back to their
 slots after the last frame.  A stream with fewer frames than j gets the identity triple from the step (its rows keep their
-state, as a finished utterance's do offline), so nothing is read back and nothing synchronises.  The per-frame code restates the
-offline kernels' (and is held to them bit for bit by the tests), so `close` returns what TransducerFrameBeamDecoder.search returns for the whole utterance, whatever the pieces.
+state, as a finished utterance's do offline), so nothing is read back and nothing synchronises.  The per-frame code is the
+offline kernels': one body, wrapped once per search (the tests hold the two wrappers to each other bit for bit), so `close`
+returns what TransducerFrameBeamDecoder.search returns for the whole utterance, whatever the pieces.
 
 `partial` reads, per stream, the live hypothesis with the best score and the stable prefix: the tokens shared by every live
 hypothesis.  Every later hypothesis is a stay or an extension of a live one (a merge lands on a live sequence), so the stable

@@ -493,8 +493,9 @@ int ea_rnnt_frame_beam_step(const float* logits, long ld, const float* lm_rows, 
 int ea_rnnt_frame_beam_finish(void* workspace, int B, int T, int beam, int nbest, int pad, int normalize, int* tokens,
                               int* lengths, float* scores, int* nhyp, ea_stream_t stream);
 /* The streamed frame-synchronous transducer beam search: the same frames, one per call, over streams that come and go
- * (csrc/rnnt_beam.hip; the per-frame code restates the offline step's and is tested against it, so a stream fed in any pieces gives bit for bit the offline
- * results of the whole utterance, whatever max_frames >= its length).  The search state of a stream lives in one of max_streams
+ * (csrc/rnnt_beam.hip; the per-frame code is the offline step's: one body with an offline and a streamed wrapper, the two
+ * tested against each other, so a stream fed in any pieces gives bit for bit the offline results of the whole utterance,
+ * whatever max_frames >= its length).  The search state of a stream lives in one of max_streams
  * slots of `state` (max_streams * ea_rnnt_frame_beam_stream_state_bytes(max_frames, beam) bytes, slot-major).  Per slot, int32
  * words: words = 2 + even(3 * tsize + 5 * beam + 2 + 2 * cap + 2 * beam + 2 * beam * 64) with cap = 1 + max_frames * beam, tsize
  * the smallest power of two >= max(64, 2 * cap) and even() rounding up to an even count: [0] frames consumed, [1] 0, then the

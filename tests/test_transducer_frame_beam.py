@@ -297,6 +297,29 @@ def test_step_kernels_refuse_bad_arguments():
 
 
 @pytest.mark.gpu
+def test_finish_without_frames():
+    """T = 0: no step has run, so the finish must not read the workspace (all bits set here: a count read from it would be
+    -1 and a score NaN).  Every utterance ends as the oracle's search over no frames does, with the empty hypothesis at score
+    0, and the other n-best entries are empty.  tokens is [B][nbest][0]; the entry point still wants a pointer."""
+    _need_gpu()
+    from espresso_amd import kernels as Kn
+
+    B, beam, nbest = 2, 3, 2
+    ref, _, _ = frame_beam_oracle(lambda t, y: None, 0, beam, beam, BLANK, nbest=nbest)
+    assert ref == [((), 0.0)]
+    ws = Kn.rnnt_frame_beam_workspace(B, 0, beam, DEV).fill_(0xFF)
+    tokens = torch.full((1,), 77, dtype=torch.int32, device=DEV)
+    lengths = torch.full((B, nbest), 77, dtype=torch.int32, device=DEV)
+    scores = torch.full((B, nbest), 77.0, device=DEV)
+    nhyp = torch.full((B,), 77, dtype=torch.int32, device=DEV)
+    for normalize in (0, 1):
+        Kn.check(Kn._lib.lib().ea_rnnt_frame_beam_finish(Kn._p(ws), B, 0, beam, nbest, 1, normalize, Kn._p(tokens), Kn._p(lengths),
+                                                         Kn._p(scores), Kn._p(nhyp), Kn._stream()), "ea_rnnt_frame_beam_finish")
+        assert nhyp.tolist() == [1] * B and lengths.tolist() == [[0, 0]] * B and tokens.tolist() == [77]
+        assert scores.tolist() == [[ref[0][1], -math.inf]] * B
+
+
+@pytest.mark.gpu
 def test_fusion_changes_the_answer():
     """Two tokens nearly tied acoustically at every emitting frame; the LM prefers one strongly: lambda = 0 picks the acoustic
     winner, lambda > 0 the LM's choice, and both equal the oracle."""
