@@ -417,14 +417,6 @@ extern "C" int ea_ctc_prefix_beam_finish(void* workspace, const float* lm_rows, 
 }
 
 // ------------------------------------------------------------------------------------------------ hotword biasing
-static int cg_tables(CgTables& g, const int* nodes, const int* edges, const int* root, int n_nodes, int n_edges, int V) {
-  // a trie: one edge into every node but the root; an empty graph is the root alone, and then the edge table may be NULL
-  if (!nodes || !root || n_nodes < 1 || n_edges < 0 || (n_edges > 0 && !edges) || n_edges != n_nodes - 1 || V < 1) return 0;
-  g.nodes = nodes; g.edges = edges; g.root = root;
-  g.n_nodes = n_nodes; g.n_edges = n_edges; g.V = V;
-  return 1;
-}
-
 extern "C" long ea_ctc_prefix_beam_bias_workspace_bytes(int B, int T, int beam) {
   const long base = ea_ctc_prefix_beam_workspace_bytes(B, T, beam);
   return base ? base + (long)B * 2L * beam * 4L : 0;
@@ -455,11 +447,8 @@ extern "C" int ea_ctc_prefix_beam_bias_finish(void* workspace, const float* lm_r
   if (B <= 0) return 0;
   if (T < 0 || beam < 1 || beam > kMaxBeam || nbest < 1 || nbest > beam || (lm_rows && eos < 0) || !cg_nodes || cg_n_nodes < 1)
     return -2;
-  CgTables g;
-  g.nodes = cg_nodes; g.edges = nullptr; g.root = nullptr;
-  g.n_nodes = cg_n_nodes; g.n_edges = 0; g.V = 0;
   hipLaunchKernelGGL(ctc_beam_finish_kernel<true>, dim3(B), dim3(64), 0, stream, workspace, lm_rows, ld_lm, lm_weight, ins_bonus,
-                     eos, T, beam, nbest, pad, tokens, lengths, scores, nhyp, g);
+                     eos, T, beam, nbest, pad, tokens, lengths, scores, nhyp, cg_nodes_only(cg_nodes, cg_n_nodes));
   return EA_CHECK_LAUNCH();
 }
 

@@ -1,7 +1,7 @@
 // Device helpers shared by the CTC prefix beam searches (ctc_beam.hip, ctc_lexicon_beam.hip): 48-bit ordering keys,
 // the workgroup-wide radix select over them, log-add-exp, the prefix hash and L2 loads of the workgroup's own writes; and the
-// one step of the hotword context graph (an Aho-Corasick automaton over the phrase trie) that the biased search, the replay
-// kernel and its host twin share.
+// one step of the hotword context graph (an Aho-Corasick automaton over the phrase trie) that the biased searches (ctc_beam.hip,
+// rnnt_beam.hip), the replay kernel and its host twin share.
 #pragma once
 #include "common.h"
 
@@ -150,6 +150,22 @@ __host__ __device__ __forceinline__ void cg_replay(const CgTables& g, const int*
   }
   *final_bias = b - cg_phi(g, q);
   *q_out = q;
+}
+
+// the table arguments of a C entry point -> g; 0 = malformed.  A trie: one edge into every node but the root; an empty graph is
+// the root alone, and then the edge table may be NULL
+inline int cg_tables(CgTables& g, const int* nodes, const int* edges, const int* root, int n_nodes, int n_edges, int V) {
+  if (!nodes || !root || n_nodes < 1 || n_edges < 0 || (n_edges > 0 && !edges) || n_edges != n_nodes - 1 || V < 1) return 0;
+  g.nodes = nodes; g.edges = edges; g.root = root;
+  g.n_nodes = n_nodes; g.n_edges = n_edges; g.V = V;
+  return 1;
+}
+// what a finish needs of the graph: phi of a node
+inline CgTables cg_nodes_only(const int* nodes, int n_nodes) {
+  CgTables g;
+  g.nodes = nodes; g.edges = nullptr; g.root = nullptr;
+  g.n_nodes = n_nodes; g.n_edges = 0; g.V = 0;
+  return g;
 }
 
 template <typename TX>

@@ -61,6 +61,26 @@
 //   rnnt_beam_stream_partial_kernel  64 threads (one wave per slot), no LDS, 22 VGPRs
 // RowLds and SelLds are left at their natural alignment of 8: aligning the row to 16 turns the radix passes' ds_read2_b64 into
 // ds_read_b128, which measured 0.1 - 0.2 us per frame slower, not faster.
+//
+// Hotword biasing (kBias instantiations, ea_rnnt_frame_beam_bias_* / ea_rnnt_frame_beam_stream_bias_*): the context graph of
+// ctc_beam.hip's BIAS kernels (ctc_beam_common.h: cg_step) on this beam.  Every hypothesis also carries a graph node q and a
+// running bias b, (root, 0) for the empty hypothesis, both functions of the token sequence alone: a stay changes neither, an
+// extension takes one automaton step, and a merge (decided by node equality, log-add-exp on s only) keeps the stay's, which
+// are what the extension would have computed.  The row phase is untouched (the K candidate tokens of a row stay the K with the
+// largest fused r_v: biasing re-ranks, it does not bring a token back).  In the select phase the lane that owns candidate
+// (j, v) walks the graph inside the candidate loop (cg_root[v], then for a slot off the root its node record, a binary search
+// over the node's edge records and the failure hops), s + b' is the ranking key (a candidate is live iff s is finite), and
+// (q', b') of ALL candidates wait in LDS for the <= beam selected ones: 33 280 B more, rather than a second walk of dependent
+// global loads by wave 0 on the path that already waits for the hash claim -- one workgroup per utterance leaves the CU's LDS
+// to it alone, so the size buys nothing back.  The finish adds b - phi(q); the partial ranks by and reports s + b.  (q, b) per
+// beam slot live BEHIND the unbiased state, whose layout stays what it is: offline behind the B workspaces (2 * beam words per
+// utterance, as ctc_beam.hip does it), streamed behind the slot, so
+//   bias words(max_frames, beam) = words(max_frames, beam) + 2 * beam.
+// The flag is a second template parameter of the four phases (the row phase ignores it: the streamed bias row kernel needs its
+// own slot stride, hence its own kernel, hence its own instantiation of select_nth).  kBias = false: arguments, layout, LDS
+// and instructions as before.  One search uses the bias calls for all of its steps, its finish and its partials.
+//   rnnt_beam_select_kernel<true>, rnnt_beam_stream_select_kernel<true>  256 threads, 103704 B LDS (SelLdsBias) -> 1 workgroup per CU
+//   (the offline bias step launches the unbiased row kernel; the other bias kernels: LDS of their unbiased twins)
 #include "common.h"
 #include "ctc_beam_common.h"
 #include "espresso_amd.h"
@@ -119,7 +139,23 @@ __device__ __forceinline__ RnntWs rnnt_ws_at(int* base, int T, int beam) {
 }
 
 // ------------------------------------------------------------------------------------------------ the phases
-// (templates on <kStreamed>: one instantiation per wrapper, see the header)
+// (templates on <kStreamed, kBias>: one instantiation per wrapper, see the header)
+// (q, b) of the biased search per beam slot, and the graph; nothing without kBias
+template <bool kBias> struct RnntBias {};
+template <> struct RnntBias<true> {
+  int* q; float* b;
+  CgTables g;
+};
+struct NoGraph {};
+template <bool kBias, class G>
+__device__ __forceinline__ RnntBias<kBias> rnnt_bias_at(int* base, int beam, const G& g) {
+  if constexpr (kBias) return {base, (float*)(base + beam), g}; else return {};
+}
+template <bool kBias, class A>
+__device__ __forceinline__ auto rnnt_graph_of(const A& a) {  // the graph of a kernel's bias arguments
+  if constexpr (kBias) return a.g; else return NoGraph{};
+}
+
 struct RowParams {  // what the row phase needs besides its row, the same for the offline and the streamed search
   int V, K, blank, eos, lm_no_blank;
   float temperature, lm_weight;
@@ -133,8 +169,12 @@ struct RowLds {
   int nc;
 };
 
-// steps 1 - 3 of the contract and the top K of the row x (LM row m or null) of live slot j; leaves the hand-over in w
-template <bool kStreamed>
+// steps 1 - 3 of the contract and the top K of the row x (LM row m or null) of live slot j; leaves the hand-over in w.
+// kBias is not read here: it only gives the streamed bias row kernel, whose slots are 2 * beam words longer, a body of its own.
+// One streamed row kernel for both families would need the slot stride among the unbiased kernel's arguments, which are kept as
+// they are; and two kernels on one instantiation would share one select_nth, which is then called instead of inlined -- what
+// cost the offline step 1.9 % when the search was first streamed (see the header).  The price is a second copy of this phase.
+template <bool kStreamed, bool kBias = false>
 __device__ __forceinline__ void rnnt_row_phase(RowLds& s, const RowParams& a, const RnntWs& w, const float* x, const float* m, int j) {
   const int tid = threadIdx.x;
   const int V = a.V, blank = a.blank, eos = a.eos;
@@ -212,13 +252,15 @@ __device__ __forceinline__ void rnnt_row_phase(RowLds& s, const RowParams& a, co
 
 // the state before frame 0: the empty hypothesis with score 0 in slot 0, node 0 in an empty table (blockDim 256; the caller
 // synchronises)
-__device__ __forceinline__ void rnnt_init(const RnntWs& w) {
+template <bool kBias>
+__device__ __forceinline__ void rnnt_init(const RnntWs& w, const RnntBias<kBias>& wb) {
   const int tid = threadIdx.x;
   for (int i = tid; i < w.tsize; i += 256) w.tab_key[i] = 0ull;
   if (tid == 0) {
     w.score[0] = 0.f; w.len[0] = 0; w.last[0] = -1; w.node[0] = 0; w.pnode[0] = -1;
     w.cnt[0] = 1; w.cnt[1] = 1;
     w.node_par[0] = -1; w.node_tok[0] = -1;
+    if constexpr (kBias) { wb.q[0] = 0; wb.b[0] = 0.f; }
   }
 }
 
@@ -239,17 +281,23 @@ struct SelLds {
   int sel_idx[kMaxBeam];
   int nsel, nfresh;
 };
+struct SelLdsBias : SelLds {
+  int q[kMaxBeam]; float b[kMaxBeam];    // per slot
+  int cq[kMaxCand]; float cb[kMaxCand];  // per candidate extension: the node and the running bias after it
+};
+template <bool kBias> using SelLdsOf = std::conditional_t<kBias, SelLdsBias, SelLds>;
 
 // merge, selection and the new state of one beam with nh hypotheses and nnodes table nodes; the triples go to rows row0 ...
-template <bool kStreamed>
-__device__ __forceinline__ void rnnt_select_phase(SelLds& s, const RnntWs& w, int beam, int K, int blank, int nh, int nnodes,
-                                                  int* parent, int* token, uint8_t* keep, long row0) {
+template <bool kStreamed, bool kBias>
+__device__ __forceinline__ void rnnt_select_phase(SelLdsOf<kBias>& s, const RnntWs& w, const RnntBias<kBias>& wb, int beam, int K,
+                                                  int blank, int nh, int nnodes, int* parent, int* token, uint8_t* keep, long row0) {
   const int tid = threadIdx.x;
   const int K1 = K + 1;
   if (tid < nh) {
     s.score[tid] = w.score[tid]; s.len[tid] = w.len[tid]; s.last[tid] = w.last[tid]; s.node[tid] = w.node[tid];
     s.pnode[tid] = w.pnode[tid]; s.rb[tid] = w.rblank[tid]; s.nc[tid] = w.rnc[tid];
     s.merged[tid] = 0ull;
+    if constexpr (kBias) { s.q[tid] = wb.q[tid]; s.b[tid] = wb.b[tid]; }
   }
   for (int i = tid; i < nh * K; i += 256) {  // (entries at or beyond a row's count are never used)
     const int j = i / K, r = i - j * K;
@@ -284,7 +332,21 @@ __device__ __forceinline__ void rnnt_select_phase(SelLds& s, const RnntWs& w, in
     float sc = NAN;
     if (q == 0) sc = s.stay[j];
     else if (q - 1 < s.nc[j] && !((s.merged[j] >> (q - 1)) & 1ull)) sc = s.score[j] + s.cval[j * K + q - 1];
-    s.key[i] = isfinite(sc) ? mk_key(sc, i) : 0ull;
+    // ranked by s + b'; one automaton step per live extension, on the lane that owns it.  cg_root[v] is loaded for every
+    // extension, not only for slots in the root: cg_step wants it as the fall-back of a walk that ends at the root, and loading
+    // it up front keeps it off the dependent chain of the walk (one 8-byte load per off-root candidate more than strictly needed)
+    if constexpr (kBias) {
+      float nb = s.b[j];
+      if (q > 0 && isfinite(sc)) {
+        const int v = s.ctok[j * K + q - 1];
+        const CgStep st = cg_step(wb.g, s.q[j], v, cg_root(wb.g, v));
+        nb += st.inc;
+        s.cq[i] = st.q; s.cb[i] = nb;
+      }
+      s.key[i] = isfinite(sc) ? mk_key(sc + nb, i) : 0ull;
+    } else {
+      s.key[i] = isfinite(sc) ? mk_key(sc, i) : 0ull;
+    }
   }
   __syncthreads();
   const uint64_t cth = select_nth([&](int i) { return s.key[i]; }, N, beam, s.sel);
@@ -300,6 +362,8 @@ __device__ __forceinline__ void rnnt_select_phase(SelLds& s, const RnntWs& w, in
   // the new state (wave 0: lane = one selected candidate, written to slot = its rank)
   float n_score = 0.f;
   int n_len = 0, n_last = -1, n_node = 0, n_pnode = -1, slot = 0, par = 0, ext = 0, fresh = 0, tslot = -1;
+  [[maybe_unused]] int n_q = 0;
+  [[maybe_unused]] float n_b = 0.f;
   if (tid < ns) {
     const int i = s.sel_idx[tid];
     const uint64_t k = s.key[i];
@@ -308,8 +372,10 @@ __device__ __forceinline__ void rnnt_select_phase(SelLds& s, const RnntWs& w, in
     par = j;
     if (q == 0) {
       n_score = s.stay[j]; n_len = s.len[j]; n_last = s.last[j]; n_node = s.node[j]; n_pnode = s.pnode[j];
+      if constexpr (kBias) { n_q = s.q[j]; n_b = s.b[j]; }
     } else {
       ext = 1;
+      if constexpr (kBias) { n_q = s.cq[i]; n_b = s.cb[i]; }
       n_score = s.score[j] + s.cval[j * K + q - 1];
       n_len = s.len[j] + 1; n_last = s.ctok[j * K + q - 1]; n_pnode = s.node[j];
       // the node of y_j + v: found in the hash table, or claimed there (distinct keys within one frame)
@@ -335,6 +401,7 @@ __device__ __forceinline__ void rnnt_select_phase(SelLds& s, const RnntWs& w, in
   __syncthreads();
   if (tid < ns) {
     w.score[slot] = n_score; w.len[slot] = n_len; w.last[slot] = n_last; w.node[slot] = n_node; w.pnode[slot] = n_pnode;
+    if constexpr (kBias) { wb.q[slot] = n_q; wb.b[slot] = n_b; }
     parent[row0 + slot] = (int)(row0 + par);
     token[row0 + slot] = ext ? n_last : blank;
     keep[row0 + slot] = (uint8_t)!ext;
@@ -344,15 +411,16 @@ __device__ __forceinline__ void rnnt_select_phase(SelLds& s, const RnntWs& w, in
   if (tid == 0) { w.cnt[0] = ns; w.cnt[1] = nnodes + s.nfresh; }
 }
 
-// final score = s, or s / max(1, |y|); the nbest best of the nh hypotheses by (-final, slot), backtracked into tokens
+// final score = s [+ b - phi(q)], or that / max(1, |y|); the nbest best of the nh hypotheses by (-final, slot), backtracked into tokens
 // [nbest][max_u] (pad-filled), lengths / scores [nbest] and *nhyp.  fresh: no step has run, the beam is the empty hypothesis
 // and w is not read.  Reads the state only (blockDim 64).
-template <bool kStreamed>
-__device__ __forceinline__ void rnnt_finish(float* s_fin, const RnntWs& w, int nh, bool fresh, int nbest, int pad, int normalize,
+template <bool kStreamed, bool kBias>
+__device__ __forceinline__ void rnnt_finish(float* s_fin, const RnntWs& w, const RnntBias<kBias>& wb, int nh, bool fresh, int nbest, int pad, int normalize,
                                             int max_u, int* tokens, int* lengths, float* scores, int* nhyp) {
   const int j = threadIdx.x;
   if (j < nh) {
-    const float s = fresh ? 0.f : w.score[j];
+    float s = fresh ? 0.f : w.score[j];
+    if constexpr (kBias) s += fresh ? 0.f : wb.b[j] - cg_phi(wb.g, wb.q[j]);
     const int n = fresh ? 0 : w.len[j];
     s_fin[j] = normalize ? s / (float)max(1, n) : s;
   }
@@ -414,15 +482,24 @@ struct SelArgs {
   int* parent; int* token; uint8_t* keep;
   int T, beam, K, blank, t;
 };
+struct BiasSelArgs : SelArgs { CgTables g; };
+
+// (q, b) of utterance b of B: behind the B unbiased workspaces
+template <bool kBias, class G, class... Unused>
+__device__ __forceinline__ RnntBias<kBias> rnnt_bias_of(void* ws, int B, int b, int T, int beam, const G& g, const Unused&...) {
+  return rnnt_bias_at<kBias>((int*)ws + (long)B * rnnt_ws_words(T, beam) + 2L * b * beam, beam, g);
+}
 
 // the select phase, one workgroup per utterance
-__global__ __launch_bounds__(256) void rnnt_beam_select_kernel(const SelArgs a) {
-  __shared__ SelLds s;
+template <bool kBias>
+__global__ __launch_bounds__(256) void rnnt_beam_select_kernel(const std::conditional_t<kBias, BiasSelArgs, SelArgs> a) {
+  __shared__ SelLdsOf<kBias> s;
   const int b = blockIdx.x;
   const RnntWs w = rnnt_ws_of(a.ws, b, a.T, a.beam);
+  const RnntBias<kBias> wb = rnnt_bias_of<kBias>(a.ws, gridDim.x, b, a.T, a.beam, rnnt_graph_of<kBias>(a));
   const long row0 = (long)b * a.beam;
   if (a.t == 0) {
-    rnnt_init(w);
+    rnnt_init<kBias>(w, wb);
     __threadfence_block();
     __syncthreads();
   }
@@ -430,42 +507,54 @@ __global__ __launch_bounds__(256) void rnnt_beam_select_kernel(const SelArgs a) 
     rnnt_identity(a.parent, a.token, a.keep, row0, a.beam, a.blank);
     return;
   }
-  rnnt_select_phase<false>(s, w, a.beam, a.K, a.blank, a.t == 0 ? 1 : w.cnt[0], a.t == 0 ? 1 : w.cnt[1], a.parent, a.token, a.keep,
-                           row0);
+  rnnt_select_phase<false, kBias>(s, w, wb, a.beam, a.K, a.blank, a.t == 0 ? 1 : w.cnt[0], a.t == 0 ? 1 : w.cnt[1], a.parent, a.token,
+                                  a.keep, row0);
 }
 
 // the finish of every utterance into tokens [B][nbest][T]; T == 0: no step has run
+// (g: the graph, one CgTables, with kBias and nothing without: the unbiased kernel keeps its parameter list)
+template <bool kBias, class... G>
 __global__ __launch_bounds__(64) void rnnt_beam_finish_kernel(void* ws, int T, int beam, int nbest, int pad, int normalize,
-                                                              int* tokens, int* lengths, float* scores, int* nhyp) {
+                                                              int* tokens, int* lengths, float* scores, int* nhyp, const G... g) {
+  static_assert(sizeof...(G) == (kBias ? 1 : 0));
   __shared__ float s_fin[kMaxBeam];
   const int b = blockIdx.x;
   const RnntWs w = rnnt_ws_of(ws, b, T, beam);
-  rnnt_finish<false>(s_fin, w, T == 0 ? 1 : w.cnt[0], T == 0, nbest, pad, normalize, T, tokens + (long)b * nbest * T,
-                     lengths + b * nbest, scores + b * nbest, nhyp + b);
+  const RnntBias<kBias> wb = rnnt_bias_of<kBias>(ws, gridDim.x, b, T, beam, g..., NoGraph{});
+  rnnt_finish<false, kBias>(s_fin, w, wb, T == 0 ? 1 : w.cnt[0], T == 0, nbest, pad, normalize, T, tokens + (long)b * nbest * T,
+                            lengths + b * nbest, scores + b * nbest, nhyp + b);
 }
 
 // ------------------------------------------------------------------------------------------------ the streamed search
 // State of one stream slot, int32 words: [0] frames consumed, [1] 0, then the offline workspace of one utterance of max_frames
-// frames (RnntWs: the row-to-select hand-over included).
-__host__ __device__ __forceinline__ long rnnt_state_words(int max_frames, int beam) { return 2 + rnnt_ws_words(max_frames, beam); }
+// frames (RnntWs: the row-to-select hand-over included), then with kBias (q, b) per beam slot.
+template <bool kBias = false>
+__host__ __device__ __forceinline__ long rnnt_state_words(int max_frames, int beam) {
+  return 2 + rnnt_ws_words(max_frames, beam) + (kBias ? 2L * beam : 0L);
+}
 
+template <bool kBias>
 struct RnntSlot {
   int* head;
   RnntWs w;
+  RnntBias<kBias> wb;
 };
-__device__ __forceinline__ RnntSlot rnnt_slot(void* state, int slot, int max_frames, int beam) {
-  RnntSlot q;
-  q.head = (int*)state + (long)slot * rnnt_state_words(max_frames, beam);
+template <bool kBias, class G>
+__device__ __forceinline__ RnntSlot<kBias> rnnt_slot(void* state, int slot, int max_frames, int beam, const G& g) {
+  RnntSlot<kBias> q;
+  q.head = (int*)state + (long)slot * rnnt_state_words<kBias>(max_frames, beam);
   q.w = rnnt_ws_at(q.head + 2, max_frames, beam);
+  q.wb = rnnt_bias_at<kBias>(q.head + 2 + rnnt_ws_words(max_frames, beam), beam, g);
   return q;
 }
 
+template <bool kBias>
 __global__ __launch_bounds__(256) void rnnt_beam_stream_reset_kernel(void* state, const int* slots, int max_streams, int max_frames,
                                                                      int beam) {
   const int slot = slots[blockIdx.x];
   if (slot < 0 || slot >= max_streams) return;
-  const RnntSlot q = rnnt_slot(state, slot, max_frames, beam);
-  rnnt_init(q.w);
+  const RnntSlot<kBias> q = rnnt_slot<kBias>(state, slot, max_frames, beam, CgTables{});
+  rnnt_init<kBias>(q.w, q.wb);
   if (threadIdx.x == 0) { q.head[0] = 0; q.head[1] = 0; }
 }
 
@@ -477,17 +566,18 @@ struct StreamRowArgs {
   int max_streams, max_frames, beam, j;
 };
 
-// the row phase of the streamed search, one workgroup per (listed stream, slot of its beam)
+// the row phase of the streamed search, one workgroup per (listed stream, slot of its beam); kBias: the slot stride only
+template <bool kBias>
 __global__ __launch_bounds__(256) void rnnt_beam_stream_row_kernel(const StreamRowArgs a) {
   __shared__ RowLds s;
   const int n = blockIdx.x, b = n / a.beam, j = n - b * a.beam;
   const int slot = a.slot_idx[b];
   if (slot < 0 || slot >= a.max_streams || a.j >= a.n_new[b]) return;
-  const RnntSlot q = rnnt_slot(a.state, slot, a.max_frames, a.beam);
+  const RnntSlot<kBias> q = rnnt_slot<kBias>(a.state, slot, a.max_frames, a.beam, CgTables{});
   const int frames = q.head[0];
   if (frames < 0 || frames >= a.max_frames) return;  // a full slot
   if (j >= q.w.cnt[0]) return;                       // dead slot: the row is not read
-  rnnt_row_phase<true>(s, a.p, q.w, a.logits + (long)n * a.ld, a.lm_rows ? a.lm_rows + (long)n * a.ld_lm : nullptr, j);
+  rnnt_row_phase<true, kBias>(s, a.p, q.w, a.logits + (long)n * a.ld, a.lm_rows ? a.lm_rows + (long)n * a.ld_lm : nullptr, j);
 }
 
 struct StreamSelArgs {
@@ -495,15 +585,16 @@ struct StreamSelArgs {
   int* parent; int* token; uint8_t* keep;
   int max_streams, max_frames, beam, K, blank, j;
 };
-
+struct BiasStreamSelArgs : StreamSelArgs { CgTables g; };
 // the select phase of the streamed search, one workgroup per listed stream; counts the frame
-__global__ __launch_bounds__(256) void rnnt_beam_stream_select_kernel(const StreamSelArgs a) {
-  __shared__ SelLds s;
+template <bool kBias>
+__global__ __launch_bounds__(256) void rnnt_beam_stream_select_kernel(const std::conditional_t<kBias, BiasStreamSelArgs, StreamSelArgs> a) {
+  __shared__ SelLdsOf<kBias> s;
   const int b = blockIdx.x;
   const long row0 = (long)b * a.beam;
   const int slot = a.slot_idx[b];
   bool due = slot >= 0 && slot < a.max_streams && a.j < a.n_new[b];
-  const RnntSlot q = rnnt_slot(a.state, due ? slot : 0, a.max_frames, a.beam);
+  const RnntSlot<kBias> q = rnnt_slot<kBias>(a.state, due ? slot : 0, a.max_frames, a.beam, rnnt_graph_of<kBias>(a));
   const int frames = due ? q.head[0] : -1;
   due = due && frames >= 0 && frames < a.max_frames;
   if (!due) {  // idle, no such slot, or a full slot: the slot is untouched
@@ -511,7 +602,7 @@ __global__ __launch_bounds__(256) void rnnt_beam_stream_select_kernel(const Stre
     return;
   }
   const int nh = min(max(q.w.cnt[0], 0), a.beam);
-  rnnt_select_phase<true>(s, q.w, a.beam, a.K, a.blank, nh, q.w.cnt[1], a.parent, a.token, a.keep, row0);
+  rnnt_select_phase<true, kBias>(s, q.w, q.wb, a.beam, a.K, a.blank, nh, q.w.cnt[1], a.parent, a.token, a.keep, row0);
   if (threadIdx.x == 0) q.head[0] = frames + 1;
 }
 
@@ -520,30 +611,34 @@ struct StreamReadArgs {
   int max_streams, max_frames, beam, nbest, pad, normalize, max_u;
   int *tokens, *lengths; float* scores; int* aux;  // aux: nhyp (finish) / stable_len (partial)
 };
+struct BiasStreamReadArgs : StreamReadArgs { CgTables g; };
 
 // readout of the given slots, as the offline kernel finishes; the state is read only
-__global__ __launch_bounds__(64) void rnnt_beam_stream_finish_kernel(const StreamReadArgs a) {
+template <bool kBias>
+__global__ __launch_bounds__(64) void rnnt_beam_stream_finish_kernel(const std::conditional_t<kBias, BiasStreamReadArgs, StreamReadArgs> a) {
   __shared__ float s_fin[kMaxBeam];
   const int b = blockIdx.x, slot = a.slots[b];
   const bool valid = slot >= 0 && slot < a.max_streams;  // no such slot: no hypothesis
-  const RnntSlot q = rnnt_slot((void*)a.state, valid ? slot : 0, a.max_frames, a.beam);
-  rnnt_finish<true>(s_fin, q.w, valid ? min(max(q.w.cnt[0], 0), a.beam) : 0, false, a.nbest, a.pad, a.normalize, a.max_u,
+  const RnntSlot<kBias> q = rnnt_slot<kBias>((void*)a.state, valid ? slot : 0, a.max_frames, a.beam, rnnt_graph_of<kBias>(a));
+  rnnt_finish<true, kBias>(s_fin, q.w, q.wb, valid ? min(max(q.w.cnt[0], 0), a.beam) : 0, false, a.nbest, a.pad, a.normalize, a.max_u,
               a.tokens + (long)b * a.nbest * a.max_u, a.lengths + b * a.nbest, a.scores + b * a.nbest, a.aux + b);
 }
 
-// The live hypothesis with the best score s (what the search prunes by; ties: the lower slot) and the length of the longest
+// The live hypothesis with the best score s (kBias: s + b; what the search prunes by; ties: the lower slot) and the length of the longest
 // common prefix of all live hypotheses: the depth of their lowest common ancestor in node_par.  Nodes are numbered in creation
 // order, so a parent's id is below its child's: lifting the highest node until all are equal ends at that ancestor.  One wave
 // per slot; the state is read only.
+template <bool kBias>
 __global__ __launch_bounds__(64) void rnnt_beam_stream_partial_kernel(const StreamReadArgs a) {
   const int b = blockIdx.x, lane = threadIdx.x, slot = a.slots[b];
   int* out = a.tokens + (long)b * a.max_u;
   const bool valid = slot >= 0 && slot < a.max_streams;
-  const RnntSlot q = rnnt_slot((void*)a.state, valid ? slot : 0, a.max_frames, a.beam);
+  const RnntSlot<kBias> q = rnnt_slot<kBias>((void*)a.state, valid ? slot : 0, a.max_frames, a.beam, CgTables{});
   const int nh = valid ? min(max(q.w.cnt[0], 0), a.beam) : 0;
   float sc = -INFINITY;
   int len = 0, node = 0;
   if (lane < nh) { sc = q.w.score[lane]; len = q.w.len[lane]; node = q.w.node[lane]; }
+  if constexpr (kBias) sc += lane < nh ? q.wb.b[lane] : 0.f;
   const bool in_set = lane < nh;
   // best: the highest score, then the lower slot (a nan score ranks below everything)
   const uint64_t key = in_set ? mk_key(sc == sc ? sc : -INFINITY, lane) : 0ull;
@@ -618,7 +713,7 @@ extern "C" int ea_rnnt_frame_beam_step(const float* logits, long ld, const float
   SelArgs s;
   s.in_len = in_len; s.ws = workspace; s.parent = parent; s.token = token; s.keep = (uint8_t*)keep;
   s.T = T; s.beam = beam; s.K = K; s.blank = blank; s.t = t;
-  hipLaunchKernelGGL(rnnt_beam_select_kernel, dim3(B), dim3(256), 0, stream, s);
+  hipLaunchKernelGGL(rnnt_beam_select_kernel<false>, dim3(B), dim3(256), 0, stream, s);
   return EA_CHECK_LAUNCH();
 }
 
@@ -627,8 +722,49 @@ extern "C" int ea_rnnt_frame_beam_finish(void* workspace, int B, int T, int beam
   if (B <= 0) return 0;
   if (!workspace || !tokens || !lengths || !scores || !nhyp || T < 0 || beam < 1 || beam > kMaxBeam || nbest < 1 || nbest > beam)
     return -2;
-  hipLaunchKernelGGL(rnnt_beam_finish_kernel, dim3(B), dim3(64), 0, stream, workspace, T, beam, nbest, pad, normalize, tokens,
+  hipLaunchKernelGGL(rnnt_beam_finish_kernel<false>, dim3(B), dim3(64), 0, stream, workspace, T, beam, nbest, pad, normalize, tokens,
                      lengths, scores, nhyp);
+  return EA_CHECK_LAUNCH();
+}
+
+// ------------------------------------------------------------------------------------------------ C ABI: hotword biasing
+extern "C" long ea_rnnt_frame_beam_bias_workspace_bytes(int B, int T, int beam) {
+  const long base = ea_rnnt_frame_beam_workspace_bytes(B, T, beam);
+  return base ? base + (long)B * 2L * beam * 4L : 0;
+}
+
+extern "C" int ea_rnnt_frame_beam_bias_step(const float* logits, long ld, const float* lm_rows, long ld_lm, int lm_no_blank,
+                                            const int* in_len, void* workspace, int* parent, int* token, void* keep,
+                                            const int* cg_nodes, const int* cg_edges, const int* cg_root, int cg_n_nodes,
+                                            int cg_n_edges, int B, int T, int V, int beam, int K, int blank, int eos,
+                                            float temperature, float lm_weight, int t, hipStream_t stream) {
+  if (B <= 0) return 0;
+  BiasSelArgs s;
+  if (!logits || !in_len || !workspace || !parent || !token || !keep || T < 1 || t < 0 || t >= T ||
+      rnnt_step_args_bad(ld, lm_rows, ld_lm, lm_no_blank, V, beam, K, blank, eos, temperature) ||
+      !cg_tables(s.g, cg_nodes, cg_edges, cg_root, cg_n_nodes, cg_n_edges, V))
+    return -2;
+  RowArgs r;  // the row phase knows nothing of the graph: the unbiased row kernel on the unbiased part of the workspace
+  r.p = rnnt_row_params(lm_rows, lm_no_blank, V, K, blank, eos, temperature, lm_weight);
+  r.logits = logits; r.ld = ld; r.lm_rows = lm_rows; r.ld_lm = ld_lm;
+  r.in_len = in_len; r.ws = workspace;
+  r.T = T; r.beam = beam; r.t = t;
+  hipLaunchKernelGGL(rnnt_beam_row_kernel, dim3(B * beam), dim3(256), 0, stream, r);
+  s.in_len = in_len; s.ws = workspace; s.parent = parent; s.token = token; s.keep = (uint8_t*)keep;
+  s.T = T; s.beam = beam; s.K = K; s.blank = blank; s.t = t;
+  hipLaunchKernelGGL(rnnt_beam_select_kernel<true>, dim3(B), dim3(256), 0, stream, s);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_rnnt_frame_beam_bias_finish(void* workspace, const int* cg_nodes, int cg_n_nodes, int B, int T, int beam, int nbest,
+                                              int pad, int normalize, int* tokens, int* lengths, float* scores, int* nhyp,
+                                              hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (!workspace || !tokens || !lengths || !scores || !nhyp || T < 0 || beam < 1 || beam > kMaxBeam || nbest < 1 || nbest > beam ||
+      !cg_nodes || cg_n_nodes < 1)
+    return -2;
+  hipLaunchKernelGGL((rnnt_beam_finish_kernel<true, CgTables>), dim3(B), dim3(64), 0, stream, workspace, T, beam, nbest, pad, normalize, tokens,
+                     lengths, scores, nhyp, cg_nodes_only(cg_nodes, cg_n_nodes));
   return EA_CHECK_LAUNCH();
 }
 
@@ -642,7 +778,7 @@ extern "C" int ea_rnnt_frame_beam_stream_reset(void* state, const int* slots, in
                                                hipStream_t stream) {
   if (n <= 0) return 0;
   if (!state || !slots || max_streams < 1 || max_frames < 1 || beam < 1 || beam > kMaxBeam) return -2;
-  hipLaunchKernelGGL(rnnt_beam_stream_reset_kernel, dim3(n), dim3(256), 0, stream, state, slots, max_streams, max_frames, beam);
+  hipLaunchKernelGGL(rnnt_beam_stream_reset_kernel<false>, dim3(n), dim3(256), 0, stream, state, slots, max_streams, max_frames, beam);
   return EA_CHECK_LAUNCH();
 }
 
@@ -659,11 +795,11 @@ extern "C" int ea_rnnt_frame_beam_stream_step(const float* logits, long ld, cons
   r.logits = logits; r.ld = ld; r.lm_rows = lm_rows; r.ld_lm = ld_lm;
   r.slot_idx = slot_idx; r.n_new = n_new; r.state = state;
   r.max_streams = max_streams; r.max_frames = max_frames; r.beam = beam; r.j = j;
-  hipLaunchKernelGGL(rnnt_beam_stream_row_kernel, dim3(n * beam), dim3(256), 0, stream, r);
+  hipLaunchKernelGGL(rnnt_beam_stream_row_kernel<false>, dim3(n * beam), dim3(256), 0, stream, r);
   StreamSelArgs s;
   s.slot_idx = slot_idx; s.n_new = n_new; s.state = state; s.parent = parent; s.token = token; s.keep = (uint8_t*)keep;
   s.max_streams = max_streams; s.max_frames = max_frames; s.beam = beam; s.K = K; s.blank = blank; s.j = j;
-  hipLaunchKernelGGL(rnnt_beam_stream_select_kernel, dim3(n), dim3(256), 0, stream, s);
+  hipLaunchKernelGGL(rnnt_beam_stream_select_kernel<false>, dim3(n), dim3(256), 0, stream, s);
   return EA_CHECK_LAUNCH();
 }
 
@@ -673,6 +809,14 @@ static bool rnnt_read_args_bad(const void* state, const int* slots, int max_stre
          beam > kMaxBeam || max_u < 0;
 }
 
+static void rnnt_read_args(StreamReadArgs& a, const void* state, const int* slots, int max_streams, int max_frames, int beam, int nbest,
+                           int pad, int normalize, int max_u, int* tokens, int* lengths, float* scores, int* aux) {
+  a.state = state; a.slots = slots;
+  a.max_streams = max_streams; a.max_frames = max_frames; a.beam = beam; a.nbest = nbest; a.pad = pad; a.normalize = normalize;
+  a.max_u = max_u;
+  a.tokens = tokens; a.lengths = lengths; a.scores = scores; a.aux = aux;
+}
+
 extern "C" int ea_rnnt_frame_beam_stream_finish(const void* state, const int* slots, int n, int max_streams, int max_frames,
                                                 int beam, int nbest, int pad, int normalize, int max_u, int* tokens, int* lengths,
                                                 float* scores, int* nhyp, hipStream_t stream) {
@@ -680,11 +824,8 @@ extern "C" int ea_rnnt_frame_beam_stream_finish(const void* state, const int* sl
   if (rnnt_read_args_bad(state, slots, max_streams, max_frames, beam, max_u, tokens, lengths, scores, nhyp) || nbest < 1 || nbest > beam)
     return -2;
   StreamReadArgs a;
-  a.state = state; a.slots = slots;
-  a.max_streams = max_streams; a.max_frames = max_frames; a.beam = beam; a.nbest = nbest; a.pad = pad; a.normalize = normalize;
-  a.max_u = max_u;
-  a.tokens = tokens; a.lengths = lengths; a.scores = scores; a.aux = nhyp;
-  hipLaunchKernelGGL(rnnt_beam_stream_finish_kernel, dim3(n), dim3(64), 0, stream, a);
+  rnnt_read_args(a, state, slots, max_streams, max_frames, beam, nbest, pad, normalize, max_u, tokens, lengths, scores, nhyp);
+  hipLaunchKernelGGL(rnnt_beam_stream_finish_kernel<false>, dim3(n), dim3(64), 0, stream, a);
   return EA_CHECK_LAUNCH();
 }
 
@@ -694,9 +835,71 @@ extern "C" int ea_rnnt_frame_beam_stream_partial(const void* state, const int* s
   if (n <= 0) return 0;
   if (rnnt_read_args_bad(state, slots, max_streams, max_frames, beam, max_u, tokens, lengths, scores, stable_len)) return -2;
   StreamReadArgs a;
-  a.state = state; a.slots = slots;
-  a.max_streams = max_streams; a.max_frames = max_frames; a.beam = beam; a.nbest = 1; a.pad = pad; a.normalize = 0; a.max_u = max_u;
-  a.tokens = tokens; a.lengths = lengths; a.scores = scores; a.aux = stable_len;
-  hipLaunchKernelGGL(rnnt_beam_stream_partial_kernel, dim3(n), dim3(64), 0, stream, a);
+  rnnt_read_args(a, state, slots, max_streams, max_frames, beam, 1, pad, 0, max_u, tokens, lengths, scores, stable_len);
+  hipLaunchKernelGGL(rnnt_beam_stream_partial_kernel<false>, dim3(n), dim3(64), 0, stream, a);
+  return EA_CHECK_LAUNCH();
+}
+
+// ------------------------------------------------------------------------------------------------ C ABI: the streamed search, biased
+extern "C" long ea_rnnt_frame_beam_stream_bias_state_bytes(int max_frames, int beam) {
+  if (max_frames < 1 || beam < 1 || beam > kMaxBeam) return 0;
+  return rnnt_state_words<true>(max_frames, beam) * 4L;
+}
+
+extern "C" int ea_rnnt_frame_beam_stream_bias_reset(void* state, const int* slots, int n, int max_streams, int max_frames, int beam,
+                                                    hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!state || !slots || max_streams < 1 || max_frames < 1 || beam < 1 || beam > kMaxBeam) return -2;
+  hipLaunchKernelGGL(rnnt_beam_stream_reset_kernel<true>, dim3(n), dim3(256), 0, stream, state, slots, max_streams, max_frames, beam);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_rnnt_frame_beam_stream_bias_step(const float* logits, long ld, const float* lm_rows, long ld_lm, int lm_no_blank,
+                                                   const int* slot_idx, const int* n_new, int j, int n, void* state, int* parent,
+                                                   int* token, void* keep, const int* cg_nodes, const int* cg_edges,
+                                                   const int* cg_root, int cg_n_nodes, int cg_n_edges, int max_streams,
+                                                   int max_frames, int V, int beam, int K, int blank, int eos, float temperature,
+                                                   float lm_weight, hipStream_t stream) {
+  if (n <= 0) return 0;
+  BiasStreamSelArgs s;
+  if (!logits || !slot_idx || !n_new || !state || !parent || !token || !keep || j < 0 || max_streams < 1 || max_frames < 1 ||
+      rnnt_step_args_bad(ld, lm_rows, ld_lm, lm_no_blank, V, beam, K, blank, eos, temperature) ||
+      !cg_tables(s.g, cg_nodes, cg_edges, cg_root, cg_n_nodes, cg_n_edges, V))
+    return -2;
+  StreamRowArgs r;
+  r.p = rnnt_row_params(lm_rows, lm_no_blank, V, K, blank, eos, temperature, lm_weight);
+  r.logits = logits; r.ld = ld; r.lm_rows = lm_rows; r.ld_lm = ld_lm;
+  r.slot_idx = slot_idx; r.n_new = n_new; r.state = state;
+  r.max_streams = max_streams; r.max_frames = max_frames; r.beam = beam; r.j = j;
+  hipLaunchKernelGGL(rnnt_beam_stream_row_kernel<true>, dim3(n * beam), dim3(256), 0, stream, r);
+  s.slot_idx = slot_idx; s.n_new = n_new; s.state = state; s.parent = parent; s.token = token; s.keep = (uint8_t*)keep;
+  s.max_streams = max_streams; s.max_frames = max_frames; s.beam = beam; s.K = K; s.blank = blank; s.j = j;
+  hipLaunchKernelGGL(rnnt_beam_stream_select_kernel<true>, dim3(n), dim3(256), 0, stream, s);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_rnnt_frame_beam_stream_bias_finish(const void* state, const int* slots, int n, int max_streams, int max_frames,
+                                                     int beam, const int* cg_nodes, int cg_n_nodes, int nbest, int pad,
+                                                     int normalize, int max_u, int* tokens, int* lengths, float* scores, int* nhyp,
+                                                     hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (rnnt_read_args_bad(state, slots, max_streams, max_frames, beam, max_u, tokens, lengths, scores, nhyp) || nbest < 1 ||
+      nbest > beam || !cg_nodes || cg_n_nodes < 1)
+    return -2;
+  BiasStreamReadArgs a;
+  rnnt_read_args(a, state, slots, max_streams, max_frames, beam, nbest, pad, normalize, max_u, tokens, lengths, scores, nhyp);
+  a.g = cg_nodes_only(cg_nodes, cg_n_nodes);
+  hipLaunchKernelGGL(rnnt_beam_stream_finish_kernel<true>, dim3(n), dim3(64), 0, stream, a);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_rnnt_frame_beam_stream_bias_partial(const void* state, const int* slots, int n, int max_streams, int max_frames,
+                                                      int beam, int pad, int max_u, int* tokens, int* lengths, float* scores,
+                                                      int* stable_len, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (rnnt_read_args_bad(state, slots, max_streams, max_frames, beam, max_u, tokens, lengths, scores, stable_len)) return -2;
+  StreamReadArgs a;
+  rnnt_read_args(a, state, slots, max_streams, max_frames, beam, 1, pad, 0, max_u, tokens, lengths, scores, stable_len);
+  hipLaunchKernelGGL(rnnt_beam_stream_partial_kernel<true>, dim3(n), dim3(64), 0, stream, a);
   return EA_CHECK_LAUNCH();
 }

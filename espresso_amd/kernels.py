@@ -745,6 +745,112 @@ def rnnt_frame_beam_stream_partial(state, slots, max_frames, beam, pad, max_u):
     return tokens, lengths, scores, stable
 
 
+def rnnt_frame_beam_bias_workspace(B, T, beam, device):
+    """Workspace of the hotword-biased frame-synchronous transducer beam search (ea_rnnt_frame_beam_bias_workspace_bytes)."""
+    return torch.empty(int(_lib.lib().ea_rnnt_frame_beam_bias_workspace_bytes(B, T, beam)), dtype=torch.uint8, device=device)
+
+
+def rnnt_frame_beam_bias_step(logits, in_len, ws, graph, out, B, T, V, beam, K, blank, t, eos=-1, temperature=1.0, lm_rows=None,
+                              lm_weight=0.0, lm_no_blank=False):
+    """rnnt_frame_beam_step with a context graph (nodes, edges, root device tables of tools.context_graph.ContextGraph.cuda());
+    ws: rnnt_frame_beam_bias_workspace(B, T, beam)."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == B * beam and logits.shape[1] >= V
+    assert in_len.dtype == torch.int32 and in_len.numel() == B
+    parent, token, keep = out
+    assert parent.numel() == token.numel() == keep.numel() == B * beam
+    assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
+    if lm_rows is not None:
+        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (B * beam, V - 1 if lm_no_blank else V)
+    check(_lib.lib().ea_rnnt_frame_beam_bias_step(_p(logits), logits.stride(0), _p(lm_rows),
+                                                  lm_rows.stride(0) if lm_rows is not None else 0, int(lm_no_blank), _p(in_len), _p(ws),
+                                                  _p(parent), _p(token), _p(keep), *_cg(graph, V), B, T, V, beam, K, blank, eos,
+                                                  temperature, lm_weight, t, _stream()), "ea_rnnt_frame_beam_bias_step")
+
+
+def rnnt_frame_beam_bias_finish(ws, graph, B, T, beam, nbest, pad, normalize=True):
+    """rnnt_frame_beam_finish of a biased search: the scores include the boosts of the completed phrases."""
+    dev = ws.device
+    tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
+    lengths = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
+    nhyp = torch.empty(B, dtype=torch.int32, device=dev)
+    nodes, _, _, n_nodes, _ = _cg(graph)
+    check(_lib.lib().ea_rnnt_frame_beam_bias_finish(_p(ws), nodes, n_nodes, B, T, beam, nbest, pad, int(bool(normalize)), _p(tokens),
+                                                    _p(lengths), _p(scores), _p(nhyp), _stream()), "ea_rnnt_frame_beam_bias_finish")
+    return tokens, lengths, scores, nhyp
+
+
+def rnnt_frame_beam_stream_bias_state(max_streams, max_frames, beam, device):
+    """(state uint8 [max_streams][bytes per slot], zero-filled; bytes per slot) of the streamed, hotword-biased frame-synchronous
+    transducer beam search (ea_rnnt_frame_beam_stream_bias_state_bytes)."""
+    nbytes = int(_lib.lib().ea_rnnt_frame_beam_stream_bias_state_bytes(max_frames, beam))
+    assert nbytes > 0 and max_streams >= 1
+    return torch.zeros(max_streams, nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def _check_rnnt_stream_bias_state(state, max_frames, beam):
+    assert state.dtype == torch.uint8 and state.is_contiguous() and state.dim() == 2
+    assert state.shape[1] == _lib.lib().ea_rnnt_frame_beam_stream_bias_state_bytes(max_frames, beam)
+
+
+def rnnt_frame_beam_stream_bias_reset(state, slots, max_frames, beam):
+    """rnnt_frame_beam_stream_reset of a biased state: the empty hypothesis sits in the graph's root with bias 0."""
+    _check_rnnt_stream_bias_state(state, max_frames, beam)
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
+    check(_lib.lib().ea_rnnt_frame_beam_stream_bias_reset(_p(state), _p(slots), slots.numel(), state.shape[0], max_frames, beam,
+                                                          _stream()), "ea_rnnt_frame_beam_stream_bias_reset")
+
+
+def rnnt_frame_beam_stream_bias_step(logits, slot_idx, n_new, j, state, graph, out, max_frames, V, beam, K, blank, eos=-1,
+                                     temperature=1.0, lm_rows=None, lm_weight=0.0, lm_no_blank=False):
+    """rnnt_frame_beam_stream_step with a context graph; state: rnnt_frame_beam_stream_bias_state."""
+    n = slot_idx.numel()
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == n * beam and logits.shape[1] >= V
+    assert slot_idx.dtype == n_new.dtype == torch.int32 and n_new.numel() == n and slot_idx.is_contiguous() and n_new.is_contiguous()
+    _check_rnnt_stream_bias_state(state, max_frames, beam)
+    parent, token, keep = out
+    assert parent.numel() == token.numel() == keep.numel() == n * beam
+    assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
+    if lm_rows is not None:
+        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (n * beam, V - 1 if lm_no_blank else V)
+    check(_lib.lib().ea_rnnt_frame_beam_stream_bias_step(_p(logits), logits.stride(0), _p(lm_rows),
+                                                         lm_rows.stride(0) if lm_rows is not None else 0, int(lm_no_blank),
+                                                         _p(slot_idx), _p(n_new), j, n, _p(state), _p(parent), _p(token), _p(keep),
+                                                         *_cg(graph, V), state.shape[0], max_frames, V, beam, K, blank, eos,
+                                                         temperature, lm_weight, _stream()), "ea_rnnt_frame_beam_stream_bias_step")
+
+
+def rnnt_frame_beam_stream_bias_finish(state, slots, graph, max_frames, beam, nbest, pad, max_u, normalize=True):
+    """rnnt_frame_beam_stream_finish of a biased state: the scores include the boosts of the completed phrases."""
+    _check_rnnt_stream_bias_state(state, max_frames, beam)
+    assert slots.dtype == torch.int32 and slots.is_contiguous()
+    n, dev = slots.numel(), state.device
+    tokens = torch.empty(n, nbest, max_u, dtype=torch.int32, device=dev)
+    lengths = torch.empty(n, nbest, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, nbest, dtype=torch.float32, device=dev)
+    nhyp = torch.empty(n, dtype=torch.int32, device=dev)
+    nodes, _, _, n_nodes, _ = _cg(graph)
+    check(_lib.lib().ea_rnnt_frame_beam_stream_bias_finish(_p(state), _p(slots), n, state.shape[0], max_frames, beam, nodes, n_nodes,
+                                                           nbest, pad, int(bool(normalize)), max_u, _p(tokens), _p(lengths), _p(scores),
+                                                           _p(nhyp), _stream()), "ea_rnnt_frame_beam_stream_bias_finish")
+    return tokens, lengths, scores, nhyp
+
+
+def rnnt_frame_beam_stream_bias_partial(state, slots, max_frames, beam, pad, max_u):
+    """rnnt_frame_beam_stream_partial of a biased state: the live hypothesis with the best score + running bias, and that value."""
+    _check_rnnt_stream_bias_state(state, max_frames, beam)
+    assert slots.dtype == torch.int32 and slots.is_contiguous()
+    n, dev = slots.numel(), state.device
+    tokens = torch.empty(n, max_u, dtype=torch.int32, device=dev)
+    lengths = torch.empty(n, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, dtype=torch.float32, device=dev)
+    stable = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.lib().ea_rnnt_frame_beam_stream_bias_partial(_p(state), _p(slots), n, state.shape[0], max_frames, beam, pad, max_u,
+                                                            _p(tokens), _p(lengths), _p(scores), _p(stable), _stream()),
+          "ea_rnnt_frame_beam_stream_bias_partial")
+    return tokens, lengths, scores, stable
+
+
 def context_graph_score(graph, tokens, lens):
     """Token rows int32 [N][L] (lens int32 [N]) replayed through a context graph on the device (ea_context_graph_score):
     (running bias fp32 [N][L], final bias fp32 [N], node int32 [N])."""

@@ -140,7 +140,8 @@ def collate(ids: List[int], utt_ids: List[str], waves: List[np.ndarray], device)
 
 
 def build_generator(args, model, dictionary, lm=None, ngram=None, context_graph=None):
-    """ngram: (NGramLanguageModel, LexiconTrie) for --search ctc_beam --ngram-lm; context_graph: the ContextGraph of --hotwords.
+    """ngram: (NGramLanguageModel, LexiconTrie) for --search ctc_beam --ngram-lm; context_graph: the ContextGraph of --hotwords
+    (--search ctc_beam) or --transducer-hotwords (--search transducer_frame_beam).
     (--search transducer_stream_beam has no generator: recognize_streaming builds its decoder from stream_beam_options.)"""
     from .sequence_generator import SequenceGenerator
     from .tools.ctc_decoder import CTCDecoder
@@ -171,18 +172,22 @@ def build_generator(args, model, dictionary, lm=None, ngram=None, context_graph=
     if args.search == "transducer_frame_beam":
         return TransducerFrameBeamDecoder([model], dictionary, beam_size=args.beam, nbest=args.nbest,
                                           beam_size_token=args.transducer_beam_size_token, temperature=args.temperature,
-                                          normalize_scores=not args.unnormalized, lm_model=lm, lm_weight=args.lm_weight)
+                                          normalize_scores=not args.unnormalized, lm_model=lm, lm_weight=args.lm_weight,
+                                          context_graph=context_graph)
     return SequenceGenerator(model if isinstance(model, (list, tuple)) else [model], dictionary, beam_size=args.beam, max_len_a=args.max_len_a, max_len_b=args.max_len_b,
                              min_len=args.min_len, normalize_scores=not args.unnormalized, len_penalty=args.lenpen,
                              unk_penalty=args.unkpen, temperature=args.temperature, lm_model=lm, lm_weight=args.lm_weight,
                              eos_factor=args.eos_factor, print_alignment=getattr(args, "print_alignment", None) is not None)
 
 
-def stream_beam_options(args, lm=None):
+def stream_beam_options(args, lm=None, context_graph=None):
     """The options of StreamingTransducerFrameBeamDecoder (after model, dictionary, max_streams, max_frames) from the command
-    line of --search transducer_stream_beam."""
-    return dict(beam_size=args.beam, nbest=args.nbest, beam_size_token=args.transducer_beam_size_token, temperature=args.temperature,
+    line of --search transducer_stream_beam; context_graph: the ContextGraph of --transducer-hotwords."""
+    opts = dict(beam_size=args.beam, nbest=args.nbest, beam_size_token=args.transducer_beam_size_token, temperature=args.temperature,
                 normalize_scores=not args.unnormalized, lm_model=lm, lm_weight=args.lm_weight)
+    if context_graph is not None:
+        opts["context_graph"] = context_graph
+    return opts
 
 
 def get_parser():
@@ -237,9 +242,16 @@ def get_parser():
                         "scaled by --lm-weight; H- scores include it).  The candidate tokens of a frame stay the "
                         "--ctc-beam-size-token best by acoustic score: biasing re-ranks hypotheses, it does not bring back a token "
                         "outside them")
+    p.add_argument("--transducer-hotwords", default=None, metavar="FILE",
+                   help="transducer_frame_beam / transducer_stream_beam: the phrase file of --hotwords (same format, --hotword-score, "
+                        "--bpe and --sentencepiece-model) for the frame-synchronous transducer beam search, offline and streamed, "
+                        "with or without --lm-path.  The extensions of a hypothesis stay the --transducer-beam-size-token best by "
+                        "acoustic (and LM-fused) score: biasing re-ranks hypotheses, it does not bring back a token outside them, so "
+                        "with it the default of that option no longer amounts to a global top --beam.  --stream-partials then shows "
+                        "the hypothesis that leads with its pending boosts counted")
     p.add_argument("--hotword-score", type=float, default=None,
-                   help="--hotwords: boost per token of the phrases that give none of their own (default 1.5)")
-    p.add_argument("--bpe", default=None, choices=["characters_asr", "sentencepiece"], help="--hotwords: sub-word tokeniser of the phrases (as speech_align --bpe)")
+                   help="--hotwords / --transducer-hotwords: boost per token of the phrases that give none of their own (default 1.5)")
+    p.add_argument("--bpe", default=None, choices=["characters_asr", "sentencepiece"], help="--hotwords / --transducer-hotwords: sub-word tokeniser of the phrases (as speech_align --bpe)")
     p.add_argument("--sentencepiece-model", default=None, help="--bpe sentencepiece: the model file")
     p.add_argument("--max-num-expansions-per-step", type=int, default=2)
     p.add_argument("--expansion-beta", type=int, default=0)
@@ -286,10 +298,14 @@ def check_ngram_args(args):
         raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
 
 
+# --hotwords is the option of the CTC prefix beam search; the transducer beam searches take the same file under a name of their own
+_HOTWORDS_HINT = " (that option biases --search ctc_beam): give the phrase file as --transducer-hotwords"
+
+
 def check_frame_beam_args(args):
     """--search transducer_frame_beam is the device-resident frame-synchronous beam search of one transducer model, alone or with
-    one sub-word LSTM LM: refused, before anything is loaded, with streaming, hotwords, n-gram / word-level LMs, alignments and
-    ensembles."""
+    one sub-word LSTM LM, with or without phrase biasing (--transducer-hotwords): refused, before anything is loaded, with
+    streaming, the CTC search's --hotwords, n-gram / word-level LMs, alignments and ensembles."""
     if args.search != "transducer_frame_beam":
         if args.transducer_beam_size_token is not None and args.search != "transducer_stream_beam":
             raise ValueError("--transducer-beam-size-token configures --search transducer_frame_beam / transducer_stream_beam")
@@ -297,7 +313,7 @@ def check_frame_beam_args(args):
     for opt, v in (("--streaming", args.streaming), ("--hotwords", args.hotwords), ("--ngram-lm", args.ngram_lm),
                    ("--word-dict", args.word_dict), ("--print-alignment", args.print_alignment is not None)):
         if v:
-            raise NotImplementedError(f"--search transducer_frame_beam is not implemented with {opt}")
+            raise NotImplementedError(f"--search transducer_frame_beam is not implemented with {opt}" + _HOTWORDS_HINT * (opt == "--hotwords"))
     if args.lm_path and len(args.lm_path.split(os.pathsep)) != 1:
         raise NotImplementedError("--search transducer_frame_beam fuses one sub-word LSTM LM: no multi-level --lm-path a:b")
     if len(args.path.split(os.pathsep)) > 1:
@@ -307,8 +323,8 @@ def check_frame_beam_args(args):
 def check_stream_beam_args(args):
     """--search transducer_stream_beam is the frame-synchronous transducer beam search of one chunk-streaming transducer model
     under --streaming, alone or with one sub-word LSTM LM (a name of its own: --search transducer_frame_beam --streaming stays
-    refused).  Refused, before anything is loaded: without --streaming, and with hotwords, n-gram / word-level LMs, multi-level
-    LMs, alignments and ensembles."""
+    refused), with or without phrase biasing (--transducer-hotwords).  Refused, before anything is loaded: without --streaming,
+    and with the CTC search's --hotwords, n-gram / word-level LMs, multi-level LMs, alignments and ensembles."""
     if args.search != "transducer_stream_beam":
         return
     if not args.streaming:
@@ -317,7 +333,7 @@ def check_stream_beam_args(args):
     for opt, v in (("--hotwords", args.hotwords), ("--ngram-lm", args.ngram_lm), ("--word-dict", args.word_dict),
                    ("--print-alignment", args.print_alignment is not None)):
         if v:
-            raise NotImplementedError(f"--search transducer_stream_beam is not implemented with {opt}")
+            raise NotImplementedError(f"--search transducer_stream_beam is not implemented with {opt}" + _HOTWORDS_HINT * (opt == "--hotwords"))
     if args.lm_path and len(args.lm_path.split(os.pathsep)) != 1:
         raise NotImplementedError("--search transducer_stream_beam fuses one sub-word LSTM LM: no multi-level --lm-path a:b")
     if len(args.path.split(os.pathsep)) > 1:
@@ -329,18 +345,25 @@ DEFAULT_HOTWORD_SCORE = 1.5
 
 def check_hotword_args(args):
     """--hotwords biases the prefix beam search of --search ctc_beam (alone or with an LSTM LM): refused, before anything is
-    loaded, with every other search, with the lexicon + n-gram search and with --streaming."""
-    if not args.hotwords:
+    loaded, with every other search, with the lexicon + n-gram search and with --streaming.  --transducer-hotwords biases the
+    frame-synchronous transducer beam search (--search transducer_frame_beam, and transducer_stream_beam under --streaming; with
+    or without an LSTM LM, partials and n-best): refused by name with every other search.  One of the two at most."""
+    if not args.hotwords and not args.transducer_hotwords:
         for opt, v in (("--hotword-score", args.hotword_score), ("--bpe", args.bpe), ("--sentencepiece-model", args.sentencepiece_model)):
             if v is not None:
                 raise ValueError(f"{opt} configures --hotwords: give --hotwords too")
         return
-    if args.search != "ctc_beam":
+    if args.hotwords and args.transducer_hotwords:
+        raise NotImplementedError("--hotwords and --transducer-hotwords name the phrase file of different searches: give one of them")
+    if args.transducer_hotwords and args.search not in ("transducer_frame_beam", "transducer_stream_beam"):
+        raise NotImplementedError("--transducer-hotwords (phrase biasing) is implemented for --search transducer_frame_beam and "
+                                  f"--search transducer_stream_beam only, not --search {args.search}")
+    if args.hotwords and args.search != "ctc_beam":
         raise NotImplementedError("--hotwords (phrase biasing) is implemented for --search ctc_beam only, not --search "
                                   f"{args.search}")
-    if args.ngram_lm:
+    if args.hotwords and args.ngram_lm:
         raise NotImplementedError("--hotwords biases the prefix beam search without a lexicon: no --ngram-lm with it")
-    if args.streaming:
+    if args.hotwords and args.streaming:
         raise NotImplementedError("--hotwords is not streamed: no --streaming with it")
     if args.hotword_score is not None and not args.hotword_score > 0:
         raise ValueError("--hotword-score must be positive")
@@ -596,12 +619,12 @@ def main(argv=None):
         non_lang_syms=args.non_lang_syms, wer_output_filter=args.wer_output_filter, bpe=args.bpe,
         sentencepiece_model=args.sentencepiece_model))
     context_graph = None
-    if args.hotwords:  # before the model: a malformed phrase file fails fast
+    if args.hotwords or args.transducer_hotwords:  # before the model: a malformed phrase file fails fast
         from .tools.context_graph import load_context_graph
 
         d = task.target_dictionary
-        context_graph = load_context_graph(args.hotwords, d, d.bos(), DEFAULT_HOTWORD_SCORE if args.hotword_score is None
-                                           else args.hotword_score)
+        context_graph = load_context_graph(args.hotwords or args.transducer_hotwords, d, d.bos(),
+                                           DEFAULT_HOTWORD_SCORE if args.hotword_score is None else args.hotword_score)
     ngram = None
     if args.ngram_lm:  # before the model: a malformed ARPA or lexicon file fails fast
         from .models.ngram_lm import NGramLanguageModel
@@ -679,7 +702,7 @@ def main(argv=None):
                                               lm_weight=args.lm_weight, word_score=args.word_score,
                                               insertion_bonus=args.ctc_insertion_bonus))
         if args.search == "transducer_stream_beam":
-            kw["stream_beam"] = stream_beam_options(args, lm)
+            kw["stream_beam"] = stream_beam_options(args, lm, context_graph)
         if not args.results_path:
             recognize_streaming(task, model, task.target_dictionary, s_ids, s_waves, dev, out=sys.stdout, **kw)
             return scorer

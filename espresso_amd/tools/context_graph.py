@@ -1,4 +1,5 @@
-"""ContextGraph — hotword (contextual phrase) biasing tables for the CTC prefix beam search (csrc/ctc_beam.hip, BIAS kernels).
+"""ContextGraph — hotword (contextual phrase) biasing tables for the CTC prefix beam search (csrc/ctc_beam.hip, BIAS kernels)
+and the frame-synchronous transducer beam search, offline and streamed (csrc/rnnt_beam.hip, kBias kernels).
 
 Phrases p_1..p_P are non-empty token-id sequences with a per-token boost s_i > 0 (natural log, added to the hypothesis score
 unweighted).  Over their trie, for a node n (root excluded): e(n) = max s_i over the phrases through n (boost of the edge into n),

@@ -22,6 +22,11 @@ returns what TransducerFrameBeamDecoder.search returns for the whole utterance, 
 hypothesis.  Every later hypothesis is a stay or an extension of a live one (a merge lands on a live sequence), so the stable
 tokens never change again.
 
+Hotword biasing: with `context_graph` (tools/context_graph.ContextGraph) the state, the reset, every step, the finish and the
+partial are those of the bias family (ea_rnnt_frame_beam_stream_bias_*): a slot also holds the automaton state and the running
+bias of every beam slot, `partial` returns the live hypothesis with the best score + running bias, and `close` returns what
+TransducerFrameBeamDecoder.search with the same graph returns.  The tables are uploaded once; the loop still reads nothing back.
+
 The prefix table of a slot is sized for `max_frames` encoder frames; a stream that would pass it is refused before anything
 is launched."""
 from typing import Dict, List
@@ -34,12 +39,13 @@ from .transducer_frame_beam_decoder import TransducerFrameBeamDecoder
 
 class StreamingTransducerFrameBeamDecoder:
     def __init__(self, model, dictionary, beam_size, max_streams, max_frames, nbest=1, beam_size_token=None, temperature=1.0,
-                 normalize_scores=True, lm_model=None, lm_weight=0.0, model_predicts_eos=False):
+                 normalize_scores=True, lm_model=None, lm_weight=0.0, model_predicts_eos=False, context_graph=None):
         # validation and defaults of the offline decoder
         o = TransducerFrameBeamDecoder(model, dictionary, beam_size=beam_size, nbest=nbest, beam_size_token=beam_size_token,
                                        temperature=temperature, normalize_scores=normalize_scores, lm_model=lm_model,
-                                       lm_weight=lm_weight, model_predicts_eos=model_predicts_eos)
+                                       lm_weight=lm_weight, model_predicts_eos=model_predicts_eos, context_graph=context_graph)
         self.offline = o
+        self.context_graph = o.context_graph
         self.model, self.lm_model, self.lm_weight = o.model, o.lm_model, o.lm_weight
         self.pad, self.blank, self.bos, self.eos, self.vocab_size = o.pad, o.blank, o.bos, o.eos, o.vocab_size
         self.beam_size, self.beam_size_token, self.nbest = o.beam_size, o.beam_size_token, o.nbest
@@ -53,7 +59,7 @@ class StreamingTransducerFrameBeamDecoder:
         self._free = list(range(self.max_streams - 1, -1, -1))
         self.streams: Dict[object, list] = {}  # stream id -> [slot, frames consumed]
         self._unreset: List[int] = []
-        self.state = None
+        self.state = self.graph = None
         dev = next(self.model.parameters()).device if self.model is not None else None
         if dev is not None and dev.type == "cuda":
             self._allocate(dev)
@@ -61,6 +67,8 @@ class StreamingTransducerFrameBeamDecoder:
     def state_bytes_per_stream(self) -> int:
         from .. import _lib
 
+        if self.context_graph is not None:
+            return int(_lib.lib().ea_rnnt_frame_beam_stream_bias_state_bytes(self.max_frames, self.beam_size))
         return int(_lib.lib().ea_rnnt_frame_beam_stream_state_bytes(self.max_frames, self.beam_size))
 
     # ---- device plumbing -------------------------------------------------------------------------------------------------
@@ -69,7 +77,9 @@ class StreamingTransducerFrameBeamDecoder:
         """The search state and the per-slot rows, once; the rows every new stream starts from (the predictor after `bos`, the
         LM after its eos)."""
         R, dec = self.max_streams * self.beam_size, self.model.decoder
-        self.state, _ = K.rnnt_frame_beam_stream_state(self.max_streams, self.max_frames, self.beam_size, device)
+        self.graph = self.offline.graph_tables(device)
+        make_state = K.rnnt_frame_beam_stream_state if self.graph is None else K.rnnt_frame_beam_stream_bias_state
+        self.state, _ = make_state(self.max_streams, self.max_frames, self.beam_size, device)
         out, st = dec.advance(torch.full((1,), self.bos, dtype=torch.int32, device=device), dec.init_state(1, device))
         self._start = [st, out]
         self.pred = dec.init_state(R, device)
@@ -106,7 +116,8 @@ class StreamingTransducerFrameBeamDecoder:
         device = self.state.device
         if self._unreset:
             slots = self._ints(self._unreset, device)
-            K.rnnt_frame_beam_stream_reset(self.state, slots, self.max_frames, self.beam_size)
+            reset = K.rnnt_frame_beam_stream_reset if self.graph is None else K.rnnt_frame_beam_stream_bias_reset
+            reset(self.state, slots, self.max_frames, self.beam_size)
             rows = self._rows_of(slots).long()
             for t, s in self._carried():
                 t.index_copy_(0, rows, s.expand(rows.numel(), -1))
@@ -166,7 +177,10 @@ class StreamingTransducerFrameBeamDecoder:
             lm_rows = K.gather_rows(self.lm_rows, rows)
         for j in range(Tm):
             logits = model.joint_step(K.gather_rows(E, frame_rows[j]), dec_out)
-            K.rnnt_frame_beam_stream_step(logits, slot_idx, n_new, j, self.state, out, lm_rows=lm_rows, **self._step)
+            if self.graph is None:
+                K.rnnt_frame_beam_stream_step(logits, slot_idx, n_new, j, self.state, out, lm_rows=lm_rows, **self._step)
+            else:
+                K.rnnt_frame_beam_stream_bias_step(logits, slot_idx, n_new, j, self.state, self.graph, out, lm_rows=lm_rows, **self._step)
             state = dec.reorder_state(state, out[0])
             dec_out, state = dec.advance(out[1], state, keep_row=out[2])
             if self.lm is not None:
@@ -193,17 +207,19 @@ class StreamingTransducerFrameBeamDecoder:
         state is left as it is."""
         dev = self._ensure(self._device())
         slots = self._ints([self.streams[sid][0] for sid in stream_ids], dev)
-        return K.rnnt_frame_beam_stream_finish(self.state, slots, self.max_frames, self.beam_size, self.nbest if nbest is None else nbest,
-                                               self.pad, self._max_u(stream_ids) if max_u is None else max_u,
-                                               normalize=self.offline.normalize_scores)
+        args = (self.max_frames, self.beam_size, self.nbest if nbest is None else nbest, self.pad,
+                self._max_u(stream_ids) if max_u is None else max_u)
+        if self.graph is None:
+            return K.rnnt_frame_beam_stream_finish(self.state, slots, *args, normalize=self.offline.normalize_scores)
+        return K.rnnt_frame_beam_stream_bias_finish(self.state, slots, self.graph, *args, normalize=self.offline.normalize_scores)
 
     @torch.no_grad()
     def partial_tensors(self, stream_ids, max_u=None):
         """Device tensors (tokens int32 [n][U], lengths, scores, stable_len) of the streams' best live hypotheses."""
         dev = self._ensure(self._device())
         slots = self._ints([self.streams[sid][0] for sid in stream_ids], dev)
-        return K.rnnt_frame_beam_stream_partial(self.state, slots, self.max_frames, self.beam_size, self.pad,
-                                                self._max_u(stream_ids) if max_u is None else max_u)
+        partial = K.rnnt_frame_beam_stream_partial if self.graph is None else K.rnnt_frame_beam_stream_bias_partial
+        return partial(self.state, slots, self.max_frames, self.beam_size, self.pad, self._max_u(stream_ids) if max_u is None else max_u)
 
     @torch.no_grad()
     def partial(self, stream_ids):

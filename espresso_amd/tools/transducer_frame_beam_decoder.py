@@ -11,7 +11,11 @@ prefix table and selection live in a device workspace; the loop runs over the pa
 utterance's length are no-ops in the kernel) and never synchronises with the host.
 
 The LM fusion is the mass-preserving one of the two other transducer decoders (transducer_greedy_decoder.py): non-blank
-log-probs get lm_weight * log P_lm and are renormalised to the non-blank mass they had; blank is untouched."""
+log-probs get lm_weight * log P_lm and are renormalised to the non-blank mass they had; blank is untouched.
+
+Hotword biasing: with `context_graph` (tools/context_graph.ContextGraph) every hypothesis also carries its state in the phrase
+automaton and a running bias; the decoder then calls the bias family of the kernels (ea_rnnt_frame_beam_bias_*) for the
+workspace, every step and the finish, with the tables uploaded once.  Without a graph the calls are the unbiased ones."""
 from typing import Dict, List
 
 import torch
@@ -24,7 +28,7 @@ class TransducerFrameBeamDecoder:
 
     def __init__(self, models, dictionary, beam_size=5, nbest=1, beam_size_token=None, temperature=1.0, normalize_scores=True,
                  lm_model=None, lm_weight=0.0, model_predicts_eos=False, bos=None, blank=None, eos=None, pad=None,
-                 symbols_to_strip_from_output=None, print_alignment=False, **kwargs):
+                 symbols_to_strip_from_output=None, print_alignment=False, context_graph=None, **kwargs):
         if isinstance(models, (list, tuple)):
             if len(models) != 1:
                 raise NotImplementedError("the frame-synchronous transducer beam search takes one model: ensembles are not implemented")
@@ -65,12 +69,27 @@ class TransducerFrameBeamDecoder:
                                  "be the same dictionary, or that dictionary without the blank")
             self.no_blank_in_lm = nlm == V - 1
             lm_model.eval()
+        if context_graph is not None and context_graph.vocab_size != V:
+            raise ValueError(f"transducer frame beam search: context graph built for {context_graph.vocab_size} tokens, dictionary has {V}")
+        self.context_graph = context_graph
+        self._graph_dev = None
 
     def cuda(self):
         self.model.cuda()
         if self.lm_model is not None:
             self.lm_model.cuda()
         return self
+
+    def graph_tables(self, device):
+        """The context graph's device tables (uploaded once per device), or None without a graph."""
+        if self.context_graph is None:
+            return None
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:  # "cuda" is the current device: the cache is keyed on the resolved one
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._graph_dev is None or self._graph_dev[0].device != device:
+            self._graph_dev = self.context_graph.cuda(device)
+        return self._graph_dev
 
     # ---------------------------------------------------------------- LM state of the beams
     def _lm_tokens(self, tokens):
@@ -112,7 +131,8 @@ class TransducerFrameBeamDecoder:
         frame_rows = (rows.unsqueeze(0) + torch.arange(Tp, device=dev, dtype=torch.int32).unsqueeze(1)).contiguous()  # [T'][N]
         out = (torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
                torch.empty(N, dtype=torch.uint8, device=dev))
-        ws = K.rnnt_frame_beam_workspace(B, Tp, beam, dev)
+        graph = self.graph_tables(dev)
+        ws = K.rnnt_frame_beam_workspace(B, Tp, beam, dev) if graph is None else K.rnnt_frame_beam_bias_workspace(B, Tp, beam, dev)
         state = dec.init_state(N, dev)
         dec_out, state = dec.advance(torch.full((N,), self.bos if bos_token is None else bos_token, dtype=torch.int32, device=dev), state)
         lm_state = lm_rows = None
@@ -122,12 +142,17 @@ class TransducerFrameBeamDecoder:
                     temperature=self.temperature, lm_weight=self.lm_weight, lm_no_blank=self.no_blank_in_lm)
         for t in range(Tp):
             logits = model.joint_step(K.gather_rows(E, frame_rows[t]), dec_out)
-            K.rnnt_frame_beam_step(logits, in_len, ws, out, t=t, lm_rows=lm_rows, **step)
+            if graph is None:
+                K.rnnt_frame_beam_step(logits, in_len, ws, out, t=t, lm_rows=lm_rows, **step)
+            else:
+                K.rnnt_frame_beam_bias_step(logits, in_len, ws, graph, out, t=t, lm_rows=lm_rows, **step)
             state = dec.reorder_state(state, out[0])
             dec_out, state = dec.advance(out[1], state, keep_row=out[2])
             if self.lm_model is not None:
                 lm_state, lm_rows = self.lm_update(lm_state, *out)
-        return K.rnnt_frame_beam_finish(ws, B, Tp, beam, self.nbest, self.pad, normalize=self.normalize_scores)
+        if graph is None:
+            return K.rnnt_frame_beam_finish(ws, B, Tp, beam, self.nbest, self.pad, normalize=self.normalize_scores)
+        return K.rnnt_frame_beam_bias_finish(ws, graph, B, Tp, beam, self.nbest, self.pad, normalize=self.normalize_scores)
 
     @torch.no_grad()
     def encode(self, sample):

@@ -530,6 +530,50 @@ int ea_rnnt_frame_beam_stream_finish(const void* state, const int* slots, int n,
 int ea_rnnt_frame_beam_stream_partial(const void* state, const int* slots, int n, int max_streams, int max_frames, int beam,
                                       int pad, int max_u, int* tokens, int* lengths, float* scores, int* stable_len,
                                       ea_stream_t stream);
+/* Hotword (contextual phrase) biasing of the frame-synchronous transducer beam search, offline and streamed
+ * (csrc/rnnt_beam.hip, the kBias instantiations).  The context graph, its packed tables (cg_nodes, cg_edges, cg_root with
+ * cg_n_edges == cg_n_nodes - 1; an empty graph = the root alone, cg_edges NULL, is legal and gives the unbiased results bit for
+ * bit) and the automaton step are those of ea_ctc_prefix_beam_bias_* above; the beam is that of ea_rnnt_frame_beam_step.  Every
+ * hypothesis carries (q, b), (root, 0) for the empty one; the unbiased score s is kept as it is.  The row phase is unchanged:
+ * the K candidate tokens of a row stay the K with the largest fused r_v, so biasing re-ranks and does not bring a token back,
+ * and with it K = beam is no longer a global top-`beam`.  An extension takes one automaton step from its parent's (q, b); a stay
+ * changes neither; a merge is decided as before and adds the scores s only — (q, b) are functions of the token sequence, so
+ * the merged hypothesis keeps the stay's.  A candidate is live iff its s is finite; the `beam` best by (-(s + b'), key) survive,
+ * keys and triples as before.  Finish: s + b - phi(q), with normalize != 0 divided by max(1, length): the unbiased final of the
+ * same tokens plus the boosts of the phrases completed along trie edges, before the division.  A phrase reached only through a
+ * failure link is not credited; phrases of at most 64 tokens; one graph per search.  One search uses the bias calls for all of
+ * its steps, its finish and its partials.  Bad arguments (those of the unbiased twin, NULL cg_nodes / cg_root, cg_edges NULL with
+ * cg_n_edges > 0, cg_n_edges != cg_n_nodes - 1) return -2 and launch nothing.
+ * ea_rnnt_frame_beam_bias_workspace_bytes / _bias_step / _bias_finish: as ea_rnnt_frame_beam_workspace_bytes / _step / _finish
+ *   with the graph (same arguments, limits and outputs); the workspace is that of the unbiased search followed by (q, b) per
+ *   slot: 2 * beam more 4-byte words per utterance.
+ * ea_rnnt_frame_beam_stream_bias_state_bytes / _bias_reset / _bias_step / _bias_finish / _bias_partial: as
+ *   ea_rnnt_frame_beam_stream_state_bytes / _reset / _step / _finish / _partial with the graph.  Per slot, int32 words:
+ *   bias words = words + 2 * beam = 2 + even(3 * tsize + 5 * beam + 2 + 2 * cap + 2 * beam + 2 * beam * 64) + 2 * beam (cap, tsize,
+ *   even() as above): the unbiased slot followed by q int32 [beam] and b fp32 [beam].  A stream fed in any pieces gives bit for
+ *   bit what the offline bias calls give for the whole utterance.  _bias_partial returns the live hypothesis with the best
+ *   s + b (ties: the lower beam slot) and that value as its score; stable_len as in the unbiased call. */
+long ea_rnnt_frame_beam_bias_workspace_bytes(int B, int T, int beam);
+int ea_rnnt_frame_beam_bias_step(const float* logits, long ld, const float* lm_rows, long ld_lm, int lm_no_blank, const int* in_len,
+                                 void* workspace, int* parent, int* token, void* keep, const int* cg_nodes, const int* cg_edges,
+                                 const int* cg_root, int cg_n_nodes, int cg_n_edges, int B, int T, int V, int beam, int K, int blank,
+                                 int eos, float temperature, float lm_weight, int t, ea_stream_t stream);
+int ea_rnnt_frame_beam_bias_finish(void* workspace, const int* cg_nodes, int cg_n_nodes, int B, int T, int beam, int nbest, int pad,
+                                   int normalize, int* tokens, int* lengths, float* scores, int* nhyp, ea_stream_t stream);
+long ea_rnnt_frame_beam_stream_bias_state_bytes(int max_frames, int beam);
+int ea_rnnt_frame_beam_stream_bias_reset(void* state, const int* slots, int n, int max_streams, int max_frames, int beam,
+                                         ea_stream_t stream);
+int ea_rnnt_frame_beam_stream_bias_step(const float* logits, long ld, const float* lm_rows, long ld_lm, int lm_no_blank,
+                                        const int* slot_idx, const int* n_new, int j, int n, void* state, int* parent, int* token,
+                                        void* keep, const int* cg_nodes, const int* cg_edges, const int* cg_root, int cg_n_nodes,
+                                        int cg_n_edges, int max_streams, int max_frames, int V, int beam, int K, int blank, int eos,
+                                        float temperature, float lm_weight, ea_stream_t stream);
+int ea_rnnt_frame_beam_stream_bias_finish(const void* state, const int* slots, int n, int max_streams, int max_frames, int beam,
+                                          const int* cg_nodes, int cg_n_nodes, int nbest, int pad, int normalize, int max_u,
+                                          int* tokens, int* lengths, float* scores, int* nhyp, ea_stream_t stream);
+int ea_rnnt_frame_beam_stream_bias_partial(const void* state, const int* slots, int n, int max_streams, int max_frames, int beam,
+                                           int pad, int max_u, int* tokens, int* lengths, float* scores, int* stable_len,
+                                           ea_stream_t stream);
 /* Word n-gram LM (ARPA) and lexicon-constrained CTC prefix beam search with its fusion (csrc/ctc_lexicon_beam.hip) — the
  * search the reference takes from Flashlight's KenLM lexicon decoder (espresso/tools/ctc_decoder.py:24-71).
  * ea_ngram_create: parses a plain-text ARPA file of order <= 6 at `path` into host tables and writes an opaque handle to
