@@ -633,6 +633,95 @@ def ctc_prefix_beam_bias_finish(ws, graph, B, T, beam, nbest, pad, lm_rows=None,
     return tokens, lengths, scores, nhyp
 
 
+def ctc_prefix_beam_stream_state(max_streams, max_frames, beam, device):
+    """(state uint8 [max_streams][bytes per slot], zero-filled; bytes per slot) of the streamed CTC prefix beam search
+    (ea_ctc_prefix_beam_stream_state_bytes)."""
+    nbytes = int(_lib.lib().ea_ctc_prefix_beam_stream_state_bytes(max_frames, beam))
+    assert nbytes > 0 and max_streams >= 1
+    return torch.zeros(max_streams, nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def _check_prefix_stream_state(state, max_frames, beam):
+    assert state.dtype == torch.uint8 and state.is_contiguous() and state.dim() == 2
+    assert state.shape[1] == _lib.lib().ea_ctc_prefix_beam_stream_state_bytes(max_frames, beam)
+
+
+def _cg_or_none(graph, V=None):
+    return _cg(graph, V) if graph is not None else (None, None, None, 0, 0)
+
+
+def ctc_prefix_beam_stream_reset(state, slots, max_frames, beam):
+    """The slots int32 [n] (device) of `state` get the search state before frame 0 (ea_ctc_prefix_beam_stream_reset)."""
+    _check_prefix_stream_state(state, max_frames, beam)
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
+    check(_lib.lib().ea_ctc_prefix_beam_stream_reset(_p(state), _p(slots), slots.numel(), state.shape[0], max_frames, beam, _stream()),
+          "ea_ctc_prefix_beam_stream_reset")
+
+
+def ctc_prefix_beam_stream_step(x, meta, state, max_frames, V, beam, K, blank, j0=0, j1=None, graph=None, lm_rows=None, lm_weight=0.0,
+                                ins_bonus=0.0, lm_out=None, ld=None):
+    """The frames [j0, j1) of the pieces of every listed stream through the CTC prefix beam search (ea_ctc_prefix_beam_stream_step;
+    j1 None: the whole pieces).  x [rows][V] fp32/bf16 log-probs packed stream by stream; meta int32 [3][n] = (slot, n_new,
+    row_off) on the device; graph: the (nodes, edges, root) device tables of a context graph, the same for every call of a search.
+    With an LM: lm_rows fp32 [n*beam][V], j1 = j0 + 1 and lm_out = (parent int32, token int32, keep uint8), each [n*beam], written
+    by the step."""
+    ld = x.stride(0) if ld is None else ld
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 2 and x.stride(-1) == 1 and x.shape[1] == V
+    assert meta.dtype == torch.int32 and meta.dim() == 2 and meta.shape[0] == 3 and meta.is_contiguous()
+    _check_prefix_stream_state(state, max_frames, beam)
+    n = meta.shape[1]
+    j1 = max(x.shape[0], j0) if j1 is None else j1
+    parent, token, keep = lm_out if lm_out is not None else (None, None, None)
+    if lm_rows is not None:
+        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (n * beam, V) and j1 == j0 + 1
+        assert parent.numel() == token.numel() == keep.numel() == n * beam
+        assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
+    check(_lib.lib().ea_ctc_prefix_beam_stream_step(_p(x), ld, int(x.dtype == torch.bfloat16), x.shape[0], _p(meta[0]), _p(meta[1]),
+                                                    _p(meta[2]), j0, j1, n, _p(state), _p(lm_rows),
+                                                    lm_rows.stride(0) if lm_rows is not None else 0, _p(parent), _p(token), _p(keep),
+                                                    *_cg_or_none(graph, V), state.shape[0], max_frames, V, beam, K, blank, lm_weight,
+                                                    ins_bonus, _stream()), "ea_ctc_prefix_beam_stream_step")
+
+
+def ctc_prefix_beam_stream_finish(state, slots, max_frames, beam, nbest, pad, max_u, graph=None, lm_rows=None, lm_weight=0.0,
+                                  ins_bonus=0.0, eos=-1):
+    """The finished hypotheses of the slots int32 [n] (device), the state left as it is (ea_ctc_prefix_beam_stream_finish);
+    lm_rows fp32 [n*beam][V] in the order of `slots`.  Returns (tokens int32 [n][nbest][max_u] pad-filled, lengths int32
+    [n][nbest], scores fp32 [n][nbest], nhyp int32 [n]), best first."""
+    _check_prefix_stream_state(state, max_frames, beam)
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and 1 <= nbest <= beam
+    n, dev = slots.numel(), state.device
+    if lm_rows is not None:
+        assert lm_rows.dtype == torch.float32 and lm_rows.dim() == 2 and lm_rows.stride(1) == 1 and lm_rows.shape[0] == n * beam
+    tokens = torch.empty(n, nbest, max_u, dtype=torch.int32, device=dev)
+    lengths = torch.empty(n, nbest, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, nbest, dtype=torch.float32, device=dev)
+    nhyp = torch.empty(n, dtype=torch.int32, device=dev)
+    nodes, _, _, n_nodes, _ = _cg_or_none(graph)
+    check(_lib.lib().ea_ctc_prefix_beam_stream_finish(_p(state), _p(slots), n, _p(lm_rows),
+                                                      lm_rows.stride(0) if lm_rows is not None else 0, lm_weight, ins_bonus, eos, nodes,
+                                                      n_nodes, state.shape[0], max_frames, beam, nbest, pad, max_u, _p(tokens),
+                                                      _p(lengths), _p(scores), _p(nhyp), _stream()), "ea_ctc_prefix_beam_stream_finish")
+    return tokens, lengths, scores, nhyp
+
+
+def ctc_prefix_beam_stream_partial(state, slots, max_frames, beam, pad, max_u, lm_weight=0.0, ins_bonus=0.0, biased=False):
+    """The best live hypothesis (by the in-beam score, with the running bias when `biased`) of the slots int32 [n] (device) and
+    the length of the beam's common prefix (ea_ctc_prefix_beam_stream_partial).  Returns (tokens int32 [n][max_u] pad-filled,
+    lengths int32 [n], scores fp32 [n], stable_len int32 [n])."""
+    _check_prefix_stream_state(state, max_frames, beam)
+    assert slots.dtype == torch.int32 and slots.is_contiguous()
+    n, dev = slots.numel(), state.device
+    tokens = torch.empty(n, max_u, dtype=torch.int32, device=dev)
+    lengths = torch.empty(n, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, dtype=torch.float32, device=dev)
+    stable = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.lib().ea_ctc_prefix_beam_stream_partial(_p(state), _p(slots), n, lm_weight, ins_bonus, int(bool(biased)), state.shape[0],
+                                                       max_frames, beam, pad, max_u, _p(tokens), _p(lengths), _p(scores), _p(stable),
+                                                       _stream()), "ea_ctc_prefix_beam_stream_partial")
+    return tokens, lengths, scores, stable
+
+
 def rnnt_frame_beam_workspace(B, T, beam, device):
     """Workspace of the frame-synchronous transducer beam search (ea_rnnt_frame_beam_workspace_bytes): the beams, prefix tables
     and per-row candidates of B utterances of at most T frames."""

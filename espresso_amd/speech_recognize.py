@@ -1,7 +1,7 @@
 """Batched recognition CLI — the decoding loop and output format of espresso/speech_recognize.py:60-360 on the HIP path:
 for every batch run the chosen search (beam search with optional LM / look-ahead word-LM / multi-level LM fusion, CTC greedy,
-CTC prefix beam search with optional LSTM-LM or lexicon + n-gram LM fusion, transducer greedy / beam / frame-synchronous beam,
-the latter also streamed), print `T-<utt>` (reference) and `H-<utt>`
+CTC prefix beam search with optional LSTM-LM or lexicon + n-gram LM fusion (both also streamed), transducer greedy / beam /
+frame-synchronous beam, the latter also streamed), print `T-<utt>` (reference) and `H-<utt>`
 (hypothesis, score in base 2) lines, accumulate WER / CER with `tools.wer.Scorer`, and close with the "Recognized N utterances
 ..." summary.
 
@@ -142,7 +142,8 @@ def collate(ids: List[int], utt_ids: List[str], waves: List[np.ndarray], device)
 def build_generator(args, model, dictionary, lm=None, ngram=None, context_graph=None):
     """ngram: (NGramLanguageModel, LexiconTrie) for --search ctc_beam --ngram-lm; context_graph: the ContextGraph of --hotwords
     (--search ctc_beam) or --transducer-hotwords (--search transducer_frame_beam).
-    (--search transducer_stream_beam has no generator: recognize_streaming builds its decoder from stream_beam_options.)"""
+    (--search transducer_stream_beam and --search ctc_stream_beam have no generator: recognize_streaming builds their decoders
+    from stream_beam_options / ctc_stream_beam_options.)"""
     from .sequence_generator import SequenceGenerator
     from .tools.ctc_decoder import CTCDecoder
     from .tools.ctc_lexicon_beam_search import CTCLexiconBeamSearchDecoder
@@ -190,6 +191,13 @@ def stream_beam_options(args, lm=None, context_graph=None):
     return opts
 
 
+def ctc_stream_beam_options(args, lm=None, context_graph=None):
+    """The options of StreamingCTCPrefixBeamDecoder (after dictionary, max_streams, max_frames) from the command line of
+    --search ctc_stream_beam; context_graph: the ContextGraph of --hotwords."""
+    return dict(beam_size=args.beam, nbest=args.nbest, beam_size_token=args.ctc_beam_size_token, lm_model=lm, lm_weight=args.lm_weight,
+                insertion_bonus=args.ctc_insertion_bonus, context_graph=context_graph)
+
+
 def get_parser():
     p = argparse.ArgumentParser("espresso_amd.speech_recognize", description=__doc__.split("\n")[0])
     p.add_argument("--path", required=True, help="state_dict (or fairseq checkpoint dict with a 'model' entry)")
@@ -201,9 +209,11 @@ def get_parser():
     p.add_argument("--wav-scp", required=True)
     p.add_argument("--text", default=None, help="reference transcripts (utt_id tokens...)")
     p.add_argument("--global-cmvn-stats-path", default=None)
-    p.add_argument("--search", default="beam", choices=["beam", "ctc", "ctc_beam", "transducer_greedy", "transducer_beam", "transducer_frame_beam", "transducer_stream_beam"],
+    p.add_argument("--search", default="beam", choices=["beam", "ctc", "ctc_beam", "transducer_greedy", "transducer_beam", "transducer_frame_beam", "transducer_stream_beam", "ctc_stream_beam"],
                    help="transducer_stream_beam is the frame-synchronous transducer beam search under --streaming (a search name of "
-                        "its own: --search transducer_frame_beam is the offline search and refuses --streaming)")
+                        "its own: --search transducer_frame_beam is the offline search and refuses --streaming); ctc_stream_beam "
+                        "likewise is the CTC prefix beam search of --search ctc_beam (alone, with --lm-path, with --hotwords) under "
+                        "--streaming")
     p.add_argument("--beam", type=int, default=10)
     p.add_argument("--nbest", type=int, default=1)
     p.add_argument("--max-len-a", type=float, default=0.08)
@@ -225,8 +235,8 @@ def get_parser():
     p.add_argument("--disable-open-vocab", action="store_true",
                    help="look-ahead / multi-level fusion: no probability mass for words outside the --word-dict lexicon")
     p.add_argument("--ctc-beam-size-token", type=int, default=None,
-                   help="ctc_beam: candidate tokens per frame (default: min(--beam, vocabulary size - 1), at most 64)")
-    p.add_argument("--ctc-insertion-bonus", type=float, default=0.0, help="ctc_beam: score added per emitted token")
+                   help="ctc_beam / ctc_stream_beam: candidate tokens per frame (default: min(--beam, vocabulary size - 1), at most 64)")
+    p.add_argument("--ctc-insertion-bonus", type=float, default=0.0, help="ctc_beam / ctc_stream_beam: score added per emitted token")
     p.add_argument("--transducer-beam-size-token", type=int, default=None,
                    help="transducer_frame_beam / transducer_stream_beam: extensions per hypothesis and frame (default: min(--beam, vocabulary size - 1), at "
                         "most 64)")
@@ -237,7 +247,7 @@ def get_parser():
                         "by characters)")
     p.add_argument("--word-score", type=float, default=-1.0, help="ctc_beam --ngram-lm: score added per completed word")
     p.add_argument("--hotwords", default=None,
-                   help="ctc_beam (without --ngram-lm): phrases to bias the search towards, one per line, optionally `<TAB>boost`; "
+                   help="ctc_beam (without --ngram-lm) / ctc_stream_beam: phrases to bias the search towards, one per line, optionally `<TAB>boost`; "
                         "`#` comments.  A hypothesis gains the boost for every token of a phrase it completes (natural log, not "
                         "scaled by --lm-weight; H- scores include it).  The candidate tokens of a frame stay the "
                         "--ctc-beam-size-token best by acoustic score: biasing re-ranks hypotheses, it does not bring back a token "
@@ -272,11 +282,11 @@ def get_parser():
                         "hypothesis (needs --results-path and matplotlib)")
     p.add_argument("--streaming", action="store_true",
                    help="chunk-by-chunk recognition of a chunk-streaming transformer encoder (--search ctc, transducer_greedy, "
-                        "transducer_stream_beam, or ctc_beam with --ngram-lm): audio is fed in pieces of --stream-chunk-ms with --streams utterances in flight")
+                        "transducer_stream_beam, ctc_stream_beam, or ctc_beam with --ngram-lm): audio is fed in pieces of --stream-chunk-ms with --streams utterances in flight")
     p.add_argument("--stream-chunk-ms", type=int, default=None, help="--streaming: audio per piece (default 400)")
     p.add_argument("--streams", type=int, default=None, help="--streaming: concurrent utterances (default 16)")
     p.add_argument("--stream-partials", action="store_true",
-                   help="--streaming --search ctc_beam --ngram-lm or --search transducer_stream_beam: after every piece print `P-<utt>`, the seconds consumed, the stable "
+                   help="--streaming --search ctc_beam --ngram-lm, --search ctc_stream_beam or --search transducer_stream_beam: after every piece print `P-<utt>`, the seconds consumed, the stable "
                         "text and the rest of the currently best hypothesis, whenever the text changed")
     p.add_argument("--wer-output-filter", default=None, help="sed-style word filter applied before WER scoring")
     p.add_argument("--non-lang-syms", default=None, help="non-language symbols (one per line), ignored by WER / CER scoring")
@@ -340,12 +350,35 @@ def check_stream_beam_args(args):
         raise NotImplementedError("--search transducer_stream_beam takes one model: ensembles (--path a.pt:b.pt) are not implemented")
 
 
+def check_ctc_stream_beam_args(args):
+    """--search ctc_stream_beam is the CTC prefix beam search of one chunk-streaming CTC model under --streaming: alone, with one
+    sub-word LSTM LM (--lm-path), with phrase biasing (--hotwords) or with both (a name of its own: --streaming --search ctc_beam
+    without --ngram-lm, and --hotwords with it, stay refused).  Refused, before anything is loaded: without --streaming, and with
+    the lexicon + n-gram search's options, word-level and multi-level LMs, alignments, ensembles and the transducer searches'
+    --transducer-hotwords."""
+    if args.search != "ctc_stream_beam":
+        return
+    if not args.streaming:
+        raise ValueError("--search ctc_stream_beam is the streamed search: give --streaming too (offline: --search ctc_beam)")
+    for opt, v in (("--ngram-lm", args.ngram_lm), ("--lexicon", args.lexicon), ("--word-dict", args.word_dict),
+                   ("--print-alignment", args.print_alignment is not None), ("--transducer-hotwords", args.transducer_hotwords)):
+        if v:
+            raise NotImplementedError(f"--search ctc_stream_beam is not implemented with {opt}" +
+                                      " (the lexicon + n-gram search is streamed as --search ctc_beam --ngram-lm)" * (opt in ("--ngram-lm", "--lexicon")) +
+                                      " (that option biases the transducer searches): give the phrase file as --hotwords" * (opt == "--transducer-hotwords"))
+    if args.lm_path and len(args.lm_path.split(os.pathsep)) != 1:
+        raise NotImplementedError("--search ctc_stream_beam fuses one sub-word LSTM LM: no multi-level --lm-path a:b")
+    if len(args.path.split(os.pathsep)) > 1:
+        raise NotImplementedError("--search ctc_stream_beam takes one model: ensembles (--path a.pt:b.pt) are not implemented")
+
+
 DEFAULT_HOTWORD_SCORE = 1.5
 
 
 def check_hotword_args(args):
-    """--hotwords biases the prefix beam search of --search ctc_beam (alone or with an LSTM LM): refused, before anything is
-    loaded, with every other search, with the lexicon + n-gram search and with --streaming.  --transducer-hotwords biases the
+    """--hotwords biases the prefix beam search of --search ctc_beam, and of --search ctc_stream_beam under --streaming (alone or
+    with an LSTM LM): refused, before anything is loaded, with every other search, with the lexicon + n-gram search and with
+    --streaming --search ctc_beam.  --transducer-hotwords biases the
     frame-synchronous transducer beam search (--search transducer_frame_beam, and transducer_stream_beam under --streaming; with
     or without an LSTM LM, partials and n-best): refused by name with every other search.  One of the two at most."""
     if not args.hotwords and not args.transducer_hotwords:
@@ -358,22 +391,23 @@ def check_hotword_args(args):
     if args.transducer_hotwords and args.search not in ("transducer_frame_beam", "transducer_stream_beam"):
         raise NotImplementedError("--transducer-hotwords (phrase biasing) is implemented for --search transducer_frame_beam and "
                                   f"--search transducer_stream_beam only, not --search {args.search}")
-    if args.hotwords and args.search != "ctc_beam":
-        raise NotImplementedError("--hotwords (phrase biasing) is implemented for --search ctc_beam only, not --search "
-                                  f"{args.search}")
+    if args.hotwords and args.search not in ("ctc_beam", "ctc_stream_beam"):
+        raise NotImplementedError("--hotwords (phrase biasing) is implemented for --search ctc_beam only (streamed: --search "
+                                  f"ctc_stream_beam), not --search {args.search}")
     if args.hotwords and args.ngram_lm:
         raise NotImplementedError("--hotwords biases the prefix beam search without a lexicon: no --ngram-lm with it")
-    if args.hotwords and args.streaming:
-        raise NotImplementedError("--hotwords is not streamed: no --streaming with it")
+    if args.hotwords and args.streaming and args.search != "ctc_stream_beam":
+        raise NotImplementedError("--hotwords is not streamed: no --streaming with it (the streamed biased search is --search "
+                                  "ctc_stream_beam)")
     if args.hotword_score is not None and not args.hotword_score > 0:
         raise ValueError("--hotword-score must be positive")
 
 
 def check_streaming_args(args):
-    """--streaming is greedy decoding (CTC or transducer), the lexicon + n-gram beam search (--search ctc_beam --ngram-lm) or
-    the frame-synchronous transducer beam search (--search transducer_stream_beam, the one search that fuses an LSTM LM under
-    streaming) of one chunk-streaming model: refused, before anything is loaded, with every other search, with LSTM-LM fusion
-    elsewhere, ensembles and alignment output."""
+    """--streaming is greedy decoding (CTC or transducer), the lexicon + n-gram beam search (--search ctc_beam --ngram-lm), the
+    CTC prefix beam search (--search ctc_stream_beam) or the frame-synchronous transducer beam search (--search
+    transducer_stream_beam; these two fuse an LSTM LM under streaming) of one chunk-streaming model: refused, before anything
+    is loaded, with every other search, with LSTM-LM fusion elsewhere, ensembles and alignment output."""
     if not args.streaming:
         for opt, v in (("--stream-chunk-ms", args.stream_chunk_ms), ("--streams", args.streams),
                        ("--stream-partials", args.stream_partials or None)):
@@ -383,19 +417,20 @@ def check_streaming_args(args):
     lexicon_beam = args.search == "ctc_beam" and bool(args.ngram_lm)
     if args.search == "ctc_beam" and not lexicon_beam:
         raise NotImplementedError("--streaming --search ctc_beam needs --ngram-lm: the lexicon + n-gram search is the prefix beam "
-                                  "search that is streamed, not the one without LM or with an LSTM LM")
-    stream_beam = args.search == "transducer_stream_beam"
-    if args.search not in ("ctc", "transducer_greedy", "ctc_beam", "transducer_stream_beam"):
+                                  "search that is streamed, not the one without LM or with an LSTM LM (that one is streamed "
+                                  "as --search ctc_stream_beam)")
+    stream_beam = args.search in ("transducer_stream_beam", "ctc_stream_beam")
+    if args.search not in ("ctc", "transducer_greedy", "ctc_beam", "transducer_stream_beam", "ctc_stream_beam"):
         raise NotImplementedError("--streaming is implemented for greedy decoding (--search ctc, --search transducer_greedy), for "
-                                  "--search ctc_beam with --ngram-lm and for --search transducer_stream_beam, not --search "
-                                  f"{args.search}")
+                                  "--search ctc_beam with --ngram-lm, for --search ctc_stream_beam and for --search "
+                                  f"transducer_stream_beam, not --search {args.search}")
     for opt, v in (("--lm-path", args.lm_path and not stream_beam), ("--word-dict", args.word_dict), ("--ngram-lm", args.ngram_lm and not lexicon_beam),
                    ("--print-alignment", args.print_alignment)):
         if v:
             raise NotImplementedError(f"--streaming decodes without LSTM-LM fusion or alignments: no {opt} with it")
     if args.stream_partials and not (lexicon_beam or stream_beam):
-        raise NotImplementedError("--stream-partials prints the partial results of --search ctc_beam --ngram-lm and of --search "
-                                  "transducer_stream_beam")
+        raise NotImplementedError("--stream-partials prints the partial results of --search ctc_beam --ngram-lm, of --search "
+                                  "ctc_stream_beam and of --search transducer_stream_beam")
     if len(args.path.split(os.pathsep)) > 1:
         raise NotImplementedError("--streaming takes one model: ensembles (--path a.pt:b.pt) are not streamed")
     if (args.stream_chunk_ms is not None and args.stream_chunk_ms <= 0) or (args.streams is not None and args.streams <= 0):
@@ -404,16 +439,18 @@ def check_streaming_args(args):
 
 def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=400, streams=16, refs=None, out=sys.stdout,
                         quiet=False, scorer=None, summary_out=None, search="ctc", max_num_expansions_per_step=2, lexicon_beam=None,
-                        partials=False, stream_beam=None):
+                        partials=False, stream_beam=None, ctc_stream_beam=None):
     """The output of `recognize` from a streamed pass: every utterance is read in pieces of `chunk_ms`, `streams` of them in
     flight; a finished utterance frees its slot for the next one (wav.scp order).  search "ctc_beam": lexicon_beam holds the
     arguments of StreamingCTCLexiconBeamDecoder after `dictionary` (n-gram LM, lexicon) and its options; its prefix tables are
     sized for the longest utterance given.  search "transducer_stream_beam": stream_beam holds the options of
-    StreamingTransducerFrameBeamDecoder (beam, n-best, LM, ...); its prefix tables are sized the same way.  partials: a `P-` line
+    StreamingTransducerFrameBeamDecoder (beam, n-best, LM, ...), search "ctc_stream_beam": ctc_stream_beam those of
+    StreamingCTCPrefixBeamDecoder; their prefix tables are sized the same way.  partials: a `P-` line
     per stream whenever its partial text changed."""
     from .models.transformer.streaming_encoder import StreamingEncoder
     from .tools.streaming_ctc_decoder import StreamingCTCDecoder
     from .tools.streaming_ctc_lexicon_beam_decoder import StreamingCTCLexiconBeamDecoder
+    from .tools.streaming_ctc_prefix_beam_decoder import StreamingCTCPrefixBeamDecoder
     from .tools.streaming_transducer_frame_beam_decoder import StreamingTransducerFrameBeamDecoder
     from .tools.streaming_transducer_greedy_decoder import StreamingTransducerGreedyDecoder
     from .tools.wer import Scorer
@@ -429,6 +466,11 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
         (ngram_lm, lexicon), opts = lexicon_beam
         max_frames = max([1] + [-(-task.frontend.num_frames(len(w)) // se.stride) for w in waves])
         dec = StreamingCTCLexiconBeamDecoder(dictionary, ngram_lm, lexicon, streams, max_frames, **opts)
+        partial_of = lambda part: (part["tokens"], len(part["stable"]))  # noqa: E731
+        strip = {dictionary.eos(), dictionary.pad()}
+    elif search == "ctc_stream_beam":
+        max_frames = max([1] + [-(-task.frontend.num_frames(len(w)) // se.stride) for w in waves])
+        dec = StreamingCTCPrefixBeamDecoder(dictionary, streams, max_frames, **ctc_stream_beam)
         partial_of = lambda part: (part["tokens"], len(part["stable"]))  # noqa: E731
         strip = {dictionary.eos(), dictionary.pad()}
     elif search == "transducer_stream_beam":
@@ -587,6 +629,7 @@ def main(argv=None):
     args = get_parser().parse_args(argv)
     check_frame_beam_args(args)
     check_stream_beam_args(args)
+    check_ctc_stream_beam_args(args)
     if args.print_alignment is not None and not args.results_path:
         raise ValueError("--print-alignment saves attention plots under --results-path: give --results-path")
     check_hotword_args(args)
@@ -613,7 +656,7 @@ def main(argv=None):
     model_name, model_cfg = resolve_model_config(args.model, args.model_config, state)
     autoregressive = args.search == "beam"
     # the criterion the checkpoint was trained with decides whether "<s>" is the blank (speech_recognition.py:324, 345-347)
-    crit = {"beam": "label_smoothed_cross_entropy_v2", "ctc": "ctc_loss", "ctc_beam": "ctc_loss"}.get(args.search, "transducer_loss")
+    crit = {"beam": "label_smoothed_cross_entropy_v2", "ctc": "ctc_loss", "ctc_beam": "ctc_loss", "ctc_stream_beam": "ctc_loss"}.get(args.search, "transducer_loss")
     task = SpeechRecognitionEspressoTask.setup_task(SpeechRecognitionEspressoConfig(
         dict=args.dict, autoregressive=autoregressive, global_cmvn_stats_path=args.global_cmvn_stats_path, criterion_name=crit,
         non_lang_syms=args.non_lang_syms, wer_output_filter=args.wer_output_filter, bpe=args.bpe,
@@ -675,8 +718,8 @@ def main(argv=None):
             if args.word_dict:
                 lm = TensorizedLookaheadLanguageModel(lm, task.target_dictionary, oov_penalty=args.oov_penalty,
                                                       open_vocab=not args.disable_open_vocab)
-    gen = None  # (the streamed transducer beam builds its own decoder in recognize_streaming, which validates the same options)
-    if args.search != "transducer_stream_beam":
+    gen = None  # (the streamed beam searches build their own decoders in recognize_streaming, which validates the same options)
+    if args.search not in ("transducer_stream_beam", "ctc_stream_beam"):
         gen = build_generator(args, members if len(members) > 1 else model, task.target_dictionary, lm, ngram, context_graph)
     scp = read_scp(args.wav_scp)
     utt_ids = list(scp.keys())
@@ -701,6 +744,8 @@ def main(argv=None):
             kw["lexicon_beam"] = (ngram, dict(beam_size=args.beam, nbest=args.nbest, beam_size_token=args.ctc_beam_size_token,
                                               lm_weight=args.lm_weight, word_score=args.word_score,
                                               insertion_bonus=args.ctc_insertion_bonus))
+        if args.search == "ctc_stream_beam":
+            kw["ctc_stream_beam"] = ctc_stream_beam_options(args, lm, context_graph)
         if args.search == "transducer_stream_beam":
             kw["stream_beam"] = stream_beam_options(args, lm, context_graph)
         if not args.results_path:

@@ -465,6 +465,57 @@ int ea_context_graph_score_host(const int* nodes_host, const int* edges_host, co
 int ea_context_graph_score(const int* nodes, const int* edges, const int* root, int n_nodes, int n_edges, int V,
                            const int* tokens, const int* lens, int N, int L, float* running, float* final_bias, int* q_out,
                            ea_stream_t stream);
+/* The streamed CTC prefix beam search: the frames of ea_ctc_prefix_beam_step / _bias_step over streams that come and go, alone,
+ * with a sub-word LM, with a context graph or with both (csrc/ctc_beam.hip; the per-frame code and the beam's load and store
+ * are the offline step's: one body with an offline and a streamed wrapper, the two tested against each other, so a stream fed in
+ * any pieces gives bit for bit the offline results of the whole utterance).  One family: the context-graph tables are optional
+ * arguments, cg_nodes == NULL is the unbiased search, otherwise the tables are validated as in ea_ctc_prefix_beam_bias_step; one
+ * search passes the same graph, or none, to all of its calls.  The search state of a stream lives in one of max_streams slots of
+ * `state` (max_streams * ea_ctc_prefix_beam_stream_state_bytes(max_frames, beam) bytes, slot-major).  Per slot, int32 words:
+ * words = 2 + even(3 * tsize + 7 * beam + 2 + 2 * cap) + 2 * beam with cap = 1 + max_frames * beam, tsize the smallest power of
+ * two >= max(64, 2 * cap) and even() rounding up to an even count: [0] frames consumed, [1] 0, then the offline workspace of one
+ * utterance of max_frames frames (hash table, beam, counters, node_par / node_tok), then q int32 [beam] and b fp32 [beam], the
+ * hypotheses' states in the context graph and running biases, which every slot has room for.  ..._state_bytes returns 0 for
+ * max_frames < 1 or beam outside [1, 64].  Node ids are assigned in lane order and the hash table is only a lookup, so the
+ * results do not depend on max_frames, which only sizes the table.  Conventions of ea_ctc_lexicon_stream_* and
+ * ea_rnnt_frame_beam_stream_*: slots / slot_idx / n_new / row_off are device int32 [n]; an entry whose slot is outside
+ * [0, max_streams) is skipped; a slot may be listed once per call; no call synchronises with the host; bad arguments return -2
+ * and launch nothing; n <= 0 returns 0.
+ * ..._reset: the listed slots get the state before frame 0 (what the offline step with t0 == 0 writes: the empty prefix, a cleared
+ *   hash; frames = 0; q = 0, b = 0).
+ * ..._step: one 256-thread workgroup per entry.  Entry b searches the frames j in [j0, min(j1, n_new[b])) of its piece, rows
+ *   row_off[b] + j of x (fp32 or bf16 [total_rows][ld] log-probs), under the contract of ea_ctc_prefix_beam_step, and advances
+ *   its slot's frame counter by the frames searched.  It is inactive — its slot untouched, its counter not advanced — if its slot
+ *   is out of range, if it has no such frame, if a row of its piece lies outside [0, total_rows), or if the piece would take the
+ *   slot past max_frames (counter - j0 + n_new[b] > max_frames: the counter stands at its value before the piece plus j0).
+ *   Without lm_rows the whole piece is one launch (j0 = 0, j1 >= the largest count).  With lm_rows (fp32 [n*beam][ld_lm], row
+ *   b * beam + beam slot) j1 == j0 + 1 is required, the launches of a piece come in the order j0 = 0, 1, ..., and the step
+ *   writes lm_parent / lm_token / lm_keep [n*beam] as the offline step does, lm_parent in rows of THIS call; an inactive entry
+ *   writes parent = its own row, token = blank, keep = 1 (what the offline step writes for t >= in_len).
+ * ..._finish: ea_ctc_prefix_beam_finish (with cg_nodes: _bias_finish) per listed slot into tokens int32 [n][nbest][max_u]
+ *   (pad-filled; longer hypotheses are cut at max_u and their lengths clipped), lengths / scores [n][nbest], nhyp [n]; lm_rows
+ *   fp32 [n*beam][ld_lm] in the order of `slots`.  The state is read only, so the call is valid mid-stream; a reset slot without
+ *   frames returns the empty hypothesis, as the offline search does for T = 0.
+ * ..._partial: per listed slot the live hypothesis with the best in-beam score log(p_blank + p_nonblank) + lm_weight * lm +
+ *   ins_bonus * |y| (+ b with biased != 0; ties: the lower beam slot) into tokens int32 [n][max_u], lengths / scores [n] (that
+ *   value), and stable_len [n]: the length of the longest common prefix of the live hypotheses with a finite in-beam score (of
+ *   all live ones when none is finite), the depth of their lowest common ancestor in node_par.  Every hypothesis a later finish
+ *   can return with a finite score starts with those tokens.  lm_weight = 0 when no LM is fused.  The state is read only. */
+long ea_ctc_prefix_beam_stream_state_bytes(int max_frames, int beam);
+int ea_ctc_prefix_beam_stream_reset(void* state, const int* slots, int n, int max_streams, int max_frames, int beam,
+                                    ea_stream_t stream);
+int ea_ctc_prefix_beam_stream_step(const void* x, long ld, int x_bf16, long total_rows, const int* slot_idx, const int* n_new,
+                                   const int* row_off, int j0, int j1, int n, void* state, const float* lm_rows, long ld_lm,
+                                   int* lm_parent, int* lm_token, void* lm_keep, const int* cg_nodes, const int* cg_edges,
+                                   const int* cg_root, int cg_n_nodes, int cg_n_edges, int max_streams, int max_frames, int V,
+                                   int beam, int K, int blank, float lm_weight, float ins_bonus, ea_stream_t stream);
+int ea_ctc_prefix_beam_stream_finish(const void* state, const int* slots, int n, const float* lm_rows, long ld_lm, float lm_weight,
+                                     float ins_bonus, int eos, const int* cg_nodes, int cg_n_nodes, int max_streams,
+                                     int max_frames, int beam, int nbest, int pad, int max_u, int* tokens, int* lengths,
+                                     float* scores, int* nhyp, ea_stream_t stream);
+int ea_ctc_prefix_beam_stream_partial(const void* state, const int* slots, int n, float lm_weight, float ins_bonus, int biased,
+                                      int max_streams, int max_frames, int beam, int pad, int max_u, int* tokens, int* lengths,
+                                      float* scores, int* stable_len, ea_stream_t stream);
 /* Frame-synchronous transducer beam search (csrc/rnnt_beam.hip; at most one symbol per encoder frame and hypothesis, equal
  * token sequences merged — "modified beam search") with optional mass-preserving shallow fusion of one sub-word LM: the
  * transducer counterpart of ea_ctc_prefix_beam_*.  Hypotheses are distinct token sequences with a score (natural log), at most
