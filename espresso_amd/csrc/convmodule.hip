@@ -699,17 +699,21 @@ __global__ __launch_bounds__(256) void dwconv_bwd_weight_kernel(const bf16_t* __
     }
     __syncthreads();
     // dw[k] += dZ[t] * U[t - PAD + k]  ->  LDS row of U = (t - t0) + k ; window x[kk] = sU[tt + grp*8 + kk]
-    float x[KG];
+    // A tap group that starts at or past KW owns no tap: it only keeps the barriers company.  (Its window would reach row
+    // TTILE + grp*8 + 6 of sU, past the ROWS + KG rows staged for KW < 31.)  The branch is uniform per wavefront.
+    if (grp * KG < KW) {
+      float x[KG];
 #pragma unroll
-    for (int kk = 0; kk < KG - 1; ++kk) x[kk + 1] = sU[grp * KG + kk][cl];
+      for (int kk = 0; kk < KG - 1; ++kk) x[kk + 1] = sU[grp * KG + kk][cl];
 #pragma unroll
-    for (int tt = 0; tt < TTILE; ++tt) {
+      for (int tt = 0; tt < TTILE; ++tt) {
 #pragma unroll
-      for (int kk = 0; kk < KG - 1; ++kk) x[kk] = x[kk + 1];
-      x[KG - 1] = sU[tt + grp * KG + KG - 1][cl];
-      const float d = sD[tt][cl];
+        for (int kk = 0; kk < KG - 1; ++kk) x[kk] = x[kk + 1];
+        x[KG - 1] = sU[tt + grp * KG + KG - 1][cl];
+        const float d = sD[tt][cl];
 #pragma unroll
-      for (int kk = 0; kk < KG; ++kk) acc[kk] += d * x[kk];
+        for (int kk = 0; kk < KG; ++kk) acc[kk] += d * x[kk];
+      }
     }
   }
   const int c = c0 + cl;
