@@ -552,6 +552,42 @@ def ctc_greedy_decode(x, in_len, B, T, V, blank, pad, ld=None, want_align=True):
     return tokens, out_len, score, align
 
 
+def _finish_outputs(n, nbest, max_u, device):
+    """The outputs of a finish: (tokens int32 [n][nbest][max_u], lengths int32 [n][nbest], scores fp32 [n][nbest], nhyp int32 [n])."""
+    return (torch.empty(n, nbest, max_u, dtype=torch.int32, device=device), torch.empty(n, nbest, dtype=torch.int32, device=device),
+            torch.empty(n, nbest, dtype=torch.float32, device=device), torch.empty(n, dtype=torch.int32, device=device))
+
+
+def _partial_outputs(n, max_u, device):
+    """The outputs of a streamed partial: (tokens int32 [n][max_u], lengths int32 [n], scores fp32 [n], stable_len int32 [n])."""
+    return (torch.empty(n, max_u, dtype=torch.int32, device=device), torch.empty(n, dtype=torch.int32, device=device),
+            torch.empty(n, dtype=torch.float32, device=device), torch.empty(n, dtype=torch.int32, device=device))
+
+
+def _stream_state(bytes_fn, max_streams, max_frames, beam, device):
+    """(state uint8 [max_streams][bytes per slot], zero-filled; bytes per slot) of a streamed search; bytes_fn: its
+    ea_*_state_bytes entry."""
+    nbytes = int(bytes_fn(max_frames, beam))
+    assert nbytes > 0 and max_streams >= 1
+    return torch.zeros(max_streams, nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def _check_stream_state(state, bytes_fn, max_frames, beam):
+    assert state.dtype == torch.uint8 and state.is_contiguous() and state.dim() == 2
+    assert state.shape[1] == bytes_fn(max_frames, beam)
+
+
+def _check_rnnt_step_args(logits, out, lm_rows, N, V, lm_no_blank):
+    """The joint's logits fp32 [N][>= V], the triple a transducer step writes and its LM rows; returns the triple."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == N and logits.shape[1] >= V
+    parent, token, keep = out
+    assert parent.numel() == token.numel() == keep.numel() == N
+    assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
+    if lm_rows is not None:
+        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (N, V - 1 if lm_no_blank else V)
+    return parent, token, keep
+
+
 def ctc_prefix_beam_workspace(B, T, beam, device):
     """Workspace of the CTC prefix beam search (ea_ctc_prefix_beam_workspace_bytes): the beams and prefix tables of B utterances."""
     return torch.empty(int(_lib.lib().ea_ctc_prefix_beam_workspace_bytes(B, T, beam)), dtype=torch.uint8, device=device)
@@ -577,10 +613,7 @@ def ctc_prefix_beam_step(x, in_len, ws, B, T, V, beam, K, blank, t0, t1, lm_rows
 def ctc_prefix_beam_finish(ws, B, T, beam, nbest, pad, lm_rows=None, lm_weight=0.0, ins_bonus=0.0, eos=-1):
     """(tokens int32 [B][nbest][T] pad-filled, lengths int32 [B][nbest], scores fp32 [B][nbest], nhyp int32 [B]), best first."""
     dev = ws.device
-    tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
-    lengths = torch.empty(B, nbest, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
-    nhyp = torch.empty(B, dtype=torch.int32, device=dev)
+    tokens, lengths, scores, nhyp = _finish_outputs(B, nbest, T, dev)
     check(_lib.lib().ea_ctc_prefix_beam_finish(_p(ws), _p(lm_rows), lm_rows.stride(0) if lm_rows is not None else 0, lm_weight,
                                                ins_bonus, eos, B, T, beam, nbest, pad, _p(tokens), _p(lengths), _p(scores),
                                                _p(nhyp), _stream()), "ea_ctc_prefix_beam_finish")
@@ -622,10 +655,7 @@ def ctc_prefix_beam_bias_step(x, in_len, ws, graph, B, T, V, beam, K, blank, t0,
 def ctc_prefix_beam_bias_finish(ws, graph, B, T, beam, nbest, pad, lm_rows=None, lm_weight=0.0, ins_bonus=0.0, eos=-1):
     """ctc_prefix_beam_finish of a biased search: the scores include the boosts of the completed phrases."""
     dev = ws.device
-    tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
-    lengths = torch.empty(B, nbest, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
-    nhyp = torch.empty(B, dtype=torch.int32, device=dev)
+    tokens, lengths, scores, nhyp = _finish_outputs(B, nbest, T, dev)
     nodes, _, _, n_nodes, _ = _cg(graph)
     check(_lib.lib().ea_ctc_prefix_beam_bias_finish(_p(ws), _p(lm_rows), lm_rows.stride(0) if lm_rows is not None else 0, lm_weight,
                                                     ins_bonus, eos, nodes, n_nodes, B, T, beam, nbest, pad, _p(tokens), _p(lengths),
@@ -636,14 +666,7 @@ def ctc_prefix_beam_bias_finish(ws, graph, B, T, beam, nbest, pad, lm_rows=None,
 def ctc_prefix_beam_stream_state(max_streams, max_frames, beam, device):
     """(state uint8 [max_streams][bytes per slot], zero-filled; bytes per slot) of the streamed CTC prefix beam search
     (ea_ctc_prefix_beam_stream_state_bytes)."""
-    nbytes = int(_lib.lib().ea_ctc_prefix_beam_stream_state_bytes(max_frames, beam))
-    assert nbytes > 0 and max_streams >= 1
-    return torch.zeros(max_streams, nbytes, dtype=torch.uint8, device=device), nbytes
-
-
-def _check_prefix_stream_state(state, max_frames, beam):
-    assert state.dtype == torch.uint8 and state.is_contiguous() and state.dim() == 2
-    assert state.shape[1] == _lib.lib().ea_ctc_prefix_beam_stream_state_bytes(max_frames, beam)
+    return _stream_state(_lib.lib().ea_ctc_prefix_beam_stream_state_bytes, max_streams, max_frames, beam, device)
 
 
 def _cg_or_none(graph, V=None):
@@ -652,7 +675,7 @@ def _cg_or_none(graph, V=None):
 
 def ctc_prefix_beam_stream_reset(state, slots, max_frames, beam):
     """The slots int32 [n] (device) of `state` get the search state before frame 0 (ea_ctc_prefix_beam_stream_reset)."""
-    _check_prefix_stream_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_ctc_prefix_beam_stream_state_bytes, max_frames, beam)
     assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
     check(_lib.lib().ea_ctc_prefix_beam_stream_reset(_p(state), _p(slots), slots.numel(), state.shape[0], max_frames, beam, _stream()),
           "ea_ctc_prefix_beam_stream_reset")
@@ -668,7 +691,7 @@ def ctc_prefix_beam_stream_step(x, meta, state, max_frames, V, beam, K, blank, j
     ld = x.stride(0) if ld is None else ld
     assert x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 2 and x.stride(-1) == 1 and x.shape[1] == V
     assert meta.dtype == torch.int32 and meta.dim() == 2 and meta.shape[0] == 3 and meta.is_contiguous()
-    _check_prefix_stream_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_ctc_prefix_beam_stream_state_bytes, max_frames, beam)
     n = meta.shape[1]
     j1 = max(x.shape[0], j0) if j1 is None else j1
     parent, token, keep = lm_out if lm_out is not None else (None, None, None)
@@ -688,15 +711,12 @@ def ctc_prefix_beam_stream_finish(state, slots, max_frames, beam, nbest, pad, ma
     """The finished hypotheses of the slots int32 [n] (device), the state left as it is (ea_ctc_prefix_beam_stream_finish);
     lm_rows fp32 [n*beam][V] in the order of `slots`.  Returns (tokens int32 [n][nbest][max_u] pad-filled, lengths int32
     [n][nbest], scores fp32 [n][nbest], nhyp int32 [n]), best first."""
-    _check_prefix_stream_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_ctc_prefix_beam_stream_state_bytes, max_frames, beam)
     assert slots.dtype == torch.int32 and slots.is_contiguous() and 1 <= nbest <= beam
     n, dev = slots.numel(), state.device
     if lm_rows is not None:
         assert lm_rows.dtype == torch.float32 and lm_rows.dim() == 2 and lm_rows.stride(1) == 1 and lm_rows.shape[0] == n * beam
-    tokens = torch.empty(n, nbest, max_u, dtype=torch.int32, device=dev)
-    lengths = torch.empty(n, nbest, dtype=torch.int32, device=dev)
-    scores = torch.empty(n, nbest, dtype=torch.float32, device=dev)
-    nhyp = torch.empty(n, dtype=torch.int32, device=dev)
+    tokens, lengths, scores, nhyp = _finish_outputs(n, nbest, max_u, dev)
     nodes, _, _, n_nodes, _ = _cg_or_none(graph)
     check(_lib.lib().ea_ctc_prefix_beam_stream_finish(_p(state), _p(slots), n, _p(lm_rows),
                                                       lm_rows.stride(0) if lm_rows is not None else 0, lm_weight, ins_bonus, eos, nodes,
@@ -709,13 +729,10 @@ def ctc_prefix_beam_stream_partial(state, slots, max_frames, beam, pad, max_u, l
     """The best live hypothesis (by the in-beam score, with the running bias when `biased`) of the slots int32 [n] (device) and
     the length of the beam's common prefix (ea_ctc_prefix_beam_stream_partial).  Returns (tokens int32 [n][max_u] pad-filled,
     lengths int32 [n], scores fp32 [n], stable_len int32 [n])."""
-    _check_prefix_stream_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_ctc_prefix_beam_stream_state_bytes, max_frames, beam)
     assert slots.dtype == torch.int32 and slots.is_contiguous()
     n, dev = slots.numel(), state.device
-    tokens = torch.empty(n, max_u, dtype=torch.int32, device=dev)
-    lengths = torch.empty(n, dtype=torch.int32, device=dev)
-    scores = torch.empty(n, dtype=torch.float32, device=dev)
-    stable = torch.empty(n, dtype=torch.int32, device=dev)
+    tokens, lengths, scores, stable = _partial_outputs(n, max_u, dev)
     check(_lib.lib().ea_ctc_prefix_beam_stream_partial(_p(state), _p(slots), n, lm_weight, ins_bonus, int(bool(biased)), state.shape[0],
                                                        max_frames, beam, pad, max_u, _p(tokens), _p(lengths), _p(scores), _p(stable),
                                                        _stream()), "ea_ctc_prefix_beam_stream_partial")
@@ -733,13 +750,8 @@ def rnnt_frame_beam_step(logits, in_len, ws, out, B, T, V, beam, K, blank, t, eo
     """Frame t of the frame-synchronous transducer beam search: logits fp32 [B*beam][>= V] (the joint's output for this frame, row
     b * beam + slot), in_len int32 [B], out = (parent int32, token int32, keep uint8), each [B*beam], written by the step.
     lm_rows fp32 [B*beam][V or V - 1 (lm_no_blank)]; eos >= 0: the model's eos is folded into blank."""
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == B * beam and logits.shape[1] >= V
     assert in_len.dtype == torch.int32 and in_len.numel() == B  # (ws: rnnt_frame_beam_workspace(B, T, beam), checked by its owner)
-    parent, token, keep = out
-    assert parent.numel() == token.numel() == keep.numel() == B * beam
-    assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
-    if lm_rows is not None:
-        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (B * beam, V - 1 if lm_no_blank else V)
+    parent, token, keep = _check_rnnt_step_args(logits, out, lm_rows, B * beam, V, lm_no_blank)
     check(_lib.lib().ea_rnnt_frame_beam_step(_p(logits), logits.stride(0), _p(lm_rows), lm_rows.stride(0) if lm_rows is not None else 0,
                                              int(lm_no_blank), _p(in_len), _p(ws), _p(parent), _p(token), _p(keep), B, T, V, beam, K,
                                              blank, eos, temperature, lm_weight, t, _stream()), "ea_rnnt_frame_beam_step")
@@ -748,10 +760,7 @@ def rnnt_frame_beam_step(logits, in_len, ws, out, B, T, V, beam, K, blank, t, eo
 def rnnt_frame_beam_finish(ws, B, T, beam, nbest, pad, normalize=True):
     """(tokens int32 [B][nbest][T] pad-filled, lengths int32 [B][nbest], scores fp32 [B][nbest], nhyp int32 [B]), best first."""
     dev = ws.device
-    tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
-    lengths = torch.empty(B, nbest, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
-    nhyp = torch.empty(B, dtype=torch.int32, device=dev)
+    tokens, lengths, scores, nhyp = _finish_outputs(B, nbest, T, dev)
     check(_lib.lib().ea_rnnt_frame_beam_finish(_p(ws), B, T, beam, nbest, pad, int(bool(normalize)), _p(tokens), _p(lengths),
                                                _p(scores), _p(nhyp), _stream()), "ea_rnnt_frame_beam_finish")
     return tokens, lengths, scores, nhyp
@@ -760,19 +769,12 @@ def rnnt_frame_beam_finish(ws, B, T, beam, nbest, pad, normalize=True):
 def rnnt_frame_beam_stream_state(max_streams, max_frames, beam, device):
     """(state uint8 [max_streams][bytes per slot], zero-filled; bytes per slot) of the streamed frame-synchronous transducer
     beam search (ea_rnnt_frame_beam_stream_state_bytes)."""
-    nbytes = int(_lib.lib().ea_rnnt_frame_beam_stream_state_bytes(max_frames, beam))
-    assert nbytes > 0 and max_streams >= 1
-    return torch.zeros(max_streams, nbytes, dtype=torch.uint8, device=device), nbytes
-
-
-def _check_rnnt_stream_state(state, max_frames, beam):
-    assert state.dtype == torch.uint8 and state.is_contiguous() and state.dim() == 2
-    assert state.shape[1] == _lib.lib().ea_rnnt_frame_beam_stream_state_bytes(max_frames, beam)
+    return _stream_state(_lib.lib().ea_rnnt_frame_beam_stream_state_bytes, max_streams, max_frames, beam, device)
 
 
 def rnnt_frame_beam_stream_reset(state, slots, max_frames, beam):
     """The slots int32 [n] (device) of `state` get the search state before frame 0 (ea_rnnt_frame_beam_stream_reset)."""
-    _check_rnnt_stream_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_rnnt_frame_beam_stream_state_bytes, max_frames, beam)
     assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
     check(_lib.lib().ea_rnnt_frame_beam_stream_reset(_p(state), _p(slots), slots.numel(), state.shape[0], max_frames, beam, _stream()),
           "ea_rnnt_frame_beam_stream_reset")
@@ -785,14 +787,9 @@ def rnnt_frame_beam_stream_step(logits, slot_idx, n_new, j, state, out, max_fram
     device; out = (parent int32, token int32, keep uint8), each [n*beam], written by the step (identity / blank / 1 for an entry
     with j >= n_new, a slot out of range or a full slot, whose state is left as it is)."""
     n = slot_idx.numel()
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == n * beam and logits.shape[1] >= V
     assert slot_idx.dtype == n_new.dtype == torch.int32 and n_new.numel() == n and slot_idx.is_contiguous() and n_new.is_contiguous()
-    _check_rnnt_stream_state(state, max_frames, beam)
-    parent, token, keep = out
-    assert parent.numel() == token.numel() == keep.numel() == n * beam
-    assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
-    if lm_rows is not None:
-        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (n * beam, V - 1 if lm_no_blank else V)
+    _check_stream_state(state, _lib.lib().ea_rnnt_frame_beam_stream_state_bytes, max_frames, beam)
+    parent, token, keep = _check_rnnt_step_args(logits, out, lm_rows, n * beam, V, lm_no_blank)
     check(_lib.lib().ea_rnnt_frame_beam_stream_step(_p(logits), logits.stride(0), _p(lm_rows),
                                                     lm_rows.stride(0) if lm_rows is not None else 0, int(lm_no_blank), _p(slot_idx),
                                                     _p(n_new), j, n, _p(state), _p(parent), _p(token), _p(keep), state.shape[0],
@@ -804,13 +801,10 @@ def rnnt_frame_beam_stream_finish(state, slots, max_frames, beam, nbest, pad, ma
     """The hypotheses of the slots int32 [n] (device) as if their streams ended now, the state left as it is
     (ea_rnnt_frame_beam_stream_finish).  Returns (tokens int32 [n][nbest][max_u] pad-filled, lengths int32 [n][nbest], scores
     fp32 [n][nbest], nhyp int32 [n]), best first."""
-    _check_rnnt_stream_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_rnnt_frame_beam_stream_state_bytes, max_frames, beam)
     assert slots.dtype == torch.int32 and slots.is_contiguous()
     n, dev = slots.numel(), state.device
-    tokens = torch.empty(n, nbest, max_u, dtype=torch.int32, device=dev)
-    lengths = torch.empty(n, nbest, dtype=torch.int32, device=dev)
-    scores = torch.empty(n, nbest, dtype=torch.float32, device=dev)
-    nhyp = torch.empty(n, dtype=torch.int32, device=dev)
+    tokens, lengths, scores, nhyp = _finish_outputs(n, nbest, max_u, dev)
     check(_lib.lib().ea_rnnt_frame_beam_stream_finish(_p(state), _p(slots), n, state.shape[0], max_frames, beam, nbest, pad,
                                                       int(bool(normalize)), max_u, _p(tokens), _p(lengths), _p(scores), _p(nhyp),
                                                       _stream()), "ea_rnnt_frame_beam_stream_finish")
@@ -821,13 +815,10 @@ def rnnt_frame_beam_stream_partial(state, slots, max_frames, beam, pad, max_u):
     """The best live hypothesis (by the raw score the search prunes by) of the slots int32 [n] (device) and the length of the
     beam's common prefix (ea_rnnt_frame_beam_stream_partial).  Returns (tokens int32 [n][max_u] pad-filled, lengths int32 [n],
     scores fp32 [n], stable_len int32 [n])."""
-    _check_rnnt_stream_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_rnnt_frame_beam_stream_state_bytes, max_frames, beam)
     assert slots.dtype == torch.int32 and slots.is_contiguous()
     n, dev = slots.numel(), state.device
-    tokens = torch.empty(n, max_u, dtype=torch.int32, device=dev)
-    lengths = torch.empty(n, dtype=torch.int32, device=dev)
-    scores = torch.empty(n, dtype=torch.float32, device=dev)
-    stable = torch.empty(n, dtype=torch.int32, device=dev)
+    tokens, lengths, scores, stable = _partial_outputs(n, max_u, dev)
     check(_lib.lib().ea_rnnt_frame_beam_stream_partial(_p(state), _p(slots), n, state.shape[0], max_frames, beam, pad, max_u,
                                                        _p(tokens), _p(lengths), _p(scores), _p(stable), _stream()),
           "ea_rnnt_frame_beam_stream_partial")
@@ -843,13 +834,8 @@ def rnnt_frame_beam_bias_step(logits, in_len, ws, graph, out, B, T, V, beam, K, 
                               lm_weight=0.0, lm_no_blank=False):
     """rnnt_frame_beam_step with a context graph (nodes, edges, root device tables of tools.context_graph.ContextGraph.cuda());
     ws: rnnt_frame_beam_bias_workspace(B, T, beam)."""
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == B * beam and logits.shape[1] >= V
     assert in_len.dtype == torch.int32 and in_len.numel() == B
-    parent, token, keep = out
-    assert parent.numel() == token.numel() == keep.numel() == B * beam
-    assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
-    if lm_rows is not None:
-        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (B * beam, V - 1 if lm_no_blank else V)
+    parent, token, keep = _check_rnnt_step_args(logits, out, lm_rows, B * beam, V, lm_no_blank)
     check(_lib.lib().ea_rnnt_frame_beam_bias_step(_p(logits), logits.stride(0), _p(lm_rows),
                                                   lm_rows.stride(0) if lm_rows is not None else 0, int(lm_no_blank), _p(in_len), _p(ws),
                                                   _p(parent), _p(token), _p(keep), *_cg(graph, V), B, T, V, beam, K, blank, eos,
@@ -859,10 +845,7 @@ def rnnt_frame_beam_bias_step(logits, in_len, ws, graph, out, B, T, V, beam, K, 
 def rnnt_frame_beam_bias_finish(ws, graph, B, T, beam, nbest, pad, normalize=True):
     """rnnt_frame_beam_finish of a biased search: the scores include the boosts of the completed phrases."""
     dev = ws.device
-    tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
-    lengths = torch.empty(B, nbest, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
-    nhyp = torch.empty(B, dtype=torch.int32, device=dev)
+    tokens, lengths, scores, nhyp = _finish_outputs(B, nbest, T, dev)
     nodes, _, _, n_nodes, _ = _cg(graph)
     check(_lib.lib().ea_rnnt_frame_beam_bias_finish(_p(ws), nodes, n_nodes, B, T, beam, nbest, pad, int(bool(normalize)), _p(tokens),
                                                     _p(lengths), _p(scores), _p(nhyp), _stream()), "ea_rnnt_frame_beam_bias_finish")
@@ -872,19 +855,12 @@ def rnnt_frame_beam_bias_finish(ws, graph, B, T, beam, nbest, pad, normalize=Tru
 def rnnt_frame_beam_stream_bias_state(max_streams, max_frames, beam, device):
     """(state uint8 [max_streams][bytes per slot], zero-filled; bytes per slot) of the streamed, hotword-biased frame-synchronous
     transducer beam search (ea_rnnt_frame_beam_stream_bias_state_bytes)."""
-    nbytes = int(_lib.lib().ea_rnnt_frame_beam_stream_bias_state_bytes(max_frames, beam))
-    assert nbytes > 0 and max_streams >= 1
-    return torch.zeros(max_streams, nbytes, dtype=torch.uint8, device=device), nbytes
-
-
-def _check_rnnt_stream_bias_state(state, max_frames, beam):
-    assert state.dtype == torch.uint8 and state.is_contiguous() and state.dim() == 2
-    assert state.shape[1] == _lib.lib().ea_rnnt_frame_beam_stream_bias_state_bytes(max_frames, beam)
+    return _stream_state(_lib.lib().ea_rnnt_frame_beam_stream_bias_state_bytes, max_streams, max_frames, beam, device)
 
 
 def rnnt_frame_beam_stream_bias_reset(state, slots, max_frames, beam):
     """rnnt_frame_beam_stream_reset of a biased state: the empty hypothesis sits in the graph's root with bias 0."""
-    _check_rnnt_stream_bias_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_rnnt_frame_beam_stream_bias_state_bytes, max_frames, beam)
     assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
     check(_lib.lib().ea_rnnt_frame_beam_stream_bias_reset(_p(state), _p(slots), slots.numel(), state.shape[0], max_frames, beam,
                                                           _stream()), "ea_rnnt_frame_beam_stream_bias_reset")
@@ -894,14 +870,9 @@ def rnnt_frame_beam_stream_bias_step(logits, slot_idx, n_new, j, state, graph, o
                                      temperature=1.0, lm_rows=None, lm_weight=0.0, lm_no_blank=False):
     """rnnt_frame_beam_stream_step with a context graph; state: rnnt_frame_beam_stream_bias_state."""
     n = slot_idx.numel()
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == n * beam and logits.shape[1] >= V
     assert slot_idx.dtype == n_new.dtype == torch.int32 and n_new.numel() == n and slot_idx.is_contiguous() and n_new.is_contiguous()
-    _check_rnnt_stream_bias_state(state, max_frames, beam)
-    parent, token, keep = out
-    assert parent.numel() == token.numel() == keep.numel() == n * beam
-    assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
-    if lm_rows is not None:
-        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (n * beam, V - 1 if lm_no_blank else V)
+    _check_stream_state(state, _lib.lib().ea_rnnt_frame_beam_stream_bias_state_bytes, max_frames, beam)
+    parent, token, keep = _check_rnnt_step_args(logits, out, lm_rows, n * beam, V, lm_no_blank)
     check(_lib.lib().ea_rnnt_frame_beam_stream_bias_step(_p(logits), logits.stride(0), _p(lm_rows),
                                                          lm_rows.stride(0) if lm_rows is not None else 0, int(lm_no_blank),
                                                          _p(slot_idx), _p(n_new), j, n, _p(state), _p(parent), _p(token), _p(keep),
@@ -911,13 +882,10 @@ def rnnt_frame_beam_stream_bias_step(logits, slot_idx, n_new, j, state, graph, o
 
 def rnnt_frame_beam_stream_bias_finish(state, slots, graph, max_frames, beam, nbest, pad, max_u, normalize=True):
     """rnnt_frame_beam_stream_finish of a biased state: the scores include the boosts of the completed phrases."""
-    _check_rnnt_stream_bias_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_rnnt_frame_beam_stream_bias_state_bytes, max_frames, beam)
     assert slots.dtype == torch.int32 and slots.is_contiguous()
     n, dev = slots.numel(), state.device
-    tokens = torch.empty(n, nbest, max_u, dtype=torch.int32, device=dev)
-    lengths = torch.empty(n, nbest, dtype=torch.int32, device=dev)
-    scores = torch.empty(n, nbest, dtype=torch.float32, device=dev)
-    nhyp = torch.empty(n, dtype=torch.int32, device=dev)
+    tokens, lengths, scores, nhyp = _finish_outputs(n, nbest, max_u, dev)
     nodes, _, _, n_nodes, _ = _cg(graph)
     check(_lib.lib().ea_rnnt_frame_beam_stream_bias_finish(_p(state), _p(slots), n, state.shape[0], max_frames, beam, nodes, n_nodes,
                                                            nbest, pad, int(bool(normalize)), max_u, _p(tokens), _p(lengths), _p(scores),
@@ -927,13 +895,10 @@ def rnnt_frame_beam_stream_bias_finish(state, slots, graph, max_frames, beam, nb
 
 def rnnt_frame_beam_stream_bias_partial(state, slots, max_frames, beam, pad, max_u):
     """rnnt_frame_beam_stream_partial of a biased state: the live hypothesis with the best score + running bias, and that value."""
-    _check_rnnt_stream_bias_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_rnnt_frame_beam_stream_bias_state_bytes, max_frames, beam)
     assert slots.dtype == torch.int32 and slots.is_contiguous()
     n, dev = slots.numel(), state.device
-    tokens = torch.empty(n, max_u, dtype=torch.int32, device=dev)
-    lengths = torch.empty(n, dtype=torch.int32, device=dev)
-    scores = torch.empty(n, dtype=torch.float32, device=dev)
-    stable = torch.empty(n, dtype=torch.int32, device=dev)
+    tokens, lengths, scores, stable = _partial_outputs(n, max_u, dev)
     check(_lib.lib().ea_rnnt_frame_beam_stream_bias_partial(_p(state), _p(slots), n, state.shape[0], max_frames, beam, pad, max_u,
                                                             _p(tokens), _p(lengths), _p(scores), _p(stable), _stream()),
           "ea_rnnt_frame_beam_stream_bias_partial")
@@ -1036,10 +1001,7 @@ def ctc_lexicon_beam_search(x, in_len, ws, ngram, trie, word_start, space, B, T,
     assert off.dtype == tok.dtype == child.dtype == word.dtype == torch.int32 and smear.dtype == torch.float32
     assert word_start is None or (word_start.dtype == torch.uint8 and word_start.numel() == V)
     dev = x.device
-    tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
-    lengths = torch.empty(B, nbest, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
-    nhyp = torch.empty(B, dtype=torch.int32, device=dev)
+    tokens, lengths, scores, nhyp = _finish_outputs(B, nbest, T, dev)
     check(_lib.lib().ea_ctc_lexicon_beam_search(_p(x), ld, int(x.dtype == torch.bfloat16), _p(in_len), _p(ws), ngram, _p(off),
                                                 _p(tok), _p(child), _p(word), _p(smear), _p(word_start), space, B, T, V, beam, K,
                                                 blank, lm_weight, word_score, ins_bonus, nbest, pad, _p(tokens), _p(lengths),
@@ -1050,19 +1012,12 @@ def ctc_lexicon_beam_search(x, in_len, ws, ngram, trie, word_start, space, B, T,
 def ctc_lexicon_stream_state(max_streams, max_frames, beam, device):
     """(state uint8 [max_streams][bytes per slot], zero-filled; bytes per slot) of the streamed lexicon beam search
     (ea_ctc_lexicon_stream_state_bytes)."""
-    nbytes = int(_lib.lib().ea_ctc_lexicon_stream_state_bytes(max_frames, beam))
-    assert nbytes > 0 and max_streams >= 1
-    return torch.zeros(max_streams, nbytes, dtype=torch.uint8, device=device), nbytes
-
-
-def _check_stream_state(state, max_frames, beam):
-    assert state.dtype == torch.uint8 and state.is_contiguous() and state.dim() == 2
-    assert state.shape[1] == _lib.lib().ea_ctc_lexicon_stream_state_bytes(max_frames, beam)
+    return _stream_state(_lib.lib().ea_ctc_lexicon_stream_state_bytes, max_streams, max_frames, beam, device)
 
 
 def ctc_lexicon_stream_reset(state, slots, ngram, max_frames, beam):
     """The slots int32 [n] (device) of `state` get the search state before frame 0 (ea_ctc_lexicon_stream_reset)."""
-    _check_stream_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_ctc_lexicon_stream_state_bytes, max_frames, beam)
     assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
     check(_lib.lib().ea_ctc_lexicon_stream_reset(_p(state), _p(slots), slots.numel(), ngram, state.shape[0], max_frames, beam,
                                                  _stream()), "ea_ctc_lexicon_stream_reset")
@@ -1075,7 +1030,7 @@ def ctc_lexicon_stream_step(x, meta, state, ngram, trie, word_start, space, max_
     ld = x.stride(0) if ld is None else ld
     assert x.dtype in (torch.float32, torch.bfloat16) and x.stride(-1) == 1 and x.shape[1] == V
     assert meta.dtype == torch.int32 and meta.dim() == 2 and meta.shape[0] == 3 and meta.is_contiguous()
-    _check_stream_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_ctc_lexicon_stream_state_bytes, max_frames, beam)
     off, tok, child, word, smear = trie
     assert off.dtype == tok.dtype == child.dtype == word.dtype == torch.int32 and smear.dtype == torch.float32
     assert word_start is None or (word_start.dtype == torch.uint8 and word_start.numel() == V)
@@ -1088,15 +1043,12 @@ def ctc_lexicon_stream_step(x, meta, state, ngram, trie, word_start, space, max_
 def ctc_lexicon_stream_finish(state, slots, ngram, trie, max_frames, beam, nbest, pad, max_u, lm_weight, word_score, ins_bonus):
     """The finished hypotheses of the slots int32 [n] (device), the state left as it is (ea_ctc_lexicon_stream_finish).
     Returns (tokens int32 [n][nbest][max_u] pad-filled, lengths int32 [n][nbest], scores fp32 [n][nbest], nhyp int32 [n])."""
-    _check_stream_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_ctc_lexicon_stream_state_bytes, max_frames, beam)
     assert slots.dtype == torch.int32 and slots.is_contiguous() and 1 <= nbest <= beam
     word, smear = trie[3], trie[4]
     assert word.dtype == torch.int32 and smear.dtype == torch.float32
     n, dev = slots.numel(), state.device
-    tokens = torch.empty(n, nbest, max_u, dtype=torch.int32, device=dev)
-    lengths = torch.empty(n, nbest, dtype=torch.int32, device=dev)
-    scores = torch.empty(n, nbest, dtype=torch.float32, device=dev)
-    nhyp = torch.empty(n, dtype=torch.int32, device=dev)
+    tokens, lengths, scores, nhyp = _finish_outputs(n, nbest, max_u, dev)
     check(_lib.lib().ea_ctc_lexicon_stream_finish(_p(state), _p(slots), n, ngram, _p(word), _p(smear), state.shape[0], max_frames,
                                                   beam, lm_weight, word_score, ins_bonus, nbest, pad, max_u, _p(tokens),
                                                   _p(lengths), _p(scores), _p(nhyp), _stream()), "ea_ctc_lexicon_stream_finish")
@@ -1107,13 +1059,10 @@ def ctc_lexicon_stream_partial(state, slots, max_frames, beam, pad, max_u, ins_b
     """The best live hypothesis of the slots int32 [n] (device) and the length of the beam's common prefix
     (ea_ctc_lexicon_stream_partial).  Returns (tokens int32 [n][max_u] pad-filled, lengths int32 [n], scores fp32 [n],
     stable_len int32 [n])."""
-    _check_stream_state(state, max_frames, beam)
+    _check_stream_state(state, _lib.lib().ea_ctc_lexicon_stream_state_bytes, max_frames, beam)
     assert slots.dtype == torch.int32 and slots.is_contiguous()
     n, dev = slots.numel(), state.device
-    tokens = torch.empty(n, max_u, dtype=torch.int32, device=dev)
-    lengths = torch.empty(n, dtype=torch.int32, device=dev)
-    scores = torch.empty(n, dtype=torch.float32, device=dev)
-    stable = torch.empty(n, dtype=torch.int32, device=dev)
+    tokens, lengths, scores, stable = _partial_outputs(n, max_u, dev)
     check(_lib.lib().ea_ctc_lexicon_stream_partial(_p(state), _p(slots), n, state.shape[0], max_frames, beam, ins_bonus, pad, max_u,
                                                    _p(tokens), _p(lengths), _p(scores), _p(stable), _stream()),
           "ea_ctc_lexicon_stream_partial")

@@ -459,22 +459,21 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
         scorer = Scorer(dictionary, wer_output_filter=None)
     se = StreamingEncoder(model, streams, frontend=task.frontend)
     partial_of = None  # a decoder's partial -> (tokens of the best hypothesis, how many of them are stable)
+    # the longest utterance's encoder frames: what a slot of the three beam searches is sized for
+    max_frames = max([1] + [-(-task.frontend.num_frames(len(w)) // se.stride) for w in waves])
     if search == "ctc":
         dec = StreamingCTCDecoder(dictionary)
         strip = {dictionary.eos(), dictionary.pad()}
     elif search == "ctc_beam":
         (ngram_lm, lexicon), opts = lexicon_beam
-        max_frames = max([1] + [-(-task.frontend.num_frames(len(w)) // se.stride) for w in waves])
         dec = StreamingCTCLexiconBeamDecoder(dictionary, ngram_lm, lexicon, streams, max_frames, **opts)
         partial_of = lambda part: (part["tokens"], len(part["stable"]))  # noqa: E731
         strip = {dictionary.eos(), dictionary.pad()}
     elif search == "ctc_stream_beam":
-        max_frames = max([1] + [-(-task.frontend.num_frames(len(w)) // se.stride) for w in waves])
         dec = StreamingCTCPrefixBeamDecoder(dictionary, streams, max_frames, **ctc_stream_beam)
         partial_of = lambda part: (part["tokens"], len(part["stable"]))  # noqa: E731
         strip = {dictionary.eos(), dictionary.pad()}
     elif search == "transducer_stream_beam":
-        max_frames = max([1] + [-(-task.frontend.num_frames(len(w)) // se.stride) for w in waves])
         dec = StreamingTransducerFrameBeamDecoder(model, dictionary, max_streams=streams, max_frames=max_frames, **stream_beam)
         strip = dec.symbols_to_strip_from_output
         partial_of = lambda part: part[:2]  # noqa: E731

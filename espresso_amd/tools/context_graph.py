@@ -177,10 +177,13 @@ class ContextGraph:
         return running, final, q
 
     def cuda(self, device=None):
-        """Upload the packed tables once; returns (nodes, edges, root) device tensors."""
+        """Upload the packed tables once per device; returns (nodes, edges, root) device tensors.  No device, or a bare "cuda",
+        is the current device: the cache is keyed on the resolved one."""
         import torch
 
-        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        device = torch.device("cuda" if device is None else device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
         if self._dev is None or self._dev[0].device != device:
             self._dev = tuple(torch.from_numpy(a).to(device) for a in (self.nodes, self.edges, self.root))
         return self._dev

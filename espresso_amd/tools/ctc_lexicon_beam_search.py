@@ -25,9 +25,10 @@ from typing import Dict, List
 import torch
 
 from .. import kernels as K
+from .beam_common import BeamDecoderMixin, hyps_from_tensors
 
 
-class CTCLexiconBeamSearchDecoder:
+class CTCLexiconBeamSearchDecoder(BeamDecoderMixin):
     MAX_BEAM = 64
 
     def __init__(self, models, dictionary, ngram_lm, lexicon, beam_size=10, nbest=1, beam_size_token=None, lm_weight=2.0,
@@ -84,22 +85,11 @@ class CTCLexiconBeamSearchDecoder:
         lprobs = self.model.get_normalized_probs(net_output, log_probs=True)  # T x B x V view of [B][T][V]
         return self.search(lprobs.transpose(0, 1), net_output["src_lengths"][0])
 
-    @torch.no_grad()
-    def decode(self, models, sample, **kwargs):
-        """(1-best tokens B x U padded with pad, scores B (-inf: no hypothesis), None) — the validation-time API of CTCDecoder."""
-        tokens, lengths, scores, _ = self._generate(sample)
-        U = max(1, int(lengths[:, 0].max()))
-        return tokens[:, 0, :U].to(torch.long), scores[:, 0], None
+    @staticmethod
+    def _empty_hypothesis():
+        """What an utterance with nothing finite gets, so that it is still printed and scored."""
+        return {"tokens": torch.zeros(0, dtype=torch.long), "score": torch.tensor(float("-inf")), "attention": None, "alignment": None}
 
     @torch.no_grad()
     def generate(self, models, sample, **kwargs) -> List[List[Dict[str, torch.Tensor]]]:
-        tokens, lengths, scores, nhyp = (t.cpu() for t in self._generate(sample))
-        out = []
-        for b in range(tokens.shape[0]):
-            hyps = [{"tokens": tokens[b, i, : int(lengths[b, i])].to(torch.long), "score": scores[b, i], "attention": None,
-                     "alignment": None} for i in range(int(nhyp[b]))]
-            if not hyps:  # nothing finite: an empty hypothesis, so that the utterance is still printed and scored
-                hyps = [{"tokens": torch.zeros(0, dtype=torch.long), "score": torch.tensor(float("-inf")), "attention": None,
-                         "alignment": None}]
-            out.append(hyps)
-        return out
+        return [hyps or [self._empty_hypothesis()] for hyps in hyps_from_tensors(*(t.cpu() for t in self._generate(sample)))]

@@ -22,9 +22,10 @@ from typing import Dict, List
 import torch
 
 from .. import kernels as K
+from .beam_common import BeamDecoderMixin, hyps_from_tensors, step_triple
 
 
-class CTCPrefixBeamSearchDecoder:
+class CTCPrefixBeamSearchDecoder(BeamDecoderMixin):
     MAX_BEAM = 64
 
     def __init__(self, models, dictionary, beam_size=10, nbest=1, beam_size_token=None, lm_model=None, lm_weight=0.0,
@@ -52,35 +53,14 @@ class CTCPrefixBeamSearchDecoder:
         if context_graph is not None and context_graph.vocab_size != V:
             raise ValueError(f"CTC prefix beam search: context graph built for {context_graph.vocab_size} tokens, dictionary has {V}")
         self.context_graph = context_graph
-        self._graph_dev = None
 
     def cuda(self):
         self.model.cuda()
         if self.lm_model is not None:
             self.lm_model.cuda()
         if self.context_graph is not None:
-            self._graph_dev = self.context_graph.cuda()
+            self.context_graph.cuda()  # uploaded once per device; `search` uploads when this was not called
         return self
-
-    # ---------------------------------------------------------------- LM state of the beams
-    def _lm_rows(self, feat):
-        logits = self.lm_model.decoder.output_layer(feat)
-        return K.log_softmax(logits, logits.shape[0], logits.shape[1], logits.stride(0))
-
-    def lm_start(self, N, device):
-        """LSTM state and log-prob rows fp32 [N][V] of N empty hypotheses (the LM's eos as BOS)."""
-        lmd = self.lm_model.decoder
-        state = lmd.init_state(N, device)
-        feat, state = lmd.advance(torch.full((N,), self.eos, dtype=torch.int32, device=device), state)
-        return state, self._lm_rows(feat)
-
-    def lm_update(self, state, parent, token, keep):
-        """After one step: every row continues row `parent` of the previous frame; rows with keep == 0 appended `token`, the
-        others keep their parent's LM state (and so recompute its row)."""
-        lmd = self.lm_model.decoder
-        state = lmd.reorder_state(state, parent)
-        feat, state = lmd.advance(token, state, keep_row=keep)
-        return state, self._lm_rows(feat)
 
     # ---------------------------------------------------------------- the search
     @torch.no_grad()
@@ -98,9 +78,7 @@ class CTCPrefixBeamSearchDecoder:
             ws = K.ctc_prefix_beam_workspace(B, T, beam, dev)
             beam_step, beam_finish = K.ctc_prefix_beam_step, K.ctc_prefix_beam_finish
         else:
-            if self._graph_dev is None or self._graph_dev[0].device != dev:  # uploaded once (here when `cuda()` was not called)
-                self._graph_dev = self.context_graph.cuda(dev)
-            graph = self._graph_dev
+            graph = self.context_graph.cuda(dev)
             ws = K.ctc_prefix_beam_bias_workspace(B, T, beam, dev)
 
             def beam_step(x, in_len, ws, **kw):
@@ -113,8 +91,7 @@ class CTCPrefixBeamSearchDecoder:
             return beam_finish(ws, B, T, beam, self.nbest, self.pad, ins_bonus=self.insertion_bonus)
         N = B * beam
         state, rows = self.lm_start(N, dev)
-        lm_out = (torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
-                  torch.empty(N, dtype=torch.uint8, device=dev))
+        lm_out = step_triple(N, dev)
         if T == 0:
             beam_step(x, in_len, ws, t0=0, t1=0, **step)
         for t in range(T):
@@ -130,14 +107,5 @@ class CTCPrefixBeamSearchDecoder:
         return self.search(lprobs.transpose(0, 1), net_output["src_lengths"][0])
 
     @torch.no_grad()
-    def decode(self, models, sample, **kwargs):
-        """(1-best tokens B x U padded with pad, scores B, None) — the validation-time API of CTCDecoder."""
-        tokens, lengths, scores, _ = self._generate(sample)
-        U = max(1, int(lengths[:, 0].max()))
-        return tokens[:, 0, :U].to(torch.long), scores[:, 0], None
-
-    @torch.no_grad()
     def generate(self, models, sample, **kwargs) -> List[List[Dict[str, torch.Tensor]]]:
-        tokens, lengths, scores, nhyp = (t.cpu() for t in self._generate(sample))
-        return [[{"tokens": tokens[b, i, : int(lengths[b, i])].to(torch.long), "score": scores[b, i], "attention": None,
-                  "alignment": None} for i in range(int(nhyp[b]))] for b in range(tokens.shape[0])]
+        return hyps_from_tensors(*(t.cpu() for t in self._generate(sample)))

@@ -1,38 +1,35 @@
 """StreamingCTCPrefixBeamDecoder — the CTC prefix beam search of tools/ctc_prefix_beam_search.py (CTCPrefixBeamSearchDecoder,
 which stays as it is) over encoder frames that arrive a chunk at a time: alone, with shallow fusion of one sub-word LSTM LM,
 with hotword biasing (`context_graph`) or with both, with the interface of StreamingCTCLexiconBeamDecoder (`open`, `accept`,
-`accept_lprobs`, `partial`, `finish`, `close`) and partial results.  The streamed form is DESIGN.md section 3.4.
+`accept_lprobs`, `partial`, `finish`, `close`) and partial results.  The streamed form is DESIGN.md section 3.4; the slot pool
+and the rows a stream carries are those of tools/beam_common.py (StreamSlots, CarriedRows).
 
 Everything a stream carries lives on the device, allocated once: the search state (frame counter, beam, prefix table with its
-hash, the hypotheses' states in the context graph and running biases: `state_bytes_per_stream()` bytes in one of `max_streams`
-slots, csrc/ctc_beam.hip) and, with an LM, its LSTM state and log-prob row as rows slot * beam + beam slot of
-[max_streams * beam]-row tensors.  `open` only marks a slot; the reset kernel and the copy of the LM-start rows are enqueued
-before the next launch that needs them.
+hash, the hypotheses' states in the context graph and running biases: `state_bytes_per_stream()` bytes per slot,
+csrc/ctc_beam.hip) and, with an LM, its LSTM state and log-prob row, which start as the LM after its eos.
 
 Without an LM `accept_lprobs` is one launch (ea_ctc_prefix_beam_stream_step) for all the streams that got frames.  With one it
-uploads (slot, n_new, row_off) in one pinned copy, gathers the listed streams' LM rows into [n * beam]-row tensors and then per
-frame index j < max(counts): the step of frame j, `lm_update(state, parent, token, keep)` — the loop of the offline decoder;
-the rows go back to their slots after the last frame.  A stream with fewer frames than j gets the identity triple from the step
-(its rows keep their state, as a finished utterance's do offline), so nothing is read back and nothing synchronises.  The
-per-frame code is the offline kernel's (one body, two wrappers), so `close` returns, bit for bit, what
-CTCPrefixBeamSearchDecoder.search returns for the whole utterance, whatever the pieces and whatever `max_frames`.
+gathers the listed streams' LM rows and then per frame index j < max(counts): the step of frame j, `lm_update(state, parent,
+token, keep)` — the loop of the offline decoder; the rows go back to their slots after the last frame.  A stream with fewer
+frames than j gets the identity triple from the step (its rows keep their state, as a finished utterance's do offline), so
+nothing is read back and nothing synchronises.  The per-frame code is the offline kernel's (one body, two wrappers), so `close`
+returns, bit for bit, what CTCPrefixBeamSearchDecoder.search returns for the whole utterance, whatever the pieces and whatever
+`max_frames`.
 
 `partial` reads, per stream, the hypothesis the beam currently ranks first (its in-beam score: LM and running bias included,
 the LM's end-of-sentence term and the bias still pending not) and the stable prefix: the tokens shared by every live hypothesis
 with a finite score.  Every later hypothesis with a finite score is a stay or an extension of one of those (a merge lands on
-the extension of one), so the stable tokens never change again.
-
-The prefix table of a slot is sized for `max_frames` encoder frames; a stream that would pass it is refused before anything
-is launched."""
+the extension of one), so the stable tokens never change again."""
 from typing import Dict, List
 
 import torch
 
 from .. import kernels as K
+from .beam_common import CarriedRows, StreamSlots, hyps_from_tensors, step_triple
 from .ctc_prefix_beam_search import CTCPrefixBeamSearchDecoder
 
 
-class StreamingCTCPrefixBeamDecoder:
+class StreamingCTCPrefixBeamDecoder(StreamSlots):
     def __init__(self, dictionary, max_streams, max_frames, beam_size=10, nbest=1, beam_size_token=None, lm_model=None, lm_weight=0.0,
                  insertion_bonus=0.0, blank=None, context_graph=None):
         # validation and defaults of the offline decoder
@@ -44,15 +41,10 @@ class StreamingCTCPrefixBeamDecoder:
         self.pad, self.eos, self.blank, self.vocab_size = o.pad, o.eos, o.blank, o.vocab_size
         self.beam_size, self.beam_size_token, self.nbest = o.beam_size, o.beam_size_token, o.nbest
         self.lm_weight, self.insertion_bonus = o.lm_weight, o.insertion_bonus
-        if max_streams < 1 or max_frames < 1:
-            raise ValueError(f"streaming CTC prefix beam search: max_streams {max_streams} and max_frames {max_frames} must be positive")
-        self.max_streams, self.max_frames = int(max_streams), int(max_frames)
+        StreamSlots.__init__(self, "streaming CTC prefix beam search", max_streams, max_frames)
         self._search = dict(max_frames=self.max_frames, V=o.vocab_size, beam=o.beam_size, K=o.beam_size_token, blank=o.blank,
                             ins_bonus=o.insertion_bonus)
-        self._free = list(range(self.max_streams - 1, -1, -1))
-        self.streams: Dict[object, list] = {}  # stream id -> [slot, frames consumed]
-        self._unreset: List[int] = []
-        self.state = self.graph = self.lm = self.lm_rows = None  # allocated on the device of the first frames
+        self.state = self.graph = self.lm = self.lm_rows = self._rows = None  # allocated on the device of the first frames
 
     def state_bytes_per_stream(self) -> int:
         from .. import _lib
@@ -67,26 +59,12 @@ class StreamingCTCPrefixBeamDecoder:
         self.state, _ = K.ctc_prefix_beam_stream_state(self.max_streams, self.max_frames, self.beam_size, device)
         if self.context_graph is not None:
             self.graph = self.context_graph.cuda(device)
-        self.lm = self.lm_rows = None
         if self.lm_model is not None:
             R = self.max_streams * self.beam_size
-            self._start = self.offline.lm_start(1, device)
+            start_state, start_rows = self.offline.lm_start(1, device)
             self.lm = self.lm_model.decoder.init_state(R, device)
-            self.lm_rows = self._start[1].new_zeros(R, self._start[1].shape[1])
-            self._beam_ar = torch.arange(self.beam_size, dtype=torch.int32, device=device)
-
-    def _ints(self, values, device):
-        host = torch.tensor(values, dtype=torch.int32)
-        if device.type == "cuda":
-            host = host.pin_memory()
-        return host.to(device, non_blocking=True)
-
-    def _carried(self):
-        """(tensor of [max_streams * beam] rows, its start row) pairs of what a stream carries besides the search state."""
-        return [(t, s) for k in self.lm for t, s in zip(self.lm[k], self._start[0][k])] + [(self.lm_rows, self._start[1])]
-
-    def _rows_of(self, slots):
-        return (slots.unsqueeze(1) * self.beam_size + self._beam_ar.unsqueeze(0)).reshape(-1)
+            self.lm_rows = start_rows.new_zeros(R, start_rows.shape[1])
+            self._rows = CarriedRows(self.beam_size, self.max_streams, [(self.lm, start_state), (self.lm_rows, start_rows)])
 
     def _ensure(self, device):
         """Buffers on `device`; slots opened since the last launch are reset and get their LM-start rows (kernels, no
@@ -98,9 +76,7 @@ class StreamingCTCPrefixBeamDecoder:
             slots = self._ints(self._unreset, device)
             K.ctc_prefix_beam_stream_reset(self.state, slots, self.max_frames, self.beam_size)
             if self.lm is not None:
-                rows = self._rows_of(slots).long()
-                for t, s in self._carried():
-                    t.index_copy_(0, rows, s.expand(rows.numel(), -1))
+                self._rows.reset(slots)
             self._unreset = []
         return device
 
@@ -112,21 +88,6 @@ class StreamingCTCPrefixBeamDecoder:
         return torch.device("cuda", torch.cuda.current_device())
 
     # ---- the streaming interface -----------------------------------------------------------------------------------------
-    def open(self, stream_ids):
-        for sid in stream_ids:
-            if sid in self.streams:
-                raise ValueError(f"stream {sid!r} is already open")
-            if not self._free:
-                raise RuntimeError(f"all {self.max_streams} stream slots are in use")
-            slot = self._free.pop()
-            self.streams[sid] = [slot, 0]
-            self._unreset.append(slot)
-
-    def _check_room(self, stream_ids, counts):
-        for sid, c in zip(stream_ids, counts):
-            if self.streams[sid][1] + int(c) > self.max_frames:
-                raise ValueError(f"stream {sid!r}: {self.streams[sid][1]} + {int(c)} encoder frames exceed max_frames {self.max_frames}")
-
     @torch.no_grad()
     def accept(self, stream_ids, logits, counts):
         """logits [sum counts][>=V] (StreamingEncoder output, stream by stream): log-softmax, then `accept_lprobs`."""
@@ -139,51 +100,32 @@ class StreamingCTCPrefixBeamDecoder:
     @torch.no_grad()
     def accept_lprobs(self, stream_ids, lprobs, counts):
         """lprobs fp32/bf16 [sum counts][V] log-probs, packed stream by stream in the order of stream_ids.  Nothing is read back."""
-        counts = [int(c) for c in counts]
-        assert len(stream_ids) == len(counts) and len(set(stream_ids)) == len(stream_ids) and lprobs.shape[0] == sum(counts)
-        self._check_room(stream_ids, counts)
-        ready, r = [], 0
-        for sid, c in zip(stream_ids, counts):
-            if c > 0:
-                ready.append((self.streams[sid], c, r))
-            r += c
+        ready, meta = self._pack(stream_ids, counts, lprobs)
         if not ready:
             return
         dev = self._ensure(lprobs.device)
-        n, Tm, beam = len(ready), max(c for _, c, _ in ready), self.beam_size
-        meta = self._ints([st[0] for st, _, _ in ready] + [c for _, c, _ in ready] + [o for _, _, o in ready], dev).view(3, n)
+        Tm = max(c for _, c, _ in ready)
         if self.lm is None:
             K.ctc_prefix_beam_stream_step(lprobs, meta, self.state, graph=self.graph, j0=0, j1=Tm, **self._search)
         else:
-            rows = self._rows_of(meta[0]).contiguous()
-            lm_state = {k: [K.gather_rows(t, rows) for t in v] for k, v in self.lm.items()}
-            lm_rows = K.gather_rows(self.lm_rows, rows)
-            lm_out = (torch.empty(n * beam, dtype=torch.int32, device=dev), torch.empty(n * beam, dtype=torch.int32, device=dev),
-                      torch.empty(n * beam, dtype=torch.uint8, device=dev))
+            rows = self._rows.rows_of(meta[0])
+            lm_state, lm_rows = self._rows.gather(rows)
+            lm_out = step_triple(len(ready) * self.beam_size, dev)
             for j in range(Tm):
                 K.ctc_prefix_beam_stream_step(lprobs, meta, self.state, graph=self.graph, j0=j, j1=j + 1, lm_rows=lm_rows,
                                               lm_weight=self.lm_weight, lm_out=lm_out, **self._search)
                 lm_state, lm_rows = self.offline.lm_update(lm_state, *lm_out)
-            rows = rows.long()
-            for k, v in self.lm.items():
-                for t, new in zip(v, lm_state[k]):
-                    t.index_copy_(0, rows, new)
-            self.lm_rows.index_copy_(0, rows, lm_rows)
-        for st, c, _ in ready:
-            st[1] += c
-
-    def _max_u(self, stream_ids):
-        return max([1] + [self.streams[sid][1] for sid in stream_ids])
+            self._rows.scatter(rows, [lm_state, lm_rows])
+        self._advance(ready)
 
     @torch.no_grad()
     def finish(self, stream_ids, nbest=None, max_u=None):
         """Device tensors (tokens int32 [n][nbest][U], lengths, scores, nhyp) of the streams as if they ended now; their
         state is left as it is."""
-        dev = self._ensure(self._device())
-        slots = self._ints([self.streams[sid][0] for sid in stream_ids], dev)
+        slots = self._slots_of(stream_ids, self._ensure(self._device()))
         lm = {}
         if self.lm is not None:
-            lm = dict(lm_rows=K.gather_rows(self.lm_rows, self._rows_of(slots).contiguous()), lm_weight=self.lm_weight, eos=self.eos)
+            lm = dict(lm_rows=K.gather_rows(self.lm_rows, self._rows.rows_of(slots)), lm_weight=self.lm_weight, eos=self.eos)
         return K.ctc_prefix_beam_stream_finish(self.state, slots, self.max_frames, self.beam_size, self.nbest if nbest is None else nbest,
                                                self.pad, self._max_u(stream_ids) if max_u is None else max_u, graph=self.graph,
                                                ins_bonus=self.insertion_bonus, **lm)
@@ -191,8 +133,7 @@ class StreamingCTCPrefixBeamDecoder:
     @torch.no_grad()
     def partial_tensors(self, stream_ids, max_u=None):
         """Device tensors (tokens int32 [n][U], lengths, scores, stable_len) of the streams' best live hypotheses."""
-        dev = self._ensure(self._device())
-        slots = self._ints([self.streams[sid][0] for sid in stream_ids], dev)
+        slots = self._slots_of(stream_ids, self._ensure(self._device()))
         return K.ctc_prefix_beam_stream_partial(self.state, slots, self.max_frames, self.beam_size, self.pad,
                                                 self._max_u(stream_ids) if max_u is None else max_u,
                                                 lm_weight=self.lm_weight if self.lm is not None else 0.0, ins_bonus=self.insertion_bonus,
@@ -204,21 +145,12 @@ class StreamingCTCPrefixBeamDecoder:
         that every later result starts with.  One readback."""
         if not stream_ids:
             return []
-        U = self._max_u(stream_ids)
-        tokens, lengths, scores, stable = self.partial_tensors(stream_ids, max_u=U)
-        packed = torch.cat([tokens, lengths[:, None], stable[:, None], scores.view(torch.int32)[:, None]], dim=1).cpu()
-        out = []
-        for row in packed:
-            n, k = int(row[U]), int(row[U + 1])
-            toks = row[:n].tolist()
-            out.append({"tokens": toks, "stable": toks[:k], "score": float(row[U + 2:U + 3].view(torch.float32))})
-        return out
+        return [{"tokens": toks, "stable": toks[:k], "score": score}
+                for toks, k, score in self._read_partial(*self.partial_tensors(stream_ids))]
 
     @torch.no_grad()
     def close(self, sid) -> List[Dict[str, torch.Tensor]]:
         """Up to nbest finished hypotheses of a stream in the generators' format; its slot is free afterwards."""
-        tokens, lengths, scores, nhyp = (t.cpu() for t in self.finish([sid]))
-        slot, _ = self.streams.pop(sid)
-        self._free.append(slot)
-        return [{"tokens": tokens[0, i, : int(lengths[0, i])].to(torch.long), "score": scores[0, i], "attention": None,
-                 "alignment": None} for i in range(int(nhyp[0]))]
+        hyps = hyps_from_tensors(*(t.cpu() for t in self.finish([sid])))[0]
+        self._release(sid)
+        return hyps

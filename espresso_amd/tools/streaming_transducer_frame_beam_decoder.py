@@ -1,22 +1,21 @@
 """StreamingTransducerFrameBeamDecoder — the frame-synchronous transducer beam search of tools/transducer_frame_beam_decoder.py
 (TransducerFrameBeamDecoder, which stays as it is) over encoder frames that arrive a chunk at a time, with the interface of the
 other streaming decoders (`open`, `accept`, `partial`, `finish`, `close`), optional shallow fusion of one sub-word LSTM LM and
-partial results.  The contract is DESIGN.md section 3.5; the streamed form is section 3.4.
+partial results.  The contract is DESIGN.md section 3.5; the streamed form is section 3.4; the slot pool and the rows a stream
+carries are those of tools/beam_common.py (StreamSlots, CarriedRows).
 
 Everything a stream carries lives on the device, allocated once: the search state (beam, prefix table, frame counter:
-`state_bytes_per_stream()` bytes in one of `max_streams` slots, csrc/rnnt_beam.hip) and, as rows slot * beam + beam slot of
-[max_streams * beam]-row tensors, the predictor's LSTM state, the predictor's output row and, with an LM, its LSTM state and
-log-prob row.  `open` only marks a slot; the reset kernel and the copy of the `bos` / LM-start rows are enqueued before the
-next launch that needs them.
+`state_bytes_per_stream()` bytes per slot, csrc/rnnt_beam.hip), the predictor's LSTM state and output row, which start as the
+predictor after `bos`, and, with an LM, its LSTM state and log-prob row, which start as the LM after its eos.
 
-`accept` runs `joint_encoder_branch` on the packed rows once, uploads (slot, n_new, row_off) in one pinned copy, gathers the
-listed streams' predictor (and LM) rows into [n * beam]-row tensors, and then per frame index j < max(counts): gathers the
-frame's encoder rows (ea_gather_rows), `joint_step`, the step (ea_rnnt_frame_beam_stream_step), `reorder_state` +
-`advance(token, state, keep_row)` for the predictor (and the LM) — the loop of the offline decoder; the rows go back to their
-slots after the last frame.  A stream with fewer frames than j gets the identity triple from the step (its rows keep their
-state, as a finished utterance's do offline), so nothing is read back and nothing synchronises.  The per-frame code is the
-offline kernels': one body, wrapped once per search (the tests hold the two wrappers to each other bit for bit), so `close`
-returns what TransducerFrameBeamDecoder.search returns for the whole utterance, whatever the pieces.
+`accept` runs `joint_encoder_branch` on the packed rows once, gathers the listed streams' predictor (and LM) rows, and then per
+frame index j < max(counts): gathers the frame's encoder rows (ea_gather_rows), `joint_step`, the step
+(ea_rnnt_frame_beam_stream_step), `reorder_state` + `advance(token, state, keep_row)` for the predictor (and the LM) — the loop
+of the offline decoder; the rows go back to their slots after the last frame.  A stream with fewer frames than j gets the
+identity triple from the step (its rows keep their state, as a finished utterance's do offline), so nothing is read back and
+nothing synchronises.  The per-frame code is the offline kernels': one body, wrapped once per search (the tests hold the two
+wrappers to each other bit for bit), so `close` returns what TransducerFrameBeamDecoder.search returns for the whole utterance,
+whatever the pieces.
 
 `partial` reads, per stream, the live hypothesis with the best score and the stable prefix: the tokens shared by every live
 hypothesis.  Every later hypothesis is a stay or an extension of a live one (a merge lands on a live sequence), so the stable
@@ -25,19 +24,17 @@ tokens never change again.
 Hotword biasing: with `context_graph` (tools/context_graph.ContextGraph) the state, the reset, every step, the finish and the
 partial are those of the bias family (ea_rnnt_frame_beam_stream_bias_*): a slot also holds the automaton state and the running
 bias of every beam slot, `partial` returns the live hypothesis with the best score + running bias, and `close` returns what
-TransducerFrameBeamDecoder.search with the same graph returns.  The tables are uploaded once; the loop still reads nothing back.
-
-The prefix table of a slot is sized for `max_frames` encoder frames; a stream that would pass it is refused before anything
-is launched."""
+TransducerFrameBeamDecoder.search with the same graph returns.  The tables are uploaded once; the loop still reads nothing back."""
 from typing import Dict, List
 
 import torch
 
 from .. import kernels as K
+from .beam_common import CarriedRows, StreamSlots, hyps_from_tensors, step_triple
 from .transducer_frame_beam_decoder import TransducerFrameBeamDecoder
 
 
-class StreamingTransducerFrameBeamDecoder:
+class StreamingTransducerFrameBeamDecoder(StreamSlots):
     def __init__(self, model, dictionary, beam_size, max_streams, max_frames, nbest=1, beam_size_token=None, temperature=1.0,
                  normalize_scores=True, lm_model=None, lm_weight=0.0, model_predicts_eos=False, context_graph=None):
         # validation and defaults of the offline decoder
@@ -50,15 +47,10 @@ class StreamingTransducerFrameBeamDecoder:
         self.pad, self.blank, self.bos, self.eos, self.vocab_size = o.pad, o.blank, o.bos, o.eos, o.vocab_size
         self.beam_size, self.beam_size_token, self.nbest = o.beam_size, o.beam_size_token, o.nbest
         self.symbols_to_strip_from_output = o.symbols_to_strip_from_output
-        if max_streams < 1 or max_frames < 1:
-            raise ValueError(f"streaming transducer frame beam search: max_streams {max_streams} and max_frames {max_frames} must be positive")
-        self.max_streams, self.max_frames = int(max_streams), int(max_frames)
+        StreamSlots.__init__(self, "streaming transducer frame beam search", max_streams, max_frames)
         self._step = dict(max_frames=self.max_frames, V=o.vocab_size, beam=o.beam_size, K=o.beam_size_token, blank=o.blank,
                           eos=o.eos if o.model_predicts_eos else -1, temperature=o.temperature, lm_weight=o.lm_weight,
                           lm_no_blank=o.no_blank_in_lm)
-        self._free = list(range(self.max_streams - 1, -1, -1))
-        self.streams: Dict[object, list] = {}  # stream id -> [slot, frames consumed]
-        self._unreset: List[int] = []
         self.state = self.graph = None
         dev = next(self.model.parameters()).device if self.model is not None else None
         if dev is not None and dev.type == "cuda":
@@ -81,32 +73,16 @@ class StreamingTransducerFrameBeamDecoder:
         make_state = K.rnnt_frame_beam_stream_state if self.graph is None else K.rnnt_frame_beam_stream_bias_state
         self.state, _ = make_state(self.max_streams, self.max_frames, self.beam_size, device)
         out, st = dec.advance(torch.full((1,), self.bos, dtype=torch.int32, device=device), dec.init_state(1, device))
-        self._start = [st, out]
         self.pred = dec.init_state(R, device)
         self.pred_out = out.new_zeros(R, out.shape[1])
+        carried = [(self.pred, st), (self.pred_out, out)]
         self.lm = self.lm_rows = None
         if self.lm_model is not None:
             lst, lrows = self.offline.lm_start(1, device)
-            self._start += [lst, lrows]
             self.lm = self.lm_model.decoder.init_state(R, device)
             self.lm_rows = lrows.new_zeros(R, lrows.shape[1])
-        self._beam_ar = torch.arange(self.beam_size, dtype=torch.int32, device=device)
-
-    def _ints(self, values, device):
-        host = torch.tensor(values, dtype=torch.int32)
-        if device.type == "cuda":
-            host = host.pin_memory()
-        return host.to(device, non_blocking=True)
-
-    def _carried(self):
-        """(tensor of [max_streams * beam] rows, its start row) pairs of everything a stream carries besides the search state."""
-        pairs = [(t, s) for k in self.pred for t, s in zip(self.pred[k], self._start[0][k])] + [(self.pred_out, self._start[1])]
-        if self.lm is not None:
-            pairs += [(t, s) for k in self.lm for t, s in zip(self.lm[k], self._start[2][k])] + [(self.lm_rows, self._start[3])]
-        return pairs
-
-    def _rows_of(self, slots):
-        return (slots.unsqueeze(1) * self.beam_size + self._beam_ar.unsqueeze(0)).reshape(-1)
+            carried += [(self.lm, lst), (self.lm_rows, lrows)]
+        self._rows = CarriedRows(self.beam_size, self.max_streams, carried)
 
     def _ensure(self, device):
         """Buffers on `device`; slots opened since the last launch are reset and get their start rows (kernels, no
@@ -118,9 +94,7 @@ class StreamingTransducerFrameBeamDecoder:
             slots = self._ints(self._unreset, device)
             reset = K.rnnt_frame_beam_stream_reset if self.graph is None else K.rnnt_frame_beam_stream_bias_reset
             reset(self.state, slots, self.max_frames, self.beam_size)
-            rows = self._rows_of(slots).long()
-            for t, s in self._carried():
-                t.index_copy_(0, rows, s.expand(rows.numel(), -1))
+            self._rows.reset(slots)
             self._unreset = []
         return device
 
@@ -128,85 +102,43 @@ class StreamingTransducerFrameBeamDecoder:
         return self.state.device if self.state is not None else next(self.model.parameters()).device
 
     # ---- the streaming interface -----------------------------------------------------------------------------------------
-    def open(self, stream_ids):
-        for sid in stream_ids:
-            if sid in self.streams:
-                raise ValueError(f"stream {sid!r} is already open")
-            if not self._free:
-                raise RuntimeError(f"all {self.max_streams} stream slots are in use")
-            slot = self._free.pop()
-            self.streams[sid] = [slot, 0]
-            self._unreset.append(slot)
-
-    def _check_room(self, stream_ids, counts):
-        for sid, c in zip(stream_ids, counts):
-            if self.streams[sid][1] + int(c) > self.max_frames:
-                raise ValueError(f"stream {sid!r}: {self.streams[sid][1]} + {int(c)} encoder frames exceed max_frames {self.max_frames}")
-
     @torch.no_grad()
     def accept(self, stream_ids, enc_rows, counts):
         """enc_rows [sum counts][C]: new encoder frames, stream by stream in the order of stream_ids (StreamingEncoder's
         output); advances every stream over its frames.  Nothing is read back."""
-        counts = [int(c) for c in counts]
-        assert len(stream_ids) == len(counts) and len(set(stream_ids)) == len(stream_ids) and enc_rows.shape[0] == sum(counts)
-        self._check_room(stream_ids, counts)
-        ready, r = [], 0
-        for sid, c in zip(stream_ids, counts):
-            if c > 0:
-                ready.append((self.streams[sid], c, r))
-            r += c
+        ready, meta = self._pack(stream_ids, counts, enc_rows)
         if not ready:
             return
         model, dec, beam = self.model, self.model.decoder, self.beam_size
         dev = self._ensure(enc_rows.device)
         E = model.joint_encoder_branch(enc_rows.contiguous()).contiguous()
         n, Tm = len(ready), max(c for _, c, _ in ready)
-        meta = self._ints([st[0] for st, _, _ in ready] + [c for _, c, _ in ready] + [o for _, _, o in ready], dev).view(3, n)
         slot_idx, n_new, row_off = meta[0], meta[1], meta[2]
-        rows = self._rows_of(slot_idx).contiguous()
+        rows = self._rows.rows_of(slot_idx)
         # encoder row of every (frame index, listed stream, beam slot); past a stream's count its last row, never used
         frame = torch.minimum(torch.arange(Tm, dtype=torch.int32, device=dev).unsqueeze(1), (n_new - 1).unsqueeze(0))
         frame_rows = (row_off.unsqueeze(0) + frame).repeat_interleave(beam, dim=1).contiguous()  # [Tm][n * beam]
-        out = (torch.empty(n * beam, dtype=torch.int32, device=dev), torch.empty(n * beam, dtype=torch.int32, device=dev),
-               torch.empty(n * beam, dtype=torch.uint8, device=dev))
-        state = {k: [K.gather_rows(t, rows) for t in v] for k, v in self.pred.items()}
-        dec_out = K.gather_rows(self.pred_out, rows)
-        lm_state = lm_rows = None
-        if self.lm is not None:
-            lm_state = {k: [K.gather_rows(t, rows) for t in v] for k, v in self.lm.items()}
-            lm_rows = K.gather_rows(self.lm_rows, rows)
+        out = step_triple(n * beam, dev)
+        state, dec_out, *lm = self._rows.gather(rows)  # lm: (LSTM state, log-prob rows) with an LM
         for j in range(Tm):
             logits = model.joint_step(K.gather_rows(E, frame_rows[j]), dec_out)
+            lm_rows = lm[1] if lm else None
             if self.graph is None:
                 K.rnnt_frame_beam_stream_step(logits, slot_idx, n_new, j, self.state, out, lm_rows=lm_rows, **self._step)
             else:
                 K.rnnt_frame_beam_stream_bias_step(logits, slot_idx, n_new, j, self.state, self.graph, out, lm_rows=lm_rows, **self._step)
             state = dec.reorder_state(state, out[0])
             dec_out, state = dec.advance(out[1], state, keep_row=out[2])
-            if self.lm is not None:
-                lm_state, lm_rows = self.offline.lm_update(lm_state, *out)
-        rows = rows.long()
-        for k, v in self.pred.items():
-            for t, new in zip(v, state[k]):
-                t.index_copy_(0, rows, new)
-        self.pred_out.index_copy_(0, rows, dec_out)
-        if self.lm is not None:
-            for k, v in self.lm.items():
-                for t, new in zip(v, lm_state[k]):
-                    t.index_copy_(0, rows, new)
-            self.lm_rows.index_copy_(0, rows, lm_rows)
-        for st, c, _ in ready:
-            st[1] += c
-
-    def _max_u(self, stream_ids):
-        return max([1] + [self.streams[sid][1] for sid in stream_ids])
+            if lm:
+                lm = self.offline.lm_update(lm[0], *out)
+        self._rows.scatter(rows, [state, dec_out, *lm])
+        self._advance(ready)
 
     @torch.no_grad()
     def finish_tensors(self, stream_ids, nbest=None, max_u=None):
         """Device tensors (tokens int32 [n][nbest][U], lengths, scores, nhyp) of the streams as if they ended now; their
         state is left as it is."""
-        dev = self._ensure(self._device())
-        slots = self._ints([self.streams[sid][0] for sid in stream_ids], dev)
+        slots = self._slots_of(stream_ids, self._ensure(self._device()))
         args = (self.max_frames, self.beam_size, self.nbest if nbest is None else nbest, self.pad,
                 self._max_u(stream_ids) if max_u is None else max_u)
         if self.graph is None:
@@ -216,8 +148,7 @@ class StreamingTransducerFrameBeamDecoder:
     @torch.no_grad()
     def partial_tensors(self, stream_ids, max_u=None):
         """Device tensors (tokens int32 [n][U], lengths, scores, stable_len) of the streams' best live hypotheses."""
-        dev = self._ensure(self._device())
-        slots = self._ints([self.streams[sid][0] for sid in stream_ids], dev)
+        slots = self._slots_of(stream_ids, self._ensure(self._device()))
         partial = K.rnnt_frame_beam_stream_partial if self.graph is None else K.rnnt_frame_beam_stream_bias_partial
         return partial(self.state, slots, self.max_frames, self.beam_size, self.pad, self._max_u(stream_ids) if max_u is None else max_u)
 
@@ -227,22 +158,16 @@ class StreamingTransducerFrameBeamDecoder:
         those every later result starts with.  One readback."""
         if not stream_ids:
             return []
-        U = self._max_u(stream_ids)
-        tokens, lengths, scores, stable = self.partial_tensors(stream_ids, max_u=U)
-        packed = torch.cat([tokens, lengths[:, None], stable[:, None], scores.view(torch.int32)[:, None]], dim=1).cpu()
-        return [(row[: int(row[U])].tolist(), int(row[U + 1]), float(row[U + 2:U + 3].view(torch.float32))) for row in packed]
+        return self._read_partial(*self.partial_tensors(stream_ids))
 
     @torch.no_grad()
     def finish(self, sid) -> List[Dict[str, torch.Tensor]]:
         """Up to nbest hypotheses of a stream in the generators' format, as if it ended now; the stream goes on."""
-        tokens, lengths, scores, nhyp = (t.cpu() for t in self.finish_tensors([sid]))
-        return [{"tokens": tokens[0, i, : int(lengths[0, i])].to(torch.long), "score": scores[0, i], "attention": None,
-                 "alignment": None} for i in range(int(nhyp[0]))]
+        return hyps_from_tensors(*(t.cpu() for t in self.finish_tensors([sid])))[0]
 
     @torch.no_grad()
     def close(self, sid) -> List[Dict[str, torch.Tensor]]:
         """`finish`, and the stream's slot is free afterwards."""
         hyps = self.finish(sid)
-        slot, _ = self.streams.pop(sid)
-        self._free.append(slot)
+        self._release(sid)
         return hyps

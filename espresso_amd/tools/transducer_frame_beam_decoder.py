@@ -21,9 +21,10 @@ from typing import Dict, List
 import torch
 
 from .. import kernels as K
+from .beam_common import BeamDecoderMixin, hyps_from_tensors, step_triple
 
 
-class TransducerFrameBeamDecoder:
+class TransducerFrameBeamDecoder(BeamDecoderMixin):
     MAX_BEAM = 64
 
     def __init__(self, models, dictionary, beam_size=5, nbest=1, beam_size_token=None, temperature=1.0, normalize_scores=True,
@@ -72,7 +73,6 @@ class TransducerFrameBeamDecoder:
         if context_graph is not None and context_graph.vocab_size != V:
             raise ValueError(f"transducer frame beam search: context graph built for {context_graph.vocab_size} tokens, dictionary has {V}")
         self.context_graph = context_graph
-        self._graph_dev = None
 
     def cuda(self):
         self.model.cuda()
@@ -82,37 +82,11 @@ class TransducerFrameBeamDecoder:
 
     def graph_tables(self, device):
         """The context graph's device tables (uploaded once per device), or None without a graph."""
-        if self.context_graph is None:
-            return None
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:  # "cuda" is the current device: the cache is keyed on the resolved one
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self._graph_dev is None or self._graph_dev[0].device != device:
-            self._graph_dev = self.context_graph.cuda(device)
-        return self._graph_dev
+        return self.context_graph.cuda(device) if self.context_graph is not None else None
 
-    # ---------------------------------------------------------------- LM state of the beams
     def _lm_tokens(self, tokens):
+        """The LM's ids: its dictionary may be the model's without the blank."""
         return torch.where(tokens > self.blank, tokens - 1, tokens) if self.no_blank_in_lm else tokens
-
-    def _lm_rows(self, feat):
-        logits = self.lm_model.decoder.output_layer(feat)
-        return K.log_softmax(logits, logits.shape[0], logits.shape[1], logits.stride(0))
-
-    def lm_start(self, N, device):
-        """LSTM state and log-prob rows fp32 [N][V or V - 1] of N empty hypotheses (the LM's eos as BOS)."""
-        lmd = self.lm_model.decoder
-        state = lmd.init_state(N, device)
-        feat, state = lmd.advance(self._lm_tokens(torch.full((N,), self.eos, dtype=torch.int32, device=device)), state)
-        return state, self._lm_rows(feat)
-
-    def lm_update(self, state, parent, token, keep):
-        """After one step: every row continues row `parent` of the previous frame; rows with keep == 0 appended `token`, the
-        others keep their parent's LM state (and so recompute its row)."""
-        lmd = self.lm_model.decoder
-        state = lmd.reorder_state(state, parent)
-        feat, state = lmd.advance(self._lm_tokens(token), state, keep_row=keep)
-        return state, self._lm_rows(feat)
 
     # ---------------------------------------------------------------- the search
     @torch.no_grad()
@@ -129,8 +103,7 @@ class TransducerFrameBeamDecoder:
         # everything the loop needs, allocated before it: the encoder rows of every (frame, slot), the triples, the workspace
         rows = (torch.arange(B, device=dev, dtype=torch.int32) * Tp).repeat_interleave(beam)
         frame_rows = (rows.unsqueeze(0) + torch.arange(Tp, device=dev, dtype=torch.int32).unsqueeze(1)).contiguous()  # [T'][N]
-        out = (torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
-               torch.empty(N, dtype=torch.uint8, device=dev))
+        out = step_triple(N, dev)
         graph = self.graph_tables(dev)
         ws = K.rnnt_frame_beam_workspace(B, Tp, beam, dev) if graph is None else K.rnnt_frame_beam_bias_workspace(B, Tp, beam, dev)
         state = dec.init_state(N, dev)
@@ -169,14 +142,5 @@ class TransducerFrameBeamDecoder:
         return self.search(*self.encode(sample), bos_token=bos_token)
 
     @torch.no_grad()
-    def decode(self, models, sample, **kwargs):
-        """(1-best tokens B x U padded with pad, scores B, None) — the validation-time API of the transducer decoders."""
-        tokens, lengths, scores, _ = self._generate(sample)
-        U = max(1, int(lengths[:, 0].max()))
-        return tokens[:, 0, :U].to(torch.long), scores[:, 0], None
-
-    @torch.no_grad()
     def generate(self, models, sample, **kwargs) -> List[List[Dict[str, torch.Tensor]]]:
-        tokens, lengths, scores, nhyp = (t.cpu() for t in self._generate(sample, bos_token=kwargs.get("bos_token", None)))
-        return [[{"tokens": tokens[b, i, : int(lengths[b, i])].to(torch.long), "score": scores[b, i], "attention": None,
-                  "alignment": None} for i in range(int(nhyp[b]))] for b in range(tokens.shape[0])]
+        return hyps_from_tensors(*(t.cpu() for t in self._generate(sample, bos_token=kwargs.get("bos_token", None))))
