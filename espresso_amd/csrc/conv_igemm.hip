@@ -254,8 +254,6 @@ struct ConvWgradArgs {
   int at, af, ntaps;
   int bt[9], bf[9];
   int chunks_per_wg;   // 64-position chunks per workgroup
-  int ablate;          // development probe (EA_CONVW_ABLATE, results meaningless): 1 no MFMAs, 2 no global loads after the prologue,
-                       // 4 no fragment reads, 8 no barrier
 };
 
 __device__ __forceinline__ int tr_sw(int r) { return (r & 3) ^ ((r >> 3) & 1); }
@@ -272,20 +270,16 @@ __device__ __forceinline__ void ds_read_tr16_x8(const uint32_t (&ad)[8], uint2 (
       : "memory");
 }
 
-// NT = taps per workgroup: 9 (a workgroup owns all nine taps of its 64 x 64 channel tile: 144 accumulator registers, two workgroups
-// per CU) or 3 (one kernel row; blockIdx.z % 3 picks it: 48 accumulators, four workgroups per CU — round 6, see the launcher)
-template <int DEPTH, int NT>
-__global__ __launch_bounds__(256, NT == 9 ? 2 : 4) void conv_wgrad_kernel(const ConvWgradArgs a) {
+// A workgroup owns the three taps of one kernel row of its 64 x 64 channel tile (blockIdx.z % 3 picks the row): 48 accumulator
+// registers, four workgroups per CU (round 6, see the launcher)
+__global__ __launch_bounds__(256, 4) void conv_wgrad_kernel(const ConvWgradArgs a) {
   constexpr int TILE = 64 * ROW_BYTES;  // 8 KiB: 64 position rows x 64 channels
-  // Ring: two dZ tiles (a chunk's tile serves its nine taps) + four X tiles, loads issued THREE steps ahead (round 6).  Rounds 2 - 5
-  // double-buffered the X tile and waited for vmcnt(0) at every step: 8 MFMAs per wavefront (~150 cycles) between a load's issue and
-  // its wait against ~2 us of last-level-cache latency — 222 us per launch, 9 % of the MFMA peak, 8 KB in flight per workgroup.
-  // (DEPTH = 1: the round 2 - 5 schedule, kept as the A/B reference: EA_CONV_WGRAD_DEPTH=1)
-  constexpr int NBUF = DEPTH == 1 ? 2 : 4;
-  static_assert(DEPTH >= 1 && DEPTH <= 3 && (NT == 9 || NT == 3), "ring of two / four X tiles");
-  const int tap0 = NT == 9 ? 0 : (int)(blockIdx.z % 3) * 3;          // first tap of this workgroup
-  const int zsplit = NT == 9 ? (int)blockIdx.z : (int)(blockIdx.z / 3);  // which slab / which range of chunks
-  __shared__ __attribute__((aligned(16))) char lds[(2 + NBUF) * TILE];  // [A0][A1][B0][B1][B2][B3]
+  // Ring: two dZ tiles (a chunk's tile serves its three taps) + two X tiles, loads issued one step ahead and waited for with
+  // vmcnt(0) at every step; the four co-resident workgroups hide the latency
+  constexpr int NT = 3, NBUF = 2;
+  const int tap0 = (int)(blockIdx.z % 3) * 3;  // first tap of this workgroup
+  const int zsplit = (int)(blockIdx.z / 3);    // which slab / which range of chunks
+  __shared__ __attribute__((aligned(16))) char lds[(2 + NBUF) * TILE];  // [A0][A1][B0][B1]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;  // wave tile: cout rows wr*32.., cin cols wc*32..
   const int co0 = blockIdx.x * 64, ci0 = blockIdx.y * 64;
@@ -375,47 +369,30 @@ __global__ __launch_bounds__(256, NT == 9 ? 2 : 4) void conv_wgrad_kernel(const 
   long ich = 0;
   auto issue_next = [&]() {
     if (is >= nsteps) return;
-    if (!(a.ablate & 2) || is < DEPTH) {
-      if (itap == 0) {
-        decode(ich);
-        issue_A((int)(ich & 1));
-      }
-      issue_B(is & (NBUF - 1), itap);
+    if (itap == 0) {
+      decode(ich);
+      issue_A((int)(ich & 1));
     }
+    issue_B(is & (NBUF - 1), itap);
     ++is;
     if (++itap == NT) { itap = 0; ++ich; }
   };
-#pragma unroll
-  for (int d = 0; d < DEPTH; ++d) issue_next();
+  issue_next();
   uint4 fa[2][2];  // dZ fragments of the current chunk: [ksub][cout tile]
   long ch = 0;
   int tap = 0;
   for (int s = 0; s < nsteps; ++s) {
-    // instructions issued after this step's X tile: the X tiles of the next two steps (2 each) + the dZ tile of a chunk one of
-    // them opens (2)
-    const int tap1 = tap + 1 == NT ? 0 : tap + 1, tap2 = tap1 + 1 == NT ? 0 : tap1 + 1;
-    int pend = 0;
-    if (DEPTH >= 2 && s + 1 < nsteps) pend += 2 + (tap1 == 0 ? 2 : 0);
-    if (DEPTH >= 3 && s + 2 < nsteps) pend += 2 + (tap2 == 0 ? 2 : 0);
-    if (pend >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (pend == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if (pend == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if (pend == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (!(a.ablate & 8)) __builtin_amdgcn_s_barrier();  // this step's tiles are complete in every wavefront's part; everyone is done with step s - 1's X tile
+    const int tap1 = tap + 1 == NT ? 0 : tap + 1;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // nothing is issued after this step's X tile
+    __builtin_amdgcn_s_barrier();  // this step's tiles are complete in every wavefront's part; everyone is done with step s - 1's X tile
     uint4 fb[2][2];
-    if (!(a.ablate & 4) || s == 0) {
-      if (tap == 0) read_frags((int)(ch & 1) * TILE, wr * 32, fa);
-      read_frags((2 + (s & (NBUF - 1))) * TILE, wc * 32, fb);
-    } else {
-      fb[0][0] = fb[0][1] = fb[1][0] = fb[1][1] = fa[0][0];
-    }
+    if (tap == 0) read_frags((int)(ch & 1) * TILE, wr * 32, fa);
+    read_frags((2 + (s & (NBUF - 1))) * TILE, wc * 32, fb);
     __builtin_amdgcn_sched_barrier(0);
-    // step s + 3 goes into the ring slot step s - 1 used (free since the barrier above); a dZ tile goes into the slot chunk ch - 1
-    // used, whose fragments every wavefront copied to registers eight or more steps ago
+    // step s + 1 goes into the ring slot step s - 1 used (free since the barrier above); a dZ tile goes into the slot chunk ch - 1
+    // used, whose fragments every wavefront copied to registers two or more steps ago
     issue_next();
     // acc[tap] += dZ_tile^T X_tile   (static tap index: the accumulators are registers)
-    if (!(a.ablate & 1)) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       if (t == tap) {
@@ -429,9 +406,6 @@ __global__ __launch_bounds__(256, NT == 9 ? 2 : 4) void conv_wgrad_kernel(const 
                   __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, fa[ks][i]),
                   __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, fb[ks][j]), acc[t][i][j], 0, 0, 0);
       }
-    }
-    } else {
-      acc[0][0][0][0] += __uint_as_float(fb[0][0].x) + __uint_as_float(fb[1][1].y);  // (keep the fragment reads alive)
     }
     tap = tap1;
     if (tap1 == 0) ++ch;
@@ -496,7 +470,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __r
 static int wgrad_split(long M, int Cin, int Cout) {
   const long chunks = (M + 63) / 64;
   const int blocks = (Cin / 64) * (Cout / 64);
-  static const long target = [] { const char* e = getenv("EA_CONV_WGRAD_WGS"); const long v = e ? atol(e) : 0; return v > 0 ? v : 256L; }();  // (tuning knob)
+  constexpr long target = 256;
   // 256 x 3 tap groups = 3 workgroups per CU in total.  512 (round 5, before the tap groups) and 1024 measure +0.07 ms per step, 128 the
   // same as 256 (profiles/r06_side_kernel_grids_ab.txt): beside the compute queue a side-queue kernel should not claim every CU
   long nsplit = (target + blocks - 1) / blocks;
@@ -604,27 +578,13 @@ static int conv3x3_wgrad_impl(const void* X, const void* dZ, float* dW, void* wo
   const int nsplit = wgrad_split(M, Cin, Cout);
   const long chunks = (M + 63) / 64;
   a.chunks_per_wg = (int)((chunks + nsplit - 1) / nsplit);
-  static const int ablate = [] { const char* e = getenv("EA_CONVW_ABLATE"); return e ? atoi(e) : 0; }();  // (development probe)
-  a.ablate = ablate;
-  // ring depth by shape (round 6, isolated at the recipe batch, us per call incl. the slab reduce, depth 1 / 3): conv 2 (64 -> 64
-  // channels, 520 k positions) 236 / 215, conv 3 (64 -> 128) 281 / 308, conv 4 (128 -> 128, 130 k positions) 174 / 178 — the kernel is
-  // bound by its LDS fragment reads and the barrier per tap, not by load latency; only the 64-output-channel shape gains
-  static const int depth_env = [] { const char* e = getenv("EA_CONV_WGRAD_DEPTH"); return e ? atoi(e) : 0; }();  // (diagnostic A/B switch)
-  const int depth = depth_env ? depth_env : (Cout <= 64 ? 3 : 1);
   // Taps per workgroup (round 6).  The kernel is bound by how many bytes its workgroups keep in flight against the ~2 - 3 us of a
   // last-level-cache / HBM read: TCC counters say the L2 misses are the compulsory ones (310 MB per launch, 46 % hit rate = the
-  // tap re-reads), 1.35 TB/s; the ablation (profiles/r06_conv_wgrad_ablation.txt) gives 299 us -> 176 without the global loads,
-  // 286 without the MFMAs.  Nine taps per workgroup = 144 accumulator registers = two workgroups per CU; three taps per
-  // workgroup = four per CU with the same 64 x 64 tile, the X band re-read by the three tap-row workgroups out of L2.
-  static const int taps_env = [] { const char* e = getenv("EA_CONV_WGRAD_TAPS"); return e ? atoi(e) : 0; }();  // (diagnostic A/B switch)
-  // isolated, us per call incl. the slab reduce, 9 / 3 taps per workgroup: conv 2 224 / 198, conv 3 297 / 271, conv 4 178 / 149;
-  // update step, same box, interleaved: 13.74 / 13.48 and 13.64 / 13.61 ms (profiles/r06_conv_wgrad_taps_ab.txt) -> 3 by default
-  const int taps = taps_env == 3 || taps_env == 9 ? taps_env : 3;
-  if (taps == 3) {
-    hipLaunchKernelGGL((conv_wgrad_kernel<1, 3>), dim3(Cout / 64, Cin / 64, nsplit * 3), dim3(256), 0, stream, a);
-  } else if (depth == 1) hipLaunchKernelGGL((conv_wgrad_kernel<1, 9>), dim3(Cout / 64, Cin / 64, nsplit), dim3(256), 0, stream, a);
-  else if (depth == 2) hipLaunchKernelGGL((conv_wgrad_kernel<2, 9>), dim3(Cout / 64, Cin / 64, nsplit), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((conv_wgrad_kernel<3, 9>), dim3(Cout / 64, Cin / 64, nsplit), dim3(256), 0, stream, a);
+  // tap re-reads), 1.35 TB/s.  Three taps per workgroup = four workgroups per CU on a 64 x 64 tile, the X band re-read by the three
+  // tap-row workgroups out of L2.  Isolated, us per call incl. the slab reduce, against nine taps per workgroup (two per CU): conv 2
+  // 198 / 224, conv 3 271 / 297, conv 4 149 / 178; update step, same box, interleaved: 13.48 / 13.74 and 13.61 / 13.64 ms
+  // (profiles/r06_conv_wgrad_taps_ab.txt).  Every shape runs the one-step-ahead ring: a deeper ring only paid with nine taps.
+  hipLaunchKernelGGL(conv_wgrad_kernel, dim3(Cout / 64, Cin / 64, nsplit * 3), dim3(256), 0, stream, a);
   const long n = (long)Cout * 9 * Cin;
   const long blocks = (n / 4 + 255) / 256;
   int zg = (int)(1024 / blocks);  // ~1024 workgroups in all

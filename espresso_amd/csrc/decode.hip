@@ -330,10 +330,9 @@ extern "C" int ea_decode_attention_probs(const void* q, const void* K, const voi
   if (dh > 64 || max_len <= 0) return -2;
   const size_t lds = (size_t)4 * ((max_len + 63) / 64 * 64) * sizeof(float);
   if (lds > 64 * 1024) return -3;
-  static const int vec_on = [] { const char* e = getenv("EA_DECODE_ATTN_VEC"); return e ? atoi(e) : 1; }();  // (diagnostic A/B switch)
   const bool aligned = ((ldq | row_stride | ldkv | koff | voff) & 7) == 0 &&
                        ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-  if (vec_on && aligned && (dh == 64 || dh == 32 || dh == 16)) {
+  if (aligned && (dh == 64 || dh == 32 || dh == 16)) {
     const dim3 grid((N * H + 3) / 4), block(256);
 #define EA_DA(D) hipLaunchKernelGGL(decode_attention_vec_kernel<D>, grid, block, lds, stream, (const bf16_t*)q, (const bf16_t*)K, (const bf16_t*)V, \
                                     kv_row, len, (bf16_t*)out, N, H, ldq, row_stride, ldkv, koff, voff, max_len, probs, ldp)

@@ -21,8 +21,6 @@
 
 #include "espresso_amd.h"
 
-void ea_gemm_corun_hint(int on);  // gemm.hip: the launches that follow share the device with side-stream work
-
 namespace {
 
 struct Arena {
@@ -240,8 +238,7 @@ struct G {
   // columns [0, n) leave as the attention kernels' query operands: q_u = (q + pos_u) * s, q_v = (q + pos_v) * s (no launch of
   // ea_relpos_q_prep); false when the shape does not qualify (the caller then runs ea_relpos_q_prep)
   bool qsplit(void* q_u, void* q_v, const float* pos_u, const float* pos_v, int n, long ld_q, float s) {
-    static const bool off = getenv("EA_NO_QSPLIT") != nullptr;  // (diagnostic A/B switch)
-    if (off || n % 128 || p.N % 8) return false;
+    if (n % 128 || p.N % 8) return false;
     p.q_u = q_u; p.q_v = q_v; p.pos_u = pos_u; p.pos_v = pos_v; p.qsplit_n = n; p.ld_q = ld_q; p.qscale = s;
     return true;
   }
@@ -251,11 +248,7 @@ struct G {
   }
 };
 
-inline void gemm(Ctx& c, G& g) {
-  if (!c.dry && c.rc == 0) ea_gemm_corun_hint(c.overlap || c.df != nullptr);
-  RUN(ea_gemm_bf16(&g.p, c.s));
-  if (!c.dry) ea_gemm_corun_hint(0);
-}
+inline void gemm(Ctx& c, G& g) { RUN(ea_gemm_bf16(&g.p, c.s)); }
 inline void gemm_on(Ctx& c, G& g, hipStream_t st) { RUN(ea_gemm_bf16(&g.p, st)); }
 
 // dW[N_out][K_in] += dy^T x (and dbias[N_out] += column sums of dy).  Deferred mode: one more problem of the layer's grouped
@@ -480,7 +473,6 @@ static void ffn_bwd(Ctx& c, const FfnSaved& f, const EaLayerShape& sh, const EaF
 
 // saved layout of the attention block is produced by the same get<> sequence in fwd and bwd
 static bool g_flash = true;
-static bool g_flash_bits_side = [] { const char* e = getenv("EA_FLASH_BITS_INLINE"); return !(e && e[0] == '1'); }();
 // fused (flash) attention: head dim 64 and no additive attention mask; decided from the shape alone so that the saved
 // layout of forward and backward agree
 static inline bool attn_fused(const EaLayerShape& sh) {
@@ -527,7 +519,7 @@ static AttnSaved attn_saved(Arena& sv, const EaLayerShape& sh) {
 // side stream first waits for the main stream — an earlier backward may still be reading the buffer.  true: launched.
 static bool keep_bits_on_side(Ctx& c, const AttnSaved& a, const EaLayerShape& sh, uint64_t seed, const EaAttnParams* w = nullptr,
                               const void* pe = nullptr) {
-  if (!(a.bits && attn_fused(sh) && !c.dry && c.rc == 0 && g_flash_bits_side && side_init(c.s))) return false;
+  if (!(a.bits && attn_fused(sh) && !c.dry && c.rc == 0 && side_init(c.s))) return false;
   hipEvent_t e0 = g_side.ev[g_side.next];
   g_side.next = (g_side.next + 1) % 32;
   if (hipEventRecord(e0, c.s) != hipSuccess || hipStreamWaitEvent(g_side.stream, e0, 0) != hipSuccess) c.rc = -1;
@@ -661,8 +653,7 @@ static void attn_bwd_tail(Ctx& c, const AttnSaved& a, const EaLayerShape& sh, co
     // dppT32[h*dh + d][r] += sum_m qv[m][h*dh + d] * dBD[h][m][r] is a "weight gradient" with dy = the head's 64 qv columns,
     // x = the head's dBD slab (both [reduction rows][columns] as they lie in memory: global_load_lds + transposing LDS reads
     // instead of the register-transposed split-K GEMM + slab reduce: 75 -> ~25 us per layer on the side stream)
-    static const bool gpp_grouped = getenv("EA_GPP_SPLITK") == nullptr;  // (diagnostic A/B switch)
-    const bool in_group = c.df && gpp_grouped && dh % 64 == 0 && c.df->grp.count + H + 3 <= EA_WGRAD_MAX;
+    const bool in_group = c.df && dh % 64 == 0 && c.df->grp.count + H + 3 <= EA_WGRAD_MAX;
     if (in_group) {
       for (int h = 0; h < H; ++h) {
         EaWgradProblem& q = c.df->grp.p[c.df->grp.count++];
@@ -733,13 +724,12 @@ static void attn_bwd(Ctx& c, const AttnSaved& a, const EaLayerShape& sh, const E
     uint16_t* t2 = sc.get<uint16_t>((size_t)M * C);
     uint16_t* dBD = sc.get<uint16_t>((size_t)Z * T * Rp);
     float* Dd = sc.get<float>((size_t)Z * T);
-    static const bool fused_dq = getenv("EA_NO_FUSED_DQ") == nullptr;  // (diagnostic A/B switch)
     RUN(ea_flash_attention_bwd(a.qu, sh.pos_mode == 1 ? a.qu : a.qv, C, a.qkv + C, a.qkv + 2 * C, 3 * C,
                                sh.pos_mode == 1 ? (const uint16_t*)pe : a.pp, C, key_len, a.o, dO, C, a.lse, Dd, t1, t2, C, dBD,
                                Rp, dqkv + C, dqkv + 2 * C, 3 * C, H, B, T, T, dh, (sh.scratch_clean && c.overlap) ? 2 : 0, scaling, seed + kProbs,
                                drop_thr(sh.p_attn),
-                               drop_scale(sh.p_attn), a.bits, fused_dq ? dqkv : nullptr, 3 * C, c.s));  // dq = t1 + t2 -> q third of dqkv
-    attn_bwd_tail(c, a, sh, w, gw, x, dy, dx, pe, dqkv, t1, t2, dBD, wqkvt, next, dpe, fused_dq);
+                               drop_scale(sh.p_attn), a.bits, dqkv, 3 * C, c.s));  // dq = t1 + t2 -> q third of dqkv
+    attn_bwd_tail(c, a, sh, w, gw, x, dy, dx, pe, dqkv, t1, t2, dBD, wqkvt, next, dpe, true);
     release(c, mark);
     return;
   }
@@ -845,8 +835,7 @@ static void conv_fwd(Ctx& c, const ConvSaved& s, const EaLayerShape& sh, const E
   gemm(c, g1);
   // BatchNorm batch statistics: fp64 (sum, sum of squares) accumulators; mean / rstd, the running statistics and the normalised
   // activation come out of ONE launch behind the depthwise kernel (no fill, no finalize launch)
-  static const bool bn_fused = getenv("EA_BN_UNFUSED") == nullptr;  // (diagnostic A/B switch)
-  const bool ring = sh.training && bn_fused && C <= 2048;  // (same decision in the sizing pass: the arena walk must not differ)
+  const bool ring = sh.training && C <= 2048;  // (same decision in the sizing pass: the arena walk must not differ)
   BnRing* R = nullptr;
   if (ring && !c.dry && c.rc == 0 && !(R = bn_ring(c.s, C))) c.rc = -1;
   double* stats = nullptr;
@@ -894,8 +883,7 @@ static void conv_bwd(Ctx& c, const ConvSaved& s, const EaLayerShape& sh, const E
   dgrad(c, g, w.pw2, pw2t, dH, M, C, C);
   // BatchNorm backward: the two per-channel sums go to a buffer the previous call's apply kernel cleared; the apply kernel adds
   // the BatchNorm parameter gradients itself (no fill launch, no bn_param_grad launch)
-  static const bool bn_fused = getenv("EA_BN_UNFUSED") == nullptr;  // (diagnostic A/B switch)
-  const bool ring = bn_fused && C <= 2048;
+  const bool ring = C <= 2048;
   BnRing* R = nullptr;
   if (ring && !c.dry && c.rc == 0 && !(R = bn_ring(c.s, C))) c.rc = -1;
   float* red = nullptr;
@@ -909,9 +897,9 @@ static void conv_bwd(Ctx& c, const ConvSaved& s, const EaLayerShape& sh, const E
   if (ring) {
     if (R && c.rc == 0) {
       red = R->red[R->ri];
-      // BatchNorm reduce, then ONE kernel: BatchNorm apply folded into the GLU / depthwise data gradient's tile staging
-      RUN(ea_bn_glu_dwconv_bwd_fused(s.Z, dH, s.mr, w.bn_g, w.bn_b, red, dZ, gw.bn_g, gw.bn_b, EA_ACT_SILU, sh.training, R->red[R->ri ^ 1],
-                                     2 * R->cap, s.Y, w.dw, dY, B, T, C, sh.KW, c.s));
+      RUN(ea_bn_act_bwd_fused(s.Z, dH, s.mr, w.bn_g, w.bn_b, red, dZ, gw.bn_g, gw.bn_b, M, C, EA_ACT_SILU, sh.training, R->red[R->ri ^ 1],
+                              2 * R->cap, c.s));
+      RUN(ea_glu_dwconv_bwd(dZ, s.Y, nullptr, w.dw, dY, nullptr, nullptr, B, T, C, sh.KW, c.s));
       if (c.rc == 0) R->ri ^= 1;
       else R->dirty = true;
     }
@@ -973,10 +961,8 @@ static int layer_fwd(Ctx& c, const EaConformerLayer* L, const EaLayerShape& sh, 
   const uint64_t seed = sh.seed;
   const EaLayerChain* ch = c.chain;
   // the attention block's keep bits need nothing but the seed: launched now, they run under the first feed-forward block instead of
-  // beside the QKV projection that the attention kernel also waits for (EA_KEEP_BITS_EARLY=0: in the attention block, as before)
-  static const bool bits_early = [] { const char* e = getenv("EA_KEEP_BITS_EARLY"); return !(e && e[0] == '0'); }();
-  static const bool pp_early = [] { const char* e = getenv("EA_POS_PROJ_EARLY"); return !(e && e[0] == '0'); }();
-  if (bits_early) c.bits_early = keep_bits_on_side(c, S.at, sh, seed + kAttn, pp_early ? &L->attn : nullptr, pe);
+  // beside the QKV projection that the attention kernel also waits for; the positional-table projection goes with them
+  c.bits_early = keep_bits_on_side(c, S.at, sh, seed + kAttn, &L->attn, pe);
   ffn_fwd(c, S.f1, sh, L->ffn1, x_in, S.x1, seed + kFfn1, 0.5f, EA_ACT_SILU, ch && ch->ln1_done);
   attn_fwd(c, S.at, sh, L->attn, S.x1, S.x2, key_len, attn_mask, pe, seed + kAttn);
   conv_fwd(c, S.cv, sh, L->conv, S.x2, S.x3, seed + kConv);

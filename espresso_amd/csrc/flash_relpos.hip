@@ -150,18 +150,6 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 __device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
-// -DRP_PROF: s_memtime stamps at the phase boundaries of the backward kernels, per-wave sums written to a.prof and averaged on
-// the host by ea_rp_bwd (EA_RP_PROF=1).  Diagnostic only: the stamps wait for lgkmcnt and so add sync points of their own.
-#ifdef RP_PROF
-#define PROF_DECL unsigned long long prof_t = __builtin_amdgcn_s_memtime(); unsigned prof_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define PROF_MARK(k) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); prof_acc[k] += (unsigned)(n_ - prof_t); prof_t = n_; }
-#define PROF_DUMP(kern) if (a.prof && (threadIdx.x & 63) == 0) { unsigned long long* o_ = a.prof + ((long)(kern) * 8192 + (long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 10; for (int k_ = 0; k_ < 10; ++k_) o_[k_] = prof_acc[k_]; }
-#else
-#define PROF_DECL
-#define PROF_MARK(k)
-#define PROF_DUMP(kern)
-#endif
-
 struct LaneK {
   int lane, w, li, g4;
   uint32_t offk[2];  // k-contiguous fragment: row li (+16 rows = +2048 bytes), slot ks*4 + g4
@@ -584,14 +572,11 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_q_kernel(const FlashBwdArgs a) 
     if (DROP) piece_next = bitp[0];
   }
   int slot_lo = 0;
-  PROF_DECL
   for (int t = 0; t < nt; ++t) {
     const int j0 = t * TK;
     jcov = min(T, j0 + TK);
-    PROF_MARK(9)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    PROF_MARK(0)
     store_dbd();  // previous tile's rows
     const int slot_hi = slot_lo == 2 ? 0 : slot_lo + 1;
     const int slot_nx = slot_hi == 2 ? 0 : slot_hi + 1;
@@ -607,7 +592,6 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_q_kernel(const FlashBwdArgs a) 
       issue_img(st + IMG, srcV, j0 + TK, w, lane);
       issue_img(lds + PP_OFF + slot_nx * IMG, srcP, pbase + 64 * (t + 2), w, lane);
     }
-    PROF_MARK(1)
     const char* sK = lds + (t & 1) * 2 * IMG;
     const char* sV = sK + IMG;
     const char* blk_lo = lds + PP_OFF + slot_lo * IMG;
@@ -637,15 +621,12 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_q_kernel(const FlashBwdArgs a) 
         acc_dp[jt] = mfma32(fr[jt & 1][3], dO[1], acc_dp[jt]);
       }
     }
-    PROF_MARK(2)
     add_band(acc_s, qv, blk_lo, blk_hi, bd, L);
-    PROF_MARK(3)
     bf16x4_t dsb[4], pdb[4];
     softmax_bwd_tile<DROP, false>(acc_s, acc_dp, dsb, pdb, lse2, Di, a.inv_keep, piece, ksh, kl - j0, g4);
-    PROF_MARK(4)
 
     // t1^T[d][i] += sum_j K^T[d][j] dS^T[j][i]
-    if (!(a.dbg & 4)) {
+    {
       bf16x8_t kf[8];
       tr_image(sK, L.tro, kf);
 #pragma unroll
@@ -655,7 +636,6 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_q_kernel(const FlashBwdArgs a) 
         for (int dt = 0; dt < 4; ++dt) acc_t1[dt] = mfma32(kf[dt * 2 + kb], db, acc_t1[dt]);
       }
     }
-    PROF_MARK(5)
     // un-skew: dBD^T[15 - i_w + j][i_w] = dS^T[j][i_w], kept as bf16 [row i_w][position c']
     wave_lds_sync();  // the skew reads above are done before the same bytes are rewritten
 #pragma unroll
@@ -668,7 +648,7 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_q_kernel(const FlashBwdArgs a) 
     }
     wave_lds_sync();
     // t2^T[d][i] += sum_c' PP^T[d][c0w + c'] dBD^T[c'][i] over the wave's 80 positions: 2 x 32 (permuted) + 16
-    if (!(a.dbg & 2)) {
+    {
       uint32_t ad[20];
       uint2 pf[20];
 #pragma unroll
@@ -698,12 +678,11 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_q_kernel(const FlashBwdArgs a) 
       for (int dt = 0; dt < 4; ++dt)
         acc_t2[dt] = mfma16(__builtin_bit_cast(bf16x4_t, pf[16 + dt]), __builtin_bit_cast(bf16x4_t, bl), acc_t2[dt]);
     }
-    PROF_MARK(6)
     // dBD[z][row][T-1-row + j] = dS[row][j]: lane = key, one 128-byte row segment per store instruction.  The values are only
     // READ here (two rows per register); the stores go out at the top of the next tile, ahead of its prefetch: vmcnt counts
     // loads and stores in one queue, so stores issued behind the prefetch would make the next `s_waitcnt vmcnt(0)` wait for
     // their write acknowledgements (11 % of the kernel in the s_memtime profile)
-    if (!(a.dbg & 1)) {
+    {
       const bf16_t* bs = ob + 15 + lane;
 #pragma unroll
       for (int k = 0; k < 8; ++k)
@@ -712,7 +691,6 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_q_kernel(const FlashBwdArgs a) 
     }
     wave_lds_sync();  // un-skew buffer reads done before the next tile's skew writes
     slot_lo = slot_hi;
-    PROF_MARK(7)
   }
   store_dbd();  // last tile
 
@@ -740,7 +718,6 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_q_kernel(const FlashBwdArgs a) 
       }
     }
   }
-  PROF_MARK(9)
   if (!a.dbd_prezeroed) {
     // columns of dBD no (row, key) pair of this workgroup wrote: r < T-1-row or r >= T-1-row + jcov
     for (int iw = 0; iw < 16; ++iw) {
@@ -760,8 +737,6 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_q_kernel(const FlashBwdArgs a) 
       }
     }
   }
-  PROF_MARK(8)
-  PROF_DUMP(0)
 }
 
 // ---- KV kernel: workgroup = (z, 64 keys), loop over query tiles -> dK, dV
@@ -846,13 +821,10 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_kv_kernel(const FlashBwdArgs a)
     row_loads(0, 0);
   }
   int slot_lo = 0;  // ring slot of block `it` (window rows 0..63); block it-1 (rows 64..127) sits one slot below
-  PROF_DECL
   for (int it = 0; it < nq; ++it) {
     const int i0 = it * TQ;
-    PROF_MARK(9)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // tile `it` landed; everyone is done with the exchange tiles of tile it-1
-    PROF_MARK(0)
     const int slot_hi = slot_lo == 0 ? 2 : slot_lo - 1;
     const int slot_nx = slot_lo == 2 ? 0 : slot_lo + 1;
     qv[0] = qv_next[0];
@@ -874,7 +846,6 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_kv_kernel(const FlashBwdArgs a)
       issue_img(st + IMG, srcG, i0 + TQ, w, lane);
       issue_img(lds + PP_OFF + slot_nx * IMG, srcP, pb0 - 64 * (it + 1), w, lane);
     }
-    PROF_MARK(1)
     const char* sQ = lds + (it & 1) * 2 * IMG;
     const char* sG = sQ + IMG;
     // phase 1: this wave's 16 rows x 64 keys
@@ -897,22 +868,17 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_kv_kernel(const FlashBwdArgs a)
         acc_s[jt] = mfma32(kf[jt][ks], qu[ks], acc_s[jt]);
         acc_dp[jt] = mfma32(vf[jt][ks], dO[ks], acc_dp[jt]);
       }
-    PROF_MARK(2)
     add_band(acc_s, qv, lds + PP_OFF + slot_lo * IMG, lds + PP_OFF + slot_hi * IMG, bd, L);
-    PROF_MARK(3)
     bf16x4_t dsb[4], pdb[4];
     softmax_bwd_tile<DROP, true>(acc_s, acc_dp, dsb, pdb, lse2, Di, a.inv_keep, piece, ksh, kl - j0, g4);
-    PROF_MARK(4)
     wave_lds_sync();  // skew reads done before the exchange tiles overwrite the buffer
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt) {
       *reinterpret_cast<bf16x4_t*>(exw + (exo ^ (jt << 5))) = dsb[jt];
       *reinterpret_cast<bf16x4_t*>(exw + 2048 + (exo ^ (jt << 5))) = pdb[jt];
     }
-    PROF_MARK(5)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // not __syncthreads(): that also waits for the prefetch (vmcnt)
     __builtin_amdgcn_s_barrier();
-    PROF_MARK(6)
     // phase 2: this wave's 16 keys, all 64 rows:  dK^T[d][j] += sum_i Qu^T[d][i] dS[i][j],  dV^T[d][j] += sum_i dO^T[d][i] Pd[i][j]
     {
       const uint32_t eb = lds_addr(exbase);
@@ -939,7 +905,6 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_kv_kernel(const FlashBwdArgs a)
       }
     }
     slot_lo = slot_nx;
-    PROF_MARK(7)
   }
   const int j = j0 + 16 * w + li;
   if (j < T) {
@@ -956,14 +921,12 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_kv_kernel(const FlashBwdArgs a)
       *reinterpret_cast<uint2*>(ov + dt * 16 + g4 * 4) = pk;
     }
   }
-  PROF_MARK(8)
-  PROF_DUMP(1)
 }
 
 }  // namespace
 
-// EA_FLASH_V1=1 (or ea_set_flash_relpos(0)): the general kernels of flash_attention.hip serve the encoder too (A/B runs, tests)
-static int g_rp_on = [] { const char* e = getenv("EA_FLASH_V1"); return e && e[0] == '1' ? 0 : 1; }();
+// ea_set_flash_relpos(0): the general kernels of flash_attention.hip serve the encoder too (A/B runs, tests)
+static int g_rp_on = 1;
 extern "C" int ea_set_flash_relpos(int on) {
   const int prev = g_rp_on;
   g_rp_on = on ? 1 : 0;
@@ -976,9 +939,9 @@ bool ea_rp_eligible(bool relpos, int T, int S, int causal, uint32_t thr, const v
 int ea_rp_keep_bits(uint16_t* bits, int H, int B, int T, uint64_t seed, uint32_t thr, hipStream_t stream) {
   const int nkt = (T + TK - 1) / TK;
   const long n = (long)H * B * nkt * (nkt * 64) * 4;
-  static const long cap = [] { const char* e = getenv("EA_KEEP_BITS_WGS"); return e ? atol(e) : 256L; }();  // (diagnostic override)
+  constexpr long cap = 256;
   long blocks = (n + 255) / 256;
-  if (cap > 0 && blocks > cap) blocks = cap;
+  if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(keep_bits_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, bits, seed, thr, H * B, T, nkt);
   return EA_CHECK_LAUNCH();
 }
@@ -990,20 +953,7 @@ int ea_rp_fwd(const FlashFwdArgs& a, hipStream_t stream) {
   return EA_CHECK_LAUNCH();
 }
 
-int ea_rp_bwd(const FlashBwdArgs& a_in, hipStream_t stream) {
-  static const int dbg = [] { const char* e = getenv("EA_RP_DBG"); return e ? atoi(e) : 0; }();
-  FlashBwdArgs a = a_in;
-  a.dbg = dbg;
-  a.prof = nullptr;
-#ifdef RP_PROF
-  static unsigned long long* prof_buf = nullptr;
-  static const int prof_on = [] { const char* e = getenv("EA_RP_PROF"); return e && e[0] == '1' ? 1 : 0; }();
-  if (prof_on) {
-    if (!prof_buf) hipMalloc(&prof_buf, 2 * 8192 * 10 * sizeof(unsigned long long));
-    hipMemsetAsync(prof_buf, 0, 2 * 8192 * 10 * sizeof(unsigned long long), stream);
-    a.prof = prof_buf;
-  }
-#endif
+int ea_rp_bwd(const FlashBwdArgs& a, hipStream_t stream) {
   const dim3 gq((unsigned)(a.nq * a.H * a.B)), gk((unsigned)(a.nk * a.H * a.B));
   if (a.thr) {
     hipLaunchKernelGGL(rp_bwd_q_kernel<true>, gq, dim3(256), 0, stream, a);
@@ -1012,32 +962,5 @@ int ea_rp_bwd(const FlashBwdArgs& a_in, hipStream_t stream) {
     hipLaunchKernelGGL(rp_bwd_q_kernel<false>, gq, dim3(256), 0, stream, a);
     hipLaunchKernelGGL(rp_bwd_kv_kernel<false>, gk, dim3(256), 0, stream, a);
   }
-#ifdef RP_PROF
-  if (a.prof) {
-    static int calls = 0;
-    if (++calls == 20) {  // one report, from a warm call
-      hipStreamSynchronize(stream);
-      static unsigned long long h[2 * 8192 * 10];
-      hipMemcpy(h, a.prof, sizeof(h), hipMemcpyDeviceToHost);
-      const char* names[2] = {"Q ", "KV"};
-      const int nw[2] = {(int)gq.x * 4, (int)gk.x * 4};
-      for (int k = 0; k < 2; ++k) {
-        double sum[10] = {0};
-        int cnt = 0;
-        for (int wv = 0; wv < nw[k] && wv < 8192; ++wv) {
-          const unsigned long long* o = h + ((long)k * 8192 + wv) * 10;
-          unsigned long long tot = 0;
-          for (int p = 0; p < 10; ++p) tot += o[p];
-          if (!tot) continue;
-          ++cnt;
-          for (int p = 0; p < 10; ++p) sum[p] += (double)o[p];
-        }
-        fprintf(stderr, "[rp prof] %s waves %d, mean s_memtime ticks per wave by phase:", names[k], cnt);
-        for (int p = 0; p < 10; ++p) fprintf(stderr, " p%d=%.0f", p, cnt ? sum[p] / cnt : 0.0);
-        fprintf(stderr, "\n");
-      }
-    }
-  }
-#endif
   return EA_CHECK_LAUNCH();
 }

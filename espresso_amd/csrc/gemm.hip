@@ -28,17 +28,9 @@
 
 // 8-wave large-tile kernels (gemm_w8.hip): takes the launch (returns 1) or leaves it to the kernels below (0)
 int ea_gemm_w8_try(const EaGemmParams& q, int nt_flag, hipStream_t stream, int* cfg_out);
-int ea_wgrad_w8_try(const EaWgradGroup& g, hipStream_t stream, int* grid_out, EaWgradGroup* rest);  // wgrad_w8.hip
-// Hint from the layer runtime (engine.hip): the launches that follow run NEXT TO side-stream work (the backward pass: grouped weight
-// gradients of 2 x 64 KB of LDS per CU).  A one-workgroup-per-CU kernel with 128 - 144 KB of LDS cannot share a CU with them: it
-// waits for both to drain and then keeps them out, so the 8-wave kernels, 10 - 15 % faster alone, lose in that half of the step
-// (round 5, same box: 14.18 ms per step with them everywhere, 13.91 without).  Thread-local: one host thread drives one stream.
-static thread_local int g_gemm_corun = 0;
-void ea_gemm_corun_hint(int on) { g_gemm_corun = on; }
-// 8-wave kernels for launches that share the device with side-queue work too (the backward's data-gradient chain): round 5 measured
-// them slower there, beside a chip-filling 4-wave weight-gradient launch; beside the 116-workgroup 8-wave one (round 6) they win:
-// 12.47 -> 12.35 ms per step (profiles/r06_side_kernel_grids_ab.txt).  EA_GEMM_W8_CORUN=0 restores the 4-wave choice.
-static const int g_w8_corun = [] { const char* e = getenv("EA_GEMM_W8_CORUN"); return e ? atoi(e) : 1; }();
+int ea_wgrad_w8_try(const EaWgradGroup& g, hipStream_t stream, int* grid_out);  // wgrad_w8.hip
+// (The 8-wave kernels are also chosen for launches that share the device with side-queue work, the backward's data-gradient chain:
+// beside the 116-workgroup 8-wave weight-gradient launch they win, 12.47 -> 12.35 ms per step, profiles/r06_side_kernel_grids_ab.txt.)
 
 namespace {
 
@@ -1064,17 +1056,16 @@ extern "C" int ea_set_gemm_variant(int v) {
 // direct-to-LDS ring kernel for launches with both operands k-contiguous: 0 off, 1 automatic ring depth (3 stages when at most
 // two workgroups land on a CU — long-K, few-tile launches such as the N = 512 projections, where a deeper ring replaces the
 // latency hiding of co-resident workgroups: 41 -> 33 us in the 12-layer FFN chain — else 2), 2..4 forced depth
-static int g_gemm_glds = [] { const char* e = getenv("EA_GEMM_GLDS"); return e ? atoi(e) : 1; }();  // (env: diagnostic override)
+static int g_gemm_glds = 1;
 extern "C" int ea_set_gemm_glds(int stages) {
   const int old = g_gemm_glds;
   g_gemm_glds = stages;
   return old;
 }
 // every operand of the epilogue whole and vector-accessible: the lean instantiation (see epilogue_chunk<FAST>)
-static int g_fast_epi = [] { const char* e = getenv("EA_GEMM_FAST_EPI"); return e ? atoi(e) : 1; }();  // (diagnostic A/B switch)
 static bool fast_epilogue_ok(const EaGemmParams& q) {
   auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  return g_fast_epi && !q.c_f32 && q.splitk == 1 && q.batch == 1 && !q.resid_f32 && q.N % 128 == 0 && (q.ldc & 7) == 0 && al(q.C) &&
+  return !q.c_f32 && q.splitk == 1 && q.batch == 1 && !q.resid_f32 && q.N % 128 == 0 && (q.ldc & 7) == 0 && al(q.C) &&
          ((q.sC_hi | q.sC_lo) & 7) == 0 && (!q.bias || al(q.bias)) &&
          (!q.aux || ((q.ldaux & 7) == 0 && al(q.aux) && ((q.sX_hi | q.sX_lo) & 7) == 0)) &&
          (!q.resid || ((q.ldr & 7) == 0 && al(q.resid) && ((q.sR_hi | q.sR_lo) & 7) == 0)) &&
@@ -1086,7 +1077,7 @@ static bool fast_epilogue_ok(const EaGemmParams& q) {
 // the columns N .. pitch - 1 of a row are padding, whatever lands there is never read
 static bool w8_ragged_ok(const EaGemmParams& q) {
   auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  return g_fast_epi && !q.c_f32 && q.splitk == 1 && q.batch == 1 && !q.resid && !q.aux && !q.C2 && !q.q_u && q.N % 4 == 0 &&
+  return !q.c_f32 && q.splitk == 1 && q.batch == 1 && !q.resid && !q.aux && !q.C2 && !q.q_u && q.N % 4 == 0 &&
          (q.ldc & 7) == 0 && q.ldc >= (q.N + 31) / 32 * 32 && al(q.C) && (!q.bias || al(q.bias));
 }
 template <int BM_, int NST>
@@ -1148,7 +1139,7 @@ extern "C" int ea_gemm_bf16(const EaGemmParams* pp, hipStream_t stream) {
   }
   // tile-height choice: 64-row tiles when 128-row tiles would leave the 256 CUs (x3 resident workgroups) under-filled
   const long tiles128 = (long)((q.N + BN - 1) / BN) * ((q.M + BM - 1) / BM) * q.batch * q.splitk;
-  static const long bm_thr = [] { const char* e = getenv("EA_GEMM_BM_THR"); return e ? atol(e) : 1536L; }();  // (diagnostic override)
+  constexpr long bm_thr = 1536;
   const bool bm64 = g_gemm_variant == 2 ? true : (g_gemm_variant == 1 ? false : (tiles128 < bm_thr));
   const int bm = bm64 ? 64 : BM;
   dim3 grid((q.N + BN - 1) / BN, (q.M + bm - 1) / bm, q.batch * q.splitk), block(256);
@@ -1169,7 +1160,7 @@ extern "C" int ea_gemm_bf16(const EaGemmParams* pp, hipStream_t stream) {
   }
   bool done = false;
   const bool kc_ok = glds_eligible(q);
-  if (kc_ok && (fast_epilogue_ok(q) || w8_ragged_ok(q)) && (!g_gemm_corun || g_w8_corun)) {  // one 512-thread workgroup per CU on a large tile when the grid fits the chip
+  if (kc_ok && (fast_epilogue_ok(q) || w8_ragged_ok(q))) {  // one 512-thread workgroup per CU on a large tile when the grid fits the chip
     int cfg = 0;
     if (ea_gemm_w8_try(q, nt_flag(q), stream, &cfg)) {
       done = true;
@@ -1216,7 +1207,7 @@ extern "C" int ea_gemm_bf16(const EaGemmParams* pp, hipStream_t stream) {
   return EA_CHECK_LAUNCH();
 }
 
-static int g_wgrad_tr = [] { const char* e = getenv("EA_WGRAD_TR"); return e ? atoi(e) : 1; }();
+static int g_wgrad_tr = 1;
 extern "C" int ea_set_wgrad_transposing_reads(int on) {
   const int old = g_wgrad_tr;
   g_wgrad_tr = on;
@@ -1239,8 +1230,7 @@ extern "C" int ea_wgrad_group(const EaWgradGroup* gp, hipStream_t stream) {
   // through the CU's LDS port per flop, which is what the co-running main-stream GEMMs are short of); the Transformer layer's
   // group of the enc-dec recipe (192 tiles) 13.10 vs 12.94 ms the other way round.  (Round 3 measured the same switch at
   // +-0.2 ms across boxes with the old forward kernels and left it off.)
-  static const int bm_env = [] { const char* e = getenv("EA_WGRAD_BM"); return e ? atoi(e) : 0; }();  // (diagnostic override)
-  static const long wgrad_bm_thr = [] { const char* e = getenv("EA_WGRAD_BM_THR"); return e ? atol(e) : 320L; }();  // (128-row tiles from here)
+  constexpr long wgrad_bm_thr = 320;  // (128-row tiles from here)
   auto aligned_for = [&](int bm) {
     // (a ragged last tile may read the columns up to the next tile boundary when the row pitch covers them: those products only
     // reach output rows / columns >= N / K, which are never stored)
@@ -1258,9 +1248,9 @@ extern "C" int ea_wgrad_group(const EaWgradGroup* gp, hipStream_t stream) {
     // the direct-to-LDS kernel needs whole tiles inside the row pitch: the preferred height first, then the other one (the
     // transducer's output layer, pitch 5056 = 79 x 64, has no whole 128-row tiling: it must not drop to the register-staged
     // kernel — 3.2 ms against 2.7 ms per batch — just because its group is large enough to prefer 128 rows)
-    bool tr64 = bm_env == 64 ? true : bm_env == 128 ? false : bm64;
+    bool tr64 = bm64;
     tr_ok = aligned_for(tr64 ? 64 : 128);
-    if (!tr_ok && bm_env == 0) {
+    if (!tr_ok) {
       tr64 = !tr64;
       tr_ok = aligned_for(tr64 ? 64 : 128);
     }
@@ -1291,21 +1281,13 @@ extern "C" int ea_wgrad_group(const EaWgradGroup* gp, hipStream_t stream) {
     hipEventRecord(pr.e0, stream);
   }
   // long reductions over chip-filling 256 x 256 tile grids (the transducer joint's slabs): the 8-wave kernel of wgrad_w8.hip
-  EaWgradGroup rest;
-  rest.count = 0;
-  if (const int took = ea_wgrad_w8_try(g, stream, nullptr, &rest)) {
+  if (ea_wgrad_w8_try(g, stream, nullptr)) {
     if (g_prof_on) {
-      for (int i = 0; i < rest.count; ++i) {  // (took == 2: the thin problems are accounted by the launch that does them)
-        pr.flops -= 2.0 * rest.p[i].M * (double)rest.p[i].N * rest.p[i].K;
-        pr.bytes -= 2.0 * rest.p[i].M * ((double)rest.p[i].N + rest.p[i].K) + 8.0 * rest.p[i].N * (double)rest.p[i].K;
-      }
       pr.bm64 = 108;
       hipEventRecord(pr.e1, stream);
       g_prof.push_back(pr);
     }
-    const int rc = EA_CHECK_LAUNCH();
-    if (took == 2 && rc == 0) return ea_wgrad_group(&rest, stream);  // (thin problems only: the 8-wave kernel declines them)
-    return rc;
+    return EA_CHECK_LAUNCH();
   }
   // rows 16-byte aligned and whole tiles readable everywhere: direct-to-LDS kernel with transposing fragment reads
   if (tr_ok) {

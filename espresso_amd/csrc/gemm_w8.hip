@@ -13,10 +13,9 @@
 // as the 4-wave kernels: outputs are bit-identical to theirs (checked by tests/test_gpu_parity.py).
 //
 // Where it is used (ea_gemm_w8_try; measurements in DESIGN.md 3.1b and profiles/r05_*): launches whose tile grid is ONE dispatch
-// round on the chip (128 < tiles <= 256: the encoder layers' forward products at M ~ 6 200 rows) while nothing else runs GEMMs
-// beside them (the layer runtime's co-run hint: backward keeps the 4-wave kernels, whose 24 - 72 KB workgroups still find room
-// next to a weight-gradient launch), and launches of >= 1 024 tiles with N >= 1 024 (the transducer joint's vocabulary projection,
-// also with a ragged N inside a padded row pitch).  8 - 24 % faster than the 4-wave kernels in isolation, 1.3 % of the update step:
+// round on the chip (128 < tiles <= 256: the encoder layers' products at M ~ 6 200 rows), and launches of >= 1 024 tiles with
+// N >= 1 024 (the transducer joint's vocabulary projection, also with a ragged N inside a padded row pitch).  8 - 24 % faster than
+// the 4-wave kernels in isolation, 1.3 % of the update step:
 // the step's GEMMs are bound by cold first tiles, the per-CU L2 -> LDS rate and lock-step epilogue writes, not by the k loop.
 #include "common.h"
 #include "espresso_amd.h"
@@ -26,8 +25,8 @@
 
 // 0 = never, 1 = automatic (default), 2 .. 5 = forced tile configuration (diagnostic): 2 = 256x256 / 2 stages, 3 = 128x128 / 4 stages,
 // 4 = 256x128 / 3 stages, 5 = 128x256 / 3 stages
-static int g_gemm_w8 = [] { const char* e = getenv("EA_GEMM_W8"); return e ? atoi(e) : 1; }();
-static long g_w8_many = [] { const char* e = getenv("EA_GEMM_W8_MANY"); return e ? atol(e) : 1024L; }();  // tiles from which "many rounds" applies
+static int g_gemm_w8 = 1;
+constexpr long kW8ManyTiles = 1024;  // tiles from which "many rounds" applies
 
 namespace {
 
@@ -362,8 +361,7 @@ int w8_kind(const EaGemmParams& q) {
   if (q.q_u) {
     // (measured in the step, round 5: 35.0 us against 31.5 us for the 4-wave kernel — this launch runs next to the side stream's
     // keep-bits kernel; the specialisation stays for forced configurations)
-    static const bool qs = [] { const char* e = getenv("EA_GEMM_W8_QSPLIT"); return e && e[0] == '1'; }();  // (A/B switch)
-    if (g_gemm_w8 == 1 && !qs) return -1;
+    if (g_gemm_w8 == 1) return -1;
     return (q.aux || q.C2 || q.resid || q.drop_thr || q.act != EA_ACT_NONE || q.out_scale != 1.f) ? -1 : W8_QSPLIT;
   }
   if (q.C2) return (q.aux || q.resid) ? -1 : W8_ACT2;
@@ -412,7 +410,7 @@ int ea_gemm_w8_try(const EaGemmParams& q, int nt_flag, hipStream_t stream, int* 
     // Many dispatch rounds (the transducer joint's vocabulary projection at 70 000 lattice rows: 5 480 tiles of 256 x 256): the round quantisation and the lock-step epilogues of the single-round case wash out, what counts is
     // operand bytes per flop — forward 722 -> 489 us isolated (profiles/r05_joint_gemm_probe.txt); the data gradient (N = 512,
     // K = 5056) gains nothing from any 8-wave tile (417 -> 406 .. 460 us) and stays with the 4-wave kernel
-    else if (rm256 * cn256 >= g_w8_many && q.N >= 1024) cfg = 2;
+    else if (rm256 * cn256 >= kW8ManyTiles && q.N >= 1024) cfg = 2;
     else return 0;
   }
   const int flags = 1 | nt_flag;

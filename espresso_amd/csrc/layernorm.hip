@@ -350,7 +350,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(
     const float* __restrict__ mean_in, const float* __restrict__ rstd_in, bf16_t* __restrict__ dx,
     float* __restrict__ dgamma, float* __restrict__ dbeta, int M, int C, int rows_per_block,
     const uint8_t* __restrict__ row_zero, uint64_t seed, uint32_t thr, float inv_keep,
-    const bf16_t* __restrict__ dx_add, float* __restrict__ partial, const LnOut2 o2, const int two_rows) {
+    const bf16_t* __restrict__ dx_add, float* __restrict__ partial, const LnOut2 o2) {
   extern __shared__ float red[];  // [4][2][C]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nch = C >> 3;
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(
       }
     }
   };
-  if (MAXC8 == 1 && two_rows) {
+  if (MAXC8 == 1) {
     // C <= 512: a wavefront's two rows of the block (r, r + 4) are in flight TOGETHER (round 6; the forward kernel's lesson,
     // ln_fwd_rows_kernel): one after the other, each row was a dependent load -> reduce -> reduce -> store chain, 11.5 us for the
     // recipe's 6 240 x 512 rows.  The rows are still accumulated in the same order: dgamma / dbeta partials are bit-identical.
@@ -652,14 +652,9 @@ extern "C" int ea_layernorm_fwd(const void* x, const float* gamma, const float* 
                                 float drop_scale, hipStream_t stream) {
   if (M <= 0) return 0;
   if (C % 8 != 0 || C > 64 * 8 * MAXC8_LIMIT) return -2;
-  static const int rw_mode = [] { const char* e = getenv("EA_LN_ROWS"); return e ? atoi(e) : 4; }();  // (diagnostic: 0 = one row per wave)
-  if (C <= 512 && M >= 2048 && rw_mode > 0) {
-    if (rw_mode >= 4)
-      hipLaunchKernelGGL((ln_fwd_rows_kernel<4>), dim3((M + 15) / 16), dim3(256), 0, stream, (const bf16_t*)x, gamma, beta, (bf16_t*)y, mean,
-                         rstd, M, C, eps, row_zero, drop_seed, drop_thr, drop_scale);
-    else
-      hipLaunchKernelGGL((ln_fwd_rows_kernel<2>), dim3((M + 7) / 8), dim3(256), 0, stream, (const bf16_t*)x, gamma, beta, (bf16_t*)y, mean,
-                         rstd, M, C, eps, row_zero, drop_seed, drop_thr, drop_scale);
+  if (C <= 512 && M >= 2048) {
+    hipLaunchKernelGGL((ln_fwd_rows_kernel<4>), dim3((M + 15) / 16), dim3(256), 0, stream, (const bf16_t*)x, gamma, beta, (bf16_t*)y, mean,
+                       rstd, M, C, eps, row_zero, drop_seed, drop_thr, drop_scale);
     return EA_CHECK_LAUNCH();
   }
   int fblocks = (M + 3) / 4;
@@ -714,12 +709,11 @@ static int ln_bwd_launch(const void* x, const void* dy, const float* gamma, cons
   if (C % 8 != 0 || C > 64 * 8 * MAXC8_LIMIT) return -2;
   const int rpb = ln_bwd_rows_per_block(M, workspace != nullptr);
   const int nblk = (M + rpb - 1) / rpb;
-  static const int two_rows = [] { const char* e = getenv("EA_LN_BWD_TWO_ROWS"); return e ? atoi(e) : 1; }();  // (diagnostic A/B switch)
   if (dy_f32) {
 #define EA_LN_BWD32(NC)                                                                                                \
   hipLaunchKernelGGL((ln_bwd_kernel<NC, float>), dim3(nblk), dim3(256), (size_t)8 * C * sizeof(float), stream,         \
                      (const bf16_t*)x, (const float*)dy, gamma, mean, rstd, (bf16_t*)dx, dgamma, dbeta, M, C, rpb,     \
-                     row_zero, drop_seed, drop_thr, drop_scale, (const bf16_t*)dx_add, (float*)workspace, o2, two_rows)
+                     row_zero, drop_seed, drop_thr, drop_scale, (const bf16_t*)dx_add, (float*)workspace, o2)
     if (C <= 512) EA_LN_BWD32(1);
     else if (C <= 1024) EA_LN_BWD32(2);
     else EA_LN_BWD32(4);
@@ -730,7 +724,7 @@ static int ln_bwd_launch(const void* x, const void* dy, const float* gamma, cons
 #define EA_LN_BWD(NC)                                                                                                  \
   hipLaunchKernelGGL((ln_bwd_kernel<NC>), dim3(nblk), dim3(256), (size_t)8 * C * sizeof(float), stream,                \
                      (const bf16_t*)x, (const bf16_t*)dy, gamma, mean, rstd, (bf16_t*)dx, dgamma, dbeta, M, C, rpb,    \
-                     row_zero, drop_seed, drop_thr, drop_scale, (const bf16_t*)dx_add, (float*)workspace, o2, two_rows)
+                     row_zero, drop_seed, drop_thr, drop_scale, (const bf16_t*)dx_add, (float*)workspace, o2)
   if (C <= 512) EA_LN_BWD(1);
   else if (C <= 1024) EA_LN_BWD(2);
   else EA_LN_BWD(4);
@@ -795,7 +789,7 @@ extern "C" int ea_layernorm_param_reduce_group(const EaLnReduceGroup* g, hipStre
     if (nblk > maxblk) maxblk = nblk;
   }
   if (n == 0) return 0;
-  static const int rs_cap = [] { const char* e = getenv("EA_LN_REDUCE_RS"); return e ? atoi(e) : 32; }();  // (tuning knob: row splits per item)
+  constexpr int rs_cap = 32;  // row splits per item
   int rs = maxblk / 32;
   if (rs < 1) rs = 1;
   if (rs > rs_cap) rs = rs_cap;

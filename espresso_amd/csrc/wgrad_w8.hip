@@ -20,7 +20,7 @@
 
 // 0 = never, 1 = automatic (default: groups that fill the chip with 256 x 256 tiles and reduce over >= 4096 rows), 2 = every
 // eligible group (tests, probes)
-static int g_wgrad_w8 = [] { const char* e = getenv("EA_WGRAD_W8"); return e ? atoi(e) : 1; }();
+static int g_wgrad_w8 = 1;
 
 namespace {
 
@@ -265,16 +265,10 @@ __device__ __forceinline__ void wg8_tile(const EaWgradGroup& g, const W8WgradTab
   }
 }
 
-// grid: 1-D, 512 threads, 128 KB of dynamic LDS (two stages).  gridDim.x == tb.start[EA_WGRAD_MAX] (the tile count): one tile per
-// workgroup.  A SMALLER grid (a multiple of 8, so that a workgroup's tiles stay on its XCD's range): every workgroup walks tiles
-// blockIdx.x, + gridDim.x, ... — for launches that run on a side queue beside the compute queue and should leave it most of the CUs.
+// grid: 1-D, 512 threads, 128 KB of dynamic LDS (two stages).  gridDim.x == tb.start[EA_WGRAD_MAX] (the tile count): one tile per workgroup.
 __global__ __launch_bounds__(512, 2) void wgrad_w8_kernel(const EaWgradGroup g, const W8WgradTable tb) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
-  const int total = tb.start[EA_WGRAD_MAX];
-  for (int vb = blockIdx.x; vb < total; vb += gridDim.x) {
-    if (vb != (int)blockIdx.x) __syncthreads();  // every wavefront is done reading the previous tile's last stage
-    wg8_tile(g, tb, vb, total, dsm);
-  }
+  wg8_tile(g, tb, blockIdx.x, tb.start[EA_WGRAD_MAX], dsm);
 }
 
 }  // namespace
@@ -285,31 +279,10 @@ extern "C" int ea_set_wgrad_w8(int mode) {
   return old;
 }
 
-static int wgrad_w8_launch(const EaWgradGroup& g, hipStream_t stream, int* grid_out, bool forced);
-// Called first by ea_wgrad_group.  Returns 1 when the group was launched here (*grid_out = workgroups), 0 to fall through, 2 when
-// only the THICK problems were launched here and `rest` received the thin ones (automatic mode, rest != NULL): a problem whose dW
-// has <= 64 rows (the per-head positional-projection gradients of an attention block: [64][2T'-1]) fills a quarter of a 256-row tile
-// and would hold a CU for the whole reduction all the same — 24 to 56 of a layer group's 116 to 148 workgroups; the 4-wave kernel
-// can do them on 64-row tiles in a second launch.
-int ea_wgrad_w8_try(const EaWgradGroup& g, hipStream_t stream, int* grid_out, EaWgradGroup* rest) {
+// Called first by ea_wgrad_group.  Returns 1 when the group was launched here (*grid_out = workgroups), 0 to fall through.
+int ea_wgrad_w8_try(const EaWgradGroup& g, hipStream_t stream, int* grid_out) {
   if (!g_wgrad_w8 || g.count <= 0) return 0;
-  // (A/B switch, default OFF: measured 12.41 / 12.43 vs 12.30 / 12.32 ms per step — the second launch walks the same 6 240 rows on a
-  // handful of workgroups and lengthens the side queue by more than the freed CUs give back; profiles/r06_side_kernel_grids_ab.txt)
-  static const bool split_thin = [] { const char* e = getenv("EA_WGRAD_W8_SPLIT_THIN"); return e && e[0] == '1'; }();
-  if (g_wgrad_w8 == 1 && rest && split_thin) {
-    EaWgradGroup thick;
-    thick.count = 0;
-    rest->count = 0;
-    for (int i = 0; i < g.count; ++i) {
-      if (g.p[i].N <= 64) rest->p[rest->count++] = g.p[i];
-      else thick.p[thick.count++] = g.p[i];
-    }
-    if (thick.count == 0) return 0;  // nothing but thin problems: not this kernel's case
-    if (rest->count > 0) return wgrad_w8_launch(thick, stream, grid_out, false) ? 2 : 0;
-  }
-  return wgrad_w8_launch(g, stream, grid_out, g_wgrad_w8 == 2);
-}
-static int wgrad_w8_launch(const EaWgradGroup& g, hipStream_t stream, int* grid_out, bool forced) {
+  const bool forced = g_wgrad_w8 == 2;
   W8WgradTable tb;
   int total = 0;
   long min_rows = 1L << 40;
@@ -329,11 +302,11 @@ static int wgrad_w8_launch(const EaWgradGroup& g, hipStream_t stream, int* grid_
   // runs next to it (gemm_glds 18 -> 50 us).  On 116 CUs, one workgroup each, with a third of the operand traffic, the same group
   // leaves 140 CUs to the compute queue: config 3 12.89 -> 12.49 ms per step, config 2 12.91 -> 12.63 (round 6,
   // profiles/r06_side_kernel_grids_ab.txt).  Smaller row counts (config 4: ~1 500 rows) gain 1 % forced and stay with the 4-wave kernel.
-  static const int min_tiles = [] { const char* e = getenv("EA_WGRAD_W8_MIN_TILES"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 48; }();  // (tuning knob)
+  constexpr int min_tiles = 48;
   // (second clause, round 6: the transducer recipe's encoder layers — ~116 tiles over ~1 500 rows — gain 1 % on this kernel beside the
   // compute queue; the enc-dec recipe's decoder layers — 64 tiles, similar row counts — lose 5 %: profiles/r06_wgrad_w8_configs_ab.txt)
-  static const int small_rows_tiles = [] { const char* e = getenv("EA_WGRAD_W8_SMALL_ROWS_TILES"); return e ? atoi(e) : 80; }();
-  const bool rule = total <= 512 && ((total >= min_tiles && min_rows >= 4096) || (small_rows_tiles > 0 && total >= small_rows_tiles && min_rows >= 1024));
+  constexpr int small_rows_tiles = 80;
+  const bool rule = total <= 512 && ((total >= min_tiles && min_rows >= 4096) || (total >= small_rows_tiles && min_rows >= 1024));
   if (!forced && !rule) return 0;
   for (int i = g.count; i <= EA_WGRAD_MAX; ++i) tb.start[i] = total;
   for (int i = g.count; i < EA_WGRAD_MAX; ++i) tb.tiles_x[i] = 1;
@@ -341,13 +314,7 @@ static int wgrad_w8_launch(const EaWgradGroup& g, hipStream_t stream, int* grid_
   static const bool attr_ok =
       hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_w8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
   if (!attr_ok) return 0;
-  // groups that do not fill the chip anyway (the encoder layers' ~116 tiles) run beside the compute queue's data-gradient chain, whose
-  // 8-wave GEMMs are ~200 workgroups of one per CU: capped at `cap` workgroups walking two tiles each, the launch takes twice as long
-  // on the side queue (which has the slack) and the chain's GEMMs fit the remaining CUs in ONE round.  0 = one workgroup per tile.
-  static const int cap = [] { const char* e = getenv("EA_WGRAD_W8_GRID"); return e ? atoi(e) : 0; }();
-  int grid = total;
-  if (cap > 0 && total < 192 && total > cap) grid = (cap + 7) & ~7;
-  hipLaunchKernelGGL(wgrad_w8_kernel, dim3(grid), dim3(512), lds, stream, g, tb);
-  if (grid_out) *grid_out = grid;
+  hipLaunchKernelGGL(wgrad_w8_kernel, dim3(total), dim3(512), lds, stream, g, tb);
+  if (grid_out) *grid_out = total;
   return 1;
 }

@@ -136,7 +136,6 @@ def end_step():
 
 
 _side_pending = {}  # device -> optimizer-only work was put on the Python-side stream since the last join
-_LINEAR_WGRAD_SIDE = os.environ.get("EA_LINEAR_WGRAD_SIDE", "1") != "0"  # (A/B switch)
 
 
 def join_side_streams():
@@ -174,8 +173,8 @@ def _zeros_f32(n, like):
 # way gets None from the autograd Function; autograd still runs its AccumulateGrad node — nothing to add — and with it the
 # post-accumulate-grad hook the data-parallel wrapper counts bucket completion with (tests/test_host_logic.py pins that
 # behaviour of torch), at the same point of the stream order as before.  Only inside an `accumulating_backward()` scope (the trainer's
-# backward calls); EA_DIRECT_GRADS=0: the autograd route everywhere (A/B switch, tests).
-_DIRECT_GRADS = os.environ.get("EA_DIRECT_GRADS", "1") != "0"
+# backward calls); set_direct_param_grads(False): the autograd route everywhere (tests).
+_DIRECT_GRADS = True
 
 
 def set_direct_param_grads(on: bool) -> bool:
@@ -306,7 +305,7 @@ def _side_stream(device):
 
 
 _aux_streams = {}
-_BRANCH_OVERLAP = os.environ.get("EA_BRANCH_OVERLAP", "1") != "0"
+_BRANCH_OVERLAP = True
 
 
 def aux_stream(device, idx):
@@ -377,7 +376,7 @@ class _Linear(torch.autograd.Function):
             # Optimizer-only products: for the big projections they go to the Python-side stream (round 6: 2 x 106 us of split-K
             # GEMM per update step were on the compute stream, in front of the data gradient the backward chain waits for);
             # `end_step()` / the data-parallel wrapper join that stream before the gradients are used.
-            side = _side_stream(dy.device) if (_LINEAR_WGRAD_SIDE and dy.is_cuda and 2.0 * M * N * Kin >= 4e9) else None
+            side = _side_stream(dy.device) if (dy.is_cuda and 2.0 * M * N * Kin >= 4e9) else None
             if side is not None:
                 cur = torch.cuda.current_stream(dy.device)
                 side.wait_stream(cur)
@@ -1127,9 +1126,6 @@ def _conformer_binding(module):
     return bind
 
 
-_WT_PREFETCH = os.environ.get("EA_WT_PREFETCH", "1") != "0"  # (A/B switch)
-
-
 def refresh_layer_transposes(layers, B, T):
     """Before a TRAINING forward pass over native Conformer layers: the transposed (k-contiguous) copies of every layer's weights —
     read only by the backward pass — are refreshed on the Python-side stream, under the sub-sampler's / first layers' forward
@@ -1142,7 +1138,7 @@ def refresh_layer_transposes(layers, B, T):
     from ._lib import EaLayerShape
 
     layers = list(layers)
-    if not _WT_PREFETCH or not layers:
+    if not layers:
         return None
     dev = layers[0].ffn1.w_1.weight.device
     if dev.type != "cuda":
@@ -1165,7 +1161,7 @@ def refresh_layer_transposes(layers, B, T):
     return side.record_event()
 
 
-_LAYER_CHAIN = os.environ.get("EA_LAYER_CHAIN", "1") != "0"  # (A/B switch)
+_LAYER_CHAIN = True
 
 
 def set_layer_chain(on: bool):
@@ -1298,7 +1294,7 @@ class _ConformerLayerNative(torch.autograd.Function):
         return (dx,) + (None,) * 11
 
 
-_LAYER_STACK = os.environ.get("EA_LAYER_STACK", "1") != "0"  # (A/B switch)
+_LAYER_STACK = True
 
 
 def set_layer_stack(on: bool):
@@ -2297,7 +2293,7 @@ class LazyJointLogits:
         return transducer_joint(self.E, self.D, self.w, self.b, self.B, self.T, self.U1, late=self.late)
 
 
-_JOINT_FUSED = os.environ.get("EA_JOINT_FUSED", "1") != "0"  # (A/B switch: 0 = always materialise the logits)
+_JOINT_FUSED = True  # (False: always materialise the logits)
 
 
 def set_joint_fused(on: bool) -> bool:
