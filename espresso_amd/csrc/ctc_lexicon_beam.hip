@@ -44,75 +44,14 @@
 #include "common.h"
 #include "ctc_beam_common.h"
 #include "espresso_amd.h"
+#include "ngram_common.h"
 
 namespace {
 
-constexpr int kMaxOrder = 6;
-constexpr int kMaxCtx = kMaxOrder - 1;
 constexpr int kLexMaxBeam = 64;
 constexpr int kLexMaxK = 64;
 constexpr int kLexMaxCand = kLexMaxBeam * (kLexMaxK + 1);
 constexpr int kLexRowLds = 5120;
-
-// ------------------------------------------------------------------------------------------------ n-gram tables
-struct NgramDev {  // device pointers of the tables, passed by value
-  int order, n1, unk, bos, eos;
-  const float* logp[kMaxOrder + 1];  // [k]: records of order k (natural log)
-  const float* bow[kMaxOrder + 1];   // [k], k < order (0 where the ARPA line has none)
-  const int* word[kMaxOrder + 1];    // [k], k >= 2: last word of the record (order 1: record i is word i)
-  const int* child[kMaxOrder + 1];   // [k], k < order: records [child[i], child[i + 1]) of order k + 1 extend record i
-};
-
-struct NgramLM {
-  int order = 0, unk = -1, bos = -1, eos = -1;
-  long counts[kMaxOrder + 1] = {};
-  std::vector<std::string> vocab;
-  std::vector<float> logp[kMaxOrder + 1], bow[kMaxOrder + 1];
-  std::vector<int> word[kMaxOrder + 1], child[kMaxOrder + 1], parent[kMaxOrder + 1];
-  void* dev_buf = nullptr;
-  NgramDev dev{}, host{};  // the same tables: device copy, host vectors
-};
-
-// the record of order k + 1 that extends record r of order k by word w (order 0: the root), -1 if none
-__host__ __device__ __forceinline__ int ng_find(const int* const* child, const int* const* word, int n1, int k, int r, int w) {
-  if (k == 0) return (w >= 0 && w < n1) ? w : -1;
-  const int* wd = word[k + 1];
-  int lo = child[k][r];
-  const int end = child[k][r + 1];
-  int hi = end;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (wd[mid] < w) lo = mid + 1; else hi = mid;
-  }
-  return (lo < end && wd[lo] == w) ? lo : -1;
-}
-
-// ln P(w | h[0..L)), h oldest first; w outside the vocabulary scores as <unk> (-inf without one)
-__host__ __device__ inline float ng_logp(const NgramDev& m, const int* h, int L, int w) {
-  if (w < 0 || w >= m.n1) w = m.unk;
-  if (w < 0) return -INFINITY;
-  if (L > m.order - 1) { h += L - (m.order - 1); L = m.order - 1; }
-  float acc = 0.f;
-  for (int l = L; l >= 0; --l) {
-    int r = 0, k = 0;
-    for (; k < l; ++k) {
-      r = ng_find(m.child, m.word, m.n1, k, r, h[L - l + k]);
-      if (r < 0) break;
-    }
-    if (k < l) continue;  // the context h[L-l..L) is absent: its backoff weight counts as 0
-    const int rw = ng_find(m.child, m.word, m.n1, l, r, w);
-    if (rw >= 0) return acc + m.logp[l + 1][rw];
-    if (l > 0) acc += m.bow[l][r];
-  }
-  return -INFINITY;  // not reached: every w in [0, n1) is a unigram
-}
-
-// contexts: fixed width W = order - 1, oldest first, front-padded with -1; the valid words are those after the last -1
-__host__ __device__ __forceinline__ int ctx_len(const int* h, int W) {
-  int L = 0;
-  while (L < W && h[W - 1 - L] >= 0) ++L;
-  return L;
-}
 
 __global__ __launch_bounds__(256) void ngram_score_kernel(const NgramDev m, const int* ctx, const int* words, int N, float* out) {
   const int i = blockIdx.x * 256 + threadIdx.x;

@@ -10,7 +10,9 @@
 //   1. r = log_softmax(logits[:V] / temperature);
 //   2. with an LM (row m = log P_lm(. | eos + y_j), weight w): for v != blank f_v = r_v + w * m_v and
 //      r_v = f_v + log sum_{v != blank} e^{r_v} - log sum_{v != blank} e^{f_v} (the non-blank mass stays); r_blank untouched.  An LM
-//      without a blank entry (lm_no_blank): token v > blank reads column v - 1;
+//      without a blank entry (lm_no_blank): token v > blank reads column v - 1.  The rows are the caller's: the LSTM LM's
+//      log-softmax, or a sub-word n-gram LM's (ngram_rows.hip; V columns, -inf where the model has no entry: such a token's f_v
+//      is -inf and it is no candidate).  Word-level LMs and a lexicon stay outside the transducer searches;
 //   3. with eos >= 0 (the model predicts eos): r_blank = logaddexp(r_blank, r_eos), r_eos = -inf;
 //   4. candidates: the stay (y_j, s_j + r_blank), key (j, 0, 0), and for the K non-blank tokens with the largest finite r_v
 //      (ties: lower id) the extensions (y_j + v, s_j + r_v), key (j, 1, v).

@@ -982,6 +982,84 @@ def ngram_score(handle, ctx, words):
     return out
 
 
+NGRAM_ROW_LDS = 5120  # columns of a row that ea_ngram_token_rows_step stages in LDS (kNgRowLds); wider rows finish in global memory
+
+
+class NgramTokenMap:
+    """The uploaded (tok2word, word2tok) pair of a sub-word n-gram LM (ea_ngram_token_map_create): tok2word int32 [V] host
+    values (>= 0 ARPA word id, -1 no ARPA entry, -2 always -inf), copied to `device` with its inverse."""
+
+    def __init__(self, ngram_handle, tok2word, device):
+        tok2word = torch.as_tensor(tok2word, dtype=torch.int32).contiguous().cpu()
+        self.V, self._h = tok2word.numel(), ctypes.c_void_p()
+        with torch.cuda.device(device):
+            check(_lib.lib().ea_ngram_token_map_create(ngram_handle, ctypes.c_void_p(tok2word.data_ptr()), self.V,
+                                                       ctypes.byref(self._h)), "ea_ngram_token_map_create")
+        self.device = torch.device(device)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        try:
+            h, self._h = self._h, None
+            if h is not None and h.value:
+                _lib.lib().ea_ngram_token_map_destroy(h)
+        except Exception:  # interpreter shutdown: the library may already be gone
+            pass
+
+
+def ngram_token_rows_start(handle, token_map, N, W, ld=None):
+    """(ctx int32 [N][max(W, 1)], rows fp32 [N][V]) of N empty hypotheses: the context [-1, ..., -1, <s>] and
+    ln P(. | <s>) over the dictionary (ea_ngram_token_rows_start).  W = order - 1; with W == 0 the one ctx column is unused."""
+    V, dev = token_map.V, token_map.device
+    ld = V if ld is None else ld
+    ctx = torch.full((N, max(W, 1)), -1, dtype=torch.int32, device=dev)
+    rows = torch.empty(N, ld, dtype=torch.float32, device=dev)
+    check(_lib.lib().ea_ngram_token_rows_start(handle, token_map.handle, V, N, _p(ctx), _p(rows), ld, _stream()),
+          "ea_ngram_token_rows_start")
+    return ctx, rows[:, :V]
+
+
+def ngram_token_rows_step(handle, token_map, ctx_in, parent, token, keep, ctx_out, rows=None, ld=None):
+    """One frame of the n-gram LM for N rows in one launch (ea_ngram_token_rows_step): row i continues row parent[i] of ctx_in
+    (keep[i]: unchanged, else token[i] appended), its context goes to ctx_out (a buffer other than ctx_in) and
+    ln P(. | context) to rows fp32 [N][V] (allocated with row stride `ld` unless given).  Returns rows."""
+    V, N = token_map.V, parent.numel()
+    assert ctx_in.dtype == ctx_out.dtype == parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
+    assert ctx_in.is_contiguous() and ctx_out.is_contiguous() and ctx_in.shape == ctx_out.shape and ctx_in.shape[0] == N
+    assert ctx_in.data_ptr() != ctx_out.data_ptr() and token.numel() == keep.numel() == N
+    if rows is None:
+        rows = torch.empty(N, V if ld is None else ld, dtype=torch.float32, device=parent.device)
+    assert rows.dtype == torch.float32 and rows.stride(1) == 1 and rows.stride(0) >= V and rows.shape[0] == N
+    check(_lib.lib().ea_ngram_token_rows_step(handle, token_map.handle, V, _p(ctx_in), _p(parent), _p(token), _p(keep), N,
+                                              _p(ctx_out), _p(rows), rows.stride(0), _stream()), "ea_ngram_token_rows_step")
+    return rows[:, :V]
+
+
+def ngram_token_rows_host(handle, tok2word, ctx_in, parent, token, keep, W, ld=None):
+    """The contract of `ngram_token_rows_step` on the host tables and numpy arrays (ea_ngram_token_rows_host; no device):
+    returns (ctx_out int32 [N][W], rows fp32 [N][V]).  parent None: the N = ctx_in start rows (ctx_in is then a row count)."""
+    import numpy as np
+
+    t2w = np.ascontiguousarray(tok2word, dtype=np.int32)
+    V = len(t2w)
+    ld = V if ld is None else ld
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    if parent is None:
+        N, args = int(ctx_in), (None, None, None, None)
+    else:
+        N = len(parent)
+        keep_arrays = (np.ascontiguousarray(ctx_in, dtype=np.int32).reshape(N, W), np.ascontiguousarray(parent, dtype=np.int32),
+                       np.ascontiguousarray(token, dtype=np.int32), np.ascontiguousarray(keep, dtype=np.uint8))
+        args = tuple(vp(a) for a in keep_arrays)
+    ctx_out = np.empty((N, W), dtype=np.int32)
+    rows = np.full((N, ld), np.nan, dtype=np.float32)
+    check(_lib.lib().ea_ngram_token_rows_host(handle, vp(t2w), V, *args, N, vp(ctx_out), vp(rows), ld), "ea_ngram_token_rows_host")
+    return ctx_out, rows[:, :V]
+
+
 def ctc_lexicon_beam_workspace(B, T, beam, device):
     """Workspace of the lexicon beam search (ea_ctc_lexicon_beam_workspace_bytes): the prefix tables of B utterances."""
     return torch.empty(int(_lib.lib().ea_ctc_lexicon_beam_workspace_bytes(B, T, beam)), dtype=torch.uint8, device=device)

@@ -245,6 +245,10 @@ def get_parser():
     p.add_argument("--lexicon", default=None,
                    help="ctc_beam --ngram-lm: `word tok1 tok2 ...` lines (default with a <space> dictionary: the ARPA words spelled "
                         "by characters)")
+    p.add_argument("--token-ngram-lm", default=None,
+                   help="ctc_beam (without --ngram-lm) / ctc_stream_beam / transducer_frame_beam / transducer_stream_beam: ARPA n-gram LM "
+                        "over the model's own sub-word units (the dictionary's symbols are its words; plain text, order <= 6), fused "
+                        "with --lm-weight in place of an LSTM LM: no --lm-path or --word-dict with it")
     p.add_argument("--word-score", type=float, default=-1.0, help="ctc_beam --ngram-lm: score added per completed word")
     p.add_argument("--hotwords", default=None,
                    help="ctc_beam (without --ngram-lm) / ctc_stream_beam: phrases to bias the search towards, one per line, optionally `<TAB>boost`; "
@@ -308,14 +312,38 @@ def check_ngram_args(args):
         raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
 
 
+TOKEN_NGRAM_SEARCHES = ("ctc_beam", "ctc_stream_beam", "transducer_frame_beam", "transducer_stream_beam")
+
+
+def check_token_ngram_args(args):
+    """--token-ngram-lm fuses an n-gram LM over the model's sub-word units into the four token-level beam searches, where they
+    otherwise fuse an LSTM LM: refused, before anything is loaded, with every other search, with the lexicon + n-gram search
+    (--ngram-lm), with an LSTM LM (--lm-path / --word-dict), with ensembles and with a weight that is not positive."""
+    if not args.token_ngram_lm:
+        return
+    if args.search not in TOKEN_NGRAM_SEARCHES:
+        raise NotImplementedError("--token-ngram-lm (sub-word n-gram LM fusion) is implemented for --search " +
+                                  ", ".join(TOKEN_NGRAM_SEARCHES) + f" only, not --search {args.search}")
+    if args.ngram_lm:
+        raise NotImplementedError("--token-ngram-lm fuses a sub-word n-gram LM into the prefix beam search without a lexicon: no "
+                                  "--ngram-lm (the word n-gram LM of the lexicon search) with it")
+    if args.lm_path or args.word_dict:
+        raise NotImplementedError("--token-ngram-lm fuses the n-gram LM alone: no --lm-path or --word-dict with it")
+    if len(args.path.split(os.pathsep)) > 1:
+        raise NotImplementedError(f"--token-ngram-lm: --search {args.search} takes one model, ensembles are not implemented")
+    if not args.lm_weight > 0:
+        raise ValueError("--token-ngram-lm needs --lm-weight > 0: the n-gram LM scores some tokens -inf")
+
+
 # --hotwords is the option of the CTC prefix beam search; the transducer beam searches take the same file under a name of their own
 _HOTWORDS_HINT = " (that option biases --search ctc_beam): give the phrase file as --transducer-hotwords"
 
 
 def check_frame_beam_args(args):
     """--search transducer_frame_beam is the device-resident frame-synchronous beam search of one transducer model, alone or with
-    one sub-word LSTM LM, with or without phrase biasing (--transducer-hotwords): refused, before anything is loaded, with
-    streaming, the CTC search's --hotwords, n-gram / word-level LMs, alignments and ensembles."""
+    one sub-word LM (an LSTM LM, --lm-path, or an n-gram LM over the same units, --token-ngram-lm), with or without phrase
+    biasing (--transducer-hotwords): refused, before anything is loaded, with streaming, the CTC search's --hotwords, the
+    lexicon search's word n-gram LM (--ngram-lm), word-level LMs, alignments and ensembles."""
     if args.search != "transducer_frame_beam":
         if args.transducer_beam_size_token is not None and args.search != "transducer_stream_beam":
             raise ValueError("--transducer-beam-size-token configures --search transducer_frame_beam / transducer_stream_beam")
@@ -332,9 +360,10 @@ def check_frame_beam_args(args):
 
 def check_stream_beam_args(args):
     """--search transducer_stream_beam is the frame-synchronous transducer beam search of one chunk-streaming transducer model
-    under --streaming, alone or with one sub-word LSTM LM (a name of its own: --search transducer_frame_beam --streaming stays
-    refused), with or without phrase biasing (--transducer-hotwords).  Refused, before anything is loaded: without --streaming,
-    and with the CTC search's --hotwords, n-gram / word-level LMs, multi-level LMs, alignments and ensembles."""
+    under --streaming, alone or with one sub-word LM (--lm-path, or --token-ngram-lm; a name of its own: --search
+    transducer_frame_beam --streaming stays refused), with or without phrase biasing (--transducer-hotwords).  Refused, before
+    anything is loaded: without --streaming, and with the CTC search's --hotwords, the lexicon search's word n-gram LM
+    (--ngram-lm), word-level LMs, multi-level LMs, alignments and ensembles."""
     if args.search != "transducer_stream_beam":
         return
     if not args.streaming:
@@ -352,7 +381,7 @@ def check_stream_beam_args(args):
 
 def check_ctc_stream_beam_args(args):
     """--search ctc_stream_beam is the CTC prefix beam search of one chunk-streaming CTC model under --streaming: alone, with one
-    sub-word LSTM LM (--lm-path), with phrase biasing (--hotwords) or with both (a name of its own: --streaming --search ctc_beam
+    sub-word LM (an LSTM LM, --lm-path, or an n-gram LM over the same units, --token-ngram-lm), with phrase biasing (--hotwords) or with both (a name of its own: --streaming --search ctc_beam
     without --ngram-lm, and --hotwords with it, stay refused).  Refused, before anything is loaded: without --streaming, and with
     the lexicon + n-gram search's options, word-level and multi-level LMs, alignments, ensembles and the transducer searches'
     --transducer-hotwords."""
@@ -626,6 +655,7 @@ def load_member(state, name, block, task, dev):
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
+    check_token_ngram_args(args)
     check_frame_beam_args(args)
     check_stream_beam_args(args)
     check_ctc_stream_beam_args(args)
@@ -675,6 +705,11 @@ def main(argv=None):
         ngram_lm = NGramLanguageModel(args.ngram_lm)
         ngram = (ngram_lm, build_lexicon(task.target_dictionary, ngram_lm, args.lexicon))
         ngram_lm.to(dev)
+    token_lm = None
+    if args.token_ngram_lm:  # before the model: a malformed ARPA file, or one over other units, fails fast
+        from .models.token_ngram_lm import TokenNGramLM
+
+        token_lm = TokenNGramLM(args.token_ngram_lm, task.target_dictionary, device=dev)
     if args.streaming:  # the encoder options streaming cannot reproduce exactly: refused before the model is built or audio is read
         from . import registry
         from .models.transformer.streaming_encoder import check_streamable
@@ -696,7 +731,7 @@ def main(argv=None):
         members.append(load_member(st, *resolve_model_config(args.model, args.model_config, st), task, dev))
     if len(members) > 1 and args.search != "beam":
         raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
-    lm = None
+    lm = token_lm
     if args.lm_path:
         class _LMTask:
             target_dictionary = source_dictionary = task.target_dictionary

@@ -1,5 +1,6 @@
 """What the beam-search decoders share on the host: the hypothesis lists of `generate`, the triple a
-step writes, the LM stepping of the offline decoders (BeamDecoderMixin), and for the three streamed decoders the pool of state
+step writes, the LM stepping of the offline decoders (BeamDecoderMixin: the LSTM LM, or the sub-word n-gram LM of
+models/token_ngram_lm.py, whose state is one int32 context row per hypothesis), and for the three streamed decoders the pool of state
 slots (StreamSlots) and the rows a stream carries between `accept` calls besides its search state (CarriedRows).
 
 A streamed decoder keeps, per open stream, one of `max_streams` slots of its device state and the number of encoder frames
@@ -28,6 +29,24 @@ def step_triple(N, device):
             torch.empty(N, dtype=torch.uint8, device=device))
 
 
+def is_token_ngram(lm_model):
+    """Whether a decoder's `lm_model` is the sub-word n-gram LM (models/token_ngram_lm.py) rather than the LSTM LM."""
+    from ..models.token_ngram_lm import TokenNGramLM
+
+    return isinstance(lm_model, TokenNGramLM)
+
+
+def check_token_ngram(lm_model, lm_weight, dictionary, blank, search_name):
+    """A decoder's constructor, for a TokenNGramLM: it is built over the decoder's dictionary and for the decoder's blank (the
+    column it holds at -inf), and its weight is positive (its rows hold -inf, and 0 * -inf in the fusion is NaN)."""
+    if list(lm_model.dictionary.symbols) != list(dictionary.symbols):
+        raise ValueError(f"{search_name}: the token n-gram LM was built for another dictionary")
+    if lm_model.blank != blank:
+        raise ValueError(f"{search_name}: the token n-gram LM was built with blank {lm_model.blank}, the search's blank is {blank}")
+    if not lm_weight > 0:
+        raise ValueError(f"{search_name}: a token n-gram LM needs lm_weight > 0 (got {lm_weight}): its rows hold -inf")
+
+
 class BeamDecoderMixin:
     """`decode` and the LM state of the beams for a decoder with `_generate`, `eos` and (for the LM methods) `lm_model`."""
 
@@ -40,7 +59,10 @@ class BeamDecoderMixin:
         return K.log_softmax(logits, logits.shape[0], logits.shape[1], logits.stride(0))
 
     def lm_start(self, N, device):
-        """LSTM state and log-prob rows fp32 [N][LM vocabulary] of N empty hypotheses (the LM's eos as BOS)."""
+        """LM state and log-prob rows fp32 [N][LM vocabulary] of N empty hypotheses: the LSTM state after the LM's eos as BOS,
+        or with a TokenNGramLM the n-gram contexts after <s>."""
+        if is_token_ngram(self.lm_model):
+            return self.lm_model.start(N, device)
         lmd = self.lm_model.decoder
         state = lmd.init_state(N, device)
         feat, state = lmd.advance(self._lm_tokens(torch.full((N,), self.eos, dtype=torch.int32, device=device)), state)
@@ -49,10 +71,18 @@ class BeamDecoderMixin:
     def lm_update(self, state, parent, token, keep):
         """After one step: every row continues row `parent` of the previous frame; rows with keep == 0 appended `token`, the
         others keep their parent's LM state (and so recompute its row)."""
+        if is_token_ngram(self.lm_model):
+            return self.lm_model.update(state, parent, token, keep)
         lmd = self.lm_model.decoder
         state = lmd.reorder_state(state, parent)
         feat, state = lmd.advance(self._lm_tokens(token), state, keep_row=keep)
         return state, self._lm_rows(feat)
+
+    def lm_init_state(self, N, device):
+        """The LM state of N rows that a reset fills before anything reads them (the streamed decoders' per-slot rows)."""
+        if is_token_ngram(self.lm_model):
+            return self.lm_model.init_state(N, device)
+        return self.lm_model.decoder.init_state(N, device)
 
     @torch.no_grad()
     def decode(self, models, sample, **kwargs):
@@ -141,7 +171,8 @@ class StreamSlots:
 
 class CarriedRows:
     """The rows the slots carry besides the search state.  `carried` lists (rows, start) pairs: `rows` an LSTM state dict
-    (name -> per-layer [max_streams * beam][H] tensors) or one [max_streams * beam][W] tensor, `start` the same with one row:
+    (name -> per-layer [max_streams * beam][H] tensors) or one [max_streams * beam][W] tensor (fp32 rows, or the int32 contexts of
+    a token n-gram LM), `start` the same with one row:
     what a new stream starts from."""
 
     def __init__(self, beam, max_streams, carried):

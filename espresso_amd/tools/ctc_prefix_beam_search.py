@@ -13,6 +13,9 @@ The search is HIP (csrc/ctc_beam.hip): without an LM the whole utterance is one 
 launch plus the LM update on the device (reorder the LSTM state by parent, advance the rows that appended a token, output
 layer, log-softmax).  `search` returns device tensors without a host synchronisation.
 
+`lm_model` may instead be a models.token_ngram_lm.TokenNGramLM, an ARPA n-gram LM over the same dictionary: the loop is the
+same, and the LM update of a frame is one launch (csrc/ngram_rows.hip) that advances the contexts and writes the rows.
+
 Hotword biasing: with `context_graph` (tools/context_graph.ContextGraph) every hypothesis also carries its state in the phrase
 automaton and a running bias that joins the score unweighted; the final score is the unbiased score of the same tokens plus
 the boosts of the phrases it completed.  The candidate tokens of a frame stay the K best by acoustic score: biasing re-ranks
@@ -22,7 +25,7 @@ from typing import Dict, List
 import torch
 
 from .. import kernels as K
-from .beam_common import BeamDecoderMixin, hyps_from_tensors, step_triple
+from .beam_common import BeamDecoderMixin, check_token_ngram, hyps_from_tensors, is_token_ngram, step_triple
 
 
 class CTCPrefixBeamSearchDecoder(BeamDecoderMixin):
@@ -45,7 +48,9 @@ class CTCPrefixBeamSearchDecoder(BeamDecoderMixin):
             raise ValueError(f"CTC prefix beam search: nbest {nbest} outside [1, beam {beam_size}]")
         self.nbest = nbest
         self.lm_model, self.lm_weight, self.insertion_bonus = lm_model, float(lm_weight), float(insertion_bonus)
-        if lm_model is not None:
+        if is_token_ngram(lm_model):
+            check_token_ngram(lm_model, self.lm_weight, dictionary, self.blank, "CTC prefix beam search")
+        elif lm_model is not None:
             lm_dict = lm_model.decoder.dictionary
             assert list(lm_dict.symbols) == list(dictionary.symbols), \
                 "CTC prefix beam search fuses an LM over the CTC model's own dictionary (blank <s> included)"

@@ -6,7 +6,8 @@ and the rows a stream carries are those of tools/beam_common.py (StreamSlots, Ca
 
 Everything a stream carries lives on the device, allocated once: the search state (frame counter, beam, prefix table with its
 hash, the hypotheses' states in the context graph and running biases: `state_bytes_per_stream()` bytes per slot,
-csrc/ctc_beam.hip) and, with an LM, its LSTM state and log-prob row, which start as the LM after its eos.
+csrc/ctc_beam.hip) and, with an LM, its LSTM state and log-prob row, which start as the LM after its eos (with a
+models.token_ngram_lm.TokenNGramLM: one int32 context row in place of the LSTM state, starting after <s>).
 
 Without an LM `accept_lprobs` is one launch (ea_ctc_prefix_beam_stream_step) for all the streams that got frames.  With one it
 gathers the listed streams' LM rows and then per frame index j < max(counts): the step of frame j, `lm_update(state, parent,
@@ -25,7 +26,7 @@ from typing import Dict, List
 import torch
 
 from .. import kernels as K
-from .beam_common import CarriedRows, StreamSlots, hyps_from_tensors, step_triple
+from .beam_common import CarriedRows, StreamSlots, hyps_from_tensors, is_token_ngram, step_triple
 from .ctc_prefix_beam_search import CTCPrefixBeamSearchDecoder
 
 
@@ -62,7 +63,7 @@ class StreamingCTCPrefixBeamDecoder(StreamSlots):
         if self.lm_model is not None:
             R = self.max_streams * self.beam_size
             start_state, start_rows = self.offline.lm_start(1, device)
-            self.lm = self.lm_model.decoder.init_state(R, device)
+            self.lm = self.offline.lm_init_state(R, device)
             self.lm_rows = start_rows.new_zeros(R, start_rows.shape[1])
             self._rows = CarriedRows(self.beam_size, self.max_streams, [(self.lm, start_state), (self.lm_rows, start_rows)])
 
@@ -83,7 +84,10 @@ class StreamingCTCPrefixBeamDecoder(StreamSlots):
     def _device(self):
         if self.state is not None:
             return self.state.device
-        if self.lm_model is not None:
+        if is_token_ngram(self.lm_model):
+            if self.lm_model.device is not None:
+                return self.lm_model.device
+        elif self.lm_model is not None:
             return next(self.lm_model.parameters()).device
         return torch.device("cuda", torch.cuda.current_device())
 

@@ -79,7 +79,7 @@ class StreamingTransducerFrameBeamDecoder(StreamSlots):
         self.lm = self.lm_rows = None
         if self.lm_model is not None:
             lst, lrows = self.offline.lm_start(1, device)
-            self.lm = self.lm_model.decoder.init_state(R, device)
+            self.lm = self.offline.lm_init_state(R, device)
             self.lm_rows = lrows.new_zeros(R, lrows.shape[1])
             carried += [(self.lm, lst), (self.lm_rows, lrows)]
         self._rows = CarriedRows(self.beam_size, self.max_streams, carried)

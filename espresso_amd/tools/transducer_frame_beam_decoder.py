@@ -11,7 +11,9 @@ prefix table and selection live in a device workspace; the loop runs over the pa
 utterance's length are no-ops in the kernel) and never synchronises with the host.
 
 The LM fusion is the mass-preserving one of the two other transducer decoders (transducer_greedy_decoder.py): non-blank
-log-probs get lm_weight * log P_lm and are renormalised to the non-blank mass they had; blank is untouched.
+log-probs get lm_weight * log P_lm and are renormalised to the non-blank mass they had; blank is untouched.  `lm_model` may
+instead be a models.token_ngram_lm.TokenNGramLM over the model's dictionary (one launch per frame, csrc/ngram_rows.hip): a
+token whose LM log-prob is -inf leaves the candidates, as any token with a non-finite fused score does.
 
 Hotword biasing: with `context_graph` (tools/context_graph.ContextGraph) every hypothesis also carries its state in the phrase
 automaton and a running bias; the decoder then calls the bias family of the kernels (ea_rnnt_frame_beam_bias_*) for the
@@ -21,7 +23,7 @@ from typing import Dict, List
 import torch
 
 from .. import kernels as K
-from .beam_common import BeamDecoderMixin, hyps_from_tensors, step_triple
+from .beam_common import BeamDecoderMixin, check_token_ngram, hyps_from_tensors, is_token_ngram, step_triple
 
 
 class TransducerFrameBeamDecoder(BeamDecoderMixin):
@@ -63,7 +65,9 @@ class TransducerFrameBeamDecoder(BeamDecoderMixin):
             self.model.eval()
         self.lm_model, self.lm_weight = lm_model, float(lm_weight)
         self.no_blank_in_lm = False
-        if lm_model is not None:
+        if is_token_ngram(lm_model):  # its rows have V columns: lm_no_blank stays False
+            check_token_ngram(lm_model, self.lm_weight, dictionary, self.blank, "transducer frame beam search")
+        elif lm_model is not None:
             nlm = len(lm_model.decoder.dictionary)
             if nlm not in (V, V - 1):
                 raise ValueError(f"transducer frame beam search: the LM's dictionary has {nlm} entries, the model's {V}: it must "

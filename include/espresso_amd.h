@@ -699,6 +699,34 @@ int ea_ctc_lexicon_stream_finish(const void* state, const int* slots, int n, con
 int ea_ctc_lexicon_stream_partial(const void* state, const int* slots, int n, int max_streams, int max_frames, int beam,
                                   float ins_bonus, int pad, int max_u, int* tokens, int* lengths, float* scores, int* stable_len,
                                   ea_stream_t stream);
+/* Sub-word n-gram LM rows for the token-level beam searches (csrc/ngram_rows.hip) — the ARPA model the reference hands to
+ * Flashlight's KenLM lexicon decoder (espresso/tools/ctc_decoder.py:24-71), queried here over the model's own dictionary
+ * and fused as `lm_rows` by ea_ctc_prefix_beam_* and ea_rnnt_frame_beam_* (offline and streamed), as the LSTM LM's rows are.
+ * `handle` is an uploaded ea_ngram_create handle of order n; W = n - 1; a context is int32 [W], oldest first, front-padded
+ * with -1 (the convention of ea_ngram_score).  tok2word int32 [V] maps a dictionary id to an ARPA word id (>= 0), to -1 (no
+ * ARPA entry: scores as <unk>, -inf without one) or to -2 (a column that is always -inf: pad, blank); no two ids share a word.
+ * ea_ngram_token_map_create: checks such a host array, uploads it with its inverse (word2tok) to the current device and
+ *   writes an opaque handle to *(void**)map_host (-2: bad map); the `tok2word` argument of the two device calls below is such
+ *   a handle.  ea_ngram_token_map_destroy frees it.
+ * ea_ngram_token_rows_step: one launch for N rows (one workgroup each).  Row i continues row parent[i] of ctx_in: with
+ *   keep[i] (uint8) its context c is ctx_in[parent[i]], otherwise that context shifted left by one with word(token[i])
+ *   appended; word(t) = tok2word[t] if >= 0, else the file's <unk>, else the id n1 that matches no n-gram.  ctx_out[i] = c
+ *   (ctx_in != ctx_out: rows are gathered by parent), and rows[i * ld + v], fp32, ld >= V, is bit for bit what
+ *   ea_ngram_score returns for (c, tok2word[v]), v < V; -2 columns are -inf.  Every row is recomputed, kept ones included.
+ *   n == 1 (W == 0): the context pointers are not read.  A parent outside [0, N) is not reported (nothing is read back): the
+ *   row then continues its own index, so that no launch reads outside ctx_in; a token outside [0, V) counts as one without
+ *   an ARPA entry.
+ * ea_ngram_token_rows_start: the context [-1, ..., -1, <s>] and its row, written to all N rows of ctx and rows.
+ * ea_ngram_token_rows_host: the same contract on the host tables and host arrays (tok2word_host the int32 [V] array itself;
+ *   parent_host == NULL: the start rows); a loop of single queries, for tests and as the kernel's yardstick. */
+int ea_ngram_token_map_create(const void* handle, const int* tok2word_host, int V, void* map_host);
+int ea_ngram_token_map_destroy(void* map);
+int ea_ngram_token_rows_step(const void* handle, const void* tok2word, int V, const int* ctx_in, const int* parent,
+                             const int* token, const void* keep, int N, int* ctx_out, float* rows, long ld, ea_stream_t stream);
+int ea_ngram_token_rows_start(const void* handle, const void* tok2word, int V, int N, int* ctx, float* rows, long ld,
+                              ea_stream_t stream);
+int ea_ngram_token_rows_host(const void* handle, const int* tok2word_host, int V, const int* ctx_in_host, const int* parent_host,
+                             const int* token_host, const void* keep_host, int N, int* ctx_out_host, float* rows_host, long ld);
 /* Label-smoothed CE — espresso/criterions/label_smoothed_cross_entropy_v2.py:49-119.  smoothing 0 = uniform, 1 = unigram
  * (prior fp32 [V], sums to one), 2 = temporal (neighbouring targets of the same sentence, weights 2:5:5:2; rows are
  * b*tgt_len + u).  out_loss[0] += sum loss, out_loss[1] += sum nll (pad rows skipped). */
