@@ -8,13 +8,12 @@
 // adjacent channels (4-byte bf16x2 accesses -> 256 B per wavefront) and slides a register window
 // along time, so every input element is read once per tile (+halo) and the 31 taps stay in VGPRs.
 #include "common.h"
+#include "convmodule_math.h"
 #include "espresso_amd.h"
 
 namespace {
 
 constexpr int KMAX = 31;
-
-__device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }  // (v_rcp_f32, see silu_f)
 
 // Depthwise-conv tiles: one workgroup = CT channels x TTILE output steps of one utterance; the input rows (plus the KW-1
 // halo) are staged once in LDS with every global load in flight at once, then each thread produces TPT consecutive outputs
@@ -23,12 +22,12 @@ __device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rc
 constexpr int CT = 64, TTILE = 64, TPT = TTILE / 4;
 
 // Y [M][2C] -> U = a*sigmoid(g) [M][C] (saved), Z = dwconv(U) [M][C] (pre-BN), stats += (sum, sumsq)
-template <int KW>
+template <int KW, int PADL>
 __global__ __launch_bounds__(256) void glu_dwconv_fwd_kernel(const bf16_t* __restrict__ Y,
                                                              const float* __restrict__ w,  // [C][KW]
                                                              bf16_t* __restrict__ U, bf16_t* __restrict__ Z,
                                                              double* __restrict__ stats, int T, int C) {
-  constexpr int PAD = (KW - 1) / 2, ROWS = TTILE + KW - 1;
+  constexpr int PAD = PADL, ROWS = TTILE + KW - 1;  // PADL frames of left context: (KW-1)/2 (symmetric) or KW-1 (causal)
   __shared__ __attribute__((aligned(16))) float su[ROWS][CT];
   __shared__ float sred[2][4][CT];
   const int c0 = blockIdx.x * CT, t0 = blockIdx.y * TTILE, b = blockIdx.z;
@@ -60,12 +59,8 @@ __global__ __launch_bounds__(256) void glu_dwconv_fwd_kernel(const bf16_t* __res
       if (i < ROWS * (CT / 8)) {
         const int row = i / (CT / 8), c8 = (i % (CT / 8)) * 8;
         const int tin = t0 - PAD + row;
-        const uint32_t aw[4] = {va[k].x, va[k].y, va[k].z, va[k].w}, gw[4] = {vg[k].x, vg[k].y, vg[k].z, vg[k].w};
         uint32_t pk[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          pk[e] = pack_bf2(__uint_as_float(aw[e] << 16) * sigmoid_f(__uint_as_float(gw[e] << 16)),
-                           __uint_as_float(aw[e] & 0xffff0000u) * sigmoid_f(__uint_as_float(gw[e] & 0xffff0000u)));
+        glu_gate8(va[k], vg[k], pk);
         const bool inside = tin >= 0 && tin < T;
         const uint4 u4 = inside ? make_uint4(pk[0], pk[1], pk[2], pk[3]) : make_uint4(0, 0, 0, 0);
         if (inside && row >= PAD && row < PAD + TTILE) *reinterpret_cast<uint4*>(U + (rowbase + tin) * C + c0 + c8) = u4;
@@ -127,11 +122,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_fwd_kernel(const bf16_t* __res
       if (vec && c0 + c8 + 8 <= C) {
         const uint4 av = *reinterpret_cast<const uint4*>(yr);
         const uint4 gv = *reinterpret_cast<const uint4*>(yr + C);
-        const uint32_t aw[4] = {av.x, av.y, av.z, av.w}, gw[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          pk[e] = pack_bf2(__uint_as_float(aw[e] << 16) * sigmoid_f(__uint_as_float(gw[e] << 16)),
-                           __uint_as_float(aw[e] & 0xffff0000u) * sigmoid_f(__uint_as_float(gw[e] & 0xffff0000u)));
+        glu_gate8(av, gv, pk);
         if (row >= PAD && row < PAD + TTILE)
           *reinterpret_cast<uint4*>(U + (rowbase + tin) * C + c0 + c8) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
       } else {
@@ -233,20 +224,13 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const bf16_t* __restric
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int c = ch * 8 + e;
-    sc[e] = mean_rstd[C + c] * gamma[c];
-    sh[e] = beta[c] - mean_rstd[c] * sc[e];
+    bn_scale_shift(mean_rstd[c], mean_rstd[C + c], gamma[c], beta[c], sc[e], sh[e]);  // (sc = rstd * gamma, sh = beta - mean * sc)
   }
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
     const long m = i / nch;
     const uint4 u = *reinterpret_cast<const uint4*>(Z + m * C + ch * 8);
-    const uint32_t wv[4] = {u.x, u.y, u.z, u.w};
     float o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float z = (e & 1) ? __uint_as_float(wv[e >> 1] & 0xffff0000u) : __uint_as_float(wv[e >> 1] << 16);
-      const float y = z * sc[e] + sh[e];
-      o[e] = act == 2 ? silu_f(y) : (act == 1 ? fmaxf(y, 0.f) : y);
-    }
+    bn_act8(u, sc, sh, act, o);
     uint4 r;
     r.x = pack_bf2(o[0], o[1]); r.y = pack_bf2(o[2], o[3]); r.z = pack_bf2(o[4], o[5]); r.w = pack_bf2(o[6], o[7]);
     *reinterpret_cast<uint4*>(Hout + m * C + ch * 8) = r;
@@ -440,17 +424,18 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const bf16_t* __r
   }
 }
 
-// dU[t] = sum_k w[k] * dZ[t + PAD - k]; then GLU backward -> dY [M][2C]   (same tiling as the forward kernel)
+// dU[t] = sum_k w[k] * dZ[t + PADL - k]; then GLU backward -> dY [M][2C]   (same tiling as the forward kernel)
 // Round 6: every global access is a 16-byte vector.  The thread mapping of the convolution (one channel, TPT consecutive time steps)
 // made the GLU operands 2 x TPT two-byte loads and the result 2 x TPT two-byte stores per thread — 64 memory instructions per
 // thread for 256 bytes, and the loads sat in the output loop behind the stores (one dependent round trip per output).  Now the
 // Y tile is staged [half][t][c] in LDS with the dZ tile, each thread updates its own cells in place, and the tile leaves as
 // 16-byte rows.  Full-width tiles only (C % 64 == 0 for this block); ragged channel tiles take the scalar path below.
-template <int KW>
+template <int KW, int PADL>
 __global__ __launch_bounds__(256) void glu_dwconv_bwd_data_kernel(const bf16_t* __restrict__ dZ, const bf16_t* __restrict__ Y,
                                                                   const float* __restrict__ w, bf16_t* __restrict__ dY,
                                                                   int T, int C) {
-  constexpr int PAD = (KW - 1) / 2, ROWS = TTILE + KW - 1;
+  // dZ rows t - (KW-1-PADL) .. t + PADL feed dU[t]: the tile is staged from PAD = KW-1-PADL rows before its first output
+  constexpr int PAD = KW - 1 - PADL, ROWS = TTILE + KW - 1;
   // one buffer, two views: [dZ tile bf16 ROWS x CT][Y / dY tile bf16 2 x TTILE x CT] (fast path) or the dZ tile in fp32 (ragged path)
   constexpr int SDZ_BYTES = ROWS * CT * 2, SY_BYTES = 2 * TTILE * CT * 2;
   static_assert(SDZ_BYTES % 16 == 0 && SDZ_BYTES + SY_BYTES >= ROWS * CT * 4, "views of the shared buffer");
@@ -505,7 +490,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_data_kernel(const bf16_t* 
       const float x = bf2f(sdz[grp * TPT + r][cl]);
 #pragma unroll
       for (int j = 0; j < TPT; ++j) {
-        const int k = j + 2 * PAD - r;
+        const int k = j + (KW - 1) - r;
         if (k >= 0 && k < KW) acc[j] += wk[k] * x;
       }
     }
@@ -550,13 +535,13 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_data_kernel(const bf16_t* 
   float acc[TPT];
 #pragma unroll
   for (int j = 0; j < TPT; ++j) acc[j] = 0.f;
-  // dU[tout] needs dZ[tout + PAD - k]: LDS row (grp*TPT + j) + 2*PAD - k, i.e. tap k = j + 2*PAD - r for row offset r
+  // dU[tout] needs dZ[tout + PADL - k]: LDS row (grp*TPT + j) + KW-1 - k, i.e. tap k = j + KW-1 - r for row offset r
 #pragma unroll
   for (int r = 0; r < TPT + KW - 1; ++r) {
     const float x = sdf[grp * TPT + r][cl];
 #pragma unroll
     for (int j = 0; j < TPT; ++j) {
-      const int k = j + 2 * PAD - r;
+      const int k = j + (KW - 1) - r;
       if (k >= 0 && k < KW) acc[j] += wk[k] * x;
     }
   }
@@ -574,14 +559,14 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_data_kernel(const bf16_t* 
   }
 }
 
-// dw[c][k] += sum_{b,t} dZ[b,t,c] * U[b,t-PAD+k,c]
+// dw[c][k] += sum_{b,t} dZ[b,t,c] * U[b,t-PADL+k,c]
 // Weight gradient of the depthwise conv: workgroup = (CT channels, one utterance), looping over 64-step time tiles staged in
 // LDS; thread (channel, tap group of 8) keeps a sliding window of U in registers.  One partial [C][KW] slab per utterance
 // (no atomics), a second kernel sums the B slabs.
-template <int KW>
+template <int KW, int PADL>
 __global__ __launch_bounds__(256) void dwconv_bwd_weight_kernel(const bf16_t* __restrict__ dZ, const bf16_t* __restrict__ U,
                                                                 float* __restrict__ part, int T, int C, int tiles_per_block) {
-  constexpr int PAD = (KW - 1) / 2, ROWS = TTILE + KW - 1, KG = 8;
+  constexpr int PAD = PADL, ROWS = TTILE + KW - 1, KG = 8;
   __shared__ __attribute__((aligned(16))) float sU[ROWS + KG][CT];
   __shared__ __attribute__((aligned(16))) float sD[TTILE][CT];
   const int c0 = blockIdx.x * CT, b = blockIdx.z;
@@ -697,38 +682,47 @@ static inline int egrid_ch(long n, int nch) {
 
 }  // namespace
 
-#define EA_KW_DISPATCH(KW, FN, ...)                  \
-  switch (KW) {                                      \
-    case 3: FN<3>(__VA_ARGS__); break;               \
-    case 7: FN<7>(__VA_ARGS__); break;               \
-    case 15: FN<15>(__VA_ARGS__); break;             \
-    case 31: FN<31>(__VA_ARGS__); break;             \
-    default: return -2;                              \
+// FN<KW, PADL>: the left pad is (KW-1)/2 (the reference's symmetric module) or KW-1 (causal: no look-ahead)
+#define EA_KW_DISPATCH(KW, CAUSAL, FN, ...)                                          \
+  switch (KW) {                                                                      \
+    case 3: if (CAUSAL) FN<3, 2>(__VA_ARGS__); else FN<3, 1>(__VA_ARGS__); break;       \
+    case 7: if (CAUSAL) FN<7, 6>(__VA_ARGS__); else FN<7, 3>(__VA_ARGS__); break;       \
+    case 15: if (CAUSAL) FN<15, 14>(__VA_ARGS__); else FN<15, 7>(__VA_ARGS__); break;   \
+    case 31: if (CAUSAL) FN<31, 30>(__VA_ARGS__); else FN<31, 15>(__VA_ARGS__); break;  \
+    default: return -2;                                                              \
   }
 
-template <int KW>
+template <int KW, int PADL>
 static void launch_glu_dwconv_fwd(dim3 grid, hipStream_t stream, const bf16_t* Y, const float* w, bf16_t* U, bf16_t* Z,
                                   double* stats, int T, int C) {
-  hipLaunchKernelGGL((glu_dwconv_fwd_kernel<KW>), grid, dim3(256), 0, stream, Y, w, U, Z, stats, T, C);
+  hipLaunchKernelGGL((glu_dwconv_fwd_kernel<KW, PADL>), grid, dim3(256), 0, stream, Y, w, U, Z, stats, T, C);
 }
-template <int KW>
+template <int KW, int PADL>
 static void launch_glu_dwconv_bwd_data(dim3 grid, hipStream_t stream, const bf16_t* dZ, const bf16_t* Y, const float* w,
                                        bf16_t* dY, int T, int C) {
-  hipLaunchKernelGGL((glu_dwconv_bwd_data_kernel<KW>), grid, dim3(256), 0, stream, dZ, Y, w, dY, T, C);
+  hipLaunchKernelGGL((glu_dwconv_bwd_data_kernel<KW, PADL>), grid, dim3(256), 0, stream, dZ, Y, w, dY, T, C);
 }
-template <int KW>
+template <int KW, int PADL>
 static void launch_dwconv_bwd_weight(dim3 grid, hipStream_t stream, const bf16_t* dZ, const bf16_t* U, float* dw, int T,
                                      int C, int tiles_per_block) {
-  hipLaunchKernelGGL((dwconv_bwd_weight_kernel<KW>), grid, dim3(256), 0, stream, dZ, U, dw, T, C, tiles_per_block);
+  hipLaunchKernelGGL((dwconv_bwd_weight_kernel<KW, PADL>), grid, dim3(256), 0, stream, dZ, U, dw, T, C, tiles_per_block);
 }
 
-extern "C" int ea_glu_dwconv_fwd(const void* Y, const float* w, void* U, void* Z, double* stats, int B, int T,
-                                 int C, int KW, hipStream_t stream) {
+static int glu_dwconv_fwd(const void* Y, const float* w, void* U, void* Z, double* stats, int B, int T, int C, int KW, bool causal,
+                          hipStream_t stream) {
   if (B <= 0 || T <= 0) return 0;
   if (C % 2) return -2;
   dim3 grid((C + CT - 1) / CT, (T + TTILE - 1) / TTILE, B);
-  EA_KW_DISPATCH(KW, launch_glu_dwconv_fwd, grid, stream, (const bf16_t*)Y, w, (bf16_t*)U, (bf16_t*)Z, stats, T, C);
+  EA_KW_DISPATCH(KW, causal, launch_glu_dwconv_fwd, grid, stream, (const bf16_t*)Y, w, (bf16_t*)U, (bf16_t*)Z, stats, T, C);
   return EA_CHECK_LAUNCH();
+}
+extern "C" int ea_glu_dwconv_fwd(const void* Y, const float* w, void* U, void* Z, double* stats, int B, int T,
+                                 int C, int KW, hipStream_t stream) {
+  return glu_dwconv_fwd(Y, w, U, Z, stats, B, T, C, KW, false, stream);
+}
+extern "C" int ea_glu_dwconv_causal_fwd(const void* Y, const float* w, void* U, void* Z, double* stats, int B, int T,
+                                        int C, int KW, hipStream_t stream) {
+  return glu_dwconv_fwd(Y, w, U, Z, stats, B, T, C, KW, true, stream);
 }
 
 extern "C" int ea_bn_finalize(const double* stats, float* mean_rstd, float* running_mean, float* running_var, int C,
@@ -1011,23 +1005,40 @@ extern "C" long ea_dwconv_wgrad_workspace_bytes(int B, int T, int C, int KW) {
   return (long)B * dw_time_blocks(T) * C * KW * (long)sizeof(float);
 }
 
-extern "C" int ea_glu_dwconv_bwd(const void* dZ, const void* Y, const void* U, const float* w, void* dY, float* dw,
-                                 void* wgrad_ws, int B, int T, int C, int KW, hipStream_t stream) {
-  if (B <= 0 || T <= 0) return 0;
-  if (C % 2) return -2;
-  dim3 grid((C + CT - 1) / CT, (T + TTILE - 1) / TTILE, B);
-  EA_KW_DISPATCH(KW, launch_glu_dwconv_bwd_data, grid, stream, (const bf16_t*)dZ, (const bf16_t*)Y, w, (bf16_t*)dY, T, C);
-  if (!dw) return EA_CHECK_LAUNCH();  // data gradient only: the caller runs ea_dwconv_bwd_weight (optimizer-only) itself
-  return ea_dwconv_bwd_weight(dZ, U, dw, wgrad_ws, B, T, C, KW, stream);
-}
-extern "C" int ea_dwconv_bwd_weight(const void* dZ, const void* U, float* dw, void* wgrad_ws, int B, int T, int C, int KW,
-                                    hipStream_t stream) {
+static int dwconv_bwd_weight(const void* dZ, const void* U, float* dw, void* wgrad_ws, int B, int T, int C, int KW, bool causal,
+                            hipStream_t stream) {
   if (B <= 0 || T <= 0) return 0;
   dim3 gridw((C + CT - 1) / CT, dw_time_blocks(T), B);
   float* part = (float*)wgrad_ws;
-  EA_KW_DISPATCH(KW, launch_dwconv_bwd_weight, gridw, stream, (const bf16_t*)dZ, (const bf16_t*)U, part, T, C, DW_TILES_PER_BLOCK);
+  EA_KW_DISPATCH(KW, causal, launch_dwconv_bwd_weight, gridw, stream, (const bf16_t*)dZ, (const bf16_t*)U, part, T, C, DW_TILES_PER_BLOCK);
   const int nslab = (int)(gridw.y * gridw.z);
   hipLaunchKernelGGL(dwconv_weight_reduce_kernel, dim3((C * KW + 255) / 256, nslab >= 16 ? 8 : 1), dim3(256), 0, stream, part, dw,
                      nslab, C * KW);
   return EA_CHECK_LAUNCH();
+}
+static int glu_dwconv_bwd(const void* dZ, const void* Y, const void* U, const float* w, void* dY, float* dw, void* wgrad_ws, int B,
+                          int T, int C, int KW, bool causal, hipStream_t stream) {
+  if (B <= 0 || T <= 0) return 0;
+  if (C % 2) return -2;
+  dim3 grid((C + CT - 1) / CT, (T + TTILE - 1) / TTILE, B);
+  EA_KW_DISPATCH(KW, causal, launch_glu_dwconv_bwd_data, grid, stream, (const bf16_t*)dZ, (const bf16_t*)Y, w, (bf16_t*)dY, T, C);
+  if (!dw) return EA_CHECK_LAUNCH();  // data gradient only: the caller runs ea_dwconv_bwd_weight (optimizer-only) itself
+  return dwconv_bwd_weight(dZ, U, dw, wgrad_ws, B, T, C, KW, causal, stream);
+}
+
+extern "C" int ea_glu_dwconv_bwd(const void* dZ, const void* Y, const void* U, const float* w, void* dY, float* dw,
+                                 void* wgrad_ws, int B, int T, int C, int KW, hipStream_t stream) {
+  return glu_dwconv_bwd(dZ, Y, U, w, dY, dw, wgrad_ws, B, T, C, KW, false, stream);
+}
+extern "C" int ea_dwconv_bwd_weight(const void* dZ, const void* U, float* dw, void* wgrad_ws, int B, int T, int C, int KW,
+                                    hipStream_t stream) {
+  return dwconv_bwd_weight(dZ, U, dw, wgrad_ws, B, T, C, KW, false, stream);
+}
+extern "C" int ea_glu_dwconv_causal_bwd(const void* dZ, const void* Y, const void* U, const float* w, void* dY, float* dw,
+                                        void* wgrad_ws, int B, int T, int C, int KW, hipStream_t stream) {
+  return glu_dwconv_bwd(dZ, Y, U, w, dY, dw, wgrad_ws, B, T, C, KW, true, stream);
+}
+extern "C" int ea_dwconv_causal_bwd_weight(const void* dZ, const void* U, float* dw, void* wgrad_ws, int B, int T, int C, int KW,
+                                           hipStream_t stream) {
+  return dwconv_bwd_weight(dZ, U, dw, wgrad_ws, B, T, C, KW, true, stream);
 }

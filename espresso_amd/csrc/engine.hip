@@ -844,7 +844,7 @@ static void conv_fwd(Ctx& c, const ConvSaved& s, const EaLayerShape& sh, const E
     if (!c.dry && c.rc == 0) c.rc = hipMemsetAsync(stats, 0, 2 * C * sizeof(double), c.s) == hipSuccess ? 0 : -1;
   }
   if (R && c.rc == 0) stats = R->st[R->si];
-  RUN(ea_glu_dwconv_fwd(s.Y, w.dw, s.U, s.Z, stats, B, T, C, sh.KW, c.s));
+  RUN((sh.conv_causal ? ea_glu_dwconv_causal_fwd : ea_glu_dwconv_fwd)(s.Y, w.dw, s.U, s.Z, stats, B, T, C, sh.KW, c.s));
   if (ring) {
     if (R) {
       if (c.rc == 0) RUN(ea_bn_act_fwd_train(s.Z, stats, s.mr, w.bn_rm, w.bn_rv, w.bn_g, w.bn_b, s.Hh, M, C, EA_ACT_SILU, (float)M, 1e-5f, 0.1f,
@@ -894,18 +894,20 @@ static void conv_bwd(Ctx& c, const ConvSaved& s, const EaLayerShape& sh, const E
   uint16_t* dZ = sc.get<uint16_t>((size_t)M * C);
   uint16_t* dY = sc.get<uint16_t>((size_t)M * 2 * C);
   char* wws = sc.get<char>((size_t)ea_dwconv_wgrad_workspace_bytes(B, T, C, sh.KW));
+  const auto dw_bwd = sh.conv_causal ? ea_glu_dwconv_causal_bwd : ea_glu_dwconv_bwd;  // (EaLayerShape.conv_causal)
+  const auto dw_wgrad = sh.conv_causal ? ea_dwconv_causal_bwd_weight : ea_dwconv_bwd_weight;
   if (ring) {
     if (R && c.rc == 0) {
       red = R->red[R->ri];
       RUN(ea_bn_act_bwd_fused(s.Z, dH, s.mr, w.bn_g, w.bn_b, red, dZ, gw.bn_g, gw.bn_b, M, C, EA_ACT_SILU, sh.training, R->red[R->ri ^ 1],
                               2 * R->cap, c.s));
-      RUN(ea_glu_dwconv_bwd(dZ, s.Y, nullptr, w.dw, dY, nullptr, nullptr, B, T, C, sh.KW, c.s));
+      RUN(dw_bwd(dZ, s.Y, nullptr, w.dw, dY, nullptr, nullptr, B, T, C, sh.KW, c.s));
       if (c.rc == 0) R->ri ^= 1;
       else R->dirty = true;
     }
   } else {
     RUN(ea_bn_act_bwd(s.Z, dH, s.mr, w.bn_g, w.bn_b, red, dZ, nullptr, nullptr, M, C, EA_ACT_SILU, sh.training, c.s));
-    RUN(ea_glu_dwconv_bwd(dZ, s.Y, s.U, w.dw, dY, nullptr, wws, B, T, C, sh.KW, c.s));
+    RUN(dw_bwd(dZ, s.Y, s.U, w.dw, dY, nullptr, wws, B, T, C, sh.KW, c.s));
   }
   if (c.df) {
     if (!c.dry) {
@@ -914,14 +916,14 @@ static void conv_bwd(Ctx& c, const ConvSaved& s, const EaLayerShape& sh, const E
       const int KW = sh.KW;
       c.df->ops.push_back([=](hipStream_t st) {
         int rc = ring ? 0 : ea_bn_param_grad(red, gwv.bn_g, gwv.bn_b, C, st);
-        if (rc == 0) rc = ea_dwconv_bwd_weight(dZ, U, gwv.dw, wws, B, T, C, KW, st);
+        if (rc == 0) rc = dw_wgrad(dZ, U, gwv.dw, wws, B, T, C, KW, st);
         return rc;
       });
     }
   } else {
     fork(c);  // BatchNorm / depthwise-filter / pointwise-1 parameter gradients: optimizer-only
     if (!ring) RUN(ea_bn_param_grad(red, gw.bn_g, gw.bn_b, C, wstream(c)));
-    RUN(ea_dwconv_bwd_weight(dZ, s.U, gw.dw, wws, B, T, C, sh.KW, wstream(c)));
+    RUN(dw_wgrad(dZ, s.U, gw.dw, wws, B, T, C, sh.KW, wstream(c)));
   }
   wgrad(c, dY, 2 * C, s.xn, C, gw.pw1, M, 2 * C, C);
   uint16_t* dxn = sc.get<uint16_t>((size_t)M * C);

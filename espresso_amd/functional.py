@@ -652,14 +652,14 @@ class _ConvModule(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ln_g, ln_b, wpw1, wdw, bn_g, bn_b, wpw2, wpw1_16, wpw2_16, running_mean, running_var, B, T, KW,
-                p_out, eps, bn_eps, bn_momentum, training):
+                p_out, eps, bn_eps, bn_momentum, training, causal=False):
         M, C = x.shape
         xn, mean, rstd = K.layernorm_fwd(x, ln_g, ln_b, eps)
         Y = _new((M, 2 * C), torch.bfloat16, x)
         K.gemm(xn, wpw1_16, Y, M, 2 * C, C, lda=C, ldb=C, ldc=2 * C)
         wdw2 = wdw.detach().reshape(C, KW).contiguous()
         stats = torch.zeros(2 * C, dtype=torch.float64, device=x.device) if training else None
-        U, Zt = K.glu_dwconv_fwd(Y, wdw2, B, T, C, KW, stats)
+        U, Zt = K.glu_dwconv_fwd(Y, wdw2, B, T, C, KW, stats, causal=causal)
         if training:
             mr = K.bn_finalize(stats, C, M, bn_eps, bn_momentum, running_mean, running_var)
         else:
@@ -669,14 +669,14 @@ class _ConvModule(torch.autograd.Function):
         y = _new((M, C), torch.bfloat16, x)
         K.gemm(Hh, wpw2_16, y, M, C, C, lda=C, ldb=C, ldc=C, drop_p=p_out, drop_seed=so, resid=x, ldr=C)
         ctx.save_for_backward(x, ln_g, mean, rstd, xn, Y, U, Zt, mr, Hh, bn_g, bn_b, wdw2, wpw1_16, wpw2_16)
-        ctx.cfg = (B, T, KW, p_out, so, training)
+        ctx.cfg = (B, T, KW, p_out, so, training, causal)
         ctx.wdw_shape = wdw.shape
         return y
 
     @staticmethod
     def backward(ctx, dy):
         (x, ln_g, mean, rstd, xn, Y, U, Zt, mr, Hh, bn_g, bn_b, wdw2, wpw1_16, wpw2_16) = ctx.saved_tensors
-        B, T, KW, p_out, so, training = ctx.cfg
+        B, T, KW, p_out, so, training, causal = ctx.cfg
         M, C = x.shape
         dy = dy.contiguous()
         g = K.scale_dropout(dy, a=1.0, drop_p=p_out, drop_seed=so) if p_out > 0 else dy
@@ -686,22 +686,23 @@ class _ConvModule(torch.autograd.Function):
         dbn_g, dbn_b = _zeros_f32(C, x), _zeros_f32(C, x)
         dZ = K.bn_act_bwd(Zt, dH, mr, bn_g, bn_b, dbn_g, dbn_b, "silu", training)
         dwdw = _zeros_f32(C * KW, x)
-        dY = K.glu_dwconv_bwd(dZ, Y, U, wdw2, dwdw, B, T, C, KW)
+        dY = K.glu_dwconv_bwd(dZ, Y, U, wdw2, dwdw, B, T, C, KW, causal=causal)
         dWpw1 = _wgrad(dY, xn, M, 2 * C, C)
         dxn = _new((M, C), torch.bfloat16, x)
         K.gemm(dY, wpw1_16, dxn, M, C, 2 * C, lda=2 * C, ldb=C, ldc=C, b_kstrided=True)
         dg, db = _zeros_f32(C, x), _zeros_f32(C, x)
         dx = K.layernorm_bwd(x, dxn, ln_g, mean, rstd, dg, db, dx_add=dy)
-        return (dx, dg, db, dWpw1.view(2 * C, C, 1), dwdw.view(ctx.wdw_shape), dbn_g, dbn_b, dWpw2.view(C, C, 1)) + (None,) * 12
+        return (dx, dg, db, dWpw1.view(2 * C, C, 1), dwdw.view(ctx.wdw_shape), dbn_g, dbn_b, dWpw2.view(C, C, 1)) + (None,) * 13
 
 
 def conv_module(x, ln_g, ln_b, wpw1, wdw, bn_g, bn_b, wpw2, running_mean, running_var, B, T, p_out=0.0, eps=1e-5,
-                bn_eps=1e-5, bn_momentum=0.1, training=True):
+                bn_eps=1e-5, bn_momentum=0.1, training=True, causal=False):
+    """causal: the depthwise convolution pads KW-1 frames on the left and none on the right (encoder.depthwise_conv_causal)."""
     C = x.shape[1]
     KW = wdw.shape[-1]
     return _ConvModule.apply(x, ln_g, ln_b, wpw1, wdw, bn_g, bn_b, wpw2, bf16_weight(wpw1).view(2 * C, C),
                              bf16_weight(wpw2).view(C, C), running_mean, running_var, B, T, KW, p_out, eps, bn_eps,
-                             bn_momentum, training)
+                             bn_momentum, training, bool(causal))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1154,6 +1155,7 @@ def refresh_layer_transposes(layers, B, T):
         sh.B, sh.T, sh.C, sh.H = B, T, m.embed_dim, m.num_heads
         sh.F = m.ffn1.w_1.weight.shape[0]
         sh.KW = m.conv_module.depthwise_conv.weight.shape[-1]
+        sh.conv_causal = int(m.conv_module.causal)
         sh.training = 1
         _lib.check(lib.ea_conformer_layer_refresh_wt(ctypes.byref(bind.L), ctypes.byref(sh), ctypes.c_void_p(side.cuda_stream)),
                    "ea_conformer_layer_refresh_wt")
@@ -1187,7 +1189,8 @@ def _chain_pre_buffer(like):
 
 
 def _chain_key(sh):
-    return (sh.B, sh.T, sh.C, sh.H, sh.F, sh.KW, sh.training, sh.has_attn_mask, sh.p_drop, sh.p_act, sh.p_attn)
+    return (sh.B, sh.T, sh.C, sh.H, sh.F, sh.KW, sh.conv_causal, sh.training, sh.has_attn_mask, sh.p_drop, sh.p_act,
+            sh.p_attn)
 
 
 class _ConformerLayerNative(torch.autograd.Function):
@@ -1203,6 +1206,7 @@ class _ConformerLayerNative(torch.autograd.Function):
         sh.B, sh.T, sh.C, sh.H = B, T, module.embed_dim, module.num_heads
         sh.F = module.ffn1.w_1.weight.shape[0]
         sh.KW = module.conv_module.depthwise_conv.weight.shape[-1]
+        sh.conv_causal = int(module.conv_module.causal)
         sh.training = int(training)
         # (the encoder refreshed this layer's transposed weight copies on a side stream before its layer loop: refresh_layer_transposes)
         sh.wt_fresh = int(bool(training) and module.__dict__.pop("_ea_wt_fresh", None) is bind)
@@ -1268,7 +1272,8 @@ class _ConformerLayerNative(torch.autograd.Function):
         scratch = _scratch_buffer(ctx.nb_scratch, x.device)
         sh = ctx.sh
         # everything the arena layout depends on (shape, which optional buffers exist, runtime switches via the byte count)
-        tag = (scratch.data_ptr(), ctx.nb_scratch, sh.B, sh.T, sh.C, sh.H, sh.F, sh.KW, sh.training, sh.has_attn_mask,
+        tag = (scratch.data_ptr(), ctx.nb_scratch, sh.B, sh.T, sh.C, sh.H, sh.F, sh.KW, sh.conv_causal, sh.training,
+                   sh.has_attn_mask,
                sh.p_drop > 0, sh.p_act > 0, sh.p_attn > 0)
         dev = str(x.device)
         half = _native_bwd_begin(sh, dev, tag, deferrable=ctx.owns_arena)
@@ -1346,6 +1351,7 @@ class _ConformerStackNative(torch.autograd.Function):
             sh.B, sh.T, sh.C, sh.H = B, T, m.embed_dim, m.num_heads
             sh.F = m.ffn1.w_1.weight.shape[0]
             sh.KW = m.conv_module.depthwise_conv.weight.shape[-1]
+            sh.conv_causal = int(m.conv_module.causal)
             sh.training = int(training)
             sh.wt_fresh = int(bool(training) and m.__dict__.pop("_ea_wt_fresh", None) is bind)
             sh.p_drop, sh.p_act, sh.p_attn = p_drop, p_act, p_attn
@@ -1387,7 +1393,8 @@ class _ConformerStackNative(torch.autograd.Function):
         halves = [None] * n
         for k in range(n - 1, -1, -1):  # the bookkeeping of n consecutive layer calls: alternating halves, clean-scratch flags
             sh = arr[k].shape
-            tag = (scratch.data_ptr(), ctx.nb_scratch, sh.B, sh.T, sh.C, sh.H, sh.F, sh.KW, sh.training, sh.has_attn_mask,
+            tag = (scratch.data_ptr(), ctx.nb_scratch, sh.B, sh.T, sh.C, sh.H, sh.F, sh.KW, sh.conv_causal, sh.training,
+                   sh.has_attn_mask,
                    sh.p_drop > 0, sh.p_act > 0, sh.p_attn > 0)
             halves[k] = _native_bwd_begin(sh, dev, tag, deferrable=True)
         dbuf = torch.empty((2,) + tuple(x.shape), dtype=x.dtype, device=x.device)

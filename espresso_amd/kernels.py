@@ -301,11 +301,12 @@ def add2_strided(a, lda, b, ldb, out, ldo, M, C, out_off=0):
     return out
 
 
-def glu_dwconv_fwd(Y, w, B, T, C, KW, stats):
+def glu_dwconv_fwd(Y, w, B, T, C, KW, stats, causal=False):
+    """causal: left padding KW-1, no look-ahead (ea_glu_dwconv_causal_fwd) instead of the symmetric (KW-1)/2."""
     U = torch.empty(B * T, C, dtype=torch.bfloat16, device=Y.device)
     Z = torch.empty(B * T, C, dtype=torch.bfloat16, device=Y.device)
-    check(_lib.lib().ea_glu_dwconv_fwd(_p(Y), _p(w), _p(U), _p(Z), _p(stats), B, T, C, KW, _stream()),
-          "ea_glu_dwconv_fwd")
+    name = "ea_glu_dwconv_causal_fwd" if causal else "ea_glu_dwconv_fwd"
+    check(getattr(_lib.lib(), name)(_p(Y), _p(w), _p(U), _p(Z), _p(stats), B, T, C, KW, _stream()), name)
     return U, Z
 
 
@@ -355,11 +356,11 @@ def bn_act_bwd(Z, dH, mean_rstd, gamma, beta, dgamma, dbeta, act, training=True)
     return dZ
 
 
-def glu_dwconv_bwd(dZ, Y, U, w, dw, B, T, C, KW):
+def glu_dwconv_bwd(dZ, Y, U, w, dw, B, T, C, KW, causal=False):
     dY = torch.empty(B * T, 2 * C, dtype=torch.bfloat16, device=Y.device)
     ws = torch.empty(int(_lib.lib().ea_dwconv_wgrad_workspace_bytes(B, T, C, KW)), dtype=torch.uint8, device=Y.device)
-    check(_lib.lib().ea_glu_dwconv_bwd(_p(dZ), _p(Y), _p(U), _p(w), _p(dY), _p(dw), _p(ws), B, T, C, KW, _stream()),
-          "ea_glu_dwconv_bwd")
+    name = "ea_glu_dwconv_causal_bwd" if causal else "ea_glu_dwconv_bwd"
+    check(getattr(_lib.lib(), name)(_p(dZ), _p(Y), _p(U), _p(w), _p(dY), _p(dw), _p(ws), B, T, C, KW, _stream()), name)
     return dY
 
 
@@ -1436,6 +1437,29 @@ def stream_attention(qu, qv, cache, pp, pp_center, meta, frames, B, H, dh, chunk
                                          _p(meta[0]), _p(meta[1]), _p(meta[2]), _p(frames), _p(out), out.stride(0), B, H, dh,
                                          chunk_size, left_chunks, max_streams, rows, _stream()), "ea_stream_attention")
     return out
+
+
+def stream_convmodule_supported(C, KW, chunk_size) -> bool:
+    return bool(_lib.lib().ea_stream_convmodule_supported(C, KW, chunk_size))
+
+
+def stream_glu_dwconv_bn_act(Y, w, mean_rstd, gamma, beta, carry, meta, B, chunk_size, want_z=False):
+    """Streamed middle of a causal conv module for the new rows of B entries (include/espresso_amd.h).  Y bf16 [rows][2C];
+    w fp32 [C][KW]; carry bf16 [max_streams][KW-1][C], updated in place; meta int32 [3][B] = (slot_idx, n_new, row_off).
+    Returns H bf16 [rows][C], or (H, Z) with want_z."""
+    rows, C = Y.shape[0], Y.shape[1] // 2
+    KW = w.shape[1]
+    assert Y.dtype == torch.bfloat16 and Y.is_contiguous() and Y.shape[1] == 2 * C
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.shape == (C, KW)
+    assert mean_rstd.dtype == torch.float32 and mean_rstd.is_contiguous() and mean_rstd.numel() == 2 * C
+    assert meta.dtype == torch.int32 and meta.shape == (3, B) and meta.is_contiguous()
+    assert carry.dtype == torch.bfloat16 and carry.is_contiguous() and carry.shape[1:] == (KW - 1, C)
+    H = torch.empty(rows, C, dtype=torch.bfloat16, device=Y.device)
+    Z = torch.empty(rows, C, dtype=torch.bfloat16, device=Y.device) if want_z else None
+    check(_lib.lib().ea_stream_glu_dwconv_bn_act(_p(Y), _p(w), _p(mean_rstd), _p(gamma), _p(beta), _p(carry), _p(meta[0]),
+                                                 _p(meta[1]), _p(meta[2]), _p(H), _p(Z), B, C, KW, chunk_size, carry.shape[0], rows,
+                                                 _stream()), "ea_stream_glu_dwconv_bn_act")
+    return (H, Z) if want_z else H
 
 
 def stream_advance(frames, meta, B, chunk_size):

@@ -30,6 +30,9 @@ class SpeechEncoderConfig:
     chunk_left_window: int = 0
     chunk_right_window: int = 0
     depthwise_conv_kernel_size: int = 31
+    # Conformer layers only (the reference has no such option): the depthwise convolution pads kernel_size - 1 frames on the left
+    # and none on the right, so a layer looks at no future frame and the encoder can be streamed (StreamingEncoder)
+    depthwise_conv_causal: bool = False
 
 
 @dataclass

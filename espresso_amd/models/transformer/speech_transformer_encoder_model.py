@@ -70,6 +70,9 @@ class SpeechTransformerEncoderBase(nn.Module):
         else:
             rels = [SinusoidalRelativePositionalEmbedding(d)] * nl
         self.rel_pos_embed = [rels[0]]
+        if getattr(cfg.encoder, "depthwise_conv_causal", False) and cfg.encoder.layer_type != "conformer":
+            raise ValueError(f"encoder.depthwise_conv_causal needs encoder.layer_type: conformer (got {cfg.encoder.layer_type}: "
+                             "only the conformer layer has a depthwise convolution)")
         if cfg.encoder.layer_type == "conformer":
             layer_cls = ConformerWithRelativePositionalEmbeddingEncoderLayer
         elif cfg.encoder.layer_type == "transformer":

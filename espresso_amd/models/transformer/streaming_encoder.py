@@ -1,4 +1,5 @@
-"""StreamingEncoder — exact chunk-by-chunk inference of a chunk-streaming transformer encoder for many streams at once.
+"""StreamingEncoder — exact chunk-by-chunk inference of a chunk-streaming transformer or causal-conformer encoder for many
+streams at once.
 
 A model trained with `encoder.chunk_size = cs > 0`, `chunk_left_window = L`, `chunk_right_window = 0` sees, for a frame of
 chunk c, the frames of chunks c-L .. c (tools/utils.py chunk_streaming_mask, always_partial_in_last=True at inference).  With
@@ -11,6 +12,12 @@ zero padding then sits only where the offline pass has it (utterance start and t
 State per stream: unconsumed feature frames (and samples) incl. the look-ahead and the left margin; one bf16 ring of
 (L+1)*cs slots x 2C per layer (kernels.stream_kv_append / stream_attention); a device frame counter.  The host mirrors
 the counters from the lengths it is given, so no device value is read back to run a chunk.
+
+Conformer layers stream only with `encoder.depthwise_conv_causal`: the depthwise convolution then reads the frame and the
+KW-1 before it, so a layer keeps, besides its K / V ring, the last KW-1 rows of the convolution's input per stream (bf16
+[KW-1][C], zero at the start of an utterance: its left padding; kernels.stream_glu_dwconv_bn_act).  BatchNorm uses the running
+statistics, as every inference pass does.  The reference's symmetric module looks (KW-1)/2 frames ahead in each layer and is
+refused.
 
 LayerNorm, the QKV / out-proj / FFN GEMMs and the sub-sampler are the offline path's kernels, run on the [sum n_new][C] rows
 of all streams that have a chunk ready."""
@@ -25,10 +32,13 @@ from ... import kernels as K
 def check_streamable(cfg):
     """Raise, naming the option, for encoder configurations whose streaming pass cannot equal the offline one."""
     e = cfg.encoder
-    if e.layer_type != "transformer":
+    causal = bool(getattr(e, "depthwise_conv_causal", False))
+    if e.layer_type != "transformer" and not (e.layer_type == "conformer" and causal):
+        ahead = (int(getattr(e, "depthwise_conv_kernel_size", 31)) - 1) // 2
         raise NotImplementedError(
-            f"streaming needs encoder.layer_type: transformer (got {e.layer_type}: the conformer's depthwise convolution looks "
-            "15 frames ahead in every layer)")
+            f"streaming needs encoder.layer_type: transformer, or conformer with encoder.depthwise_conv_causal: true (got "
+            f"{e.layer_type} with depthwise_conv_causal: {causal}: the symmetric depthwise convolution looks {ahead} frames ahead in "
+            "every layer)")
     if int(e.chunk_size) <= 0:
         raise NotImplementedError("streaming needs a chunk-streaming model: encoder.chunk_size must be > 0")
     if int(e.chunk_right_window) > 0:
@@ -41,6 +51,12 @@ def check_streamable(cfg):
     tc = speech_utils.eval_str_nested_list_or_tuple(e.transformer_context, type=int)
     if tc is not None and (tc[0] is not None or tc[1] is not None):
         raise NotImplementedError("streaming does not implement encoder.transformer_context (use chunk_size / chunk_left_window)")
+    if e.layer_type == "conformer":
+        C, KW, cs = int(e.embed_dim), int(e.depthwise_conv_kernel_size), int(e.chunk_size)
+        if C % 8 or KW not in (3, 7, 15, 31) or cs > 128:  # what ea_stream_convmodule_supported refuses
+            raise NotImplementedError(
+                f"streaming a conformer needs encoder.embed_dim % 8 == 0, encoder.depthwise_conv_kernel_size in (3, 7, 15, 31) and "
+                f"encoder.chunk_size <= 128 (got embed_dim {C}, depthwise_conv_kernel_size {KW}, chunk_size {cs})")
 
 
 class _Stream:
@@ -87,6 +103,23 @@ class StreamingEncoder:
         nl = len(enc.layers)
         self.caches = [torch.zeros(self.max_streams, self.W, 2 * self.C, dtype=torch.bfloat16, device=self.device) for _ in range(nl)]
         self.frames = torch.zeros(self.max_streams, dtype=torch.int32, device=self.device)
+        # conformer layers: the last KW-1 rows of the depthwise convolution's input per stream, and BatchNorm's mean / rstd from
+        # the running statistics (constants of an inference pass)
+        self.conformer = cfg.encoder.layer_type == "conformer"
+        self.KW = int(cfg.encoder.depthwise_conv_kernel_size) if self.conformer else 0
+        self.carries, self._bn_mr, self._dw_w, self._carry_all = [], [], [], None
+        if self.conformer:
+            if not K.stream_convmodule_supported(self.C, self.KW, self.cs):
+                raise NotImplementedError(f"ea_stream_glu_dwconv_bn_act does not take embed_dim {self.C}, depthwise_conv_kernel_size "
+                                          f"{self.KW}, chunk_size {self.cs}")
+            # one allocation [layers][max_streams][KW-1][C], so that open() clears a slot's rows of every layer in one launch
+            self._carry_all = torch.zeros(nl, self.max_streams, self.KW - 1, self.C, dtype=torch.bfloat16, device=self.device)
+            self.carries = [self._carry_all[i] for i in range(nl)]
+            with torch.no_grad():
+                for l in enc.layers:
+                    bn = l.conv_module.batch_norm
+                    self._bn_mr.append(K.bn_from_running(bn.running_mean, bn.running_var, bn.eps))
+                    self._dw_w.append(l.conv_module.depthwise_conv.weight.detach().float().reshape(self.C, self.KW).contiguous())
         self.streams: Dict[object, _Stream] = {}
         self._free = list(range(self.max_streams - 1, -1, -1))
         self._zero_table = None
@@ -110,7 +143,7 @@ class StreamingEncoder:
         return pp
 
     def cache_bytes_per_stream(self) -> int:
-        return len(self.caches) * self.W * 2 * self.C * 2
+        return len(self.caches) * self.W * 2 * self.C * 2 + len(self.carries) * (self.KW - 1) * self.C * 2
 
     # ---- stream management ---------------------------------------------------------------------------------------------
     def open(self, stream_ids: Sequence):
@@ -122,6 +155,8 @@ class StreamingEncoder:
             st = _Stream(self._free.pop())
             self.streams[sid] = st
             self.frames[st.slot:st.slot + 1].zero_()
+            if self._carry_all is not None:  # the utterance's left zero padding
+                self._carry_all[:, st.slot].zero_()
 
     def close(self, stream_ids: Sequence):
         for sid in stream_ids:
@@ -265,8 +300,9 @@ class StreamingEncoder:
             x = self._add_positions(x, pos64)
         if enc.layernorm_embedding is not None:
             x = F.layer_norm(x, enc.layernorm_embedding.weight, enc.layernorm_embedding.bias)
+        run_layer = self._conformer_layer if self.conformer else self._layer
         for li, layer in enumerate(enc.layers):
-            x = self._layer(layer, li, x, meta, B, M)
+            x = run_layer(layer, li, x, meta, B, M)
         if enc.layer_norm is not None:
             x = F.layer_norm(x, enc.layer_norm.weight, enc.layer_norm.bias)
         K.stream_advance(self.frames, meta, B, cs)
@@ -293,10 +329,10 @@ class StreamingEncoder:
             table = enc._sin_table
         return F.add_positions(x, table, pos, enc.embed_scale)
 
-    def _layer(self, layer, li, x, meta, B, M):
+    def _attention(self, layer, li, x, meta, B, M, pre_ln):
+        """x + out_proj(attention over the ring cache) of the new rows; `pre_ln`: LayerNorm before the QKV projection."""
         C, H, dh, cs, L = self.C, self.H, self.dh, self.cs, self.L
         a = layer.self_attn
-        pre_ln = layer.normalize_before
         pp = self._pp[li]
         ln1 = layer.self_attn_layer_norm
         xn = K.layernorm_fwd(x, ln1.weight, ln1.bias, 1e-5)[0] if pre_ln else x
@@ -315,6 +351,12 @@ class StreamingEncoder:
         o = K.stream_attention(qu, qv, self.caches[li], pp, self.W - 1, meta, self.frames, B, H, dh, cs, L)
         y = torch.empty(M, C, dtype=torch.bfloat16, device=x.device)
         K.gemm(o, F.bf16_weight(a.out_proj.weight), y, M, C, C, lda=C, ldb=C, ldc=C, bias=a.out_proj.bias, resid=x, ldr=C)
+        return y
+
+    def _layer(self, layer, li, x, meta, B, M):
+        pre_ln = layer.normalize_before
+        ln1 = layer.self_attn_layer_norm
+        y = self._attention(layer, li, x, meta, B, M, pre_ln)
         act = "silu" if layer.activation_fn == "swish" else layer.activation_fn
         fl = layer.final_layer_norm
         if pre_ln:
@@ -323,3 +365,24 @@ class StreamingEncoder:
         y = F.layer_norm(y, ln1.weight, ln1.bias)
         y = F.ffn_module(y, None, None, layer.fc1.weight, layer.fc1.bias, layer.fc2.weight, layer.fc2.bias, act=act, out_scale=1.0)
         return F.layer_norm(y, fl.weight, fl.bias)
+
+    def _conformer_layer(self, layer, li, x, meta, B, M):
+        """ConformerWithRelativePositionalEmbeddingEncoderLayer.forward for the new rows: ffn1, attention over the ring cache, the
+        convolution module with the carried rows, ffn2, final LayerNorm."""
+        C = self.C
+        f = layer.ffn1
+        x = F.ffn_module(x, f.layer_norm.weight, f.layer_norm.bias, f.w_1.weight, f.w_1.bias, f.w_2.weight, f.w_2.bias, act="silu",
+                         out_scale=0.5)
+        x = self._attention(layer, li, x, meta, B, M, True)
+        c = layer.conv_module
+        xn = K.layernorm_fwd(x, c.layer_norm.weight, c.layer_norm.bias, 1e-5)[0]
+        Y = torch.empty(M, 2 * C, dtype=torch.bfloat16, device=x.device)
+        K.gemm(xn, F.bf16_weight(c.pointwise_conv1.weight).view(2 * C, C), Y, M, 2 * C, C, lda=C, ldb=C, ldc=2 * C)
+        Hh = K.stream_glu_dwconv_bn_act(Y, self._dw_w[li], self._bn_mr[li], c.batch_norm.weight, c.batch_norm.bias, self.carries[li],
+                                        meta, B, self.cs)
+        y = torch.empty(M, C, dtype=torch.bfloat16, device=x.device)
+        K.gemm(Hh, F.bf16_weight(c.pointwise_conv2.weight).view(C, C), y, M, C, C, lda=C, ldb=C, ldc=C, resid=x, ldr=C)
+        f = layer.ffn2
+        y = F.ffn_module(y, f.layer_norm.weight, f.layer_norm.bias, f.w_1.weight, f.w_1.bias, f.w_2.weight, f.w_2.bias, act="silu",
+                         out_scale=0.5)
+        return F.layer_norm(y, layer.final_layer_norm.weight, layer.final_layer_norm.bias)

@@ -88,9 +88,10 @@ class MultiheadAttentionParams(nn.Module):
 class ConvolutionModule(nn.Module):
     """fairseq/modules/conformer_layer.py:21-77 storage."""
 
-    def __init__(self, dim, kernel_size):
+    def __init__(self, dim, kernel_size, causal=False):
         super().__init__()
         assert (kernel_size - 1) % 2 == 0
+        self.causal = bool(causal)  # depthwise conv: left padding kernel_size - 1, no look-ahead (same parameters either way)
         self.layer_norm = LayerNormParams(dim)
         self.pointwise_conv1 = ConvParams(dim, 2 * dim, 1, bias=False)
         self.depthwise_conv = ConvParams(dim, dim, kernel_size, groups=dim, bias=False)
@@ -110,7 +111,8 @@ class ConformerWithRelativePositionalEmbeddingEncoderLayer(nn.Module):
         self.self_attn = MultiheadAttentionParams(d, self.num_heads, relpos=positional_embedding is not None,
                                                   positional_embedding=positional_embedding)
         self.self_attn_layer_norm = LayerNormParams(d)
-        self.conv_module = ConvolutionModule(d, cfg.encoder.depthwise_conv_kernel_size)
+        self.conv_module = ConvolutionModule(d, cfg.encoder.depthwise_conv_kernel_size,
+                                             causal=getattr(cfg.encoder, "depthwise_conv_causal", False))
         self.ffn2 = FeedForwardModule(d, cfg.encoder.ffn_embed_dim)
         self.final_layer_norm = LayerNormParams(d)
 
@@ -147,7 +149,7 @@ class ConformerWithRelativePositionalEmbeddingEncoderLayer(nn.Module):
         x = F.conv_module(x, c.layer_norm.weight, c.layer_norm.bias, c.pointwise_conv1.weight, c.depthwise_conv.weight,
                           c.batch_norm.weight, c.batch_norm.bias, c.pointwise_conv2.weight, c.batch_norm.running_mean,
                           c.batch_norm.running_var, B, T, p_out=p_drop, bn_eps=c.batch_norm.eps,
-                          bn_momentum=c.batch_norm.momentum, training=tr)
+                          bn_momentum=c.batch_norm.momentum, training=tr, causal=c.causal)
         if tr and not getattr(self, "_counters_managed", False):
             c.batch_norm.num_batches_tracked += 1
         f = self.ffn2

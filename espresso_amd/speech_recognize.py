@@ -285,7 +285,7 @@ def get_parser():
                    help="collect the attention alignments; --search beam saves RESULTS_PATH/attn_plots/<utt>.pdf of the best "
                         "hypothesis (needs --results-path and matplotlib)")
     p.add_argument("--streaming", action="store_true",
-                   help="chunk-by-chunk recognition of a chunk-streaming transformer encoder (--search ctc, transducer_greedy, "
+                   help="chunk-by-chunk recognition of a chunk-streaming transformer or causal-conformer encoder (--search ctc, transducer_greedy, "
                         "transducer_stream_beam, ctc_stream_beam, or ctc_beam with --ngram-lm): audio is fed in pieces of --stream-chunk-ms with --streams utterances in flight")
     p.add_argument("--stream-chunk-ms", type=int, default=None, help="--streaming: audio per piece (default 400)")
     p.add_argument("--streams", type=int, default=None, help="--streaming: concurrent utterances (default 16)")
@@ -717,7 +717,7 @@ def main(argv=None):
         cfg_cls = getattr(registry.MODEL_REGISTRY[model_name], "config_class", None)
         cfg0 = cfg_cls.from_dict(model_cfg) if cfg_cls is not None else None
         if cfg0 is None or not hasattr(cfg0, "encoder") or not hasattr(cfg0.encoder, "chunk_size"):
-            raise NotImplementedError(f"--streaming needs a chunk-streaming transformer encoder model, not {model_name}")
+            raise NotImplementedError(f"--streaming needs a chunk-streaming transformer or causal-conformer encoder model, not {model_name}")
         check_streamable(cfg0)
     if args.search in ("transducer_frame_beam", "transducer_stream_beam"):  # before the weights are loaded: a transducer model
         from . import registry

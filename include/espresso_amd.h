@@ -8,6 +8,10 @@
  * tasks,tools}) binds these through ctypes (espresso_amd/_lib.py); INTEGRATION.md shows the stub
  * a reference maintainer would add.  Each declaration cites the reference code it replaces
  * (paths relative to the reference root).
+ * Entry points without a counterpart in the reference say so where they are declared: the streaming
+ * kernels (ea_stream_*) and the causal depthwise convolution of the Conformer convolution module
+ * (ea_glu_dwconv_causal_*, ea_dwconv_causal_bwd_weight, EaLayerShape.conv_causal, ea_stream_glu_dwconv_bn_act), which
+ * exists so that a Conformer encoder can be streamed: the reference's module pads symmetrically.
  *
  * Conventions: every function returns 0 on success, a negative value on a launch/argument
  * error; all pointers are DEVICE pointers unless the name ends in _host; `stream` is a
@@ -305,7 +309,8 @@ int ea_add2_strided_bf16(const void* a, long lda, const void* b, long ldb, void*
 
 /* ------------------------------------------------------------------------------------------
  * Conformer convolution module middle — fairseq/modules/conformer_layer.py:79-101:
- * GLU -> depthwise Conv1d (k in {3,7,15,31}, pad (k-1)/2, no bias) -> BatchNorm1d -> SiLU.
+ * GLU -> depthwise Conv1d (k in {3,7,15,31}, pad (k-1)/2, no bias) -> BatchNorm1d -> SiLU; a causal variant (left pad k-1)
+ * follows the symmetric entry points, and csrc/stream_convmodule.hip streams it chunk by chunk.
  * Y: bf16 [B*T][2C] (pointwise_conv1 output); U,Z,H: bf16 [B*T][C]; w: fp32 [C][KW];
  * stats: fp64 [2][C] (sum, sum of squares) zeroed by the caller — double accumulators make the atomics' order invisible
  * in the fp32 statistics (reproducible forward); red: fp32 [2][C] zeroed by the caller; mean_rstd: fp32 [2][C].
@@ -327,6 +332,16 @@ int ea_glu_dwconv_bwd(const void* dZ, const void* Y, const void* U, const float*
                       void* wgrad_ws, int B, int T, int C, int KW, ea_stream_t stream);
 /* ea_glu_dwconv_bwd with dw == NULL computes dY only; the depthwise weight gradient (optimizer-only) on its own: */
 int ea_dwconv_bwd_weight(const void* dZ, const void* U, float* dw, void* wgrad_ws, int B, int T, int C, int KW, ea_stream_t stream);
+/* The CAUSAL depthwise convolution (encoder.depthwise_conv_causal; the reference has no such option): left padding KW-1 and no
+ * look-ahead, Z[t] = sum_k w[k] * U[t - (KW-1) + k] per utterance with zeros before frame 0, where the symmetric entry points
+ * above read U[t - (KW-1)/2 + k].  Same arguments, layouts, tap order, fp32 accumulation and bf16 rounding points as their
+ * twins (the same kernel templates with another left pad); ea_dwconv_wgrad_workspace_bytes serves both. */
+int ea_glu_dwconv_causal_fwd(const void* Y, const float* w, void* U, void* Z, double* stats, int B, int T, int C, int KW,
+                             ea_stream_t stream);
+int ea_glu_dwconv_causal_bwd(const void* dZ, const void* Y, const void* U, const float* w, void* dY, float* dw,
+                             void* wgrad_ws, int B, int T, int C, int KW, ea_stream_t stream);
+int ea_dwconv_causal_bwd_weight(const void* dZ, const void* U, float* dw, void* wgrad_ws, int B, int T, int C, int KW,
+                                ea_stream_t stream);
 /* Training-mode BatchNorm + activation forward in one launch (ea_bn_finalize + ea_bn_act_fwd): mean / rstd come straight from
  * the fp64 batch sums `stats` ([2][C]: sum, sum of squares over n rows), are recorded in mean_rstd for the backward pass, the
  * running statistics are updated (torch.nn.BatchNorm1d: momentum, unbiased variance), and zero_next (fp64 [zero_n] or NULL) is
@@ -824,6 +839,9 @@ typedef struct EaLayerShape {
    * update (the caller ran ea_conformer_layer_refresh_wt after the optimizer step, typically on another stream under the
    * sub-sampler's forward pass) - the forward call then skips its own transposes.  0 = the call refreshes them itself. */
   int wt_fresh;
+  /* Conformer layer: 1 = the convolution module's depthwise convolution is causal (ea_glu_dwconv_causal_*: left pad KW-1, no
+   * look-ahead; encoder.depthwise_conv_causal), 0 = the reference's symmetric one. */
+  int conv_causal;
 } EaLayerShape;
 
 /* Dropout sites of a layer call (FairseqDropout calls of the reference, cited per site) and the mask stream each one uses.
@@ -1182,6 +1200,24 @@ int ea_stream_attention(const void* qu, const void* qv, long ldq, const void* ca
                         ea_stream_t stream);
 int ea_stream_advance(int* frames, const int* slot_idx, const int* n_new, int B, int chunk_size, int max_streams,
                       ea_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Streamed causal Conformer convolution module (csrc/stream_convmodule.hip): GLU -> causal depthwise conv -> BatchNorm1d
+ * (running statistics) -> SiLU for the new rows of every stream that has a chunk ready, with the same meta rows as
+ * ea_stream_attention.
+ *   Y         : bf16 [total_rows][2C], pointwise_conv1 output of the new rows.
+ *   w         : fp32 [C][KW];  mean_rstd : fp32 [2][C] from ea_bn_from_running;  gamma, beta : fp32 [C].
+ *   carry     : one layer's state, bf16 [max_streams][KW-1][C]: the last KW-1 rows of U = bf16(a * sigmoid(g)) of each stream,
+ *               oldest first.  A zeroed slab is the utterance's left zero padding.
+ * For an entry with 0 < n = n_new[b] <= chunk_size, a slot in range and rows inside the buffer: X = [carry[slot] ; U_new]
+ * (KW-1+n rows), Z[j] = bf16(sum_k w[k] * X[j+k]) (taps ascending, fp32), H[j] = bf16(silu(Z[j]*sc + sh)) with sc = rstd*gamma,
+ * sh = beta - mean*sc (ea_bn_act_fwd's arithmetic), then carry[slot] <- the last KW-1 rows of X.  Any other entry is skipped:
+ * nothing of it is read or written.  H, Z : bf16 [total_rows][C]; Z (the pre-BatchNorm value) may be NULL.
+ * ea_stream_convmodule_supported: C % 8 == 0, KW in {3,7,15,31}, chunk_size <= 128; the launcher returns -2 otherwise. */
+int ea_stream_convmodule_supported(int C, int KW, int chunk_size);
+int ea_stream_glu_dwconv_bn_act(const void* Y, const float* w, const float* mean_rstd, const float* gamma, const float* beta,
+                                void* carry, const int* slot_idx, const int* n_new, const int* row_off, void* H, void* Z, int B,
+                                int C, int KW, int chunk_size, int max_streams, int total_rows, ea_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,8 @@ next to the offline masked encode of the same utterances.
 
 Model: the encoder shape of transformer_ctc_librispeech.yaml (12 transformer layers, 512 / 8 heads / FFN 2048, sinusoidal
 relative positions, conv front-end 64-64-128-128, V = 5004) with `chunk_size` cs, `chunk_left_window` L, random weights.
+`--layer-type conformer`: the same shape with Conformer layers whose depthwise convolution (31 taps) is causal
+(`encoder.depthwise_conv_causal`), the only Conformer that streams.
 Input: seeded random 80-dim features, `--seconds` of audio per utterance (the offline masked path takes at most 1024 encoder
 frames = 40.9 s), every stream fed one chunk's worth of feature frames (4 * cs) per call, in lockstep; finished utterances
 are followed by new ones until `--chunks` timed calls are made after one warm-up utterance.
@@ -33,14 +35,16 @@ class _Task:
         self.target_dictionary = AsrDictionary.from_symbols([f"t{i}" for i in range(V - 5)], enable_bos=True)
 
 
-def build(cs, L, layers, dev):
+def build(cs, L, layers, dev, layer_type="transformer"):
     from espresso_amd.models.transformer.speech_transformer_config import SpeechTransformerConfig
     from espresso_amd.models.transformer.speech_transformer_encoder_model import SpeechTransformerEncoderModel
 
     cfg = SpeechTransformerConfig()
     e = cfg.encoder
     e.embed_dim, e.ffn_embed_dim, e.layers, e.attention_heads = 512, 2048, layers, 8
-    e.normalize_before, e.relative_positional_embeddings, e.learned_pos, e.layer_type = True, True, False, "transformer"
+    e.normalize_before, e.relative_positional_embeddings, e.learned_pos, e.layer_type = True, True, False, layer_type
+    if layer_type == "conformer":
+        e.depthwise_conv_causal, e.depthwise_conv_kernel_size = True, 31
     e.conv_channels = "[64, 64, 128, 128]"
     e.chunk_size, e.chunk_left_window, e.chunk_right_window = cs, L, 0
     cfg.dropout = cfg.attention_dropout = cfg.activation_dropout = 0.0
@@ -53,7 +57,7 @@ def build(cs, L, layers, dev):
 def run(streams, cs, args, dev):
     from espresso_amd.models.transformer.streaming_encoder import StreamingEncoder
 
-    model = build(cs, args.left, args.layers, dev)
+    model = build(cs, args.left, args.layers, dev, args.layer_type)
     T = int(args.seconds * 100)
     g = torch.Generator(device=dev).manual_seed(1)
     feats = torch.randn(streams, T, 80, device=dev, generator=g)
@@ -88,6 +92,7 @@ def run(streams, cs, args, dev):
     audio = (rounds - 1) * streams * args.seconds
     offline = float(np.median(off[1:]))
     return {"streams": streams, "chunk_size": cs, "left_chunks": args.left, "chunk_audio_ms": piece * 10, "layers": args.layers,
+            "layer_type": args.layer_type,
             "timed_calls": len(times), "chunk_ms_median": round(float(np.median(ts)), 3), "chunk_ms_p95": round(float(np.percentile(ts, 95)), 3),
             "stream_rtf": round(float(ts.sum() / 1e3 / audio), 5), "encoder_frames": emitted,
             "offline_ms": round(offline * 1e3, 2), "offline_rtf": round(offline / (streams * args.seconds), 5),
@@ -100,6 +105,8 @@ def main():
     p.add_argument("--chunk-sizes", default="16,32")
     p.add_argument("--left", type=int, default=3)
     p.add_argument("--layers", type=int, default=12)
+    p.add_argument("--layer-type", choices=["transformer", "conformer"], default="transformer",
+                   help="conformer: causal depthwise convolution, 31 taps")
     p.add_argument("--seconds", type=float, default=30.0)
     p.add_argument("--chunks", type=int, default=200, help="timed accept calls per configuration (at least)")
     args = p.parse_args()
