@@ -28,6 +28,22 @@
 // max_frames frames, (q, b)) and its rows at row_off[b] of a packed piece.  Both instantiate the same body, so a stream fed in
 // any pieces gives the offline results bit for bit; nodes are numbered in lane order and the hash is a lookup only, so
 // max_frames, which sizes the table, does not change them.  LDS as above.
+//
+// Time stamps (kTimes instantiations, ea_ctc_prefix_beam_times_* / ea_ctc_prefix_beam_stream_times_*): every hypothesis also
+// carries vb / vnb, which are pb / pnb with max in place of log-add-exp (the score of its best single alignment path; the LM,
+// bonus and bias terms are functions of the token sequence and stay out), and eb / enb, pointers into a per-utterance pool of
+// time nodes (parent time node, frame); node 0 = no tokens.  Stay: vb' = max(vb, vnb) + x[blank] with the pointer of the larger
+// (tie: eb); vnb' = vnb + x[last], enb' = enb.  Extension by c: from (vb, eb) if c == last, else from the larger of (vb, eb),
+// (vnb, enb) (tie: the blank one); vnb'' = that + x[c], a NEW time node (its pointer, t); vb'' = -inf.  An extension that merges
+// into a stay replaces the stay's (vnb', enb') only if it is strictly larger.  Time nodes are made for selected candidates only,
+// numbered in lane order: at most `beam` per frame, so the pool has the prefix table's cap = 1 + T * beam.  Nothing of this
+// enters a ranking key: tokens, scores and triples are those of the search without times, bit for bit.  The finish walks the
+// chain of the larger pointer (tie: eb) into times[u] = the frame at which token u starts on that path, and returns max(vb, vnb).
+// The state lives in a SEPARATE caller-allocated times workspace; the beam workspace / stream state is the twin's, unchanged.
+// Per utterance (offline, T frames) or per stream slot (T = max_frames), 4-byte words:
+//   times words(T, beam) = 4 * beam + 2 + 2 * cap,  cap = 1 + T * beam
+// (vb, vnb fp32 [beam]; eb, enb int32 [beam]; the node counter and a pad word; tpar [cap], tfrm [cap]).  The step kernels write
+// tpar / tfrm and only the finish reads them, across a kernel boundary.  LDS: 1 032 bytes more than the twin's.
 #include "common.h"
 #include "ctc_beam_common.h"
 #include "espresso_amd.h"
@@ -93,7 +109,35 @@ struct StepArgs {
   int T, t0, t1;
 };
 struct BiasStepArgs : StepArgs { CgTables g; };
+struct TimesStepArgs : BiasStepArgs { void* tws; };
 struct NoBias {};
+struct NoTimes {};
+
+// the times workspace of one utterance / stream slot (see the header)
+struct TimesWs {
+  float *vb, *vnb;
+  int *eb, *enb, *cnt /*[0] = time nodes*/, *tpar, *tfrm;
+  int cap;
+};
+template <bool kTimes> using TimesOf = std::conditional_t<kTimes, TimesWs, NoTimes>;
+__host__ __device__ __forceinline__ long times_ws_words(int T, int beam) { return 4L * beam + 2 + 2 * beam_ws_cap(T, beam); }
+__device__ __forceinline__ TimesWs times_ws(void* tws, long idx, int T, int beam) {
+  TimesWs w;
+  w.cap = (int)beam_ws_cap(T, beam);
+  int* base = (int*)tws + idx * times_ws_words(T, beam);
+  w.vb = (float*)base;
+  w.vnb = w.vb + beam;
+  w.eb = base + 2L * beam;
+  w.enb = w.eb + beam;
+  w.cnt = w.enb + beam;
+  w.tpar = w.cnt + 2;
+  w.tfrm = w.tpar + w.cap;
+  return w;
+}
+template <bool kTimes>
+__device__ __forceinline__ TimesOf<kTimes> times_of(void* tws, long idx, int T, int beam) {
+  if constexpr (kTimes) return times_ws(tws, idx, T, beam); else return NoTimes{};
+}
 template <bool BIAS> using GraphOf = std::conditional_t<BIAS, CgTables, NoBias>;
 template <bool BIAS, class A>
 __device__ __forceinline__ GraphOf<BIAS> graph_of(const A& a) {  // the graph of a kernel's bias arguments
@@ -114,9 +158,16 @@ template <> struct BiasLds<true> {
   int rchild[kMaxK]; float rboost[kMaxK];   // the root's edge by each candidate token of the frame
 };
 
+template <bool kTimes> struct TimesLds {};
+template <> struct TimesLds<true> {
+  float vb[kMaxBeam], vnb[kMaxBeam];  // per slot: the Viterbi scores and their time-node pointers
+  int eb[kMaxBeam], enb[kMaxBeam];
+  int ntn, ntfresh;
+};
+
 // LDS of a step kernel: the beam, which lives here over the frames of one launch, and the scratch of one frame
-template <bool BIAS>
-struct FrameLds : BiasLds<BIAS> {
+template <bool BIAS, bool kTimes = false>
+struct FrameLds : BiasLds<BIAS>, TimesLds<kTimes> {
   uint64_t key[kMaxCand];
   SelectScratch sel;
   unsigned long long merged[kMaxBeam];                       // bit r of slot j: extension (j, r) merged into a stay
@@ -131,7 +182,8 @@ struct FrameLds : BiasLds<BIAS> {
 };
 
 // the state before frame 0: the empty prefix, an empty node table; the caller synchronises
-__device__ __forceinline__ void ctc_beam_init(const BeamWs& w, const BiasWs* bw) {
+template <bool kTimes = false>
+__device__ __forceinline__ void ctc_beam_init(const BeamWs& w, const BiasWs* bw, const TimesOf<kTimes>& tw = {}) {
   const int tid = threadIdx.x;
   for (int i = tid; i < w.tsize; i += 256) w.tab_key[i] = 0ull;
   if (tid == 0) {
@@ -140,24 +192,39 @@ __device__ __forceinline__ void ctc_beam_init(const BeamWs& w, const BiasWs* bw)
     w.cnt[0] = 1; w.cnt[1] = 1;
     w.node_par[0] = -1; w.node_tok[0] = -1;
     if (bw) { bw->q[0] = 0; bw->b[0] = 0.f; }
+    if constexpr (kTimes) {
+      tw.vb[0] = 0.f; tw.vnb[0] = -INFINITY; tw.eb[0] = 0; tw.enb[0] = 0;
+      tw.cnt[0] = 1; tw.cnt[1] = 0;
+      tw.tpar[0] = -1; tw.tfrm[0] = -1;
+    }
   }
 }
 
 // beam <-> workspace; the caller synchronises after the load
-template <bool BIAS>
-__device__ __forceinline__ void ctc_beam_load(FrameLds<BIAS>& s, const BeamWs& w, const BiasWs& bw, int beam) {
+template <bool BIAS, bool kTimes = false>
+__device__ __forceinline__ void ctc_beam_load(FrameLds<BIAS, kTimes>& s, const BeamWs& w, const BiasWs& bw, int beam,
+                                              const TimesOf<kTimes>& tw = {}) {
   const int tid = threadIdx.x;
   if (tid == 0) { s.nhyp = ld_l2(w.cnt); s.nnodes = ld_l2(w.cnt + 1); }
+  if constexpr (kTimes) {
+    if (tid == 0) s.ntn = ld_l2(tw.cnt);
+    if (tid < beam) { s.vb[tid] = tw.vb[tid]; s.vnb[tid] = tw.vnb[tid]; s.eb[tid] = tw.eb[tid]; s.enb[tid] = tw.enb[tid]; }
+  }
   if (tid < beam) {
     s.pb[tid] = w.pb[tid]; s.pnb[tid] = w.pnb[tid]; s.lm[tid] = w.lm[tid];
     s.len[tid] = w.len[tid]; s.last[tid] = w.last[tid]; s.node[tid] = w.node[tid]; s.pnode[tid] = w.pnode[tid];
     if constexpr (BIAS) { s.q[tid] = bw.q[tid]; s.b[tid] = bw.b[tid]; }
   }
 }
-template <bool BIAS>
-__device__ __forceinline__ void ctc_beam_store(const FrameLds<BIAS>& s, const BeamWs& w, const BiasWs& bw, int beam) {
+template <bool BIAS, bool kTimes = false>
+__device__ __forceinline__ void ctc_beam_store(const FrameLds<BIAS, kTimes>& s, const BeamWs& w, const BiasWs& bw, int beam,
+                                               const TimesOf<kTimes>& tw = {}) {
   const int tid = threadIdx.x;
   if (tid == 0) { w.cnt[0] = s.nhyp; w.cnt[1] = s.nnodes; }
+  if constexpr (kTimes) {
+    if (tid == 0) tw.cnt[0] = s.ntn;
+    if (tid < beam) { tw.vb[tid] = s.vb[tid]; tw.vnb[tid] = s.vnb[tid]; tw.eb[tid] = s.eb[tid]; tw.enb[tid] = s.enb[tid]; }
+  }
   if (tid < beam) {
     w.pb[tid] = s.pb[tid]; w.pnb[tid] = s.pnb[tid]; w.lm[tid] = s.lm[tid];
     w.len[tid] = s.len[tid]; w.last[tid] = s.last[tid]; w.node[tid] = s.node[tid]; w.pnode[tid] = s.pnode[tid];
@@ -174,10 +241,11 @@ __device__ __forceinline__ void ctc_beam_identity(const FrameParams& a, long row
 }
 
 // One frame over the beam in LDS: the row xr, the prefix table of w; row0 = the first row of this entry in lm_rows and in the
-// triple arrays.  The one body of the offline and the streamed step kernels.
-template <typename TX, bool BIAS>
-__device__ __forceinline__ void ctc_beam_frame(FrameLds<BIAS>& s, const FrameParams& a, const BeamWs& w, const TX* xr, long row0,
-                                               const GraphOf<BIAS>& g) {
+// triple arrays.  The one body of the offline and the streamed step kernels.  kTimes: t = the frame's number, tw = its pool.
+template <typename TX, bool BIAS, bool kTimes = false>
+__device__ __forceinline__ void ctc_beam_frame(FrameLds<BIAS, kTimes>& s, const FrameParams& a, const BeamWs& w, const TX* xr,
+                                               long row0, const GraphOf<BIAS>& g, [[maybe_unused]] int t = 0,
+                                               const TimesOf<kTimes>& tw = {}) {
   const int tid = threadIdx.x;
   const int beam = a.beam, K = a.K, K1 = a.K + 1;
   const float lw = a.lm_rows ? a.lm_weight : 0.f;
@@ -237,6 +305,30 @@ __device__ __forceinline__ void ctc_beam_frame(FrameLds<BIAS>& s, const FramePar
   };
   auto ext_pnb = [&](int j, int r) { return (s.ctok[r] == s.last[j] ? s.pb[j] : lae(s.pb[j], s.pnb[j])) + s.cx[r]; };
   auto ext_lm = [&](int j, int r) { return a.lm_rows ? s.lm[j] + a.lm_rows[(row0 + j) * a.ld_lm + s.ctok[r]] : 0.f; };
+  // kTimes: the same with max; `e` the time node the path comes from, `fresh` = a new node (e, t) is due if this one survives
+  struct Vit { float v; int e; bool fresh; };
+  [[maybe_unused]] auto ext_vit = [&](int j, int r) -> Vit {
+    if constexpr (kTimes) {
+      const bool nb = s.ctok[r] != s.last[j] && s.vnb[j] > s.vb[j];
+      return {(nb ? s.vnb[j] : s.vb[j]) + s.cx[r], nb ? s.enb[j] : s.eb[j], true};
+    } else {
+      return {0.f, 0, false};
+    }
+  };
+  [[maybe_unused]] auto stay_vit = [&](int j) -> Vit {
+    if constexpr (kTimes) {
+      const int r = s.lrank[j];
+      Vit o{r >= 0 ? s.vnb[j] + s.cx[r] : -INFINITY, s.enb[j], false};
+      const int src = s.msrc[j];
+      if (src >= 0) {
+        const Vit x = ext_vit(src, r);
+        if (x.v > o.v) o = x;
+      }
+      return o;
+    } else {
+      return {0.f, 0, false};
+    }
+  };
   const int N = nh * K1;
   for (int i = tid; i < N; i += 256) {
     const int j = i / K1, q = i - j * K1;
@@ -275,6 +367,9 @@ __device__ __forceinline__ void ctc_beam_frame(FrameLds<BIAS>& s, const FramePar
   int n_len = 0, n_last = -1, n_node = 0, n_pnode = -1, slot = 0, par = 0, ext = 0, fresh = 0, tslot = -1;
   int n_q = 0;
   float n_b = 0.f;
+  [[maybe_unused]] float n_vb = 0.f;
+  [[maybe_unused]] int n_eb = 0;
+  [[maybe_unused]] Vit n_nb{0.f, 0, false};
   if (tid < ns) {
     const int i = s.sel_idx[tid];
     const uint64_t k = s.key[i];
@@ -285,8 +380,13 @@ __device__ __forceinline__ void ctc_beam_frame(FrameLds<BIAS>& s, const FramePar
       n_pb = lae(s.pb[j], s.pnb[j]) + xb; n_pnb = stay_pnb(j); n_lm = s.lm[j];
       n_len = s.len[j]; n_last = s.last[j]; n_node = s.node[j]; n_pnode = s.pnode[j];
       if constexpr (BIAS) { n_q = s.q[j]; n_b = s.b[j]; }
+      if constexpr (kTimes) {
+        n_vb = fmaxf(s.vb[j], s.vnb[j]) + xb; n_eb = s.vnb[j] > s.vb[j] ? s.enb[j] : s.eb[j];
+        n_nb = stay_vit(j);
+      }
     } else {
       ext = 1;
+      if constexpr (kTimes) { n_vb = -INFINITY; n_nb = ext_vit(j, q - 1); }
       if constexpr (BIAS) { n_q = s.cq[i]; n_b = s.cb[i]; }
       const int r = q - 1;
       n_pb = -INFINITY; n_pnb = ext_pnb(j, r); n_lm = ext_lm(j, r);
@@ -310,8 +410,22 @@ __device__ __forceinline__ void ctc_beam_frame(FrameLds<BIAS>& s, const FramePar
       if (id < w.cap) { w.node_par[id] = n_pnode; w.node_tok[id] = n_last; }
     }
     if (tid == 0) s.nfresh = __popcll(fm);
+    if constexpr (kTimes) {  // fresh time nodes likewise; an extension's blank pointer is its new node too (vb = -inf)
+      const unsigned long long tm = __ballot(n_nb.fresh);
+      if (n_nb.fresh) {
+        const int id = s.ntn + __popcll(tm & ((1ull << tid) - 1ull));
+        if (id < tw.cap) { tw.tpar[id] = n_nb.e; tw.tfrm[id] = t; }
+        n_nb.e = id;
+        if (ext) n_eb = id;
+      }
+      if (tid == 0) s.ntfresh = __popcll(tm);
+    }
   }
   __syncthreads();
+  if constexpr (kTimes) {
+    if (tid < ns) { s.vb[slot] = n_vb; s.vnb[slot] = n_nb.v; s.eb[slot] = n_eb; s.enb[slot] = n_nb.e; }
+    if (tid == 0) s.ntn += s.ntfresh;
+  }
   if (tid < ns) {
     s.pb[slot] = n_pb; s.pnb[slot] = n_pnb; s.lm[slot] = n_lm;
     s.len[slot] = n_len; s.last[slot] = n_last; s.node[slot] = n_node; s.pnode[slot] = n_pnode;
@@ -330,39 +444,49 @@ __device__ __forceinline__ void ctc_beam_frame(FrameLds<BIAS>& s, const FramePar
 }
 
 // the offline search: one workgroup per utterance of the batch, frames [t0, t1)
-template <typename TX, bool BIAS>
-__global__ __launch_bounds__(256) void ctc_beam_step_kernel(const std::conditional_t<BIAS, BiasStepArgs, StepArgs> a) {
-  __shared__ FrameLds<BIAS> s;
+template <bool kTimes, class A>
+__device__ __forceinline__ void* times_arg(const A& a) {  // the times workspace of a kernel's arguments
+  if constexpr (kTimes) return a.tws; else return nullptr;
+}
+
+template <typename TX, bool BIAS, bool kTimes = false>
+__global__ __launch_bounds__(256) void ctc_beam_step_kernel(
+    const std::conditional_t<kTimes, TimesStepArgs, std::conditional_t<BIAS, BiasStepArgs, StepArgs>> a) {
+  __shared__ FrameLds<BIAS, kTimes> s;
   const int b = blockIdx.x;
   const int beam = a.p.beam;
   const BeamWs w = beam_ws(a.ws, b, a.T, beam);
   const BiasWs bw = BIAS ? bias_ws(a.ws, gridDim.x, b, a.T, beam) : BiasWs{nullptr, nullptr};
+  const TimesOf<kTimes> tw = times_of<kTimes>(times_arg<kTimes>(a), b, a.T, beam);
   const int L = min(a.in_len[b], a.T);
   const long row0 = (long)b * beam;
 
   if (a.t0 == 0) {
-    ctc_beam_init(w, BIAS ? &bw : nullptr);
+    ctc_beam_init<kTimes>(w, BIAS ? &bw : nullptr, tw);
     __threadfence_block();
     __syncthreads();
   }
-  ctc_beam_load<BIAS>(s, w, bw, beam);
+  ctc_beam_load<BIAS, kTimes>(s, w, bw, beam, tw);
   __syncthreads();
   for (int t = a.t0; t < a.t1; ++t) {
     if (t >= L) {  // past the end of this utterance: the beam stands still
       ctc_beam_identity(a.p, row0);
       continue;
     }
-    ctc_beam_frame<TX, BIAS>(s, a.p, w, (const TX*)a.x + ((long)b * a.T + t) * a.ld, row0, graph_of<BIAS>(a));
+    ctc_beam_frame<TX, BIAS, kTimes>(s, a.p, w, (const TX*)a.x + ((long)b * a.T + t) * a.ld, row0, graph_of<BIAS>(a), t, tw);
   }
-  ctc_beam_store<BIAS>(s, w, bw, beam);
+  ctc_beam_store<BIAS, kTimes>(s, w, bw, beam, tw);
 }
 
 // final score = s(y) + lm_weight * log P_lm(eos | y) [+ b - phi(q)]; the nbest best, sorted, backtracked into token rows of max_u
 // entries (longer hypotheses are cut there).  64 threads; lm_rows: the rows of this beam; nh: its hypotheses
-template <bool BIAS>
+// kTimes: also times [nbest][max_u] (the start frame of every token on the best path, -1 after the hypothesis) and vscores
+template <bool BIAS, bool kTimes = false>
 __device__ __forceinline__ void ctc_beam_finish(float* s_fin, const BeamWs& w, const BiasWs& bw, int nh, const float* lm_rows,
                                                 long ld_lm, float lm_weight, float ins_bonus, int eos, int nbest, int pad, int max_u,
-                                                int* tokens, int* lengths, float* scores, int* nhyp, const GraphOf<BIAS>& g) {
+                                                int* tokens, int* lengths, float* scores, int* nhyp, const GraphOf<BIAS>& g,
+                                                const TimesOf<kTimes>& tw = {}, [[maybe_unused]] int* times = nullptr,
+                                                [[maybe_unused]] float* vscores = nullptr) {
   const int j = threadIdx.x;
   if (j < nh) {
     float s = lae(w.pb[j], w.pnb[j]) + ins_bonus * (float)w.len[j];
@@ -387,6 +511,17 @@ __device__ __forceinline__ void ctc_beam_finish(float* s_fin, const BeamWs& w, c
       }
       lengths[rank] = min(n, max_u);
       scores[rank] = s;
+      if constexpr (kTimes) {
+        int* tout = times + (long)rank * max_u;
+        for (int u = 0; u < max_u; ++u) tout[u] = -1;
+        const float vb = tw.vb[j], vnb = tw.vnb[j];
+        int e = vnb > vb ? tw.enb[j] : tw.eb[j];
+        for (int u = n - 1; u >= 0 && e > 0 && e < tw.cap; --u) {
+          if (u < max_u) tout[u] = tw.tfrm[e];
+          e = tw.tpar[e];
+        }
+        vscores[rank] = fmaxf(vb, vnb);
+      }
     }
   }
   for (int r = nh + j; r < nbest; r += 64) {
@@ -394,6 +529,10 @@ __device__ __forceinline__ void ctc_beam_finish(float* s_fin, const BeamWs& w, c
     for (int u = 0; u < max_u; ++u) out[u] = pad;
     lengths[r] = 0;
     scores[r] = -INFINITY;
+    if constexpr (kTimes) {
+      for (int u = 0; u < max_u; ++u) times[(long)r * max_u + u] = -1;
+      vscores[r] = -INFINITY;
+    }
   }
 }
 
@@ -408,6 +547,27 @@ __global__ __launch_bounds__(64) void ctc_beam_finish_kernel(void* ws, const flo
   const BiasWs bw = BIAS ? bias_ws(ws, gridDim.x, b, T, beam) : BiasWs{nullptr, nullptr};
   ctc_beam_finish<BIAS>(s_fin, w, bw, w.cnt[0], lm_rows ? lm_rows + (long)b * beam * ld_lm : nullptr, ld_lm, lm_weight, ins_bonus, eos,
                         nbest, pad, T, tokens + (long)b * nbest * T, lengths + b * nbest, scores + b * nbest, nhyp + b, g);
+}
+
+struct TimesFinishArgs {
+  void *ws, *tws;
+  const float* lm_rows; long ld_lm;
+  float lm_weight, ins_bonus;
+  int eos, T, beam, nbest, pad;
+  int *tokens, *lengths; float* scores; int* nhyp;
+  int* times; float* vscores;
+  CgTables g;
+};
+template <bool BIAS>
+__global__ __launch_bounds__(64) void ctc_beam_times_finish_kernel(const TimesFinishArgs a) {
+  __shared__ float s_fin[kMaxBeam];
+  const int b = blockIdx.x, T = a.T, beam = a.beam, nbest = a.nbest;
+  const BeamWs w = beam_ws(a.ws, b, T, beam);
+  const BiasWs bw = BIAS ? bias_ws(a.ws, gridDim.x, b, T, beam) : BiasWs{nullptr, nullptr};
+  ctc_beam_finish<BIAS, true>(s_fin, w, bw, w.cnt[0], a.lm_rows ? a.lm_rows + (long)b * beam * a.ld_lm : nullptr, a.ld_lm, a.lm_weight,
+                              a.ins_bonus, a.eos, nbest, a.pad, T, a.tokens + (long)b * nbest * T, a.lengths + b * nbest,
+                              a.scores + b * nbest, a.nhyp + b, graph_of<BIAS>(a), times_ws(a.tws, b, T, beam),
+                              a.times + (long)b * nbest * T, a.vscores + b * nbest);
 }
 
 // ------------------------------------------------------------------------------------------------ the streamed search
@@ -430,12 +590,16 @@ __device__ __forceinline__ CtcSlot ctc_slot(void* state, int slot, int max_frame
   return q;
 }
 
+// (tstate: the times slots, one void* with kTimes and nothing without: the kernel without times keeps its parameter list)
+template <bool kTimes = false, class... TS>
 __global__ __launch_bounds__(256) void ctc_beam_stream_reset_kernel(void* state, const int* slots, int max_streams, int max_frames,
-                                                                    int beam) {
+                                                                    int beam, TS... tstate) {
+  static_assert(sizeof...(TS) == (kTimes ? 1 : 0));
   const int slot = slots[blockIdx.x];
   if (slot < 0 || slot >= max_streams) return;
   const CtcSlot q = ctc_slot(state, slot, max_frames, beam);
-  ctc_beam_init(q.w, &q.bw);
+  if constexpr (kTimes) ctc_beam_init<true>(q.w, &q.bw, times_ws(tstate..., slot, max_frames, beam));
+  else ctc_beam_init(q.w, &q.bw);
   if (threadIdx.x == 0) { q.head[0] = 0; q.head[1] = 0; }
 }
 
@@ -447,14 +611,17 @@ struct StreamStepArgs {
   int max_streams, max_frames, j0, j1;
 };
 struct BiasStreamStepArgs : StreamStepArgs { CgTables g; };
+struct TimesStreamStepArgs : BiasStreamStepArgs { void* tws; };
 
 // One workgroup per listed stream: the frames [j0, min(j1, n_new)) of its piece over its slot's state.  An entry without such a
 // frame, one with out-of-range values and one whose piece would pass max_frames leave the slot untouched (identity triple).
 // The slot's counter stands at its value before the piece plus j0 (the LM path steps through the piece one launch per frame),
 // so the whole piece fits iff counter - j0 + n_new <= max_frames; that also bounds the frames of this launch, hence the nodes.
-template <typename TX, bool BIAS>
-__global__ __launch_bounds__(256) void ctc_beam_stream_step_kernel(const std::conditional_t<BIAS, BiasStreamStepArgs, StreamStepArgs> a) {
-  __shared__ FrameLds<BIAS> s;
+// kTimes: the times slot goes with the slot (untouched where the slot is); frame numbers count from the stream's first frame.
+template <typename TX, bool BIAS, bool kTimes = false>
+__global__ __launch_bounds__(256) void ctc_beam_stream_step_kernel(
+    const std::conditional_t<kTimes, TimesStreamStepArgs, std::conditional_t<BIAS, BiasStreamStepArgs, StreamStepArgs>> a) {
+  __shared__ FrameLds<BIAS, kTimes> s;
   const int b = blockIdx.x;
   const int beam = a.p.beam;
   const long row0 = (long)b * beam;
@@ -469,11 +636,12 @@ __global__ __launch_bounds__(256) void ctc_beam_stream_step_kernel(const std::co
     ctc_beam_identity(a.p, row0);
     return;
   }
-  ctc_beam_load<BIAS>(s, q.w, q.bw, beam);
+  const TimesOf<kTimes> tw = times_of<kTimes>(times_arg<kTimes>(a), slot, a.max_frames, beam);
+  ctc_beam_load<BIAS, kTimes>(s, q.w, q.bw, beam, tw);
   __syncthreads();
   for (int j = a.j0; j < j1; ++j)
-    ctc_beam_frame<TX, BIAS>(s, a.p, q.w, (const TX*)a.x + (r0 + j) * a.ld, row0, graph_of<BIAS>(a));
-  ctc_beam_store<BIAS>(s, q.w, q.bw, beam);
+    ctc_beam_frame<TX, BIAS, kTimes>(s, a.p, q.w, (const TX*)a.x + (r0 + j) * a.ld, row0, graph_of<BIAS>(a), frames + (j - a.j0), tw);
+  ctc_beam_store<BIAS, kTimes>(s, q.w, q.bw, beam, tw);
   if (threadIdx.x == 0) q.head[0] = frames + (j1 - a.j0);
 }
 
@@ -485,6 +653,7 @@ struct StreamReadArgs {
   int *tokens, *lengths; float* scores; int* aux;  // aux: nhyp (finish) / stable_len (partial)
 };
 struct BiasStreamReadArgs : StreamReadArgs { CgTables g; };
+struct TimesStreamReadArgs : BiasStreamReadArgs { const void* tws; int* times; float* vscores; };
 
 // readout of the given slots, as the offline kernel finishes; the state is read only
 template <bool BIAS>
@@ -497,6 +666,19 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_finish_kernel(const std::c
                         a.lm_rows ? a.lm_rows + (long)b * a.beam * a.ld_lm : nullptr, a.ld_lm, a.lm_weight, a.ins_bonus, a.eos, a.nbest,
                         a.pad, a.max_u, a.tokens + (long)b * a.nbest * a.max_u, a.lengths + b * a.nbest, a.scores + b * a.nbest,
                         a.aux + b, graph_of<BIAS>(a));
+}
+template <bool BIAS>
+__global__ __launch_bounds__(64) void ctc_beam_stream_times_finish_kernel(const TimesStreamReadArgs a) {
+  __shared__ float s_fin[kMaxBeam];
+  const int b = blockIdx.x, slot = a.slots[b];
+  const bool valid = slot >= 0 && slot < a.max_streams;
+  const CtcSlot q = ctc_slot((void*)a.state, valid ? slot : 0, a.max_frames, a.beam);
+  ctc_beam_finish<BIAS, true>(s_fin, q.w, q.bw, valid ? min(max(q.w.cnt[0], 0), a.beam) : 0,
+                              a.lm_rows ? a.lm_rows + (long)b * a.beam * a.ld_lm : nullptr, a.ld_lm, a.lm_weight, a.ins_bonus, a.eos,
+                              a.nbest, a.pad, a.max_u, a.tokens + (long)b * a.nbest * a.max_u, a.lengths + b * a.nbest,
+                              a.scores + b * a.nbest, a.aux + b, graph_of<BIAS>(a),
+                              times_ws((void*)a.tws, valid ? slot : 0, a.max_frames, a.beam),
+                              a.times + (long)b * a.nbest * a.max_u, a.vscores + b * a.nbest);
 }
 
 // The live hypothesis with the best in-beam score log(pb + pnb) + lm_weight * lm + ins_bonus * len (+ b when biased; ties: the
@@ -753,6 +935,133 @@ extern "C" int ea_ctc_prefix_beam_stream_partial(const void* state, const int* s
   stream_read_args(a, state, slots, nullptr, 0, lm_weight, ins_bonus, -1, biased != 0, max_streams, max_frames, beam, 1, pad, max_u,
                    tokens, lengths, scores, stable_len);
   hipLaunchKernelGGL(ctc_beam_stream_partial_kernel, dim3(n), dim3(64), 0, stream, a);
+  return EA_CHECK_LAUNCH();
+}
+
+// ------------------------------------------------------------------------------------------------ C ABI: time stamps
+extern "C" long ea_ctc_prefix_beam_times_workspace_bytes(int B, int T, int beam) {
+  if (B <= 0 || T < 0 || beam < 1 || beam > kMaxBeam) return 0;
+  return (long)B * times_ws_words(T, beam) * 4L;
+}
+
+extern "C" int ea_ctc_prefix_beam_times_step(const void* x, long ld, int x_bf16, const int* in_len, void* workspace,
+                                             void* times_workspace, const float* lm_rows, long ld_lm, int* lm_parent, int* lm_token,
+                                             void* lm_keep, const int* cg_nodes, const int* cg_edges, const int* cg_root,
+                                             int cg_n_nodes, int cg_n_edges, int B, int T, int V, int beam, int K, int blank,
+                                             float lm_weight, float ins_bonus, int t0, int t1, hipStream_t stream) {
+  if (B <= 0) return 0;
+  TimesStepArgs a;
+  if (!x || !in_len || !workspace || !times_workspace ||
+      !step_args_ok(ld, lm_rows, ld_lm, lm_parent, lm_token, lm_keep, T, V, beam, K, blank, t0, t1) ||
+      (cg_nodes && !cg_tables(a.g, cg_nodes, cg_edges, cg_root, cg_n_nodes, cg_n_edges, V)))
+    return -2;
+  fill_step_args(a, x, ld, in_len, workspace, lm_rows, ld_lm, lm_parent, lm_token, lm_keep, T, V, beam, K, blank, lm_weight,
+                 ins_bonus, t0, t1);
+  a.tws = times_workspace;
+  if (cg_nodes) {
+    if (x_bf16)
+      hipLaunchKernelGGL((ctc_beam_step_kernel<bf16_t, true, true>), dim3(B), dim3(256), 0, stream, a);
+    else
+      hipLaunchKernelGGL((ctc_beam_step_kernel<float, true, true>), dim3(B), dim3(256), 0, stream, a);
+  } else {
+    if (x_bf16)
+      hipLaunchKernelGGL((ctc_beam_step_kernel<bf16_t, false, true>), dim3(B), dim3(256), 0, stream, a);
+    else
+      hipLaunchKernelGGL((ctc_beam_step_kernel<float, false, true>), dim3(B), dim3(256), 0, stream, a);
+  }
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_ctc_prefix_beam_times_finish(void* workspace, const void* times_workspace, const float* lm_rows, long ld_lm,
+                                               float lm_weight, float ins_bonus, int eos, const int* cg_nodes, int cg_n_nodes, int B,
+                                               int T, int beam, int nbest, int pad, int* tokens, int* lengths, float* scores,
+                                               int* nhyp, int* times, float* vscores, hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (!workspace || !times_workspace || !tokens || !lengths || !scores || !nhyp || !times || !vscores || T < 0 || beam < 1 ||
+      beam > kMaxBeam || nbest < 1 || nbest > beam || (lm_rows && eos < 0) || (cg_nodes && cg_n_nodes < 1))
+    return -2;
+  TimesFinishArgs a;
+  a.ws = workspace; a.tws = (void*)times_workspace;
+  a.lm_rows = lm_rows; a.ld_lm = ld_lm; a.lm_weight = lm_weight; a.ins_bonus = ins_bonus;
+  a.eos = eos; a.T = T; a.beam = beam; a.nbest = nbest; a.pad = pad;
+  a.tokens = tokens; a.lengths = lengths; a.scores = scores; a.nhyp = nhyp; a.times = times; a.vscores = vscores;
+  if (cg_nodes) {
+    a.g = cg_nodes_only(cg_nodes, cg_n_nodes);
+    hipLaunchKernelGGL(ctc_beam_times_finish_kernel<true>, dim3(B), dim3(64), 0, stream, a);
+  } else {
+    a.g = CgTables{};
+    hipLaunchKernelGGL(ctc_beam_times_finish_kernel<false>, dim3(B), dim3(64), 0, stream, a);
+  }
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" long ea_ctc_prefix_beam_stream_times_state_bytes(int max_frames, int beam) {
+  if (max_frames < 1 || beam < 1 || beam > kMaxBeam) return 0;
+  return times_ws_words(max_frames, beam) * 4L;
+}
+
+extern "C" int ea_ctc_prefix_beam_stream_times_reset(void* state, void* times_state, const int* slots, int n, int max_streams,
+                                                     int max_frames, int beam, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!state || !times_state || !slots || max_streams < 1 || max_frames < 1 || beam < 1 || beam > kMaxBeam) return -2;
+  hipLaunchKernelGGL((ctc_beam_stream_reset_kernel<true, void*>), dim3(n), dim3(256), 0, stream, state, slots, max_streams, max_frames,
+                     beam, times_state);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_ctc_prefix_beam_stream_times_step(const void* x, long ld, int x_bf16, long total_rows, const int* slot_idx,
+                                                    const int* n_new, const int* row_off, int j0, int j1, int n, void* state,
+                                                    void* times_state, const float* lm_rows, long ld_lm, int* lm_parent,
+                                                    int* lm_token, void* lm_keep, const int* cg_nodes, const int* cg_edges,
+                                                    const int* cg_root, int cg_n_nodes, int cg_n_edges, int max_streams,
+                                                    int max_frames, int V, int beam, int K, int blank, float lm_weight,
+                                                    float ins_bonus, hipStream_t stream) {
+  if (n <= 0) return 0;
+  TimesStreamStepArgs a;
+  if (!x || !slot_idx || !n_new || !row_off || !state || !times_state || total_rows < 0 || j0 < 0 || j1 < j0 ||
+      (lm_rows && j1 != j0 + 1) || max_streams < 1 || max_frames < 1 ||
+      !frame_args_ok(ld, lm_rows, ld_lm, lm_parent, lm_token, lm_keep, V, beam, K, blank) ||
+      (cg_nodes && !cg_tables(a.g, cg_nodes, cg_edges, cg_root, cg_n_nodes, cg_n_edges, V)))
+    return -2;
+  a.x = x; a.ld = ld; a.total_rows = total_rows;
+  a.slot_idx = slot_idx; a.n_new = n_new; a.row_off = row_off;
+  a.state = state; a.tws = times_state;
+  a.p = frame_params(lm_rows, ld_lm, lm_parent, lm_token, lm_keep, V, beam, K, blank, lm_weight, ins_bonus);
+  a.max_streams = max_streams; a.max_frames = max_frames; a.j0 = j0; a.j1 = j1;
+  if (cg_nodes) {
+    if (x_bf16)
+      hipLaunchKernelGGL((ctc_beam_stream_step_kernel<bf16_t, true, true>), dim3(n), dim3(256), 0, stream, a);
+    else
+      hipLaunchKernelGGL((ctc_beam_stream_step_kernel<float, true, true>), dim3(n), dim3(256), 0, stream, a);
+  } else {
+    if (x_bf16)
+      hipLaunchKernelGGL((ctc_beam_stream_step_kernel<bf16_t, false, true>), dim3(n), dim3(256), 0, stream, a);
+    else
+      hipLaunchKernelGGL((ctc_beam_stream_step_kernel<float, false, true>), dim3(n), dim3(256), 0, stream, a);
+  }
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_ctc_prefix_beam_stream_times_finish(const void* state, const void* times_state, const int* slots, int n,
+                                                      const float* lm_rows, long ld_lm, float lm_weight, float ins_bonus, int eos,
+                                                      const int* cg_nodes, int cg_n_nodes, int max_streams, int max_frames, int beam,
+                                                      int nbest, int pad, int max_u, int* tokens, int* lengths, float* scores,
+                                                      int* nhyp, int* times, float* vscores, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (stream_read_args_bad(state, slots, max_streams, max_frames, beam, max_u, tokens, lengths, scores, nhyp) || !times_state ||
+      !times || !vscores || nbest < 1 || nbest > beam || (lm_rows && (eos < 0 || ld_lm <= eos)) || (cg_nodes && cg_n_nodes < 1))
+    return -2;
+  TimesStreamReadArgs a;
+  stream_read_args(a, state, slots, lm_rows, ld_lm, lm_weight, ins_bonus, eos, cg_nodes != nullptr, max_streams, max_frames, beam,
+                   nbest, pad, max_u, tokens, lengths, scores, nhyp);
+  a.tws = times_state; a.times = times; a.vscores = vscores;
+  if (cg_nodes) {
+    a.g = cg_nodes_only(cg_nodes, cg_n_nodes);
+    hipLaunchKernelGGL(ctc_beam_stream_times_finish_kernel<true>, dim3(n), dim3(64), 0, stream, a);
+  } else {
+    a.g = CgTables{};
+    hipLaunchKernelGGL(ctc_beam_stream_times_finish_kernel<false>, dim3(n), dim3(64), 0, stream, a);
+  }
   return EA_CHECK_LAUNCH();
 }
 

@@ -83,6 +83,21 @@
 // and instructions as before.  One search uses the bias calls for all of its steps, its finish and its partials.
 //   rnnt_beam_select_kernel<true>, rnnt_beam_stream_select_kernel<true>  256 threads, 103704 B LDS (SelLdsBias) -> 1 workgroup per CU
 //   (the offline bias step launches the unbiased row kernel; the other bias kernels: LDS of their unbiased twins)
+//
+// Time stamps (kTimes instantiations, ea_rnnt_frame_beam_times_* / ea_rnnt_frame_beam_stream_times_*): every hypothesis also
+// carries v, which accumulates the same fused r as s with max in place of log-add-exp at a merge (the score of its best single
+// alignment path), and e, a pointer into a per-utterance pool of time nodes (parent time node, frame); node 0 = no tokens.
+// Stay: v' = v + r_blank, e' = e.  Extension by u: v'' = v + r_u and a NEW time node (e, t).  An extension that merges into a
+// stay replaces the stay's (v', e') only if it is strictly larger.  Time nodes are made for selected candidates only, numbered
+// in lane order: at most `beam` per frame, so the pool has the prefix table's cap.  Nothing of this enters a ranking key:
+// tokens, scores and triples are those of the search without times, bit for bit.  The finish walks the chain of e into
+// times[u] = the frame at which token u is emitted on that path, and returns v (never normalised).  The flag is a third
+// template parameter of the select phase, the init and the finish; the row phase is untouched (the times step launches the
+// twin's row kernel).  The state lives in a SEPARATE caller-allocated times workspace; the beam workspace / stream state is
+// the twin's (biased or not), unchanged.  Per utterance (T frames) or per stream slot (T = max_frames), 4-byte words:
+//   times words(T, beam) = 2 * beam + 2 + 2 * cap,  cap = 1 + T * beam
+// (v fp32 [beam]; e int32 [beam]; the node counter and a pad word; tpar [cap], tfrm [cap]).  The select kernels write tpar /
+// tfrm and only the finish reads them, across a kernel boundary.  LDS: 1 032 bytes more than the twin's select kernel.
 #include "common.h"
 #include "ctc_beam_common.h"
 #include "espresso_amd.h"
@@ -156,6 +171,28 @@ __device__ __forceinline__ RnntBias<kBias> rnnt_bias_at(int* base, int beam, con
 template <bool kBias, class A>
 __device__ __forceinline__ auto rnnt_graph_of(const A& a) {  // the graph of a kernel's bias arguments
   if constexpr (kBias) return a.g; else return NoGraph{};
+}
+
+// the times workspace of one utterance / stream slot (see the header); nothing without kTimes
+struct RnntTimesWs {
+  float* v;
+  int *e, *cnt /*[0] = time nodes*/, *tpar, *tfrm;
+  int cap, t;  // t: the number of the frame a step is at
+};
+struct NoTimes {};
+template <bool kTimes> using RnntTimes = std::conditional_t<kTimes, RnntTimesWs, NoTimes>;
+__host__ __device__ __forceinline__ long rnnt_times_words(int T, int beam) { return 2L * beam + 2 + 2 * rnnt_ws_cap(T, beam); }
+__device__ __forceinline__ RnntTimesWs rnnt_times_at(void* tws, long idx, int T, int beam, int t) {
+  RnntTimesWs w;
+  w.cap = (int)rnnt_ws_cap(T, beam);
+  w.t = t;
+  int* base = (int*)tws + idx * rnnt_times_words(T, beam);
+  w.v = (float*)base;
+  w.e = base + beam;
+  w.cnt = w.e + beam;
+  w.tpar = w.cnt + 2;
+  w.tfrm = w.tpar + w.cap;
+  return w;
 }
 
 struct RowParams {  // what the row phase needs besides its row, the same for the offline and the streamed search
@@ -254,8 +291,8 @@ __device__ __forceinline__ void rnnt_row_phase(RowLds& s, const RowParams& a, co
 
 // the state before frame 0: the empty hypothesis with score 0 in slot 0, node 0 in an empty table (blockDim 256; the caller
 // synchronises)
-template <bool kBias>
-__device__ __forceinline__ void rnnt_init(const RnntWs& w, const RnntBias<kBias>& wb) {
+template <bool kBias, bool kTimes = false>
+__device__ __forceinline__ void rnnt_init(const RnntWs& w, const RnntBias<kBias>& wb, const RnntTimes<kTimes>& tw = {}) {
   const int tid = threadIdx.x;
   for (int i = tid; i < w.tsize; i += 256) w.tab_key[i] = 0ull;
   if (tid == 0) {
@@ -263,6 +300,11 @@ __device__ __forceinline__ void rnnt_init(const RnntWs& w, const RnntBias<kBias>
     w.cnt[0] = 1; w.cnt[1] = 1;
     w.node_par[0] = -1; w.node_tok[0] = -1;
     if constexpr (kBias) { wb.q[0] = 0; wb.b[0] = 0.f; }
+    if constexpr (kTimes) {
+      tw.v[0] = 0.f; tw.e[0] = 0;
+      tw.cnt[0] = 1; tw.cnt[1] = 0;
+      tw.tpar[0] = -1; tw.tfrm[0] = -1;
+    }
   }
 }
 
@@ -288,13 +330,26 @@ struct SelLdsBias : SelLds {
   int cq[kMaxCand]; float cb[kMaxCand];  // per candidate extension: the node and the running bias after it
 };
 template <bool kBias> using SelLdsOf = std::conditional_t<kBias, SelLdsBias, SelLds>;
+template <bool kBias>
+struct SelLdsTimes : SelLdsOf<kBias> {
+  float v[kMaxBeam], vstay[kMaxBeam];  // per slot: the Viterbi score; that of its stay
+  int e[kMaxBeam], esrc[kMaxBeam];     // its time node; the slot whose extension beat the stay (-1: none)
+  int ntfresh;
+};
+template <bool kBias, bool kTimes> using SelLdsT = std::conditional_t<kTimes, SelLdsTimes<kBias>, SelLdsOf<kBias>>;
 
 // merge, selection and the new state of one beam with nh hypotheses and nnodes table nodes; the triples go to rows row0 ...
-template <bool kStreamed, bool kBias>
-__device__ __forceinline__ void rnnt_select_phase(SelLdsOf<kBias>& s, const RnntWs& w, const RnntBias<kBias>& wb, int beam, int K,
-                                                  int blank, int nh, int nnodes, int* parent, int* token, uint8_t* keep, long row0) {
+template <bool kStreamed, bool kBias, bool kTimes = false>
+__device__ __forceinline__ void rnnt_select_phase(SelLdsT<kBias, kTimes>& s, const RnntWs& w, const RnntBias<kBias>& wb, int beam, int K,
+                                                  int blank, int nh, int nnodes, int* parent, int* token, uint8_t* keep, long row0,
+                                                  const RnntTimes<kTimes>& tw = {}) {
   const int tid = threadIdx.x;
   const int K1 = K + 1;
+  [[maybe_unused]] int ntn = 0;
+  if constexpr (kTimes) {
+    ntn = tw.cnt[0];
+    if (tid < nh) { s.v[tid] = tw.v[tid]; s.e[tid] = tw.e[tid]; }
+  }
   if (tid < nh) {
     s.score[tid] = w.score[tid]; s.len[tid] = w.len[tid]; s.last[tid] = w.last[tid]; s.node[tid] = w.node[tid];
     s.pnode[tid] = w.pnode[tid]; s.rb[tid] = w.rblank[tid]; s.nc[tid] = w.rnc[tid];
@@ -311,6 +366,9 @@ __device__ __forceinline__ void rnnt_select_phase(SelLdsOf<kBias>& s, const Rnnt
   // stays; a stay absorbs the extension y' + v == y (y' in the beam, v among its candidates)
   if (tid < nh) {
     float st = s.score[tid] + s.rb[tid];
+    [[maybe_unused]] float vst = 0.f;
+    [[maybe_unused]] int esrc = -1;
+    if constexpr (kTimes) vst = s.v[tid] + s.rb[tid];
     if (s.len[tid] > 0) {
       int src = -1;
       for (int j = 0; j < nh; ++j) src = s.node[j] == s.pnode[tid] ? j : src;
@@ -320,10 +378,15 @@ __device__ __forceinline__ void rnnt_select_phase(SelLdsOf<kBias>& s, const Rnnt
           if (s.ctok[src * K + r] == s.last[tid]) {
             atomicOr(&s.merged[src], 1ull << r);
             st = lae(st, s.score[src] + s.cval[src * K + r]);
+            if constexpr (kTimes) {
+              const float vx = s.v[src] + s.cval[src * K + r];
+              if (vx > vst) { vst = vx; esrc = src; }
+            }
           }
       }
     }
     s.stay[tid] = st;
+    if constexpr (kTimes) { s.vstay[tid] = vst; s.esrc[tid] = esrc; }
   }
   __syncthreads();
 
@@ -366,6 +429,8 @@ __device__ __forceinline__ void rnnt_select_phase(SelLdsOf<kBias>& s, const Rnnt
   int n_len = 0, n_last = -1, n_node = 0, n_pnode = -1, slot = 0, par = 0, ext = 0, fresh = 0, tslot = -1;
   [[maybe_unused]] int n_q = 0;
   [[maybe_unused]] float n_b = 0.f;
+  [[maybe_unused]] float n_v = 0.f;
+  [[maybe_unused]] int n_e = 0, tfresh = 0;
   if (tid < ns) {
     const int i = s.sel_idx[tid];
     const uint64_t k = s.key[i];
@@ -375,9 +440,14 @@ __device__ __forceinline__ void rnnt_select_phase(SelLdsOf<kBias>& s, const Rnnt
     if (q == 0) {
       n_score = s.stay[j]; n_len = s.len[j]; n_last = s.last[j]; n_node = s.node[j]; n_pnode = s.pnode[j];
       if constexpr (kBias) { n_q = s.q[j]; n_b = s.b[j]; }
+      if constexpr (kTimes) {
+        const int es = s.esrc[j];
+        n_v = s.vstay[j]; tfresh = es >= 0; n_e = s.e[es >= 0 ? es : j];
+      }
     } else {
       ext = 1;
       if constexpr (kBias) { n_q = s.cq[i]; n_b = s.cb[i]; }
+      if constexpr (kTimes) { n_v = s.v[j] + s.cval[j * K + q - 1]; tfresh = 1; n_e = s.e[j]; }
       n_score = s.score[j] + s.cval[j * K + q - 1];
       n_len = s.len[j] + 1; n_last = s.ctok[j * K + q - 1]; n_pnode = s.node[j];
       // the node of y_j + v: found in the hash table, or claimed there (distinct keys within one frame)
@@ -399,8 +469,21 @@ __device__ __forceinline__ void rnnt_select_phase(SelLdsOf<kBias>& s, const Rnnt
       if (id < w.cap) { w.node_par[id] = n_pnode; w.node_tok[id] = n_last; }
     }
     if (tid == 0) s.nfresh = __popcll(fm);
+    if constexpr (kTimes) {  // fresh time nodes likewise
+      const unsigned long long tm = __ballot(tfresh);
+      if (tfresh) {
+        const int id = ntn + __popcll(tm & ((1ull << tid) - 1ull));
+        if (id < tw.cap) { tw.tpar[id] = n_e; tw.tfrm[id] = tw.t; }
+        n_e = id;
+      }
+      if (tid == 0) s.ntfresh = __popcll(tm);
+    }
   }
   __syncthreads();
+  if constexpr (kTimes) {
+    if (tid < ns) { tw.v[slot] = n_v; tw.e[slot] = n_e; }
+    if (tid == 0) tw.cnt[0] = ntn + s.ntfresh;
+  }
   if (tid < ns) {
     w.score[slot] = n_score; w.len[slot] = n_len; w.last[slot] = n_last; w.node[slot] = n_node; w.pnode[slot] = n_pnode;
     if constexpr (kBias) { wb.q[slot] = n_q; wb.b[slot] = n_b; }
@@ -416,9 +499,13 @@ __device__ __forceinline__ void rnnt_select_phase(SelLdsOf<kBias>& s, const Rnnt
 // final score = s [+ b - phi(q)], or that / max(1, |y|); the nbest best of the nh hypotheses by (-final, slot), backtracked into tokens
 // [nbest][max_u] (pad-filled), lengths / scores [nbest] and *nhyp.  fresh: no step has run, the beam is the empty hypothesis
 // and w is not read.  Reads the state only (blockDim 64).
-template <bool kStreamed, bool kBias>
+// kTimes: also times [nbest][max_u] (the frame at which every token is emitted on the best path, -1 after the hypothesis) and
+// vscores [nbest] (v, not normalised)
+template <bool kStreamed, bool kBias, bool kTimes = false>
 __device__ __forceinline__ void rnnt_finish(float* s_fin, const RnntWs& w, const RnntBias<kBias>& wb, int nh, bool fresh, int nbest, int pad, int normalize,
-                                            int max_u, int* tokens, int* lengths, float* scores, int* nhyp) {
+                                            int max_u, int* tokens, int* lengths, float* scores, int* nhyp,
+                                            const RnntTimes<kTimes>& tw = {}, [[maybe_unused]] int* times = nullptr,
+                                            [[maybe_unused]] float* vscores = nullptr) {
   const int j = threadIdx.x;
   if (j < nh) {
     float s = fresh ? 0.f : w.score[j];
@@ -444,6 +531,16 @@ __device__ __forceinline__ void rnnt_finish(float* s_fin, const RnntWs& w, const
       }
       lengths[rank] = n;
       scores[rank] = s;
+      if constexpr (kTimes) {
+        int* tout = times + (long)rank * max_u;
+        for (int u = 0; u < max_u; ++u) tout[u] = -1;
+        int e = fresh ? 0 : tw.e[j];
+        for (int u = len - 1; u >= 0 && e > 0 && e < tw.cap; --u) {
+          if (u < max_u) tout[u] = tw.tfrm[e];
+          e = tw.tpar[e];
+        }
+        vscores[rank] = fresh ? 0.f : tw.v[j];
+      }
     }
   }
   for (int r = nh + j; r < nbest; r += 64) {
@@ -451,6 +548,10 @@ __device__ __forceinline__ void rnnt_finish(float* s_fin, const RnntWs& w, const
     for (int u = 0; u < max_u; ++u) out[u] = pad;
     lengths[r] = 0;
     scores[r] = -INFINITY;
+    if constexpr (kTimes) {
+      for (int u = 0; u < max_u; ++u) times[(long)r * max_u + u] = -1;
+      vscores[r] = -INFINITY;
+    }
   }
 }
 
@@ -485,6 +586,7 @@ struct SelArgs {
   int T, beam, K, blank, t;
 };
 struct BiasSelArgs : SelArgs { CgTables g; };
+struct TimesSelArgs : BiasSelArgs { void* tws; };
 
 // (q, b) of utterance b of B: behind the B unbiased workspaces
 template <bool kBias, class G, class... Unused>
@@ -493,15 +595,22 @@ __device__ __forceinline__ RnntBias<kBias> rnnt_bias_of(void* ws, int B, int b, 
 }
 
 // the select phase, one workgroup per utterance
-template <bool kBias>
-__global__ __launch_bounds__(256) void rnnt_beam_select_kernel(const std::conditional_t<kBias, BiasSelArgs, SelArgs> a) {
-  __shared__ SelLdsOf<kBias> s;
+template <bool kTimes, class A>
+__device__ __forceinline__ RnntTimes<kTimes> rnnt_times_of(const A& a, long idx, int T, int beam, int t) {
+  if constexpr (kTimes) return rnnt_times_at((void*)a.tws, idx, T, beam, t); else return NoTimes{};
+}
+
+template <bool kBias, bool kTimes = false>
+__global__ __launch_bounds__(256) void rnnt_beam_select_kernel(
+    const std::conditional_t<kTimes, TimesSelArgs, std::conditional_t<kBias, BiasSelArgs, SelArgs>> a) {
+  __shared__ SelLdsT<kBias, kTimes> s;
   const int b = blockIdx.x;
   const RnntWs w = rnnt_ws_of(a.ws, b, a.T, a.beam);
   const RnntBias<kBias> wb = rnnt_bias_of<kBias>(a.ws, gridDim.x, b, a.T, a.beam, rnnt_graph_of<kBias>(a));
+  const RnntTimes<kTimes> tw = rnnt_times_of<kTimes>(a, b, a.T, a.beam, a.t);
   const long row0 = (long)b * a.beam;
   if (a.t == 0) {
-    rnnt_init<kBias>(w, wb);
+    rnnt_init<kBias, kTimes>(w, wb, tw);
     __threadfence_block();
     __syncthreads();
   }
@@ -509,8 +618,8 @@ __global__ __launch_bounds__(256) void rnnt_beam_select_kernel(const std::condit
     rnnt_identity(a.parent, a.token, a.keep, row0, a.beam, a.blank);
     return;
   }
-  rnnt_select_phase<false, kBias>(s, w, wb, a.beam, a.K, a.blank, a.t == 0 ? 1 : w.cnt[0], a.t == 0 ? 1 : w.cnt[1], a.parent, a.token,
-                                  a.keep, row0);
+  rnnt_select_phase<false, kBias, kTimes>(s, w, wb, a.beam, a.K, a.blank, a.t == 0 ? 1 : w.cnt[0], a.t == 0 ? 1 : w.cnt[1], a.parent,
+                                          a.token, a.keep, row0, tw);
 }
 
 // the finish of every utterance into tokens [B][nbest][T]; T == 0: no step has run
@@ -525,6 +634,24 @@ __global__ __launch_bounds__(64) void rnnt_beam_finish_kernel(void* ws, int T, i
   const RnntBias<kBias> wb = rnnt_bias_of<kBias>(ws, gridDim.x, b, T, beam, g..., NoGraph{});
   rnnt_finish<false, kBias>(s_fin, w, wb, T == 0 ? 1 : w.cnt[0], T == 0, nbest, pad, normalize, T, tokens + (long)b * nbest * T,
                             lengths + b * nbest, scores + b * nbest, nhyp + b);
+}
+
+struct TimesFinishArgs {
+  void* ws; const void* tws;
+  int T, beam, nbest, pad, normalize;
+  int *tokens, *lengths; float* scores; int* nhyp;
+  int* times; float* vscores;
+  CgTables g;
+};
+template <bool kBias>
+__global__ __launch_bounds__(64) void rnnt_beam_times_finish_kernel(const TimesFinishArgs a) {
+  __shared__ float s_fin[kMaxBeam];
+  const int b = blockIdx.x, T = a.T, beam = a.beam, nbest = a.nbest;
+  const RnntWs w = rnnt_ws_of(a.ws, b, T, beam);
+  const RnntBias<kBias> wb = rnnt_bias_of<kBias>(a.ws, gridDim.x, b, T, beam, a.g);
+  rnnt_finish<false, kBias, true>(s_fin, w, wb, T == 0 ? 1 : w.cnt[0], T == 0, nbest, a.pad, a.normalize, T, a.tokens + (long)b * nbest * T,
+                                  a.lengths + b * nbest, a.scores + b * nbest, a.nhyp + b, rnnt_times_at((void*)a.tws, b, T, beam, 0),
+                                  a.times + (long)b * nbest * T, a.vscores + b * nbest);
 }
 
 // ------------------------------------------------------------------------------------------------ the streamed search
@@ -550,13 +677,16 @@ __device__ __forceinline__ RnntSlot<kBias> rnnt_slot(void* state, int slot, int 
   return q;
 }
 
-template <bool kBias>
+// (tstate: the times slots, one void* with kTimes and nothing without: the kernels without times keep their parameter list)
+template <bool kBias, bool kTimes = false, class... TS>
 __global__ __launch_bounds__(256) void rnnt_beam_stream_reset_kernel(void* state, const int* slots, int max_streams, int max_frames,
-                                                                     int beam) {
+                                                                     int beam, TS... tstate) {
+  static_assert(sizeof...(TS) == (kTimes ? 1 : 0));
   const int slot = slots[blockIdx.x];
   if (slot < 0 || slot >= max_streams) return;
   const RnntSlot<kBias> q = rnnt_slot<kBias>(state, slot, max_frames, beam, CgTables{});
-  rnnt_init<kBias>(q.w, q.wb);
+  if constexpr (kTimes) rnnt_init<kBias, true>(q.w, q.wb, rnnt_times_at(tstate..., slot, max_frames, beam, 0));
+  else rnnt_init<kBias>(q.w, q.wb);
   if (threadIdx.x == 0) { q.head[0] = 0; q.head[1] = 0; }
 }
 
@@ -588,10 +718,13 @@ struct StreamSelArgs {
   int max_streams, max_frames, beam, K, blank, j;
 };
 struct BiasStreamSelArgs : StreamSelArgs { CgTables g; };
+struct TimesStreamSelArgs : BiasStreamSelArgs { void* tws; };
 // the select phase of the streamed search, one workgroup per listed stream; counts the frame
-template <bool kBias>
-__global__ __launch_bounds__(256) void rnnt_beam_stream_select_kernel(const std::conditional_t<kBias, BiasStreamSelArgs, StreamSelArgs> a) {
-  __shared__ SelLdsOf<kBias> s;
+// (kTimes: the times slot goes with the slot, untouched where the slot is; the frame's number is the slot's counter)
+template <bool kBias, bool kTimes = false>
+__global__ __launch_bounds__(256) void rnnt_beam_stream_select_kernel(
+    const std::conditional_t<kTimes, TimesStreamSelArgs, std::conditional_t<kBias, BiasStreamSelArgs, StreamSelArgs>> a) {
+  __shared__ SelLdsT<kBias, kTimes> s;
   const int b = blockIdx.x;
   const long row0 = (long)b * a.beam;
   const int slot = a.slot_idx[b];
@@ -604,7 +737,8 @@ __global__ __launch_bounds__(256) void rnnt_beam_stream_select_kernel(const std:
     return;
   }
   const int nh = min(max(q.w.cnt[0], 0), a.beam);
-  rnnt_select_phase<true, kBias>(s, q.w, q.wb, a.beam, a.K, a.blank, nh, q.w.cnt[1], a.parent, a.token, a.keep, row0);
+  rnnt_select_phase<true, kBias, kTimes>(s, q.w, q.wb, a.beam, a.K, a.blank, nh, q.w.cnt[1], a.parent, a.token, a.keep, row0,
+                                         rnnt_times_of<kTimes>(a, slot, a.max_frames, a.beam, frames));
   if (threadIdx.x == 0) q.head[0] = frames + 1;
 }
 
@@ -614,6 +748,7 @@ struct StreamReadArgs {
   int *tokens, *lengths; float* scores; int* aux;  // aux: nhyp (finish) / stable_len (partial)
 };
 struct BiasStreamReadArgs : StreamReadArgs { CgTables g; };
+struct TimesStreamReadArgs : BiasStreamReadArgs { const void* tws; int* times; float* vscores; };
 
 // readout of the given slots, as the offline kernel finishes; the state is read only
 template <bool kBias>
@@ -624,6 +759,18 @@ __global__ __launch_bounds__(64) void rnnt_beam_stream_finish_kernel(const std::
   const RnntSlot<kBias> q = rnnt_slot<kBias>((void*)a.state, valid ? slot : 0, a.max_frames, a.beam, rnnt_graph_of<kBias>(a));
   rnnt_finish<true, kBias>(s_fin, q.w, q.wb, valid ? min(max(q.w.cnt[0], 0), a.beam) : 0, false, a.nbest, a.pad, a.normalize, a.max_u,
               a.tokens + (long)b * a.nbest * a.max_u, a.lengths + b * a.nbest, a.scores + b * a.nbest, a.aux + b);
+}
+
+template <bool kBias>
+__global__ __launch_bounds__(64) void rnnt_beam_stream_times_finish_kernel(const TimesStreamReadArgs a) {
+  __shared__ float s_fin[kMaxBeam];
+  const int b = blockIdx.x, slot = a.slots[b];
+  const bool valid = slot >= 0 && slot < a.max_streams;
+  const RnntSlot<kBias> q = rnnt_slot<kBias>((void*)a.state, valid ? slot : 0, a.max_frames, a.beam, a.g);
+  rnnt_finish<true, kBias, true>(s_fin, q.w, q.wb, valid ? min(max(q.w.cnt[0], 0), a.beam) : 0, false, a.nbest, a.pad, a.normalize,
+                                 a.max_u, a.tokens + (long)b * a.nbest * a.max_u, a.lengths + b * a.nbest, a.scores + b * a.nbest,
+                                 a.aux + b, rnnt_times_at((void*)a.tws, valid ? slot : 0, a.max_frames, a.beam, 0),
+                                 a.times + (long)b * a.nbest * a.max_u, a.vscores + b * a.nbest);
 }
 
 // The live hypothesis with the best score s (kBias: s + b; what the search prunes by; ties: the lower slot) and the length of the longest
@@ -903,5 +1050,128 @@ extern "C" int ea_rnnt_frame_beam_stream_bias_partial(const void* state, const i
   StreamReadArgs a;
   rnnt_read_args(a, state, slots, max_streams, max_frames, beam, 1, pad, 0, max_u, tokens, lengths, scores, stable_len);
   hipLaunchKernelGGL(rnnt_beam_stream_partial_kernel<true>, dim3(n), dim3(64), 0, stream, a);
+  return EA_CHECK_LAUNCH();
+}
+
+// ------------------------------------------------------------------------------------------------ C ABI: time stamps
+extern "C" long ea_rnnt_frame_beam_times_workspace_bytes(int B, int T, int beam) {
+  if (B <= 0 || T < 0 || beam < 1 || beam > kMaxBeam) return 0;
+  return (long)B * rnnt_times_words(T, beam) * 4L;
+}
+
+extern "C" int ea_rnnt_frame_beam_times_step(const float* logits, long ld, const float* lm_rows, long ld_lm, int lm_no_blank,
+                                             const int* in_len, void* workspace, void* times_workspace, int* parent, int* token,
+                                             void* keep, const int* cg_nodes, const int* cg_edges, const int* cg_root,
+                                             int cg_n_nodes, int cg_n_edges, int B, int T, int V, int beam, int K, int blank, int eos,
+                                             float temperature, float lm_weight, int t, hipStream_t stream) {
+  if (B <= 0) return 0;
+  TimesSelArgs s;
+  if (!logits || !in_len || !workspace || !times_workspace || !parent || !token || !keep || T < 1 || t < 0 || t >= T ||
+      rnnt_step_args_bad(ld, lm_rows, ld_lm, lm_no_blank, V, beam, K, blank, eos, temperature) ||
+      (cg_nodes && !cg_tables(s.g, cg_nodes, cg_edges, cg_root, cg_n_nodes, cg_n_edges, V)))
+    return -2;
+  RowArgs r;  // the row phase knows nothing of times or the graph: the twin's row kernel
+  r.p = rnnt_row_params(lm_rows, lm_no_blank, V, K, blank, eos, temperature, lm_weight);
+  r.logits = logits; r.ld = ld; r.lm_rows = lm_rows; r.ld_lm = ld_lm;
+  r.in_len = in_len; r.ws = workspace;
+  r.T = T; r.beam = beam; r.t = t;
+  hipLaunchKernelGGL(rnnt_beam_row_kernel, dim3(B * beam), dim3(256), 0, stream, r);
+  s.in_len = in_len; s.ws = workspace; s.parent = parent; s.token = token; s.keep = (uint8_t*)keep;
+  s.T = T; s.beam = beam; s.K = K; s.blank = blank; s.t = t;
+  s.tws = times_workspace;
+  if (cg_nodes)
+    hipLaunchKernelGGL((rnnt_beam_select_kernel<true, true>), dim3(B), dim3(256), 0, stream, s);
+  else
+    hipLaunchKernelGGL((rnnt_beam_select_kernel<false, true>), dim3(B), dim3(256), 0, stream, s);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_rnnt_frame_beam_times_finish(void* workspace, const void* times_workspace, const int* cg_nodes, int cg_n_nodes,
+                                               int B, int T, int beam, int nbest, int pad, int normalize, int* tokens, int* lengths,
+                                               float* scores, int* nhyp, int* times, float* vscores, hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (!workspace || !times_workspace || !tokens || !lengths || !scores || !nhyp || !times || !vscores || T < 0 || beam < 1 ||
+      beam > kMaxBeam || nbest < 1 || nbest > beam || (cg_nodes && cg_n_nodes < 1))
+    return -2;
+  TimesFinishArgs a;
+  a.ws = workspace; a.tws = times_workspace;
+  a.T = T; a.beam = beam; a.nbest = nbest; a.pad = pad; a.normalize = normalize;
+  a.tokens = tokens; a.lengths = lengths; a.scores = scores; a.nhyp = nhyp; a.times = times; a.vscores = vscores;
+  if (cg_nodes) {
+    a.g = cg_nodes_only(cg_nodes, cg_n_nodes);
+    hipLaunchKernelGGL(rnnt_beam_times_finish_kernel<true>, dim3(B), dim3(64), 0, stream, a);
+  } else {
+    a.g = CgTables{};
+    hipLaunchKernelGGL(rnnt_beam_times_finish_kernel<false>, dim3(B), dim3(64), 0, stream, a);
+  }
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" long ea_rnnt_frame_beam_stream_times_state_bytes(int max_frames, int beam) {
+  if (max_frames < 1 || beam < 1 || beam > kMaxBeam) return 0;
+  return rnnt_times_words(max_frames, beam) * 4L;
+}
+
+extern "C" int ea_rnnt_frame_beam_stream_times_reset(void* state, void* times_state, const int* slots, int n, int biased,
+                                                     int max_streams, int max_frames, int beam, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!state || !times_state || !slots || max_streams < 1 || max_frames < 1 || beam < 1 || beam > kMaxBeam) return -2;
+  if (biased)
+    hipLaunchKernelGGL((rnnt_beam_stream_reset_kernel<true, true, void*>), dim3(n), dim3(256), 0, stream, state, slots, max_streams,
+                       max_frames, beam, times_state);
+  else
+    hipLaunchKernelGGL((rnnt_beam_stream_reset_kernel<false, true, void*>), dim3(n), dim3(256), 0, stream, state, slots, max_streams,
+                       max_frames, beam, times_state);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_rnnt_frame_beam_stream_times_step(const float* logits, long ld, const float* lm_rows, long ld_lm, int lm_no_blank,
+                                                    const int* slot_idx, const int* n_new, int j, int n, void* state,
+                                                    void* times_state, int* parent, int* token, void* keep, const int* cg_nodes,
+                                                    const int* cg_edges, const int* cg_root, int cg_n_nodes, int cg_n_edges,
+                                                    int max_streams, int max_frames, int V, int beam, int K, int blank, int eos,
+                                                    float temperature, float lm_weight, hipStream_t stream) {
+  if (n <= 0) return 0;
+  TimesStreamSelArgs s;
+  if (!logits || !slot_idx || !n_new || !state || !times_state || !parent || !token || !keep || j < 0 || max_streams < 1 ||
+      max_frames < 1 || rnnt_step_args_bad(ld, lm_rows, ld_lm, lm_no_blank, V, beam, K, blank, eos, temperature) ||
+      (cg_nodes && !cg_tables(s.g, cg_nodes, cg_edges, cg_root, cg_n_nodes, cg_n_edges, V)))
+    return -2;
+  StreamRowArgs r;
+  r.p = rnnt_row_params(lm_rows, lm_no_blank, V, K, blank, eos, temperature, lm_weight);
+  r.logits = logits; r.ld = ld; r.lm_rows = lm_rows; r.ld_lm = ld_lm;
+  r.slot_idx = slot_idx; r.n_new = n_new; r.state = state;
+  r.max_streams = max_streams; r.max_frames = max_frames; r.beam = beam; r.j = j;
+  s.slot_idx = slot_idx; s.n_new = n_new; s.state = state; s.parent = parent; s.token = token; s.keep = (uint8_t*)keep;
+  s.max_streams = max_streams; s.max_frames = max_frames; s.beam = beam; s.K = K; s.blank = blank; s.j = j;
+  s.tws = times_state;
+  if (cg_nodes) {
+    hipLaunchKernelGGL(rnnt_beam_stream_row_kernel<true>, dim3(n * beam), dim3(256), 0, stream, r);
+    hipLaunchKernelGGL((rnnt_beam_stream_select_kernel<true, true>), dim3(n), dim3(256), 0, stream, s);
+  } else {
+    hipLaunchKernelGGL(rnnt_beam_stream_row_kernel<false>, dim3(n * beam), dim3(256), 0, stream, r);
+    hipLaunchKernelGGL((rnnt_beam_stream_select_kernel<false, true>), dim3(n), dim3(256), 0, stream, s);
+  }
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_rnnt_frame_beam_stream_times_finish(const void* state, const void* times_state, const int* slots, int n,
+                                                      int max_streams, int max_frames, int beam, const int* cg_nodes, int cg_n_nodes,
+                                                      int nbest, int pad, int normalize, int max_u, int* tokens, int* lengths,
+                                                      float* scores, int* nhyp, int* times, float* vscores, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (rnnt_read_args_bad(state, slots, max_streams, max_frames, beam, max_u, tokens, lengths, scores, nhyp) || !times_state || !times ||
+      !vscores || nbest < 1 || nbest > beam || (cg_nodes && cg_n_nodes < 1))
+    return -2;
+  TimesStreamReadArgs a;
+  rnnt_read_args(a, state, slots, max_streams, max_frames, beam, nbest, pad, normalize, max_u, tokens, lengths, scores, nhyp);
+  a.tws = times_state; a.times = times; a.vscores = vscores;
+  if (cg_nodes) {
+    a.g = cg_nodes_only(cg_nodes, cg_n_nodes);
+    hipLaunchKernelGGL(rnnt_beam_stream_times_finish_kernel<true>, dim3(n), dim3(64), 0, stream, a);
+  } else {
+    a.g = CgTables{};
+    hipLaunchKernelGGL(rnnt_beam_stream_times_finish_kernel<false>, dim3(n), dim3(64), 0, stream, a);
+  }
   return EA_CHECK_LAUNCH();
 }

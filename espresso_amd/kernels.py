@@ -906,6 +906,202 @@ def rnnt_frame_beam_stream_bias_partial(state, slots, max_frames, beam, pad, max
     return tokens, lengths, scores, stable
 
 
+# ---- time stamps for the four beam searches (the kTimes kernels of csrc/ctc_beam.hip and csrc/rnnt_beam.hip) -----------------
+def _times_outputs(n, nbest, max_u, device):
+    """(times int32 [n][nbest][max_u], vscores fp32 [n][nbest]) of a finish with time stamps."""
+    return torch.empty(n, nbest, max_u, dtype=torch.int32, device=device), torch.empty(n, nbest, dtype=torch.float32, device=device)
+
+
+def _check_times_state(tstate, bytes_fn, max_frames, beam, state):
+    assert tstate.dtype == torch.uint8 and tstate.is_contiguous() and tstate.dim() == 2 and tstate.device == state.device
+    assert tstate.shape == (state.shape[0], bytes_fn(max_frames, beam))
+
+
+def ctc_prefix_beam_times_workspace(B, T, beam, device):
+    """Times workspace of the CTC prefix beam search (ea_ctc_prefix_beam_times_workspace_bytes), beside its beam workspace."""
+    return torch.empty(int(_lib.lib().ea_ctc_prefix_beam_times_workspace_bytes(B, T, beam)), dtype=torch.uint8, device=device)
+
+
+def ctc_prefix_beam_times_step(x, in_len, ws, tws, B, T, V, beam, K, blank, t0, t1, graph=None, lm_rows=None, lm_weight=0.0,
+                               ins_bonus=0.0, lm_out=None, ld=None):
+    """ctc_prefix_beam_step (graph None; ws its workspace) or ctc_prefix_beam_bias_step (ws the bias workspace) that also follows
+    every hypothesis' best alignment path in tws (ctc_prefix_beam_times_workspace)."""
+    L = _lib.lib()
+    ld = x.stride(0) if ld is None else ld
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.stride(-1) == 1 and x.shape[0] == B * T and x.shape[1] == V
+    assert in_len.dtype == torch.int32 and in_len.numel() == B
+    assert ws.numel() >= (L.ea_ctc_prefix_beam_workspace_bytes if graph is None else L.ea_ctc_prefix_beam_bias_workspace_bytes)(B, T, beam)
+    assert tws.dtype == torch.uint8 and tws.numel() >= L.ea_ctc_prefix_beam_times_workspace_bytes(B, T, beam)
+    parent, token, keep = lm_out if lm_out is not None else (None, None, None)
+    if lm_rows is not None:
+        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (B * beam, V) and t1 == t0 + 1
+        assert parent.numel() == token.numel() == keep.numel() == B * beam
+        assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
+    check(L.ea_ctc_prefix_beam_times_step(_p(x), ld, int(x.dtype == torch.bfloat16), _p(in_len), _p(ws), _p(tws), _p(lm_rows),
+                                          lm_rows.stride(0) if lm_rows is not None else 0, _p(parent), _p(token), _p(keep),
+                                          *_cg_or_none(graph, V), B, T, V, beam, K, blank, lm_weight, ins_bonus, t0, t1, _stream()),
+          "ea_ctc_prefix_beam_times_step")
+
+
+def ctc_prefix_beam_times_finish(ws, tws, B, T, beam, nbest, pad, graph=None, lm_rows=None, lm_weight=0.0, ins_bonus=0.0, eos=-1):
+    """ctc_prefix_beam_finish / _bias_finish and (times int32 [B][nbest][T], -1 after the hypothesis; vscores fp32 [B][nbest])."""
+    dev = ws.device
+    tokens, lengths, scores, nhyp = _finish_outputs(B, nbest, T, dev)
+    times, vscores = _times_outputs(B, nbest, T, dev)
+    nodes, _, _, n_nodes, _ = _cg_or_none(graph)
+    check(_lib.lib().ea_ctc_prefix_beam_times_finish(_p(ws), _p(tws), _p(lm_rows), lm_rows.stride(0) if lm_rows is not None else 0,
+                                                     lm_weight, ins_bonus, eos, nodes, n_nodes, B, T, beam, nbest, pad, _p(tokens),
+                                                     _p(lengths), _p(scores), _p(nhyp), _p(times), _p(vscores), _stream()),
+          "ea_ctc_prefix_beam_times_finish")
+    return tokens, lengths, scores, nhyp, times, vscores
+
+
+def ctc_prefix_beam_stream_times_state(max_streams, max_frames, beam, device):
+    """(times state uint8 [max_streams][bytes per slot], bytes per slot) beside a ctc_prefix_beam_stream_state."""
+    return _stream_state(_lib.lib().ea_ctc_prefix_beam_stream_times_state_bytes, max_streams, max_frames, beam, device)
+
+
+def ctc_prefix_beam_stream_times_reset(state, tstate, slots, max_frames, beam):
+    """ctc_prefix_beam_stream_reset of the slots and of their times slots (ea_ctc_prefix_beam_stream_times_reset)."""
+    L = _lib.lib()
+    _check_stream_state(state, L.ea_ctc_prefix_beam_stream_state_bytes, max_frames, beam)
+    _check_times_state(tstate, L.ea_ctc_prefix_beam_stream_times_state_bytes, max_frames, beam, state)
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
+    check(L.ea_ctc_prefix_beam_stream_times_reset(_p(state), _p(tstate), _p(slots), slots.numel(), state.shape[0], max_frames, beam,
+                                                  _stream()), "ea_ctc_prefix_beam_stream_times_reset")
+
+
+def ctc_prefix_beam_stream_times_step(x, meta, state, tstate, max_frames, V, beam, K, blank, j0=0, j1=None, graph=None, lm_rows=None,
+                                      lm_weight=0.0, ins_bonus=0.0, lm_out=None, ld=None):
+    """ctc_prefix_beam_stream_step that also follows every hypothesis' best alignment path in the streams' times slots."""
+    L = _lib.lib()
+    ld = x.stride(0) if ld is None else ld
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 2 and x.stride(-1) == 1 and x.shape[1] == V
+    assert meta.dtype == torch.int32 and meta.dim() == 2 and meta.shape[0] == 3 and meta.is_contiguous()
+    _check_stream_state(state, L.ea_ctc_prefix_beam_stream_state_bytes, max_frames, beam)
+    _check_times_state(tstate, L.ea_ctc_prefix_beam_stream_times_state_bytes, max_frames, beam, state)
+    n = meta.shape[1]
+    j1 = max(x.shape[0], j0) if j1 is None else j1
+    parent, token, keep = lm_out if lm_out is not None else (None, None, None)
+    if lm_rows is not None:
+        assert lm_rows.dtype == torch.float32 and lm_rows.stride(1) == 1 and lm_rows.shape == (n * beam, V) and j1 == j0 + 1
+        assert parent.numel() == token.numel() == keep.numel() == n * beam
+        assert parent.dtype == token.dtype == torch.int32 and keep.dtype == torch.uint8
+    check(L.ea_ctc_prefix_beam_stream_times_step(_p(x), ld, int(x.dtype == torch.bfloat16), x.shape[0], _p(meta[0]), _p(meta[1]),
+                                                 _p(meta[2]), j0, j1, n, _p(state), _p(tstate), _p(lm_rows),
+                                                 lm_rows.stride(0) if lm_rows is not None else 0, _p(parent), _p(token), _p(keep),
+                                                 *_cg_or_none(graph, V), state.shape[0], max_frames, V, beam, K, blank, lm_weight,
+                                                 ins_bonus, _stream()), "ea_ctc_prefix_beam_stream_times_step")
+
+
+def ctc_prefix_beam_stream_times_finish(state, tstate, slots, max_frames, beam, nbest, pad, max_u, graph=None, lm_rows=None,
+                                        lm_weight=0.0, ins_bonus=0.0, eos=-1):
+    """ctc_prefix_beam_stream_finish and (times int32 [n][nbest][max_u], vscores fp32 [n][nbest]); frames count from the
+    stream's first frame.  The states are read only."""
+    L = _lib.lib()
+    _check_stream_state(state, L.ea_ctc_prefix_beam_stream_state_bytes, max_frames, beam)
+    _check_times_state(tstate, L.ea_ctc_prefix_beam_stream_times_state_bytes, max_frames, beam, state)
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and 1 <= nbest <= beam
+    n, dev = slots.numel(), state.device
+    if lm_rows is not None:
+        assert lm_rows.dtype == torch.float32 and lm_rows.dim() == 2 and lm_rows.stride(1) == 1 and lm_rows.shape[0] == n * beam
+    tokens, lengths, scores, nhyp = _finish_outputs(n, nbest, max_u, dev)
+    times, vscores = _times_outputs(n, nbest, max_u, dev)
+    nodes, _, _, n_nodes, _ = _cg_or_none(graph)
+    check(L.ea_ctc_prefix_beam_stream_times_finish(_p(state), _p(tstate), _p(slots), n, _p(lm_rows),
+                                                   lm_rows.stride(0) if lm_rows is not None else 0, lm_weight, ins_bonus, eos, nodes,
+                                                   n_nodes, state.shape[0], max_frames, beam, nbest, pad, max_u, _p(tokens),
+                                                   _p(lengths), _p(scores), _p(nhyp), _p(times), _p(vscores), _stream()),
+          "ea_ctc_prefix_beam_stream_times_finish")
+    return tokens, lengths, scores, nhyp, times, vscores
+
+
+def rnnt_frame_beam_times_workspace(B, T, beam, device):
+    """Times workspace of the frame-synchronous transducer beam search (ea_rnnt_frame_beam_times_workspace_bytes)."""
+    return torch.empty(int(_lib.lib().ea_rnnt_frame_beam_times_workspace_bytes(B, T, beam)), dtype=torch.uint8, device=device)
+
+
+def rnnt_frame_beam_times_step(logits, in_len, ws, tws, out, B, T, V, beam, K, blank, t, graph=None, eos=-1, temperature=1.0,
+                               lm_rows=None, lm_weight=0.0, lm_no_blank=False):
+    """rnnt_frame_beam_step (graph None) or rnnt_frame_beam_bias_step (ws the bias workspace) that also follows every hypothesis'
+    best alignment path in tws (rnnt_frame_beam_times_workspace)."""
+    L = _lib.lib()
+    assert in_len.dtype == torch.int32 and in_len.numel() == B
+    assert tws.dtype == torch.uint8 and tws.numel() >= L.ea_rnnt_frame_beam_times_workspace_bytes(B, T, beam)
+    parent, token, keep = _check_rnnt_step_args(logits, out, lm_rows, B * beam, V, lm_no_blank)
+    check(L.ea_rnnt_frame_beam_times_step(_p(logits), logits.stride(0), _p(lm_rows), lm_rows.stride(0) if lm_rows is not None else 0,
+                                          int(lm_no_blank), _p(in_len), _p(ws), _p(tws), _p(parent), _p(token), _p(keep),
+                                          *_cg_or_none(graph, V), B, T, V, beam, K, blank, eos, temperature, lm_weight, t, _stream()),
+          "ea_rnnt_frame_beam_times_step")
+
+
+def rnnt_frame_beam_times_finish(ws, tws, B, T, beam, nbest, pad, graph=None, normalize=True):
+    """rnnt_frame_beam_finish / _bias_finish and (times int32 [B][nbest][T], -1 after the hypothesis; vscores fp32 [B][nbest])."""
+    dev = ws.device
+    tokens, lengths, scores, nhyp = _finish_outputs(B, nbest, T, dev)
+    times, vscores = _times_outputs(B, nbest, T, dev)
+    nodes, _, _, n_nodes, _ = _cg_or_none(graph)
+    check(_lib.lib().ea_rnnt_frame_beam_times_finish(_p(ws), _p(tws), nodes, n_nodes, B, T, beam, nbest, pad, int(bool(normalize)),
+                                                     _p(tokens), _p(lengths), _p(scores), _p(nhyp), _p(times), _p(vscores), _stream()),
+          "ea_rnnt_frame_beam_times_finish")
+    return tokens, lengths, scores, nhyp, times, vscores
+
+
+def rnnt_frame_beam_stream_times_state(max_streams, max_frames, beam, device):
+    """(times state uint8 [max_streams][bytes per slot], bytes per slot) beside a rnnt_frame_beam_stream_state / _bias_state."""
+    return _stream_state(_lib.lib().ea_rnnt_frame_beam_stream_times_state_bytes, max_streams, max_frames, beam, device)
+
+
+def _rnnt_state_bytes_fn(biased):
+    L = _lib.lib()
+    return L.ea_rnnt_frame_beam_stream_bias_state_bytes if biased else L.ea_rnnt_frame_beam_stream_state_bytes
+
+
+def rnnt_frame_beam_stream_times_reset(state, tstate, slots, max_frames, beam, biased=False):
+    """rnnt_frame_beam_stream_reset (biased: _bias_reset) of the slots and of their times slots."""
+    L = _lib.lib()
+    _check_stream_state(state, _rnnt_state_bytes_fn(biased), max_frames, beam)
+    _check_times_state(tstate, L.ea_rnnt_frame_beam_stream_times_state_bytes, max_frames, beam, state)
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
+    check(L.ea_rnnt_frame_beam_stream_times_reset(_p(state), _p(tstate), _p(slots), slots.numel(), int(bool(biased)), state.shape[0],
+                                                  max_frames, beam, _stream()), "ea_rnnt_frame_beam_stream_times_reset")
+
+
+def rnnt_frame_beam_stream_times_step(logits, slot_idx, n_new, j, state, tstate, out, max_frames, V, beam, K, blank, graph=None, eos=-1,
+                                      temperature=1.0, lm_rows=None, lm_weight=0.0, lm_no_blank=False):
+    """rnnt_frame_beam_stream_step (graph None) or _bias_step (state a bias state) that also follows every hypothesis' best
+    alignment path in the streams' times slots."""
+    L = _lib.lib()
+    n = slot_idx.numel()
+    assert slot_idx.dtype == n_new.dtype == torch.int32 and n_new.numel() == n and slot_idx.is_contiguous() and n_new.is_contiguous()
+    _check_stream_state(state, _rnnt_state_bytes_fn(graph is not None), max_frames, beam)
+    _check_times_state(tstate, L.ea_rnnt_frame_beam_stream_times_state_bytes, max_frames, beam, state)
+    parent, token, keep = _check_rnnt_step_args(logits, out, lm_rows, n * beam, V, lm_no_blank)
+    check(L.ea_rnnt_frame_beam_stream_times_step(_p(logits), logits.stride(0), _p(lm_rows),
+                                                 lm_rows.stride(0) if lm_rows is not None else 0, int(lm_no_blank), _p(slot_idx),
+                                                 _p(n_new), j, n, _p(state), _p(tstate), _p(parent), _p(token), _p(keep),
+                                                 *_cg_or_none(graph, V), state.shape[0], max_frames, V, beam, K, blank, eos, temperature,
+                                                 lm_weight, _stream()), "ea_rnnt_frame_beam_stream_times_step")
+
+
+def rnnt_frame_beam_stream_times_finish(state, tstate, slots, max_frames, beam, nbest, pad, max_u, graph=None, normalize=True):
+    """rnnt_frame_beam_stream_finish / _bias_finish and (times int32 [n][nbest][max_u], vscores fp32 [n][nbest]); frames count
+    from the stream's first frame.  The states are read only."""
+    L = _lib.lib()
+    _check_stream_state(state, _rnnt_state_bytes_fn(graph is not None), max_frames, beam)
+    _check_times_state(tstate, L.ea_rnnt_frame_beam_stream_times_state_bytes, max_frames, beam, state)
+    assert slots.dtype == torch.int32 and slots.is_contiguous()
+    n, dev = slots.numel(), state.device
+    tokens, lengths, scores, nhyp = _finish_outputs(n, nbest, max_u, dev)
+    times, vscores = _times_outputs(n, nbest, max_u, dev)
+    nodes, _, _, n_nodes, _ = _cg_or_none(graph)
+    check(L.ea_rnnt_frame_beam_stream_times_finish(_p(state), _p(tstate), _p(slots), n, state.shape[0], max_frames, beam, nodes, n_nodes,
+                                                   nbest, pad, int(bool(normalize)), max_u, _p(tokens), _p(lengths), _p(scores),
+                                                   _p(nhyp), _p(times), _p(vscores), _stream()),
+          "ea_rnnt_frame_beam_stream_times_finish")
+    return tokens, lengths, scores, nhyp, times, vscores
+
+
 def context_graph_score(graph, tokens, lens):
     """Token rows int32 [N][L] (lens int32 [N]) replayed through a context graph on the device (ea_context_graph_score):
     (running bias fp32 [N][L], final bias fp32 [N], node int32 [N])."""

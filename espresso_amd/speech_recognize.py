@@ -62,11 +62,13 @@ def shard_batches(batches: List[List[int]], num_shards: int, shard_id: int) -> L
 
 
 def recognize(task, model, generator, batches: Iterable[dict], dictionary, refs: Optional[Dict[str, str]] = None, out=sys.stdout,
-              nbest: int = 1, quiet: bool = False, bpe_symbol=None, scorer=None, summary_out=None, attn_plot_dir=None):
+              nbest: int = 1, quiet: bool = False, bpe_symbol=None, scorer=None, summary_out=None, attn_plot_dir=None,
+              ctm_hyps=None):
     """The loop of espresso/speech_recognize.py:226-330.  `batches` yield dicts with `utt_ids`, `wav`, `wav_offsets`,
     `num_samples` (device tensors / lists as produced by `collate`).  `summary_out`: a second stream for the closing summary
     lines (stdout while `out` is decode.log); `attn_plot_dir`: save the best hypothesis' alignment of every utterance there
-    (plot_attention) when the generator returns one.  Returns (scorer, stats)."""
+    (plot_attention) when the generator returns one.  `ctm_hyps`: a dict that gets utterance -> (its best hypothesis, the symbols stripped from the text) (--ctm).
+    Returns (scorer, stats)."""
     from .tools.utils import plot_attention
     from .tools.wer import Scorer
 
@@ -101,6 +103,8 @@ def recognize(task, model, generator, batches: Iterable[dict], dictionary, refs:
                     if refs is not None and utt in refs:
                         scorer.add_evaluation(utt, refs[utt], hypo_str)
                     num_tok += len(toks)
+                    if ctm_hyps is not None:
+                        ctm_hyps[utt] = (hypo, strip)
         num_sent += len(sample["utt_ids"])
     lines = ["NOTE: hypothesis and token scores are output in base 2",
              "Recognized {:,} utterances ({} tokens) in {:.1f}s ({:.2f} sentences/s, {:.2f} tokens/s), RTF {:.4f}".format(
@@ -161,7 +165,8 @@ def build_generator(args, model, dictionary, lm=None, ngram=None, context_graph=
     if args.search == "ctc_beam":
         return CTCPrefixBeamSearchDecoder([model], dictionary, beam_size=args.beam, nbest=args.nbest,
                                           beam_size_token=args.ctc_beam_size_token, lm_model=lm, lm_weight=args.lm_weight,
-                                          insertion_bonus=args.ctc_insertion_bonus, context_graph=context_graph)
+                                          insertion_bonus=args.ctc_insertion_bonus, context_graph=context_graph,
+                                          token_times=bool(getattr(args, "ctm", None)))
     if args.search == "transducer_greedy":
         return TransducerGreedyDecoder([model], dictionary, max_num_expansions_per_step=args.max_num_expansions_per_step,
                                        lm_model=lm, lm_weight=args.lm_weight)
@@ -174,7 +179,7 @@ def build_generator(args, model, dictionary, lm=None, ngram=None, context_graph=
         return TransducerFrameBeamDecoder([model], dictionary, beam_size=args.beam, nbest=args.nbest,
                                           beam_size_token=args.transducer_beam_size_token, temperature=args.temperature,
                                           normalize_scores=not args.unnormalized, lm_model=lm, lm_weight=args.lm_weight,
-                                          context_graph=context_graph)
+                                          context_graph=context_graph, token_times=bool(getattr(args, "ctm", None)))
     return SequenceGenerator(model if isinstance(model, (list, tuple)) else [model], dictionary, beam_size=args.beam, max_len_a=args.max_len_a, max_len_b=args.max_len_b,
                              min_len=args.min_len, normalize_scores=not args.unnormalized, len_penalty=args.lenpen,
                              unk_penalty=args.unkpen, temperature=args.temperature, lm_model=lm, lm_weight=args.lm_weight,
@@ -188,14 +193,19 @@ def stream_beam_options(args, lm=None, context_graph=None):
                 normalize_scores=not args.unnormalized, lm_model=lm, lm_weight=args.lm_weight)
     if context_graph is not None:
         opts["context_graph"] = context_graph
+    if getattr(args, "ctm", None):
+        opts["token_times"] = True
     return opts
 
 
 def ctc_stream_beam_options(args, lm=None, context_graph=None):
     """The options of StreamingCTCPrefixBeamDecoder (after dictionary, max_streams, max_frames) from the command line of
     --search ctc_stream_beam; context_graph: the ContextGraph of --hotwords."""
-    return dict(beam_size=args.beam, nbest=args.nbest, beam_size_token=args.ctc_beam_size_token, lm_model=lm, lm_weight=args.lm_weight,
+    opts = dict(beam_size=args.beam, nbest=args.nbest, beam_size_token=args.ctc_beam_size_token, lm_model=lm, lm_weight=args.lm_weight,
                 insertion_bonus=args.ctc_insertion_bonus, context_graph=context_graph)
+    if getattr(args, "ctm", None):
+        opts["token_times"] = True
+    return opts
 
 
 def get_parser():
@@ -284,6 +294,14 @@ def get_parser():
     p.add_argument("--print-alignment", nargs="?", const="hard", default=None, choices=["hard", "soft"],
                    help="collect the attention alignments; --search beam saves RESULTS_PATH/attn_plots/<utt>.pdf of the best "
                         "hypothesis (needs --results-path and matplotlib)")
+    p.add_argument("--ctm", default=None, metavar="FILE",
+                   help="ctc_beam (without --ngram-lm) / ctc_stream_beam / transducer_frame_beam / transducer_stream_beam: also write the "
+                        "best hypothesis of every utterance as CTM lines (`utt 1 start dur unit 1.00`, `-` = stdout): each token at "
+                        "the encoder frame where it starts on the hypothesis' best alignment path, one frame long; the search then "
+                        "follows that path on the device")
+    p.add_argument("--ctm-unit", default="token", choices=["token", "word"],
+                   help="--ctm units: tokens, or words (<space> tokens / pieces that begin with the sentencepiece mark separate "
+                        "words; a word runs from its first token's start to its last token's start + one frame)")
     p.add_argument("--streaming", action="store_true",
                    help="chunk-by-chunk recognition of a chunk-streaming transformer or causal-conformer encoder (--search ctc, transducer_greedy, "
                         "transducer_stream_beam, ctc_stream_beam, or ctc_beam with --ngram-lm): audio is fed in pieces of --stream-chunk-ms with --streams utterances in flight")
@@ -313,6 +331,43 @@ def check_ngram_args(args):
 
 
 TOKEN_NGRAM_SEARCHES = ("ctc_beam", "ctc_stream_beam", "transducer_frame_beam", "transducer_stream_beam")
+CTM_SEARCHES = TOKEN_NGRAM_SEARCHES  # the four device-resident token-level beam searches
+
+
+def check_ctm_args(args):
+    """--ctm writes the time stamps the four token-level beam searches follow on the device: refused, before anything is
+    loaded, for every other search (the attention decoder, the greedy decoders, the Adaptive Expansion Search, the lexicon +
+    n-gram search)."""
+    if not args.ctm:
+        return
+    if args.search not in CTM_SEARCHES or (args.search == "ctc_beam" and args.ngram_lm):
+        raise NotImplementedError("--ctm (time stamps of the recognised tokens / words) is implemented for --search " +
+                                  ", ".join(CTM_SEARCHES) + " only (ctc_beam without --ngram-lm), not --search " + args.search +
+                                  " --ngram-lm" * bool(args.ngram_lm) + "; speech_align writes a CTM for a known transcript")
+
+
+def hypothesis_ctm_lines(utt, hypo, dictionary, strip, unit, seconds_per_frame):
+    """The CTM lines of one hypothesis with "times": every kept token spans [start, start + 1) encoder frames; words as
+    tools/forced_aligner.word_spans groups them."""
+    from .tools.forced_aligner import ctm_lines, utterance_units
+
+    pairs = [(int(t), int(f)) for t, f in zip(hypo["tokens"].tolist(), hypo["times"].tolist()) if int(t) not in strip]
+    result = {"tokens": [t for t, _ in pairs], "start": [f for _, f in pairs], "end": [f + 1 for _, f in pairs]}
+    return ctm_lines(utt, utterance_units(result, dictionary, unit), seconds_per_frame)
+
+
+def write_ctm(path, utt_ids, ctm_hyps, dictionary, unit, seconds_per_frame):
+    """--ctm: the lines of every recognised utterance, in the order of utt_ids."""
+    out = sys.stdout if path == "-" else open(path, "w", encoding="utf-8")
+    try:
+        for utt in utt_ids:
+            if utt in ctm_hyps:
+                hypo, strip = ctm_hyps[utt]
+                for line in hypothesis_ctm_lines(utt, hypo, dictionary, strip, unit, seconds_per_frame):
+                    print(line, file=out)
+    finally:
+        if out is not sys.stdout:
+            out.close()
 
 
 def check_token_ngram_args(args):
@@ -468,14 +523,14 @@ def check_streaming_args(args):
 
 def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=400, streams=16, refs=None, out=sys.stdout,
                         quiet=False, scorer=None, summary_out=None, search="ctc", max_num_expansions_per_step=2, lexicon_beam=None,
-                        partials=False, stream_beam=None, ctc_stream_beam=None):
+                        partials=False, stream_beam=None, ctc_stream_beam=None, ctm_hyps=None):
     """The output of `recognize` from a streamed pass: every utterance is read in pieces of `chunk_ms`, `streams` of them in
     flight; a finished utterance frees its slot for the next one (wav.scp order).  search "ctc_beam": lexicon_beam holds the
     arguments of StreamingCTCLexiconBeamDecoder after `dictionary` (n-gram LM, lexicon) and its options; its prefix tables are
     sized for the longest utterance given.  search "transducer_stream_beam": stream_beam holds the options of
     StreamingTransducerFrameBeamDecoder (beam, n-best, LM, ...), search "ctc_stream_beam": ctc_stream_beam those of
     StreamingCTCPrefixBeamDecoder; their prefix tables are sized the same way.  partials: a `P-` line
-    per stream whenever its partial text changed."""
+    per stream whenever its partial text changed.  ctm_hyps: a dict that gets utterance -> (its best hypothesis, the symbols stripped from the text) (--ctm)."""
     from .models.transformer.streaming_encoder import StreamingEncoder
     from .tools.streaming_ctc_decoder import StreamingCTCDecoder
     from .tools.streaming_ctc_lexicon_beam_decoder import StreamingCTCLexiconBeamDecoder
@@ -565,6 +620,8 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
                 if refs is not None and utt in refs:
                     scorer.add_evaluation(utt, refs[utt], hypo_str)
                 num_tok += len(hypo["tokens"])
+                if ctm_hyps is not None:
+                    ctm_hyps[utt] = (hypo, strip)
         audio_s += len(waves[i]) / 16000.0
     n = len(utt_ids)
     lines = ["NOTE: hypothesis and token scores are output in base 2",
@@ -655,6 +712,7 @@ def load_member(state, name, block, task, dev):
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
+    check_ctm_args(args)
     check_token_ngram_args(args)
     check_frame_beam_args(args)
     check_stream_beam_args(args)
@@ -768,12 +826,22 @@ def main(argv=None):
 
     scorer = Scorer(task.target_dictionary, wer_output_filter=args.wer_output_filter)
     stream = (collate(b, utt_ids, waves, dev) for b in batches)
+    ctm_hyps = {} if args.ctm else None
+
+    def finish_ctm():
+        if ctm_hyps is not None:
+            from .tools.forced_aligner import frame_seconds
+
+            write_ctm(args.ctm, utt_ids, ctm_hyps, task.target_dictionary, args.ctm_unit,
+                      frame_seconds(model, task.frontend.frame_shift / task.frontend.sample_rate))
+
     if args.streaming:
         mine = [i for b in batches for i in b]
         mine.sort()
         s_ids, s_waves = [utt_ids[i] for i in mine], [waves[i] for i in mine]
         kw = dict(chunk_ms=args.stream_chunk_ms or 400, streams=args.streams or 16, refs=refs, quiet=args.quiet, scorer=scorer,
-                  search=args.search, max_num_expansions_per_step=args.max_num_expansions_per_step, partials=args.stream_partials)
+                  search=args.search, max_num_expansions_per_step=args.max_num_expansions_per_step, partials=args.stream_partials,
+                  ctm_hyps=ctm_hyps)
         if args.search == "ctc_beam":
             kw["lexicon_beam"] = (ngram, dict(beam_size=args.beam, nbest=args.nbest, beam_size_token=args.ctc_beam_size_token,
                                               lm_weight=args.lm_weight, word_score=args.word_score,
@@ -784,10 +852,12 @@ def main(argv=None):
             kw["stream_beam"] = stream_beam_options(args, lm, context_graph)
         if not args.results_path:
             recognize_streaming(task, model, task.target_dictionary, s_ids, s_waves, dev, out=sys.stdout, **kw)
+            finish_ctm()
             return scorer
         os.makedirs(args.results_path, exist_ok=True)
         with open(os.path.join(args.results_path, "decode.log"), "w", buffering=1, encoding="utf-8") as log:
             recognize_streaming(task, model, task.target_dictionary, s_ids, s_waves, dev, out=log, summary_out=sys.stdout, **kw)
+        finish_ctm()
         has_target = refs is not None and all(u in refs for u in s_ids)
         if has_target:
             scorer.add_ordered_utt_list(s_ids)
@@ -795,14 +865,16 @@ def main(argv=None):
         return scorer
     if not args.results_path:
         recognize(task, model, gen, stream, task.target_dictionary, refs, out=sys.stdout, nbest=args.nbest, quiet=args.quiet,
-                  scorer=scorer)
+                  scorer=scorer, ctm_hyps=ctm_hyps)
+        finish_ctm()
         return scorer
     os.makedirs(args.results_path, exist_ok=True)
     # attention plots only for the attention decoder (the reference's is_attention_model: not the CTC / transducer criteria)
     plot_dir = os.path.join(args.results_path, "attn_plots") if args.print_alignment is not None and args.search == "beam" else None
     with open(os.path.join(args.results_path, "decode.log"), "w", buffering=1, encoding="utf-8") as log:
         recognize(task, model, gen, stream, task.target_dictionary, refs, out=log, nbest=args.nbest, quiet=args.quiet, scorer=scorer,
-                  summary_out=sys.stdout, attn_plot_dir=plot_dir)
+                  summary_out=sys.stdout, attn_plot_dir=plot_dir, ctm_hyps=ctm_hyps)
+    finish_ctm()
     decoded = [u for b in batches for u in (utt_ids[i] for i in b)]
     has_target = refs is not None and all(u in refs for u in decoded)
     if has_target:  # wav.scp order of the utterances this process decoded (the reference: dataset.tgt.utt_ids)

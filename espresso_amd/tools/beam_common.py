@@ -16,11 +16,19 @@ import torch
 from .. import kernels as K
 
 
-def hyps_from_tensors(tokens, lengths, scores, nhyp) -> List[List[Dict[str, torch.Tensor]]]:
+def hyps_from_tensors(tokens, lengths, scores, nhyp, times=None, vscores=None) -> List[List[Dict[str, torch.Tensor]]]:
     """Host tensors (tokens [B][nbest][U], lengths [B][nbest], scores [B][nbest], nhyp [B]) of a search -> per utterance its
-    nhyp hypotheses in the generators' format, best first."""
-    return [[{"tokens": tokens[b, i, : int(lengths[b, i])].to(torch.long), "score": scores[b, i], "attention": None,
+    nhyp hypotheses in the generators' format, best first.  With the outputs of a search with time stamps (times int32
+    [B][nbest][U], vscores fp32 [B][nbest]) every hypothesis also has "times" (int64 [len]: the encoder frame at which each
+    token starts on its best alignment path) and "viterbi_score" (that path's score)."""
+    hyps = [[{"tokens": tokens[b, i, : int(lengths[b, i])].to(torch.long), "score": scores[b, i], "attention": None,
               "alignment": None} for i in range(int(nhyp[b]))] for b in range(tokens.shape[0])]
+    if times is not None:
+        for b, utt in enumerate(hyps):
+            for i, h in enumerate(utt):
+                h["times"] = times[b, i, : int(lengths[b, i])].to(torch.long)
+                h["viterbi_score"] = vscores[b, i]
+    return hyps
 
 
 def step_triple(N, device):
@@ -103,6 +111,12 @@ class StreamSlots:
         self._free = list(range(self.max_streams - 1, -1, -1))
         self.streams: Dict[object, list] = {}
         self._unreset: List[int] = []  # slots opened since the last reset launch
+        self.times_state = None  # the per-slot state of the time stamps, for a decoder asked for them
+
+    def _allocate_times(self, make_state, beam, device):
+        """The times state beside the search state (make_state: the K.*_stream_times_state of the search); the decoder's reset
+        launch resets a slot's times slot with the slot."""
+        self.times_state, _ = make_state(self.max_streams, self.max_frames, beam, device)
 
     def open(self, stream_ids):
         for sid in stream_ids:

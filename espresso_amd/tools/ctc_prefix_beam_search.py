@@ -19,7 +19,12 @@ same, and the LM update of a frame is one launch (csrc/ngram_rows.hip) that adva
 Hotword biasing: with `context_graph` (tools/context_graph.ContextGraph) every hypothesis also carries its state in the phrase
 automaton and a running bias that joins the score unweighted; the final score is the unbiased score of the same tokens plus
 the boosts of the phrases it completed.  The candidate tokens of a frame stay the K best by acoustic score: biasing re-ranks
-hypotheses, it does not bring back a token outside the top K.  Without a graph the search calls what it always called."""
+hypotheses, it does not bring back a token outside the top K.  Without a graph the search calls what it always called.
+
+Time stamps: with `token_times=True` the search runs the times family of the kernels (ea_ctc_prefix_beam_times_*), which follows
+the best single alignment path of every hypothesis, and `search` also returns times int32 [B][nbest][T] (the frame at which each
+token starts on that path, -1 after the hypothesis) and vscores fp32 [B][nbest] (that path's score); `generate` puts them into
+the hypotheses as "times" and "viterbi_score".  Tokens and scores are those of the search without times, bit for bit."""
 from typing import Dict, List
 
 import torch
@@ -32,7 +37,7 @@ class CTCPrefixBeamSearchDecoder(BeamDecoderMixin):
     MAX_BEAM = 64
 
     def __init__(self, models, dictionary, beam_size=10, nbest=1, beam_size_token=None, lm_model=None, lm_weight=0.0,
-                 insertion_bonus=0.0, blank=None, context_graph=None, **kwargs):
+                 insertion_bonus=0.0, blank=None, context_graph=None, token_times=False, **kwargs):
         self.model = models[0] if isinstance(models, (list, tuple)) else models
         self.pad = dictionary.pad()
         self.eos = dictionary.eos()
@@ -58,6 +63,7 @@ class CTCPrefixBeamSearchDecoder(BeamDecoderMixin):
         if context_graph is not None and context_graph.vocab_size != V:
             raise ValueError(f"CTC prefix beam search: context graph built for {context_graph.vocab_size} tokens, dictionary has {V}")
         self.context_graph = context_graph
+        self.token_times = bool(token_times)
 
     def cuda(self):
         self.model.cuda()
@@ -72,14 +78,24 @@ class CTCPrefixBeamSearchDecoder(BeamDecoderMixin):
     def search(self, lprobs, in_len):
         """lprobs fp32/bf16 [B][T][V] log-probs (row-contiguous), in_len int [B] -> device tensors (tokens int32
         [B][nbest][T] pad-filled, lengths int32 [B][nbest], scores fp32 [B][nbest] natural log, nhyp int32 [B]), best
-        first.  No host synchronisation."""
+        first; with token_times also (times int32 [B][nbest][T], vscores fp32 [B][nbest]).  No host synchronisation."""
         B, T, V = lprobs.shape
         assert V == self.vocab_size and lprobs.stride(2) == 1 and lprobs.stride(0) == T * lprobs.stride(1)
         x = lprobs.view(B * T, V) if lprobs.is_contiguous() else lprobs.reshape(B * T, V)
         in_len = in_len.to(device=lprobs.device, dtype=torch.int32).contiguous()
         dev, beam, Kt = lprobs.device, self.beam_size, self.beam_size_token
         step = dict(B=B, T=T, V=V, beam=beam, K=Kt, blank=self.blank, ins_bonus=self.insertion_bonus)
-        if self.context_graph is None:
+        if self.token_times:
+            graph = self.context_graph.cuda(dev) if self.context_graph is not None else None
+            ws = (K.ctc_prefix_beam_workspace if graph is None else K.ctc_prefix_beam_bias_workspace)(B, T, beam, dev)
+            tws = K.ctc_prefix_beam_times_workspace(B, T, beam, dev)
+
+            def beam_step(x, in_len, ws, **kw):
+                K.ctc_prefix_beam_times_step(x, in_len, ws, tws, graph=graph, **kw)
+
+            def beam_finish(ws, *a, **kw):
+                return K.ctc_prefix_beam_times_finish(ws, tws, *a, graph=graph, **kw)
+        elif self.context_graph is None:
             ws = K.ctc_prefix_beam_workspace(B, T, beam, dev)
             beam_step, beam_finish = K.ctc_prefix_beam_step, K.ctc_prefix_beam_finish
         else:

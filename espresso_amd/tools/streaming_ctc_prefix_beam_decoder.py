@@ -20,7 +20,12 @@ returns, bit for bit, what CTCPrefixBeamSearchDecoder.search returns for the who
 `partial` reads, per stream, the hypothesis the beam currently ranks first (its in-beam score: LM and running bias included,
 the LM's end-of-sentence term and the bias still pending not) and the stable prefix: the tokens shared by every live hypothesis
 with a finite score.  Every later hypothesis with a finite score is a stay or an extension of one of those (a merge lands on
-the extension of one), so the stable tokens never change again."""
+the extension of one), so the stable tokens never change again.
+
+Time stamps: with `token_times=True` a slot also has a times slot (K.ctc_prefix_beam_stream_times_state), the reset, the steps and
+the finish are those of the times family (ea_ctc_prefix_beam_stream_times_*), `finish` also returns (times, vscores) with frames
+counted from the stream's first frame, and `close` puts "times" and "viterbi_score" into the hypotheses: what the offline
+decoder with token_times returns for the whole utterance.  `partial` carries no times."""
 from typing import Dict, List
 
 import torch
@@ -32,7 +37,7 @@ from .ctc_prefix_beam_search import CTCPrefixBeamSearchDecoder
 
 class StreamingCTCPrefixBeamDecoder(StreamSlots):
     def __init__(self, dictionary, max_streams, max_frames, beam_size=10, nbest=1, beam_size_token=None, lm_model=None, lm_weight=0.0,
-                 insertion_bonus=0.0, blank=None, context_graph=None):
+                 insertion_bonus=0.0, blank=None, context_graph=None, token_times=False):
         # validation and defaults of the offline decoder
         o = CTCPrefixBeamSearchDecoder([None], dictionary, beam_size=beam_size, nbest=nbest, beam_size_token=beam_size_token,
                                        lm_model=lm_model, lm_weight=lm_weight, insertion_bonus=insertion_bonus, blank=blank,
@@ -46,6 +51,7 @@ class StreamingCTCPrefixBeamDecoder(StreamSlots):
         self._search = dict(max_frames=self.max_frames, V=o.vocab_size, beam=o.beam_size, K=o.beam_size_token, blank=o.blank,
                             ins_bonus=o.insertion_bonus)
         self.state = self.graph = self.lm = self.lm_rows = self._rows = None  # allocated on the device of the first frames
+        self.token_times = bool(token_times)
 
     def state_bytes_per_stream(self) -> int:
         from .. import _lib
@@ -58,6 +64,8 @@ class StreamingCTCPrefixBeamDecoder(StreamSlots):
         """The search state, the graph tables and, with an LM, the per-slot rows and the row every new stream starts from (the
         LM after its eos), once."""
         self.state, _ = K.ctc_prefix_beam_stream_state(self.max_streams, self.max_frames, self.beam_size, device)
+        if self.token_times:
+            self._allocate_times(K.ctc_prefix_beam_stream_times_state, self.beam_size, device)
         if self.context_graph is not None:
             self.graph = self.context_graph.cuda(device)
         if self.lm_model is not None:
@@ -75,7 +83,10 @@ class StreamingCTCPrefixBeamDecoder(StreamSlots):
         device = self.state.device
         if self._unreset:
             slots = self._ints(self._unreset, device)
-            K.ctc_prefix_beam_stream_reset(self.state, slots, self.max_frames, self.beam_size)
+            if self.token_times:
+                K.ctc_prefix_beam_stream_times_reset(self.state, self.times_state, slots, self.max_frames, self.beam_size)
+            else:
+                K.ctc_prefix_beam_stream_reset(self.state, slots, self.max_frames, self.beam_size)
             if self.lm is not None:
                 self._rows.reset(slots)
             self._unreset = []
@@ -109,30 +120,38 @@ class StreamingCTCPrefixBeamDecoder(StreamSlots):
             return
         dev = self._ensure(lprobs.device)
         Tm = max(c for _, c, _ in ready)
+        if self.token_times:
+            def step(lprobs, meta, state, **kw):
+                K.ctc_prefix_beam_stream_times_step(lprobs, meta, state, self.times_state, **kw)
+        else:
+            step = K.ctc_prefix_beam_stream_step
         if self.lm is None:
-            K.ctc_prefix_beam_stream_step(lprobs, meta, self.state, graph=self.graph, j0=0, j1=Tm, **self._search)
+            step(lprobs, meta, self.state, graph=self.graph, j0=0, j1=Tm, **self._search)
         else:
             rows = self._rows.rows_of(meta[0])
             lm_state, lm_rows = self._rows.gather(rows)
             lm_out = step_triple(len(ready) * self.beam_size, dev)
             for j in range(Tm):
-                K.ctc_prefix_beam_stream_step(lprobs, meta, self.state, graph=self.graph, j0=j, j1=j + 1, lm_rows=lm_rows,
-                                              lm_weight=self.lm_weight, lm_out=lm_out, **self._search)
+                step(lprobs, meta, self.state, graph=self.graph, j0=j, j1=j + 1, lm_rows=lm_rows, lm_weight=self.lm_weight,
+                     lm_out=lm_out, **self._search)
                 lm_state, lm_rows = self.offline.lm_update(lm_state, *lm_out)
             self._rows.scatter(rows, [lm_state, lm_rows])
         self._advance(ready)
 
     @torch.no_grad()
     def finish(self, stream_ids, nbest=None, max_u=None):
-        """Device tensors (tokens int32 [n][nbest][U], lengths, scores, nhyp) of the streams as if they ended now; their
-        state is left as it is."""
+        """Device tensors (tokens int32 [n][nbest][U], lengths, scores, nhyp; with token_times also times int32 [n][nbest][U]
+        and vscores) of the streams as if they ended now; their state is left as it is."""
         slots = self._slots_of(stream_ids, self._ensure(self._device()))
         lm = {}
         if self.lm is not None:
             lm = dict(lm_rows=K.gather_rows(self.lm_rows, self._rows.rows_of(slots)), lm_weight=self.lm_weight, eos=self.eos)
-        return K.ctc_prefix_beam_stream_finish(self.state, slots, self.max_frames, self.beam_size, self.nbest if nbest is None else nbest,
-                                               self.pad, self._max_u(stream_ids) if max_u is None else max_u, graph=self.graph,
-                                               ins_bonus=self.insertion_bonus, **lm)
+        args = (slots, self.max_frames, self.beam_size, self.nbest if nbest is None else nbest, self.pad,
+                self._max_u(stream_ids) if max_u is None else max_u)
+        if self.token_times:
+            return K.ctc_prefix_beam_stream_times_finish(self.state, self.times_state, *args, graph=self.graph,
+                                                         ins_bonus=self.insertion_bonus, **lm)
+        return K.ctc_prefix_beam_stream_finish(self.state, *args, graph=self.graph, ins_bonus=self.insertion_bonus, **lm)
 
     @torch.no_grad()
     def partial_tensors(self, stream_ids, max_u=None):

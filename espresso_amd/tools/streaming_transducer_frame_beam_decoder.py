@@ -24,7 +24,12 @@ tokens never change again.
 Hotword biasing: with `context_graph` (tools/context_graph.ContextGraph) the state, the reset, every step, the finish and the
 partial are those of the bias family (ea_rnnt_frame_beam_stream_bias_*): a slot also holds the automaton state and the running
 bias of every beam slot, `partial` returns the live hypothesis with the best score + running bias, and `close` returns what
-TransducerFrameBeamDecoder.search with the same graph returns.  The tables are uploaded once; the loop still reads nothing back."""
+TransducerFrameBeamDecoder.search with the same graph returns.  The tables are uploaded once; the loop still reads nothing back.
+
+Time stamps: with `token_times=True` a slot also has a times slot (K.rnnt_frame_beam_stream_times_state), the reset, the steps and
+the finish are those of the times family (ea_rnnt_frame_beam_stream_times_*), `finish_tensors` also returns (times, vscores) with
+frames counted from the stream's first frame, and `finish` / `close` put "times" and "viterbi_score" into the hypotheses: what the
+offline decoder with token_times returns for the whole utterance.  `partial` carries no times."""
 from typing import Dict, List
 
 import torch
@@ -36,7 +41,7 @@ from .transducer_frame_beam_decoder import TransducerFrameBeamDecoder
 
 class StreamingTransducerFrameBeamDecoder(StreamSlots):
     def __init__(self, model, dictionary, beam_size, max_streams, max_frames, nbest=1, beam_size_token=None, temperature=1.0,
-                 normalize_scores=True, lm_model=None, lm_weight=0.0, model_predicts_eos=False, context_graph=None):
+                 normalize_scores=True, lm_model=None, lm_weight=0.0, model_predicts_eos=False, context_graph=None, token_times=False):
         # validation and defaults of the offline decoder
         o = TransducerFrameBeamDecoder(model, dictionary, beam_size=beam_size, nbest=nbest, beam_size_token=beam_size_token,
                                        temperature=temperature, normalize_scores=normalize_scores, lm_model=lm_model,
@@ -52,6 +57,7 @@ class StreamingTransducerFrameBeamDecoder(StreamSlots):
                           eos=o.eos if o.model_predicts_eos else -1, temperature=o.temperature, lm_weight=o.lm_weight,
                           lm_no_blank=o.no_blank_in_lm)
         self.state = self.graph = None
+        self.token_times = bool(token_times)
         dev = next(self.model.parameters()).device if self.model is not None else None
         if dev is not None and dev.type == "cuda":
             self._allocate(dev)
@@ -72,6 +78,8 @@ class StreamingTransducerFrameBeamDecoder(StreamSlots):
         self.graph = self.offline.graph_tables(device)
         make_state = K.rnnt_frame_beam_stream_state if self.graph is None else K.rnnt_frame_beam_stream_bias_state
         self.state, _ = make_state(self.max_streams, self.max_frames, self.beam_size, device)
+        if self.token_times:
+            self._allocate_times(K.rnnt_frame_beam_stream_times_state, self.beam_size, device)
         out, st = dec.advance(torch.full((1,), self.bos, dtype=torch.int32, device=device), dec.init_state(1, device))
         self.pred = dec.init_state(R, device)
         self.pred_out = out.new_zeros(R, out.shape[1])
@@ -92,8 +100,12 @@ class StreamingTransducerFrameBeamDecoder(StreamSlots):
         device = self.state.device
         if self._unreset:
             slots = self._ints(self._unreset, device)
-            reset = K.rnnt_frame_beam_stream_reset if self.graph is None else K.rnnt_frame_beam_stream_bias_reset
-            reset(self.state, slots, self.max_frames, self.beam_size)
+            if self.token_times:
+                K.rnnt_frame_beam_stream_times_reset(self.state, self.times_state, slots, self.max_frames, self.beam_size,
+                                                     biased=self.graph is not None)
+            else:
+                reset = K.rnnt_frame_beam_stream_reset if self.graph is None else K.rnnt_frame_beam_stream_bias_reset
+                reset(self.state, slots, self.max_frames, self.beam_size)
             self._rows.reset(slots)
             self._unreset = []
         return device
@@ -123,7 +135,10 @@ class StreamingTransducerFrameBeamDecoder(StreamSlots):
         for j in range(Tm):
             logits = model.joint_step(K.gather_rows(E, frame_rows[j]), dec_out)
             lm_rows = lm[1] if lm else None
-            if self.graph is None:
+            if self.token_times:
+                K.rnnt_frame_beam_stream_times_step(logits, slot_idx, n_new, j, self.state, self.times_state, out, graph=self.graph,
+                                                    lm_rows=lm_rows, **self._step)
+            elif self.graph is None:
                 K.rnnt_frame_beam_stream_step(logits, slot_idx, n_new, j, self.state, out, lm_rows=lm_rows, **self._step)
             else:
                 K.rnnt_frame_beam_stream_bias_step(logits, slot_idx, n_new, j, self.state, self.graph, out, lm_rows=lm_rows, **self._step)
@@ -136,11 +151,14 @@ class StreamingTransducerFrameBeamDecoder(StreamSlots):
 
     @torch.no_grad()
     def finish_tensors(self, stream_ids, nbest=None, max_u=None):
-        """Device tensors (tokens int32 [n][nbest][U], lengths, scores, nhyp) of the streams as if they ended now; their
-        state is left as it is."""
+        """Device tensors (tokens int32 [n][nbest][U], lengths, scores, nhyp; with token_times also times int32 [n][nbest][U]
+        and vscores) of the streams as if they ended now; their state is left as it is."""
         slots = self._slots_of(stream_ids, self._ensure(self._device()))
         args = (self.max_frames, self.beam_size, self.nbest if nbest is None else nbest, self.pad,
                 self._max_u(stream_ids) if max_u is None else max_u)
+        if self.token_times:
+            return K.rnnt_frame_beam_stream_times_finish(self.state, self.times_state, slots, *args, graph=self.graph,
+                                                         normalize=self.offline.normalize_scores)
         if self.graph is None:
             return K.rnnt_frame_beam_stream_finish(self.state, slots, *args, normalize=self.offline.normalize_scores)
         return K.rnnt_frame_beam_stream_bias_finish(self.state, slots, self.graph, *args, normalize=self.offline.normalize_scores)

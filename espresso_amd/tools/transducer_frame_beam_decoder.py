@@ -17,7 +17,12 @@ token whose LM log-prob is -inf leaves the candidates, as any token with a non-f
 
 Hotword biasing: with `context_graph` (tools/context_graph.ContextGraph) every hypothesis also carries its state in the phrase
 automaton and a running bias; the decoder then calls the bias family of the kernels (ea_rnnt_frame_beam_bias_*) for the
-workspace, every step and the finish, with the tables uploaded once.  Without a graph the calls are the unbiased ones."""
+workspace, every step and the finish, with the tables uploaded once.  Without a graph the calls are the unbiased ones.
+
+Time stamps: with `token_times=True` the steps and the finish are those of the times family (ea_rnnt_frame_beam_times_*), which
+follows the best single alignment path of every hypothesis, and `search` also returns times int32 [B][nbest][T'] (the frame at
+which each token is emitted on that path, -1 after the hypothesis) and vscores fp32 [B][nbest] (that path's score, never
+normalised); `generate` puts them into the hypotheses as "times" and "viterbi_score"."""
 from typing import Dict, List
 
 import torch
@@ -31,7 +36,7 @@ class TransducerFrameBeamDecoder(BeamDecoderMixin):
 
     def __init__(self, models, dictionary, beam_size=5, nbest=1, beam_size_token=None, temperature=1.0, normalize_scores=True,
                  lm_model=None, lm_weight=0.0, model_predicts_eos=False, bos=None, blank=None, eos=None, pad=None,
-                 symbols_to_strip_from_output=None, print_alignment=False, context_graph=None, **kwargs):
+                 symbols_to_strip_from_output=None, print_alignment=False, context_graph=None, token_times=False, **kwargs):
         if isinstance(models, (list, tuple)):
             if len(models) != 1:
                 raise NotImplementedError("the frame-synchronous transducer beam search takes one model: ensembles are not implemented")
@@ -77,6 +82,7 @@ class TransducerFrameBeamDecoder(BeamDecoderMixin):
         if context_graph is not None and context_graph.vocab_size != V:
             raise ValueError(f"transducer frame beam search: context graph built for {context_graph.vocab_size} tokens, dictionary has {V}")
         self.context_graph = context_graph
+        self.token_times = bool(token_times)
 
     def cuda(self):
         self.model.cuda()
@@ -97,7 +103,8 @@ class TransducerFrameBeamDecoder(BeamDecoderMixin):
     def search(self, E, enc_len, bos_token=None):
         """E fp32 [B][T'][J] (the joint's encoder branch, `joint_encoder_branch`), enc_len int [B] on the device -> device
         tensors (tokens int32 [B][nbest][T'] pad-filled, lengths int32 [B][nbest], scores fp32 [B][nbest] natural log, nhyp
-        int32 [B]), best first.  No host synchronisation."""
+        int32 [B]), best first; with token_times also (times int32 [B][nbest][T'], vscores fp32 [B][nbest]).  No host
+        synchronisation."""
         model, dec = self.model, self.model.decoder
         B, Tp, J = E.shape
         dev, beam, V = E.device, self.beam_size, self.vocab_size
@@ -110,6 +117,7 @@ class TransducerFrameBeamDecoder(BeamDecoderMixin):
         out = step_triple(N, dev)
         graph = self.graph_tables(dev)
         ws = K.rnnt_frame_beam_workspace(B, Tp, beam, dev) if graph is None else K.rnnt_frame_beam_bias_workspace(B, Tp, beam, dev)
+        tws = K.rnnt_frame_beam_times_workspace(B, Tp, beam, dev) if self.token_times else None
         state = dec.init_state(N, dev)
         dec_out, state = dec.advance(torch.full((N,), self.bos if bos_token is None else bos_token, dtype=torch.int32, device=dev), state)
         lm_state = lm_rows = None
@@ -119,7 +127,9 @@ class TransducerFrameBeamDecoder(BeamDecoderMixin):
                     temperature=self.temperature, lm_weight=self.lm_weight, lm_no_blank=self.no_blank_in_lm)
         for t in range(Tp):
             logits = model.joint_step(K.gather_rows(E, frame_rows[t]), dec_out)
-            if graph is None:
+            if tws is not None:
+                K.rnnt_frame_beam_times_step(logits, in_len, ws, tws, out, t=t, graph=graph, lm_rows=lm_rows, **step)
+            elif graph is None:
                 K.rnnt_frame_beam_step(logits, in_len, ws, out, t=t, lm_rows=lm_rows, **step)
             else:
                 K.rnnt_frame_beam_bias_step(logits, in_len, ws, graph, out, t=t, lm_rows=lm_rows, **step)
@@ -127,6 +137,8 @@ class TransducerFrameBeamDecoder(BeamDecoderMixin):
             dec_out, state = dec.advance(out[1], state, keep_row=out[2])
             if self.lm_model is not None:
                 lm_state, lm_rows = self.lm_update(lm_state, *out)
+        if tws is not None:
+            return K.rnnt_frame_beam_times_finish(ws, tws, B, Tp, beam, self.nbest, self.pad, graph=graph, normalize=self.normalize_scores)
         if graph is None:
             return K.rnnt_frame_beam_finish(ws, B, Tp, beam, self.nbest, self.pad, normalize=self.normalize_scores)
         return K.rnnt_frame_beam_bias_finish(ws, graph, B, Tp, beam, self.nbest, self.pad, normalize=self.normalize_scores)

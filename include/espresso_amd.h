@@ -524,6 +524,51 @@ int ea_ctc_prefix_beam_stream_finish(const void* state, const int* slots, int n,
 int ea_ctc_prefix_beam_stream_partial(const void* state, const int* slots, int n, float lm_weight, float ins_bonus, int biased,
                                       int max_streams, int max_frames, int beam, int pad, int max_u, int* tokens, int* lengths,
                                       float* scores, int* stable_len, ea_stream_t stream);
+/* Time stamps for the CTC prefix beam search, offline and streamed (csrc/ctc_beam.hip, the kTimes instantiations).  Every
+ * hypothesis also carries vb / vnb: pb / pnb with max in place of log-add-exp, the score of its best single alignment path (the
+ * LM, insertion-bonus and bias terms depend on the tokens only and stay out), and eb / enb: pointers into a per-utterance pool of
+ * time nodes (parent time node, frame), node 0 = no tokens.  Stay: vb' = max(vb, vnb) + x[blank] with the pointer of the larger
+ * (tie: eb); vnb' = vnb + x[last] (-inf if last is no candidate), enb' = enb.  Extension by c: from (vb, eb) if c == last, else
+ * from the larger of (vb, eb), (vnb, enb) (tie: the blank one): vnb'' = that + x[c] with a new time node (its pointer, t),
+ * vb'' = -inf.  An extension merging into a stay replaces the stay's (vnb', enb') only if strictly larger.  Time nodes are made
+ * for selected candidates only (<= beam per frame, numbered in lane order).  Tokens, scores, n-best order and the triples are
+ * those of the search without times, bit for bit.  Each call takes the arguments of its twin (the graph tables optional as in
+ * ea_ctc_prefix_beam_stream_*: cg_nodes == NULL is the unbiased search on the unbiased workspace, otherwise the workspace is the
+ * bias one) plus a separate times workspace / times state; the beam workspace / stream state is the twin's, unchanged.
+ * 4-byte words per utterance (T frames) or per stream slot (T = max_frames):
+ *   times words = 4 * beam + 2 + 2 * cap, cap = 1 + T * beam
+ * (vb, vnb fp32 [beam]; eb, enb int32 [beam]; node counter, 0; tpar int32 [cap]; tfrm int32 [cap]).  ..._bytes return 0 for
+ * arguments out of range.  Bad arguments (those of the twin, a NULL times buffer or output) return -2 and launch nothing.
+ * ..._times_step / _stream_times_step: as the twin; the launch with t0 == 0 also initialises the times workspace; a streamed entry
+ *   that is not due leaves its slot and its times slot untouched.  Streamed frames count from the stream's first frame.
+ * ..._stream_times_reset: resets the listed slots of `state` as ..._stream_reset does, and their times slots.
+ * ..._times_finish / _stream_times_finish: as the twin, and times int32 [..][nbest][max_u] (offline: max_u = T): times[u] = the
+ *   frame at which token u starts on the best path of the larger of (vb, vnb) (tie: eb), -1 after the hypothesis, cut at max_u
+ *   as tokens is; vscores fp32 [..][nbest] = max(vb, vnb) (-inf where there is no hypothesis).  Read only: valid mid-stream. */
+long ea_ctc_prefix_beam_times_workspace_bytes(int B, int T, int beam);
+int ea_ctc_prefix_beam_times_step(const void* x, long ld, int x_bf16, const int* in_len, void* workspace, void* times_workspace,
+                                  const float* lm_rows, long ld_lm, int* lm_parent, int* lm_token, void* lm_keep,
+                                  const int* cg_nodes, const int* cg_edges, const int* cg_root, int cg_n_nodes, int cg_n_edges,
+                                  int B, int T, int V, int beam, int K, int blank, float lm_weight, float ins_bonus, int t0, int t1,
+                                  ea_stream_t stream);
+int ea_ctc_prefix_beam_times_finish(void* workspace, const void* times_workspace, const float* lm_rows, long ld_lm, float lm_weight,
+                                    float ins_bonus, int eos, const int* cg_nodes, int cg_n_nodes, int B, int T, int beam,
+                                    int nbest, int pad, int* tokens, int* lengths, float* scores, int* nhyp, int* times,
+                                    float* vscores, ea_stream_t stream);
+long ea_ctc_prefix_beam_stream_times_state_bytes(int max_frames, int beam);
+int ea_ctc_prefix_beam_stream_times_reset(void* state, void* times_state, const int* slots, int n, int max_streams, int max_frames,
+                                          int beam, ea_stream_t stream);
+int ea_ctc_prefix_beam_stream_times_step(const void* x, long ld, int x_bf16, long total_rows, const int* slot_idx, const int* n_new,
+                                         const int* row_off, int j0, int j1, int n, void* state, void* times_state,
+                                         const float* lm_rows, long ld_lm, int* lm_parent, int* lm_token, void* lm_keep,
+                                         const int* cg_nodes, const int* cg_edges, const int* cg_root, int cg_n_nodes,
+                                         int cg_n_edges, int max_streams, int max_frames, int V, int beam, int K, int blank,
+                                         float lm_weight, float ins_bonus, ea_stream_t stream);
+int ea_ctc_prefix_beam_stream_times_finish(const void* state, const void* times_state, const int* slots, int n, const float* lm_rows,
+                                           long ld_lm, float lm_weight, float ins_bonus, int eos, const int* cg_nodes,
+                                           int cg_n_nodes, int max_streams, int max_frames, int beam, int nbest, int pad, int max_u,
+                                           int* tokens, int* lengths, float* scores, int* nhyp, int* times, float* vscores,
+                                           ea_stream_t stream);
 /* Frame-synchronous transducer beam search (csrc/rnnt_beam.hip; at most one symbol per encoder frame and hypothesis, equal
  * token sequences merged — "modified beam search") with optional mass-preserving shallow fusion of one sub-word LM: the
  * transducer counterpart of ea_ctc_prefix_beam_*.  Hypotheses are distinct token sequences with a score (natural log), at most
@@ -633,6 +678,46 @@ int ea_rnnt_frame_beam_stream_bias_finish(const void* state, const int* slots, i
 int ea_rnnt_frame_beam_stream_bias_partial(const void* state, const int* slots, int n, int max_streams, int max_frames, int beam,
                                            int pad, int max_u, int* tokens, int* lengths, float* scores, int* stable_len,
                                            ea_stream_t stream);
+/* Time stamps for the frame-synchronous transducer beam search, offline and streamed (csrc/rnnt_beam.hip, the kTimes
+ * instantiations).  Every hypothesis also carries v, which accumulates the same fused r as its score with max in place of
+ * log-add-exp at a merge (the score of its best single alignment path), and e, a pointer into a per-utterance pool of time
+ * nodes (parent time node, frame), node 0 = no tokens.  Stay: v' = v + r_blank, e' = e.  Extension by u: v'' = v + r_u with a
+ * new time node (e, t).  An extension merging into a stay replaces the stay's (v', e') only if strictly larger.  Time nodes are
+ * made for selected candidates only (<= beam per frame).  Tokens, scores, n-best order and the triples are those of the search
+ * without times, bit for bit; the row phase is the twin's.  Each call takes the arguments of its twin with the graph tables
+ * optional (cg_nodes == NULL: the unbiased search on the unbiased workspace / state; otherwise the bias workspace / state) plus
+ * a separate times workspace / times state; the beam workspace / stream state is the twin's, unchanged.  4-byte words per
+ * utterance (T frames) or per stream slot (T = max_frames):
+ *   times words = 2 * beam + 2 + 2 * cap, cap = 1 + T * beam
+ * (v fp32 [beam]; e int32 [beam]; node counter, 0; tpar int32 [cap]; tfrm int32 [cap]).  ..._bytes return 0 for arguments out of
+ * range.  Bad arguments (those of the twin, a NULL times buffer or output) return -2 and launch nothing.
+ * ..._times_step / _stream_times_step: as the twin; the step with t == 0 also initialises the times workspace; a streamed entry
+ *   that is not active leaves its slot and its times slot untouched.  Streamed frames count from the stream's first frame.
+ * ..._stream_times_reset: resets the listed slots of `state` (biased != 0: a bias state) as the twin's reset does, and their
+ *   times slots.
+ * ..._times_finish / _stream_times_finish: as the twin, and times int32 [..][nbest][max_u] (offline: max_u = T): times[u] = the
+ *   frame at which token u is emitted on that path, -1 after the hypothesis, cut at max_u as tokens is; vscores fp32
+ *   [..][nbest] = v, never normalised (-inf where there is no hypothesis).  Read only: valid mid-stream. */
+long ea_rnnt_frame_beam_times_workspace_bytes(int B, int T, int beam);
+int ea_rnnt_frame_beam_times_step(const float* logits, long ld, const float* lm_rows, long ld_lm, int lm_no_blank, const int* in_len,
+                                  void* workspace, void* times_workspace, int* parent, int* token, void* keep, const int* cg_nodes,
+                                  const int* cg_edges, const int* cg_root, int cg_n_nodes, int cg_n_edges, int B, int T, int V,
+                                  int beam, int K, int blank, int eos, float temperature, float lm_weight, int t, ea_stream_t stream);
+int ea_rnnt_frame_beam_times_finish(void* workspace, const void* times_workspace, const int* cg_nodes, int cg_n_nodes, int B, int T,
+                                    int beam, int nbest, int pad, int normalize, int* tokens, int* lengths, float* scores, int* nhyp,
+                                    int* times, float* vscores, ea_stream_t stream);
+long ea_rnnt_frame_beam_stream_times_state_bytes(int max_frames, int beam);
+int ea_rnnt_frame_beam_stream_times_reset(void* state, void* times_state, const int* slots, int n, int biased, int max_streams,
+                                          int max_frames, int beam, ea_stream_t stream);
+int ea_rnnt_frame_beam_stream_times_step(const float* logits, long ld, const float* lm_rows, long ld_lm, int lm_no_blank,
+                                         const int* slot_idx, const int* n_new, int j, int n, void* state, void* times_state,
+                                         int* parent, int* token, void* keep, const int* cg_nodes, const int* cg_edges,
+                                         const int* cg_root, int cg_n_nodes, int cg_n_edges, int max_streams, int max_frames, int V,
+                                         int beam, int K, int blank, int eos, float temperature, float lm_weight, ea_stream_t stream);
+int ea_rnnt_frame_beam_stream_times_finish(const void* state, const void* times_state, const int* slots, int n, int max_streams,
+                                           int max_frames, int beam, const int* cg_nodes, int cg_n_nodes, int nbest, int pad,
+                                           int normalize, int max_u, int* tokens, int* lengths, float* scores, int* nhyp, int* times,
+                                           float* vscores, ea_stream_t stream);
 /* Word n-gram LM (ARPA) and lexicon-constrained CTC prefix beam search with its fusion (csrc/ctc_lexicon_beam.hip) — the
  * search the reference takes from Flashlight's KenLM lexicon decoder (espresso/tools/ctc_decoder.py:24-71).
  * ea_ngram_create: parses a plain-text ARPA file of order <= 6 at `path` into host tables and writes an opaque handle to
