@@ -1151,6 +1151,42 @@ def rnnt_viterbi_align(lpb, lpy, logit_lengths, target_lengths):
     return emit_frame, score
 
 
+def ctc_prefix_posteriors(x, targets, utt, in_len, tgt_len, B, T, V, blank, ld=None, want_psi=False):
+    """Per-token posteriors (ea_ctc_prefix_posteriors) of hypotheses targets int32 [N][Lmax] under x [B*T][V] fp32/bf16
+    log-probs (batch-major, row pitch ld); hypothesis n reads utterance utt[n].  Returns (logc fp32 [N][Lmax + 1], total fp32
+    [N]) and, with want_psi, psi fp32 [N][Lmax], all on the device."""
+    ld = x.stride(0) if ld is None else ld
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.stride(-1) == 1 and x.shape[0] == B * T and x.shape[1] == V
+    assert targets.dtype == torch.int32 and targets.is_contiguous() and targets.dim() == 2
+    N, Lmax = targets.shape
+    assert utt.dtype == tgt_len.dtype == in_len.dtype == torch.int32 and utt.numel() == tgt_len.numel() == N and in_len.numel() == B
+    assert utt.is_contiguous() and tgt_len.is_contiguous() and in_len.is_contiguous()
+    dev = x.device
+    logc = torch.empty(N, Lmax + 1, dtype=torch.float32, device=dev)
+    total = torch.empty(N, dtype=torch.float32, device=dev)
+    psi = torch.empty(N, Lmax, dtype=torch.float32, device=dev) if want_psi else None
+    check(_lib.lib().ea_ctc_prefix_posteriors(_p(x), ld, int(x.dtype == torch.bfloat16), _p(targets), _p(utt), _p(in_len),
+                                              _p(tgt_len), _p(logc), _p(total), _p(psi), N, B, T, V, Lmax,
+                                              blank, _stream()), "ea_ctc_prefix_posteriors")
+    return (logc, total, psi) if want_psi else (logc, total)
+
+
+def rnnt_prefix_posteriors(lpb, lpy, logit_lengths, target_lengths, want_psi=False):
+    """Per-token posteriors (ea_rnnt_prefix_posteriors) over transducer lattices lpb / lpy fp32 [B][T][U1] (ea_rnnt_scan's
+    meaning).  Returns (logc fp32 [B][U1], total fp32 [B]) and, with want_psi, psi fp32 [B][U1 - 1], all on the device."""
+    B, T, U1 = lpb.shape
+    assert lpb.dtype == lpy.dtype == torch.float32 and lpb.is_contiguous() and lpy.is_contiguous() and lpy.shape == lpb.shape
+    assert logit_lengths.dtype == target_lengths.dtype == torch.int32 and logit_lengths.numel() == target_lengths.numel() == B
+    assert logit_lengths.is_contiguous() and target_lengths.is_contiguous()
+    dev = lpb.device
+    logc = torch.empty(B, U1, dtype=torch.float32, device=dev)
+    total = torch.empty(B, dtype=torch.float32, device=dev)
+    psi = torch.empty(B, U1 - 1, dtype=torch.float32, device=dev) if want_psi else None
+    check(_lib.lib().ea_rnnt_prefix_posteriors(_p(lpb), _p(lpy), _p(logit_lengths), _p(target_lengths), _p(logc), _p(total),
+                                               _p(psi), B, T, U1, _stream()), "ea_rnnt_prefix_posteriors")
+    return (logc, total, psi) if want_psi else (logc, total)
+
+
 def _lattice_views(ws, off_b, off_y, B, T, U1):
     n = B * T * U1
     return (ws[off_b:off_b + 4 * n].view(torch.float32).view(B, T, U1), ws[off_y:off_y + 4 * n].view(torch.float32).view(B, T, U1))

@@ -7,7 +7,8 @@ space-separated tokens).  The model kind decides the aligner: an encoder-only CT
 -> `TransducerForcedAligner` (tools/forced_aligner.py); attention encoder-decoder models are refused.  Seconds per encoder
 frame = the front-end's frame shift x the model's sub-sampling factor.  `--scores` gets one line per utterance (id, encoder
 frames, tokens, Viterbi log-prob, log-prob per frame); utterances whose transcript cannot be aligned (too few frames) are
-marked `infeasible` there and left out of the CTM."""
+marked `infeasible` there and left out of the CTM.  With `--confidence` the last CTM column is the acoustic model's posterior of
+the unit (tools/token_posteriors.py) instead of 1.00."""
 import argparse
 import math
 import os
@@ -42,6 +43,9 @@ def get_parser():
     p.add_argument("--unit", default="token", choices=["token", "word"],
                    help="CTM units: tokens, or words (<space> tokens / pieces that begin with the sentencepiece mark separate words)")
     p.add_argument("--scores", default=None, help="per-utterance alignment scores file")
+    p.add_argument("--confidence", action="store_true",
+                   help="the CTM's last column carries the model's posterior of the unit given the audio and the transcript before it "
+                        "(tools/token_posteriors.py; a word: the product over its tokens) instead of 1.00: transcript verification")
     return p
 
 
@@ -86,6 +90,7 @@ def main(argv=None):
         model_kind(args.model)
     from .tasks.speech_recognition import SpeechRecognitionEspressoConfig, SpeechRecognitionEspressoTask
     from .tools.forced_aligner import CTCForcedAligner, TransducerForcedAligner, ctm_lines, frame_seconds, utterance_units
+    from .tools.token_posteriors import unit_confidences
 
     state = _load_file(args.path)
     model_name, model_cfg = resolve_model_config(args.model, args.model_config, state)
@@ -101,7 +106,7 @@ def main(argv=None):
         sentencepiece_model=args.sentencepiece_model))
     d = task.target_dictionary
     model = load_member(state, model_name, model_cfg, task, dev)
-    aligner = (CTCForcedAligner if kind == "ctc" else TransducerForcedAligner)([model], d)
+    aligner = (CTCForcedAligner if kind == "ctc" else TransducerForcedAligner)([model], d, token_posteriors=args.confidence)
 
     scp = read_scp(args.wav_scp)
     texts = read_text(args.text)
@@ -132,7 +137,11 @@ def main(argv=None):
         for u in order:
             r = results[u]
             if r["feasible"]:
-                for line in ctm_lines(u, utterance_units(r, d, args.unit), spf):
+                conf = None
+                if args.confidence:
+                    conf = unit_confidences([d[int(t)] for t in r["tokens"]], r["token_posteriors"], args.unit,
+                                            space=getattr(d, "space_word", "<space>"))
+                for line in ctm_lines(u, utterance_units(r, d, args.unit), spf, confidences=conf):
                     print(line, file=ctm)
     finally:
         if ctm is not sys.stdout:

@@ -69,6 +69,7 @@ def recognize(task, model, generator, batches: Iterable[dict], dictionary, refs:
     lines (stdout while `out` is decode.log); `attn_plot_dir`: save the best hypothesis' alignment of every utterance there
     (plot_attention) when the generator returns one.  `ctm_hyps`: a dict that gets utterance -> (its best hypothesis, the symbols stripped from the text) (--ctm).
     Returns (scorer, stats)."""
+    from .tools.token_posteriors import confidence_line
     from .tools.utils import plot_attention
     from .tools.wer import Scorer
 
@@ -95,6 +96,9 @@ def recognize(task, model, generator, batches: Iterable[dict], dictionary, refs:
                 hypo_str = dictionary.string(torch.tensor([t for t in toks.tolist() if t not in strip]), bpe_symbol=bpe_symbol)
                 if not quiet:
                     print("H-{}\t{}\t{}".format(utt, hypo_str, float(hypo["score"]) / math.log(2)), file=out)
+                    if hypo.get("token_posteriors") is not None:  # --confidence: the labels the model emitted, then the end
+                        print(confidence_line(utt, [f for t, f in zip(toks.tolist(), hypo["token_posteriors"].tolist())
+                                                    if t not in strip], float(hypo["end_posterior"])), file=out)
                 if j == 0:
                     if enc_lens is not None and hypo.get("attention") is not None:
                         os.makedirs(attn_plot_dir, exist_ok=True)
@@ -156,8 +160,9 @@ def build_generator(args, model, dictionary, lm=None, ngram=None, context_graph=
     from .tools.transducer_frame_beam_decoder import TransducerFrameBeamDecoder
     from .tools.transducer_greedy_decoder import TransducerGreedyDecoder
 
+    post = bool(getattr(args, "confidence", False))
     if args.search == "ctc":
-        return CTCDecoder([model], dictionary)
+        return CTCDecoder([model], dictionary, token_posteriors=post)
     if args.search == "ctc_beam" and ngram is not None:
         return CTCLexiconBeamSearchDecoder([model], dictionary, *ngram, beam_size=args.beam, nbest=args.nbest,
                                            beam_size_token=args.ctc_beam_size_token, lm_weight=args.lm_weight,
@@ -166,20 +171,21 @@ def build_generator(args, model, dictionary, lm=None, ngram=None, context_graph=
         return CTCPrefixBeamSearchDecoder([model], dictionary, beam_size=args.beam, nbest=args.nbest,
                                           beam_size_token=args.ctc_beam_size_token, lm_model=lm, lm_weight=args.lm_weight,
                                           insertion_bonus=args.ctc_insertion_bonus, context_graph=context_graph,
-                                          token_times=bool(getattr(args, "ctm", None)))
+                                          token_times=bool(getattr(args, "ctm", None)), token_posteriors=post)
     if args.search == "transducer_greedy":
         return TransducerGreedyDecoder([model], dictionary, max_num_expansions_per_step=args.max_num_expansions_per_step,
-                                       lm_model=lm, lm_weight=args.lm_weight)
+                                       lm_model=lm, lm_weight=args.lm_weight, token_posteriors=post)
     if args.search == "transducer_beam":
         return TransducerBeamSearchDecoder([model], dictionary, beam_size=args.beam,
                                            max_num_expansions_per_step=args.max_num_expansions_per_step, expansion_beta=args.expansion_beta,
                                            expansion_gamma=args.expansion_gamma, prefix_alpha=args.prefix_alpha, lm_model=lm,
-                                           lm_weight=args.lm_weight)
+                                           lm_weight=args.lm_weight, token_posteriors=post)
     if args.search == "transducer_frame_beam":
         return TransducerFrameBeamDecoder([model], dictionary, beam_size=args.beam, nbest=args.nbest,
                                           beam_size_token=args.transducer_beam_size_token, temperature=args.temperature,
                                           normalize_scores=not args.unnormalized, lm_model=lm, lm_weight=args.lm_weight,
-                                          context_graph=context_graph, token_times=bool(getattr(args, "ctm", None)))
+                                          context_graph=context_graph, token_times=bool(getattr(args, "ctm", None)),
+                                          token_posteriors=post)
     return SequenceGenerator(model if isinstance(model, (list, tuple)) else [model], dictionary, beam_size=args.beam, max_len_a=args.max_len_a, max_len_b=args.max_len_b,
                              min_len=args.min_len, normalize_scores=not args.unnormalized, len_penalty=args.lenpen,
                              unk_penalty=args.unkpen, temperature=args.temperature, lm_model=lm, lm_weight=args.lm_weight,
@@ -302,6 +308,11 @@ def get_parser():
     p.add_argument("--ctm-unit", default="token", choices=["token", "word"],
                    help="--ctm units: tokens, or words (<space> tokens / pieces that begin with the sentencepiece mark separate "
                         "words; a word runs from its first token's start to its last token's start + one frame)")
+    p.add_argument("--confidence", action="store_true",
+                   help="ctc / ctc_beam (without --ngram-lm) / transducer_greedy / transducer_beam / transducer_frame_beam: after every "
+                        "`H-<utt>` line print `C-<utt>`, the acoustic model's posterior of every emitted token given the audio and "
+                        "the tokens before it, then that of ending there (no LM, bonus or bias in them); --ctm then carries the unit's "
+                        "probability (a word: the product over its tokens) instead of 1.00")
     p.add_argument("--streaming", action="store_true",
                    help="chunk-by-chunk recognition of a chunk-streaming transformer or causal-conformer encoder (--search ctc, transducer_greedy, "
                         "transducer_stream_beam, ctc_stream_beam, or ctc_beam with --ngram-lm): audio is fed in pieces of --stream-chunk-ms with --streams utterances in flight")
@@ -346,14 +357,48 @@ def check_ctm_args(args):
                                   " --ngram-lm" * bool(args.ngram_lm) + "; speech_align writes a CTM for a known transcript")
 
 
+CONFIDENCE_SEARCHES = ("ctc", "ctc_beam", "transducer_greedy", "transducer_beam", "transducer_frame_beam")
+
+
+def check_confidence_args(args):
+    """--confidence prints the acoustic model's per-token posteriors (tools/token_posteriors.py) of the offline CTC and
+    transducer searches: refused, before anything is loaded, for the attention decoder (its hypotheses carry positional
+    scores), the lexicon + n-gram search (its units are words), every --streaming search (the posterior needs the whole
+    utterance's lattice), ensembles, and a transducer that predicts <eos>."""
+    if not getattr(args, "confidence", False):
+        return
+    if args.streaming or args.search in ("transducer_stream_beam", "ctc_stream_beam"):
+        raise NotImplementedError("--confidence is not streamed: the posterior of a token needs the whole utterance's lattice (no "
+                                  "--streaming, --search ctc_stream_beam or --search transducer_stream_beam with it)")
+    if args.search not in CONFIDENCE_SEARCHES:
+        raise NotImplementedError("--confidence (per-token posteriors) is implemented for --search " + ", ".join(CONFIDENCE_SEARCHES) +
+                                  f" only, not --search {args.search}")
+    if args.ngram_lm:
+        raise NotImplementedError("--confidence scores the model's sub-word tokens: no --ngram-lm with it (the units of the lexicon "
+                                  "search are words)")
+    if len(args.path.split(os.pathsep)) > 1:
+        raise NotImplementedError("--confidence is the posterior of one model: ensembles (--path a.pt:b.pt) are not implemented")
+    if getattr(args, "model_predicts_eos", False):
+        raise NotImplementedError("--confidence is not implemented for a transducer that predicts <eos> (model_predicts_eos)")
+
+
 def hypothesis_ctm_lines(utt, hypo, dictionary, strip, unit, seconds_per_frame):
     """The CTM lines of one hypothesis with "times": every kept token spans [start, start + 1) encoder frames; words as
-    tools/forced_aligner.word_spans groups them."""
+    tools/forced_aligner.word_spans groups them.  A hypothesis with "token_posteriors" (--confidence) carries the unit's
+    probability in the last column instead of 1.00."""
     from .tools.forced_aligner import ctm_lines, utterance_units
+    from .tools.token_posteriors import unit_confidences
 
-    pairs = [(int(t), int(f)) for t, f in zip(hypo["tokens"].tolist(), hypo["times"].tolist()) if int(t) not in strip]
+    keep = [k for k, t in enumerate(hypo["tokens"].tolist()) if int(t) not in strip]
+    toks, times = hypo["tokens"].tolist(), hypo["times"].tolist()
+    pairs = [(int(toks[k]), int(times[k])) for k in keep]
     result = {"tokens": [t for t, _ in pairs], "start": [f for _, f in pairs], "end": [f + 1 for _, f in pairs]}
-    return ctm_lines(utt, utterance_units(result, dictionary, unit), seconds_per_frame)
+    conf = None
+    if hypo.get("token_posteriors") is not None:
+        post = hypo["token_posteriors"].tolist()
+        conf = unit_confidences([dictionary[t] for t, _ in pairs], [post[k] for k in keep], unit,
+                                space=getattr(dictionary, "space_word", "<space>"))
+    return ctm_lines(utt, utterance_units(result, dictionary, unit), seconds_per_frame, confidences=conf)
 
 
 def write_ctm(path, utt_ids, ctm_hyps, dictionary, unit, seconds_per_frame):
@@ -713,6 +758,7 @@ def load_member(state, name, block, task, dev):
 def main(argv=None):
     args = get_parser().parse_args(argv)
     check_ctm_args(args)
+    check_confidence_args(args)
     check_token_ngram_args(args)
     check_frame_beam_args(args)
     check_stream_beam_args(args)

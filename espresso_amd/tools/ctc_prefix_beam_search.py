@@ -24,20 +24,25 @@ hypotheses, it does not bring back a token outside the top K.  Without a graph t
 Time stamps: with `token_times=True` the search runs the times family of the kernels (ea_ctc_prefix_beam_times_*), which follows
 the best single alignment path of every hypothesis, and `search` also returns times int32 [B][nbest][T] (the frame at which each
 token starts on that path, -1 after the hypothesis) and vscores fp32 [B][nbest] (that path's score); `generate` puts them into
-the hypotheses as "times" and "viterbi_score".  Tokens and scores are those of the search without times, bit for bit."""
+the hypotheses as "times" and "viterbi_score".  Tokens and scores are those of the search without times, bit for bit.
+
+Posteriors: with `token_posteriors=True` every hypothesis also carries the acoustic model's own per-token posteriors
+(tools/token_posteriors.py: "token_posteriors", "end_posterior", "posterior_score" — no LM, bonus or bias in them), computed from
+the log-probs the search read; the search itself is unchanged."""
 from typing import Dict, List
 
 import torch
 
 from .. import kernels as K
 from .beam_common import BeamDecoderMixin, check_token_ngram, hyps_from_tensors, is_token_ngram, step_triple
+from .token_posteriors import CTCTokenPosteriors, attach_posteriors, nbest_rows, score_rows
 
 
 class CTCPrefixBeamSearchDecoder(BeamDecoderMixin):
     MAX_BEAM = 64
 
     def __init__(self, models, dictionary, beam_size=10, nbest=1, beam_size_token=None, lm_model=None, lm_weight=0.0,
-                 insertion_bonus=0.0, blank=None, context_graph=None, token_times=False, **kwargs):
+                 insertion_bonus=0.0, blank=None, context_graph=None, token_times=False, token_posteriors=False, **kwargs):
         self.model = models[0] if isinstance(models, (list, tuple)) else models
         self.pad = dictionary.pad()
         self.eos = dictionary.eos()
@@ -64,6 +69,7 @@ class CTCPrefixBeamSearchDecoder(BeamDecoderMixin):
             raise ValueError(f"CTC prefix beam search: context graph built for {context_graph.vocab_size} tokens, dictionary has {V}")
         self.context_graph = context_graph
         self.token_times = bool(token_times)
+        self.posteriors = CTCTokenPosteriors(dictionary, blank=self.blank) if token_posteriors else None
 
     def cuda(self):
         self.model.cuda()
@@ -122,11 +128,28 @@ class CTCPrefixBeamSearchDecoder(BeamDecoderMixin):
                            ins_bonus=self.insertion_bonus, eos=self.eos)
 
     @torch.no_grad()
-    def _generate(self, sample):
+    def _generate(self, sample, posteriors=None):
+        """posteriors: a list that gets the device rows of `score_rows` for the hypotheses, row = utterance * nbest + rank."""
         net_output = self.model(**sample["net_input"])
         lprobs = self.model.get_normalized_probs(net_output, log_probs=True)  # T x B x V view of [B][T][V]
-        return self.search(lprobs.transpose(0, 1), net_output["src_lengths"][0])
+        out = self.search(lprobs.transpose(0, 1), net_output["src_lengths"][0])
+        if posteriors is not None:
+            posteriors.extend(self.score_hypotheses(lprobs.transpose(0, 1), net_output["src_lengths"][0], out))
+        return out
+
+    @torch.no_grad()
+    def score_hypotheses(self, lprobs, in_len, out):
+        """The device rows (token factors [B * nbest][T], end factors, posterior scores) of what `search` returned for lprobs."""
+        tokens, lengths, _, nhyp = out[:4]
+        ln, utt = nbest_rows(lengths, nhyp)
+        return score_rows(self.posteriors, lprobs, in_len, tokens.reshape(-1, tokens.shape[2]), ln, utt, (self.blank, self.pad))
 
     @torch.no_grad()
     def generate(self, models, sample, **kwargs) -> List[List[Dict[str, torch.Tensor]]]:
-        return hyps_from_tensors(*(t.cpu() for t in self._generate(sample)))
+        rows = [] if self.posteriors is not None else None
+        out = self._generate(sample, posteriors=rows)
+        hyps = hyps_from_tensors(*(t.cpu() for t in out))
+        if rows is not None:
+            nbest = out[0].shape[1]
+            attach_posteriors([u[i] if i < len(u) else None for u in hyps for i in range(nbest)], *(t.cpu() for t in rows))
+        return hyps

@@ -61,19 +61,30 @@ def _results(host: np.ndarray, B: int, L: int, end_offset: Optional[int] = None)
     return out
 
 
+def _attach_posteriors(results: List[Dict], logc, total):
+    """The keys of tools/token_posteriors.py for the transcripts of a batch, from the kernels' device rows (one more host copy)."""
+    logc, total = logc.cpu().numpy(), total.cpu().numpy()
+    for b, r in enumerate(results):
+        n = len(r["tokens"])
+        r["token_posteriors"] = logc[b, :n].copy()
+        r["end_posterior"] = float(logc[b, n])
+        r["posterior_score"] = float(total[b])
+
+
 class CTCForcedAligner:
     """Viterbi alignment of transcripts with an encoder-only CTC model (blank = "<s>", as in the `ctc_loss` criterion)."""
 
-    def __init__(self, models, dictionary, blank=None):
+    def __init__(self, models, dictionary, blank=None, token_posteriors=False):
         self.model = models[0] if isinstance(models, (list, tuple)) else models
         self.dictionary = dictionary
         self.blank = dictionary.bos() if blank is None else blank
+        self.token_posteriors = bool(token_posteriors)
 
     @torch.no_grad()
     def align(self, sample, targets, target_lengths=None) -> List[Dict]:
         """targets: [B][Lmax] token ids (tensor, host or device) with target_lengths, or a list of B id lists.  Returns per
         utterance: tokens, start / end (encoder frames, [start, end)), score (Viterbi log-prob), frames (valid encoder frames),
-        feasible."""
+        feasible; with token_posteriors also the three keys of tools/token_posteriors.py for the transcript."""
         net_output = self.model(**sample["net_input"])
         lprobs = self.model.get_normalized_probs(net_output, log_probs=True)  # T x B x V view of [B][T][V]
         Tp, B, V = lprobs.shape
@@ -82,7 +93,43 @@ class CTCForcedAligner:
         tg, tl = _pad_targets(targets, target_lengths, 0, flat.device)
         ts, te, _, score = K.ctc_viterbi_align(flat, tg, enc_len, tl, B, Tp, V, self.blank)
         host = torch.cat([tg.flatten(), ts.flatten(), te.flatten(), tl, enc_len, score.view(torch.int32)]).cpu().numpy()
-        return _results(host, B, tg.shape[1])
+        out = _results(host, B, tg.shape[1])
+        if self.token_posteriors:
+            utt = torch.arange(B, dtype=torch.int32, device=flat.device)
+            _attach_posteriors(out, *K.ctc_prefix_posteriors(flat, tg, utt, enc_len, tl, B, Tp, V, self.blank))
+        return out
+
+
+@torch.no_grad()
+def joint_lattice(m, E, enc_len, tg, tl, bos, pad, blank, fused=True):
+    """The transducer lattice of targets tg int32 [B][U] (lengths tl int32 [B]) from the joint network's encoder branch E
+    [B * T'][J] (row = utterance * T' + frame) and encoder lengths int32 [B]: the predictor teacher-forced on bos y1 ... yU, then
+    the fused output layer + log-sum-exp pass of the RNN-T loss (`fused=False`, or a shape the fused kernels do not take: the
+    materialised logits).  Returns (lpb, lpy fp32 [B][T'][U+1], loss fp32 [B]).  The forced aligner and the per-token posteriors
+    (tools/token_posteriors.py) both read the lattice here."""
+    B = enc_len.numel()
+    T = E.shape[0] // B
+    U1 = tg.shape[1] + 1
+    prev = torch.full((B, U1), pad, dtype=torch.long, device=tg.device)
+    prev[:, 0] = bos
+    cols = torch.arange(U1 - 1, device=tg.device).unsqueeze(0)
+    prev[:, 1:] = torch.where(cols < tl.unsqueeze(1), tg.long(), torch.full_like(prev[:, 1:], pad))
+    dec, _ = m.decoder.extract_features(prev)
+    D = m._joint_decoder_branch(dec.reshape(B * U1, -1)).contiguous()
+    w, b = m.fc_out_params()
+    V = w.shape[0]
+    w16 = K.cast_f32_to_bf16(w.detach().contiguous())
+    Z = K.joint_add_relu(E, D, B, T, U1) if fused else None
+    if fused and U1 <= 512 and E.dtype == D.dtype == torch.float32 and K.joint_rnnt_supported(Z, w16):
+        loss, ws = K.joint_rnnt_loss_fwd(Z, w16, b, tg, enc_len, tl, B, T, U1, blank)
+        lpb, lpy = K.joint_rnnt_lattice(ws, B, T, U1, V)
+    else:
+        from .. import functional as F
+
+        logits = F.transducer_joint(E, D, w, b, B, T, U1)
+        loss, ws = K.rnnt_loss_fwd(logits, tg, enc_len, tl, blank)
+        lpb, lpy = K.rnnt_lattice(ws, B, T, U1)
+    return lpb, lpy, loss
 
 
 class TransducerForcedAligner:
@@ -90,13 +137,14 @@ class TransducerForcedAligner:
     with the `transducer_loss` criterion).  `fused=False` forces the materialised-logits lattice (what shapes the fused joint
     does not take use anyway)."""
 
-    def __init__(self, models, dictionary, blank=None, bos=None, fused=True):
+    def __init__(self, models, dictionary, blank=None, bos=None, fused=True, token_posteriors=False):
         self.model = models[0] if isinstance(models, (list, tuple)) else models
         self.dictionary = dictionary
         self.blank = dictionary.bos() if blank is None else blank
         self.bos = dictionary.eos() if bos is None else bos
         self.pad = dictionary.pad()
         self.fused = fused
+        self.token_posteriors = bool(token_posteriors)
 
     @torch.no_grad()
     def lattice(self, sample, tg, tl):
@@ -106,29 +154,8 @@ class TransducerForcedAligner:
         enc = m.encoder(ni["src_tokens"], ni["src_lengths"])
         x = enc["_x_bt"][0]
         enc_len = enc["src_lengths"][0].to(torch.int32).contiguous()
-        B = enc_len.numel()
-        T = x.shape[0] // B
-        U1 = tg.shape[1] + 1
-        prev = torch.full((B, U1), self.pad, dtype=torch.long, device=tg.device)
-        prev[:, 0] = self.bos
-        cols = torch.arange(U1 - 1, device=tg.device).unsqueeze(0)
-        prev[:, 1:] = torch.where(cols < tl.unsqueeze(1), tg.long(), torch.full_like(prev[:, 1:], self.pad))
-        dec, _ = m.decoder.extract_features(prev)
-        D = m._joint_decoder_branch(dec.reshape(B * U1, -1)).contiguous()
-        E = m.joint_encoder_branch(x).contiguous()
-        w, b = m.fc_out_params()
-        V = w.shape[0]
-        w16 = K.cast_f32_to_bf16(w.detach().contiguous())
-        Z = K.joint_add_relu(E, D, B, T, U1) if self.fused else None
-        if self.fused and U1 <= 512 and E.dtype == D.dtype == torch.float32 and K.joint_rnnt_supported(Z, w16):
-            loss, ws = K.joint_rnnt_loss_fwd(Z, w16, b, tg, enc_len, tl, B, T, U1, self.blank)
-            lpb, lpy = K.joint_rnnt_lattice(ws, B, T, U1, V)
-        else:
-            from .. import functional as F
-
-            logits = F.transducer_joint(E, D, w, b, B, T, U1)
-            loss, ws = K.rnnt_loss_fwd(logits, tg, enc_len, tl, self.blank)
-            lpb, lpy = K.rnnt_lattice(ws, B, T, U1)
+        lpb, lpy, loss = joint_lattice(m, m.joint_encoder_branch(x).contiguous(), enc_len, tg, tl, self.bos, self.pad, self.blank,
+                                       self.fused)
         return lpb, lpy, enc_len, loss
 
     @torch.no_grad()
@@ -139,7 +166,10 @@ class TransducerForcedAligner:
         lpb, lpy, enc_len, _ = self.lattice(sample, tg, tl)
         emit, score = K.rnnt_viterbi_align(lpb, lpy, enc_len, tl)
         host = torch.cat([tg.flatten(), emit.flatten(), emit.flatten(), tl, enc_len, score.view(torch.int32)]).cpu().numpy()
-        return _results(host, tg.shape[0], tg.shape[1], end_offset=1)
+        out = _results(host, tg.shape[0], tg.shape[1], end_offset=1)
+        if self.token_posteriors:
+            _attach_posteriors(out, *K.rnnt_prefix_posteriors(lpb.contiguous(), lpy.contiguous(), enc_len, tl))
+        return out
 
 
 # ------------------------------------------------------------------------------------------------ frames, words, CTM
@@ -172,11 +202,15 @@ def word_spans(symbols: Sequence[str], starts: Sequence[int], ends: Sequence[int
     return [(w, s, e) for w, s, e in words if w]
 
 
-def ctm_lines(utt: str, units, seconds_per_frame: float) -> List[str]:
-    """`utt 1 start dur unit conf` lines (seconds, 3 decimals); units = [(text, start_frame, end_frame)].  The transcript is
-    given, not recognised: the confidence column is 1.00."""
-    return ["{} 1 {:.3f} {:.3f} {} 1.00".format(utt, s * seconds_per_frame, (e - s) * seconds_per_frame, text)
-            for text, s, e in units]
+def ctm_lines(utt: str, units, seconds_per_frame: float, confidences: Optional[Sequence[float]] = None) -> List[str]:
+    """`utt 1 start dur unit conf` lines (seconds, 3 decimals); units = [(text, start_frame, end_frame)].  The confidence column
+    is 1.00 unless `confidences` gives one probability per unit (token_posteriors.unit_confidences), written to 2 decimals."""
+    if confidences is None:
+        return ["{} 1 {:.3f} {:.3f} {} 1.00".format(utt, s * seconds_per_frame, (e - s) * seconds_per_frame, text)
+                for text, s, e in units]
+    assert len(confidences) == len(units), (len(confidences), len(units))
+    return ["{} 1 {:.3f} {:.3f} {} {:.2f}".format(utt, s * seconds_per_frame, (e - s) * seconds_per_frame, text, c)
+            for (text, s, e), c in zip(units, confidences)]
 
 
 def utterance_units(result: Dict, dictionary, unit: str = "token"):

@@ -20,6 +20,7 @@ import torch
 import torch.nn.functional as TF
 
 from .. import kernels as K
+from .token_posteriors import TransducerTokenPosteriors, attach_posteriors, score_rows
 
 
 class _Pool:
@@ -168,12 +169,18 @@ class TransducerBeamSearchDecoder:
     def __init__(self, models, dictionary, beam_size=1, max_len=0, max_num_expansions_per_step=2, expansion_beta=0,
                  expansion_gamma=None, prefix_alpha=None, normalize_scores=True, temperature=1.0, eos=None, bos=None, blank=None,
                  pad=None, model_predicts_eos=False, symbols_to_strip_from_output=None, lm_model=None, lm_weight=1.0,
-                 print_alignment=False, **kwargs):
+                 print_alignment=False, token_posteriors=False, **kwargs):
         self.model = models[0]
         self.eos = dictionary.eos() if eos is None else eos
         self.bos = dictionary.eos() if bos is None else bos
         self.blank = dictionary.bos() if blank is None else blank
         self.pad = dictionary.pad() if pad is None else pad
+        # the acoustic model's own per-token posteriors of every hypothesis (tools/token_posteriors.py): no LM, temperature 1,
+        # the standard lattice although this search caps the expansions per frame
+        if token_posteriors and model_predicts_eos:
+            raise NotImplementedError("transducer beam search: token_posteriors with model_predicts_eos is not implemented (the search folds "
+                                      "<eos> into blank, the posterior's lattice does not)")
+        self.posteriors = TransducerTokenPosteriors(self.model, dictionary, blank=self.blank, bos=self.bos) if token_posteriors else None
         self.model_predicts_eos = model_predicts_eos
         strip = {self.eos, self.bos, self.blank}
         self.symbols_to_strip_from_output = strip.union(symbols_to_strip_from_output) if symbols_to_strip_from_output else strip
@@ -208,17 +215,33 @@ class TransducerBeamSearchDecoder:
 
     @torch.no_grad()
     def generate(self, models, sample, **kwargs):
-        tokens_list, scores_list, _ = self._generate(sample, bos_token=kwargs.get("bos_token", None))
+        rows = [] if self.posteriors is not None else None
+        tokens_list, scores_list, _ = self._generate(sample, bos_token=kwargs.get("bos_token", None), posteriors=rows)
         out = []
         for toks, scs in zip(tokens_list, scores_list):
             out.append([{"tokens": toks[j][toks[j] != self.pad], "score": scs[j], "attention": None, "alignment": None}
                         for j in range(toks.shape[0])])
+        if rows is not None:
+            flat = [h for u in out for h in u]
+            attach_posteriors(flat, *self._posterior_rows(flat, [b for b, u in enumerate(out) for _ in u], *rows))
         return out
 
+    def _posterior_rows(self, hyps, utt, E, enc_len, bos_token):
+        """Host rows (token factors, end factors, posterior scores) of the hypotheses `hyps` (utterance utt[n]) under E."""
+        dev = E.device
+        L = max([1] + [len(h["tokens"]) for h in hyps])
+        tokens = torch.stack([TF.pad(h["tokens"].cpu().long(), (0, L - len(h["tokens"])), value=self.pad) for h in hyps]).to(dev)
+        lengths = torch.tensor([len(h["tokens"]) for h in hyps], dtype=torch.int32, device=dev)
+        drop = (self.blank, self.pad)
+        rows = score_rows(self.posteriors, E, enc_len, tokens, lengths, torch.tensor(utt, dtype=torch.int32, device=dev), drop,
+                          bos_token=bos_token)
+        return [t.cpu() for t in rows]
+
     @torch.no_grad()
-    def _generate(self, sample, bos_token: Optional[int] = None, only: Optional[List[int]] = None):
+    def _generate(self, sample, bos_token: Optional[int] = None, only: Optional[List[int]] = None, posteriors=None):
         """only: search just these utterances of the batch (same encoder pass; the others return None) — lets a test compare a
-        search that shared its launches with the other utterances against the same search running alone."""
+        search that shared its launches with the other utterances against the same search running alone.
+        posteriors: a list that gets what `_posterior_rows` needs of this encoder pass (E [B][T'][J], encoder lengths, bos)."""
         net_input = sample["net_input"]
         enc = self.model.encoder(net_input["src_tokens"], net_input["src_lengths"])
         x = enc["_x_bt"][0]
@@ -228,6 +251,8 @@ class TransducerBeamSearchDecoder:
         dev = x.device
         self._E = self.model.joint_encoder_branch(x).contiguous()  # [bsz * T'][J], row = utterance * T' + frame
         self._Tp = Tp
+        if posteriors is not None:
+            posteriors.extend([self._E.view(bsz, Tp, -1), enc["src_lengths"][0], bos_token])
         # Predictor / LM states live in append-only row pools that are released when a group of searches ends: frames x
         # expansions x beam rows per utterance, (layers x H x 10 + H x 2) bytes per row.  The utterances of a batch are therefore
         # searched in groups whose estimated pool size stays under `state_pool_budget_bytes` (one group for ordinary batches; the

@@ -29,6 +29,7 @@ import torch
 
 from .. import kernels as K
 from .beam_common import BeamDecoderMixin, check_token_ngram, hyps_from_tensors, is_token_ngram, step_triple
+from .token_posteriors import TransducerTokenPosteriors, attach_posteriors, nbest_rows, score_rows
 
 
 class TransducerFrameBeamDecoder(BeamDecoderMixin):
@@ -36,7 +37,8 @@ class TransducerFrameBeamDecoder(BeamDecoderMixin):
 
     def __init__(self, models, dictionary, beam_size=5, nbest=1, beam_size_token=None, temperature=1.0, normalize_scores=True,
                  lm_model=None, lm_weight=0.0, model_predicts_eos=False, bos=None, blank=None, eos=None, pad=None,
-                 symbols_to_strip_from_output=None, print_alignment=False, context_graph=None, token_times=False, **kwargs):
+                 symbols_to_strip_from_output=None, print_alignment=False, context_graph=None, token_times=False,
+                 token_posteriors=False, **kwargs):
         if isinstance(models, (list, tuple)):
             if len(models) != 1:
                 raise NotImplementedError("the frame-synchronous transducer beam search takes one model: ensembles are not implemented")
@@ -83,6 +85,12 @@ class TransducerFrameBeamDecoder(BeamDecoderMixin):
             raise ValueError(f"transducer frame beam search: context graph built for {context_graph.vocab_size} tokens, dictionary has {V}")
         self.context_graph = context_graph
         self.token_times = bool(token_times)
+        # the acoustic model's own per-token posteriors of every hypothesis (tools/token_posteriors.py): no LM, no bias,
+        # temperature 1, the standard lattice (any number of symbols per frame) although this search allows one
+        if token_posteriors and model_predicts_eos:
+            raise NotImplementedError("transducer frame beam search: token_posteriors with model_predicts_eos is not implemented (the search folds "
+                                      "<eos> into blank, the posterior's lattice does not)")
+        self.posteriors = TransducerTokenPosteriors(self.model, dictionary, blank=self.blank, bos=self.bos) if token_posteriors else None
 
     def cuda(self):
         self.model.cuda()
@@ -154,9 +162,28 @@ class TransducerFrameBeamDecoder(BeamDecoderMixin):
         return self.model.joint_encoder_branch(x).view(B, x.shape[0] // B, -1), enc_len
 
     @torch.no_grad()
-    def _generate(self, sample, bos_token=None):
-        return self.search(*self.encode(sample), bos_token=bos_token)
+    def _generate(self, sample, bos_token=None, posteriors=None):
+        """posteriors: a list that gets the device rows of `score_rows` for the hypotheses, row = utterance * nbest + rank."""
+        E, enc_len = self.encode(sample)
+        out = self.search(E, enc_len, bos_token=bos_token)
+        if posteriors is not None:
+            posteriors.extend(self.score_hypotheses(E, enc_len, out, bos_token=bos_token))
+        return out
+
+    @torch.no_grad()
+    def score_hypotheses(self, E, enc_len, out, bos_token=None):
+        """The device rows (token factors [B * nbest][T'], end factors, posterior scores) of what `search` returned for E."""
+        tokens, lengths, _, nhyp = out[:4]
+        ln, utt = nbest_rows(lengths, nhyp)
+        return score_rows(self.posteriors, E, enc_len, tokens.reshape(-1, tokens.shape[2]), ln, utt, (self.blank, self.pad),
+                          bos_token=bos_token)
 
     @torch.no_grad()
     def generate(self, models, sample, **kwargs) -> List[List[Dict[str, torch.Tensor]]]:
-        return hyps_from_tensors(*(t.cpu() for t in self._generate(sample, bos_token=kwargs.get("bos_token", None))))
+        rows = [] if self.posteriors is not None else None
+        out = self._generate(sample, bos_token=kwargs.get("bos_token", None), posteriors=rows)
+        hyps = hyps_from_tensors(*(t.cpu() for t in out))
+        if rows is not None:
+            nbest = out[0].shape[1]
+            attach_posteriors([u[i] if i < len(u) else None for u in hyps for i in range(nbest)], *(t.cpu() for t in rows))
+        return hyps

@@ -6,18 +6,23 @@ like the reference; `generate()` wraps them in fairseq's hypothesis dicts.
 
 Compute: encoder, predictor step (LSTM cell kernels), joint step (add-relu kernel + MFMA GEMM) and log-softmax run on the
 HIP kernels; the per-expansion bookkeeping is a handful of tiny tensor ops on the device, with the one host
-synchronisation per expansion that the reference has too (`blank_mask.all()`)."""
+synchronisation per expansion that the reference has too (`blank_mask.all()`).
+
+With `token_posteriors=True` every hypothesis also carries the acoustic model's own per-token posteriors (tools/token_posteriors.py)
+of the labels it emitted, at their positions in "tokens" (0 at the blanks), from the same encoder pass: no LM, temperature 1, the
+standard lattice although this search caps the symbols per frame.  Tokens and scores are unchanged."""
 from typing import Optional
 
 import torch
 
 from .. import kernels as K
+from .token_posteriors import TransducerTokenPosteriors, attach_posteriors, score_rows
 
 
 class TransducerGreedyDecoder:
     def __init__(self, models, dictionary, max_len=0, max_num_expansions_per_step=2, temperature=1.0, eos=None, bos=None,
                  blank=None, model_predicts_eos=False, symbols_to_strip_from_output=None, lm_model=None, lm_weight=1.0,
-                 print_alignment=False, **kwargs):
+                 print_alignment=False, token_posteriors=False, **kwargs):
         self.model = models[0]
         self.eos = dictionary.eos() if eos is None else eos
         self.bos = dictionary.eos() if bos is None else bos
@@ -40,6 +45,10 @@ class TransducerGreedyDecoder:
             assert nlm in (self.vocab_size, self.vocab_size - 1)
             self.no_blank_in_lm = nlm == self.vocab_size - 1
             lm_model.eval()
+        if token_posteriors and model_predicts_eos:
+            raise NotImplementedError("greedy transducer search: token_posteriors with model_predicts_eos is not implemented (the search folds "
+                                      "<eos> into blank, the posterior's lattice does not)")
+        self.posteriors = TransducerTokenPosteriors(self.model, dictionary, blank=self.blank, bos=self.bos) if token_posteriors else None
 
     @torch.no_grad()
     def decode(self, models, sample, **kwargs):
@@ -47,13 +56,18 @@ class TransducerGreedyDecoder:
 
     @torch.no_grad()
     def generate(self, models, sample, **kwargs):
-        tokens, scores, alignments = self._generate(sample, bos_token=kwargs.get("bos_token", None))
-        return [[{"tokens": tokens[i], "score": scores[i], "attention": None,
+        rows = [] if self.posteriors is not None else None
+        tokens, scores, alignments = self._generate(sample, bos_token=kwargs.get("bos_token", None), posteriors=rows)
+        hyps = [[{"tokens": tokens[i], "score": scores[i], "attention": None,
                   "alignment": alignments[i] if (self.print_alignment and alignments is not None) else None}]
                 for i in range(tokens.size(0))]
+        if rows is not None:
+            attach_posteriors([h[0] for h in hyps], *rows)
+        return hyps
 
     @torch.no_grad()
-    def _generate(self, sample, bos_token: Optional[int] = None):
+    def _generate(self, sample, bos_token: Optional[int] = None, posteriors=None):
+        """posteriors: a list that gets the device rows of `score_rows` for the decoded tokens (token_posteriors)."""
         net_input = sample["net_input"]
         model = self.model
         enc = model.encoder(net_input["src_tokens"], net_input["src_lengths"])
@@ -119,4 +133,10 @@ class TransducerGreedyDecoder:
                     lm_state = {n: [torch.where(keep, o, nw) for o, nw in zip(lm_state[n], new_lm_state[n])] for n in lm_state}
                 k += 1
         alignments = tokens if self.print_alignment else None
+        if posteriors is not None:
+            flat = tokens.view(bsz, -1)
+            every = torch.full((bsz,), flat.shape[1], dtype=torch.int32, device=dev)
+            drop = (self.blank,)
+            posteriors.extend(score_rows(self.posteriors, E, enc_len, flat, every, torch.arange(bsz, dtype=torch.int32, device=dev),
+                                         drop, bos_token=bos_token))
         return tokens.view(bsz, -1), scores.view(bsz, -1).sum(-1), alignments

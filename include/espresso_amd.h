@@ -1244,6 +1244,34 @@ int ea_ctc_viterbi_align(const void* x, long ld, int x_bf16, const int* targets,
 long ea_rnnt_viterbi_workspace_bytes(int B, int T, int U1);
 int ea_rnnt_viterbi_align(const float* lpb, const float* lpy, const int* logit_lengths, const int* target_lengths,
                           void* workspace, int* emit_frame, float* score, int B, int T, int U1, ea_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-token posteriors of a given label sequence (csrc/prefix_posterior.hip): the sum-product twins of the two aligners.  The
+ * reference has them for attention-decoder hypotheses only (positional_scores); CTC and transducer hypotheses get them here.
+ *   Psi_i = log P(the model's output starts with y1 .. yi | x), summed over all continuations and all alignments (Psi_0 = 0);
+ *   log c_i = Psi_i - Psi_{i-1}: the posterior of token i given the audio and the tokens before it;
+ *   log c_end = total - Psi_U, and sum_i log c_i + log c_end = total = log P(y | x) = -(CTC / RNN-T loss).
+ * One workgroup per hypothesis, no workspace, outputs stay on the device (no host synchronisation).
+ * Outputs of both: logc fp32 [N][Lmax + 1] (ea_rnnt_...: [B][U1]): position i < U holds log c_{i+1}, position U holds log c_end,
+ *   positions past U hold 0; total fp32 [N]; psi fp32 [N][Lmax] ([B][U1 - 1]) or NULL: position i < U holds Psi_{i+1}, 0 past U.
+ *   Every logc entry is clamped to <= 0.  Zero probability or an infeasible hypothesis: from the first i with Psi_i = -inf on,
+ *   every factor and total are -inf, never NaN.
+ *
+ * ea_ctc_prefix_posteriors: x fp32 or bf16 (x_bf16) [B][T][ld] log-probs (ld >= V), targets int32 [N][Lmax], tgt_len int32 [N]
+ *   (clamped to Lmax), utt int32 [N]: the row of x and in_len that hypothesis n reads (an n-best list shares its utterance's
+ *   log-probs), in_len int32 [B] (clamped to T).  Lattice and move rules of ea_ctc_loss / ea_ctc_viterbi_align, log-add-exp for
+ *   max; Psi_i = log sum_t x_t(y_i) * (alpha_{t-1}(blank before y_i) + [y_i != y_{i-1}] * alpha_{t-1}(y_{i-1})), the mass that
+ *   ENTERS token i's state at frame t (at t = 0 only token 1, with x_0(y_1)); total = lse(alpha_T(S-1), alpha_T(S-2)).
+ *   in_len == U == 0: total 0.  A target id outside [0, V) or equal to blank, or utt[n] outside [0, B): that hypothesis's
+ *   outputs are NaN.  Returns -2 for Lmax > 1023, Lmax < 1, ld < V or blank outside [0, V).
+ * ea_rnnt_prefix_posteriors: lpb / lpy fp32 [B][T][U1] as in ea_rnnt_scan, one lattice per hypothesis; logit_lengths /
+ *   target_lengths int32 [B].  Psi_{u+1} = lse_{t < T_b} (alpha(t,u) + lpy(t,u)); total = alpha(T_b-1, U_b) + lpb(T_b-1, U_b)
+ *   (= -loss of ea_rnnt_scan); T_b == 0: total and the factors 0 .. U_b are -inf.  Returns -2 for U1 > 1024 or T < 1. */
+int ea_ctc_prefix_posteriors(const void* x, long ld, int x_bf16, const int* targets, const int* utt, const int* in_len,
+                             const int* tgt_len, float* logc, float* total, float* psi, int N, int B, int T, int V, int Lmax,
+                             int blank, ea_stream_t stream);
+int ea_rnnt_prefix_posteriors(const float* lpb, const float* lpy, const int* logit_lengths, const int* target_lengths,
+                              float* logc, float* total, float* psi, int B, int T, int U1, ea_stream_t stream);
 /* Joint network element-wise stages (espresso/models/transformer/speech_transformer_transducer_base.py:276-299):
  * Z[b][t][u] = relu(E[b][t] + D[b][u]) (bf16, E [B*T][J], D [B*U1][J], Z [B*T*U1][J], J % 8 == 0) and its backward
  * reductions dE[b][t] = sum_u dZ[b][t][u], dD[b][u] = sum_t dZ[b][t][u] (either output may be NULL). */
