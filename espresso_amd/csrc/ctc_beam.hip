@@ -44,6 +44,13 @@
 //   times words(T, beam) = 4 * beam + 2 + 2 * cap,  cap = 1 + T * beam
 // (vb, vnb fp32 [beam]; eb, enb int32 [beam]; the node counter and a pad word; tpar [cap], tfrm [cap]).  The step kernels write
 // tpar / tfrm and only the finish reads them, across a kernel boundary.  LDS: 1 032 bytes more than the twin's.
+//
+// Endpointing (ea_ctc_prefix_beam_stream_endpoint): a read-only probe of a slot and its times slot after an accept: for the live
+// hypothesis the partial kernel reports, its length L and E, the frame of its last token on its best path (tfrm of the pointer of
+// the larger of (vb, eb), (vnb, enb), tie eb: what the times finish writes as times[L - 1]), and the first rule that holds of
+// silence (F - 1 - E frames without a token), empty and length (endpoint_rule, ctc_beam_common.h).  The caller then reads the
+// finish and resets the slot: the stream goes on in a new segment, whose results are those of the offline search over its frames
+// alone.  One wave per slot, no LDS.
 #include "common.h"
 #include "ctc_beam_common.h"
 #include "espresso_amd.h"
@@ -736,6 +743,55 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_partial_kernel(const Strea
   }
 }
 
+struct StreamEndpointArgs {
+  const void *state, *tws; const int* slots;
+  float lm_weight, ins_bonus;
+  int biased, max_streams, max_frames, beam, silence_frames, empty_frames, segment_frames;
+  int* out;
+};
+
+// The endpoint probe: per listed slot out[b] = (rule, F, L, E) for F = the slot's frame counter and the live hypothesis the partial
+// kernel above reports (the same score, tie rule and handling of non-finite scores, restated here so that the partial kernel's code
+// stays what it is): L = its length, E = the frame of its last token on its best path, which is what the times finish writes as
+// times[L - 1] for it (the pointer of the larger of (vb, eb), (vnb, enb); tie: eb), -1 when L == 0.  A slot without frames or
+// without a hypothesis has the empty hypothesis; a slot out of range writes (0, 0, 0, -1).  One wave per slot, no LDS; the state
+// and the times state are read only.
+__global__ __launch_bounds__(64) void ctc_beam_stream_endpoint_kernel(const StreamEndpointArgs a) {
+  const int b = blockIdx.x, lane = threadIdx.x, slot = a.slots[b];
+  int* out = a.out + 4L * b;
+  if (slot < 0 || slot >= a.max_streams) {
+    if (lane == 0) { out[0] = 0; out[1] = 0; out[2] = 0; out[3] = -1; }
+    return;
+  }
+  const CtcSlot q = ctc_slot((void*)a.state, slot, a.max_frames, a.beam);
+  const TimesWs tw = times_ws((void*)a.tws, slot, a.max_frames, a.beam);
+  const int F = max(q.head[0], 0);
+  const int nh = F > 0 ? min(max(q.w.cnt[0], 0), a.beam) : 0;
+  float sc = -INFINITY;
+  int len = 0;
+  if (lane < nh) {
+    len = q.w.len[lane];
+    sc = lae(q.w.pb[lane], q.w.pnb[lane]) + a.lm_weight * q.w.lm[lane] + a.ins_bonus * (float)len;
+    if (a.biased) sc += q.bw.b[lane];
+  }
+  const uint64_t key = lane < nh ? mk_key(sc == sc ? sc : -INFINITY, lane) : 0ull;
+  uint64_t best = key;
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint64_t other = __shfl_xor(best, o, 64);
+    best = other > best ? other : best;
+  }
+  if (nh > 0 ? key == best : lane == 0) {
+    const int L = nh > 0 ? max(len, 0) : 0;
+    int E = -1;
+    if (L > 0) {
+      const int e = tw.vnb[lane] > tw.vb[lane] ? tw.enb[lane] : tw.eb[lane];
+      if (e > 0 && e < tw.cap) E = tw.tfrm[e];
+    }
+    out[0] = endpoint_rule(F, L, E, a.silence_frames, a.empty_frames, a.segment_frames);
+    out[1] = F; out[2] = L; out[3] = E;
+  }
+}
+
 // replay of token rows through the context graph: one lane per row
 __global__ __launch_bounds__(256) void context_graph_score_kernel(const CgTables g, const int* tokens, const int* lens, int N,
                                                                    int L, float* running, float* final_bias, int* q_out) {
@@ -1062,6 +1118,22 @@ extern "C" int ea_ctc_prefix_beam_stream_times_finish(const void* state, const v
     a.g = CgTables{};
     hipLaunchKernelGGL(ctc_beam_stream_times_finish_kernel<false>, dim3(n), dim3(64), 0, stream, a);
   }
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_ctc_prefix_beam_stream_endpoint(const void* state, const void* times_state, const int* slots, int n,
+                                                  float lm_weight, float ins_bonus, int biased, int max_streams, int max_frames,
+                                                  int beam, int silence_frames, int empty_frames, int segment_frames, int* out,
+                                                  hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!state || !times_state || !slots || !out || max_streams < 1 || max_frames < 1 || beam < 1 || beam > kMaxBeam) return -2;
+  StreamEndpointArgs a;
+  a.state = state; a.tws = times_state; a.slots = slots;
+  a.lm_weight = lm_weight; a.ins_bonus = ins_bonus;
+  a.biased = biased != 0; a.max_streams = max_streams; a.max_frames = max_frames; a.beam = beam;
+  a.silence_frames = silence_frames; a.empty_frames = empty_frames; a.segment_frames = segment_frames;
+  a.out = out;
+  hipLaunchKernelGGL(ctc_beam_stream_endpoint_kernel, dim3(n), dim3(64), 0, stream, a);
   return EA_CHECK_LAUNCH();
 }
 

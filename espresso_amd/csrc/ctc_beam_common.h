@@ -34,6 +34,16 @@ __device__ __forceinline__ uint64_t ord32(float f) {
 // unique 48-bit key: larger value first, then lower index (0 = absent)
 __device__ __forceinline__ uint64_t mk_key(float v, int idx) { return (ord32(v) << 16) | (uint64_t)(0xFFFF - idx); }
 
+// The endpoint rule of the streamed searches (ea_*_stream_endpoint) for a slot with F frames whose best live hypothesis has L
+// tokens, the last of them starting at frame E of its best path (-1 when L == 0): the first that holds of 1 "silence" (L > 0 and
+// F - 1 - E >= silence), 2 "empty" (L == 0 and F >= empty), 3 "length" (F >= segment), else 0; a threshold <= 0 is switched off.
+__host__ __device__ __forceinline__ int endpoint_rule(int F, int L, int E, int silence, int empty, int segment) {
+  if (silence > 0 && L > 0 && F - 1 - E >= silence) return 1;
+  if (empty > 0 && L == 0 && F >= empty) return 2;
+  if (segment > 0 && F >= segment) return 3;
+  return 0;
+}
+
 struct SelectScratch {
   unsigned hist[256];
   uint64_t prefix;

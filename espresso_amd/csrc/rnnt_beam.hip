@@ -61,6 +61,7 @@
 //   rnnt_beam_finish_kernel, rnnt_beam_stream_finish_kernel  64 threads, 256 B LDS, 18 VGPRs
 //   rnnt_beam_stream_reset_kernel    256 threads, no LDS, 6 VGPRs
 //   rnnt_beam_stream_partial_kernel  64 threads (one wave per slot), no LDS, 22 VGPRs
+//   rnnt_beam_stream_endpoint_kernel 64 threads (one wave per slot), no LDS; reads the slot and its times slot only
 // RowLds and SelLds are left at their natural alignment of 8: aligning the row to 16 turns the radix passes' ds_read2_b64 into
 // ds_read_b128, which measured 0.1 - 0.2 us per frame slower, not faster.
 //
@@ -98,6 +99,12 @@
 //   times words(T, beam) = 2 * beam + 2 + 2 * cap,  cap = 1 + T * beam
 // (v fp32 [beam]; e int32 [beam]; the node counter and a pad word; tpar [cap], tfrm [cap]).  The select kernels write tpar /
 // tfrm and only the finish reads them, across a kernel boundary.  LDS: 1 032 bytes more than the twin's select kernel.
+//
+// Endpointing (ea_rnnt_frame_beam_stream_endpoint): a read-only probe of a slot and its times slot after an accept: for the live
+// hypothesis the partial kernel reports, its length L and E = tfrm[e], the frame of its last token on its best path (what the
+// times finish writes as times[L - 1]), and the first rule that holds of silence (F - 1 - E frames without a token), empty and
+// length (endpoint_rule, ctc_beam_common.h).  The caller then reads the finish and resets the slot: the stream goes on in a new
+// segment, whose results are those of the offline search over its frames alone.
 #include "common.h"
 #include "ctc_beam_common.h"
 #include "espresso_amd.h"
@@ -822,6 +829,52 @@ __global__ __launch_bounds__(64) void rnnt_beam_stream_partial_kernel(const Stre
   }
 }
 
+struct StreamEndpointArgs {
+  const void *state, *tws; const int* slots;
+  int max_streams, max_frames, beam, silence_frames, empty_frames, segment_frames;
+  int* out;
+};
+
+// The endpoint probe: per listed slot out[b] = (rule, F, L, E) for F = the slot's frame counter and the live hypothesis the partial
+// kernel above reports (the same score and tie rule, restated here so that the partial kernel's code stays what it is): L = its
+// length, E = tfrm[e], the frame at which its last token is emitted on its best path, which is what the times finish writes as
+// times[L - 1] for it, -1 when L == 0.  A slot without frames or without a hypothesis has the empty hypothesis; a slot out of
+// range writes (0, 0, 0, -1).  One wave per slot, no LDS; the state and the times state are read only.  kBias: the slot stride
+// and the + b of the ranking.
+template <bool kBias>
+__global__ __launch_bounds__(64) void rnnt_beam_stream_endpoint_kernel(const StreamEndpointArgs a) {
+  const int b = blockIdx.x, lane = threadIdx.x, slot = a.slots[b];
+  int* out = a.out + 4L * b;
+  if (slot < 0 || slot >= a.max_streams) {
+    if (lane == 0) { out[0] = 0; out[1] = 0; out[2] = 0; out[3] = -1; }
+    return;
+  }
+  const RnntSlot<kBias> q = rnnt_slot<kBias>((void*)a.state, slot, a.max_frames, a.beam, CgTables{});
+  const RnntTimesWs tw = rnnt_times_at((void*)a.tws, slot, a.max_frames, a.beam, 0);
+  const int F = max(q.head[0], 0);
+  const int nh = F > 0 ? min(max(q.w.cnt[0], 0), a.beam) : 0;
+  float sc = -INFINITY;
+  int len = 0;
+  if (lane < nh) { sc = q.w.score[lane]; len = q.w.len[lane]; }
+  if constexpr (kBias) sc += lane < nh ? q.wb.b[lane] : 0.f;
+  const uint64_t key = lane < nh ? mk_key(sc == sc ? sc : -INFINITY, lane) : 0ull;
+  uint64_t best = key;
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint64_t other = __shfl_xor(best, o, 64);
+    best = other > best ? other : best;
+  }
+  if (nh > 0 ? key == best : lane == 0) {
+    const int L = nh > 0 ? max(len, 0) : 0;
+    int E = -1;
+    if (L > 0) {
+      const int e = tw.e[lane];
+      if (e > 0 && e < tw.cap) E = tw.tfrm[e];
+    }
+    out[0] = endpoint_rule(F, L, E, a.silence_frames, a.empty_frames, a.segment_frames);
+    out[1] = F; out[2] = L; out[3] = E;
+  }
+}
+
 }  // namespace
 
 // weight 0 is no fusion: the LM rows are not read (an entry of -inf times 0 would be NaN)
@@ -1173,5 +1226,22 @@ extern "C" int ea_rnnt_frame_beam_stream_times_finish(const void* state, const v
     a.g = CgTables{};
     hipLaunchKernelGGL(rnnt_beam_stream_times_finish_kernel<false>, dim3(n), dim3(64), 0, stream, a);
   }
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_rnnt_frame_beam_stream_endpoint(const void* state, const void* times_state, const int* slots, int n, int biased,
+                                                  int max_streams, int max_frames, int beam, int silence_frames, int empty_frames,
+                                                  int segment_frames, int* out, hipStream_t stream) {
+  if (n <= 0) return 0;
+  if (!state || !times_state || !slots || !out || max_streams < 1 || max_frames < 1 || beam < 1 || beam > kMaxBeam) return -2;
+  StreamEndpointArgs a;
+  a.state = state; a.tws = times_state; a.slots = slots;
+  a.max_streams = max_streams; a.max_frames = max_frames; a.beam = beam;
+  a.silence_frames = silence_frames; a.empty_frames = empty_frames; a.segment_frames = segment_frames;
+  a.out = out;
+  if (biased)
+    hipLaunchKernelGGL(rnnt_beam_stream_endpoint_kernel<true>, dim3(n), dim3(64), 0, stream, a);
+  else
+    hipLaunchKernelGGL(rnnt_beam_stream_endpoint_kernel<false>, dim3(n), dim3(64), 0, stream, a);
   return EA_CHECK_LAUNCH();
 }

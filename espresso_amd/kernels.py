@@ -1016,6 +1016,24 @@ def ctc_prefix_beam_stream_times_finish(state, tstate, slots, max_frames, beam, 
     return tokens, lengths, scores, nhyp, times, vscores
 
 
+def ctc_prefix_beam_stream_endpoint(state, tstate, slots, max_frames, beam, silence_frames, empty_frames, segment_frames, lm_weight=0.0,
+                                    ins_bonus=0.0, biased=False):
+    """The endpoint probe of the slots int32 [n] (device) of a streamed search with times (ea_ctc_prefix_beam_stream_endpoint):
+    int32 [n][4] = (rule, F, L, E) for the hypothesis ctc_prefix_beam_stream_partial reports with the same lm_weight, ins_bonus
+    and biased.  A threshold <= 0 switches its rule off; a missing times state is refused by the entry point.  Read only."""
+    L = _lib.lib()
+    _check_stream_state(state, L.ea_ctc_prefix_beam_stream_state_bytes, max_frames, beam)
+    if tstate is not None:
+        _check_times_state(tstate, L.ea_ctc_prefix_beam_stream_times_state_bytes, max_frames, beam, state)
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
+    n = slots.numel()
+    out = torch.empty(n, 4, dtype=torch.int32, device=state.device)
+    check(L.ea_ctc_prefix_beam_stream_endpoint(_p(state), _p(tstate), _p(slots), n, lm_weight, ins_bonus, int(bool(biased)),
+                                               state.shape[0], max_frames, beam, int(silence_frames), int(empty_frames),
+                                               int(segment_frames), _p(out), _stream()), "ea_ctc_prefix_beam_stream_endpoint")
+    return out
+
+
 def rnnt_frame_beam_times_workspace(B, T, beam, device):
     """Times workspace of the frame-synchronous transducer beam search (ea_rnnt_frame_beam_times_workspace_bytes)."""
     return torch.empty(int(_lib.lib().ea_rnnt_frame_beam_times_workspace_bytes(B, T, beam)), dtype=torch.uint8, device=device)
@@ -1100,6 +1118,23 @@ def rnnt_frame_beam_stream_times_finish(state, tstate, slots, max_frames, beam, 
                                                    _p(nhyp), _p(times), _p(vscores), _stream()),
           "ea_rnnt_frame_beam_stream_times_finish")
     return tokens, lengths, scores, nhyp, times, vscores
+
+
+def rnnt_frame_beam_stream_endpoint(state, tstate, slots, max_frames, beam, silence_frames, empty_frames, segment_frames, biased=False):
+    """The endpoint probe of the slots int32 [n] (device) of a streamed search with times (ea_rnnt_frame_beam_stream_endpoint;
+    biased: a bias state): int32 [n][4] = (rule, F, L, E) for the hypothesis rnnt_frame_beam_stream_partial / _bias_partial
+    reports.  A threshold <= 0 switches its rule off; a missing times state is refused by the entry point.  Read only."""
+    L = _lib.lib()
+    _check_stream_state(state, _rnnt_state_bytes_fn(biased), max_frames, beam)
+    if tstate is not None:
+        _check_times_state(tstate, L.ea_rnnt_frame_beam_stream_times_state_bytes, max_frames, beam, state)
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
+    n = slots.numel()
+    out = torch.empty(n, 4, dtype=torch.int32, device=state.device)
+    check(L.ea_rnnt_frame_beam_stream_endpoint(_p(state), _p(tstate), _p(slots), n, int(bool(biased)), state.shape[0], max_frames, beam,
+                                               int(silence_frames), int(empty_frames), int(segment_frames), _p(out), _stream()),
+          "ea_rnnt_frame_beam_stream_endpoint")
+    return out
 
 
 def context_graph_score(graph, tokens, lens):

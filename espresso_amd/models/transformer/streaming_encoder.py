@@ -232,6 +232,13 @@ class StreamingEncoder:
         return (flat[0] if len(flat) == 1 else torch.cat(flat)), counts
 
     # ---- chunk scheduling (host integers only) ----------------------------------------------------------------------------
+    def max_rows_per_accept(self, n_samples: int) -> int:
+        """An upper bound on the encoder frames one `accept_waveform` of at most n_samples new samples returns for a stream: the
+        rows of the new feature frames, plus what the stream held back (less than a chunk and the receptive field of its last
+        row), which a final piece flushes."""
+        n = n_samples // self.frontend.frame_shift + 2  # the samples left over from the last piece complete one more frame
+        return -(-n // self.stride) + self.cs + -(-(self.rf + 1) // self.stride) + 1
+
     def _out_total(self, st):
         return -(-st.total // self.stride)
 

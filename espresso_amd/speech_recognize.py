@@ -214,6 +214,18 @@ def ctc_stream_beam_options(args, lm=None, context_graph=None):
     return opts
 
 
+def endpoint_options(args, seconds_per_frame):
+    """The `endpoint` / `seconds_per_frame` arguments of recognize_streaming from the command line of --stream-endpoint: the
+    three thresholds in encoder frames (a positive number of seconds is at least one frame; <= 0 stays switched off)."""
+    from .tools.beam_common import EndpointRules
+
+    def frames(seconds):
+        return max(1, int(round(seconds / seconds_per_frame))) if seconds > 0 else 0
+
+    return dict(endpoint=EndpointRules(frames(args.endpoint_silence_s), frames(args.endpoint_empty_s), frames(args.endpoint_max_segment_s)),
+                seconds_per_frame=seconds_per_frame)
+
+
 def get_parser():
     p = argparse.ArgumentParser("espresso_amd.speech_recognize", description=__doc__.split("\n")[0])
     p.add_argument("--path", required=True, help="state_dict (or fairseq checkpoint dict with a 'model' entry)")
@@ -321,6 +333,18 @@ def get_parser():
     p.add_argument("--stream-partials", action="store_true",
                    help="--streaming --search ctc_beam --ngram-lm, --search ctc_stream_beam or --search transducer_stream_beam: after every piece print `P-<utt>`, the seconds consumed, the stable "
                         "text and the rest of the currently best hypothesis, whenever the text changed")
+    p.add_argument("--stream-endpoint", action="store_true",
+                   help="--streaming --search ctc_stream_beam or --search transducer_stream_beam (1-best): decode audio of any length as "
+                        "consecutive segments.  After every piece the device decides whether the utterance in a stream has ended "
+                        "(--endpoint-silence-s, --endpoint-empty-s, --endpoint-max-segment-s); the segment is then finalised and printed "
+                        "as `S-<utt>`, its start and end in seconds, the rule and its text, the stream's search state starts afresh, and "
+                        "`H-<utt>` is the segments' text joined.  The state of a stream is sized for one segment, not for the utterance")
+    p.add_argument("--endpoint-silence-s", type=float, default=0.8,
+                   help="--stream-endpoint: end a segment with text once this long has passed since its last token began (<= 0: never)")
+    p.add_argument("--endpoint-empty-s", type=float, default=5.0,
+                   help="--stream-endpoint: end a segment without text after this long (<= 0: never)")
+    p.add_argument("--endpoint-max-segment-s", type=float, default=20.0,
+                   help="--stream-endpoint: end every segment after this long; it sizes the per-stream search state (must be positive)")
     p.add_argument("--wer-output-filter", default=None, help="sed-style word filter applied before WER scoring")
     p.add_argument("--non-lang-syms", default=None, help="non-language symbols (one per line), ignored by WER / CER scoring")
     return p
@@ -536,10 +560,11 @@ def check_streaming_args(args):
     """--streaming is greedy decoding (CTC or transducer), the lexicon + n-gram beam search (--search ctc_beam --ngram-lm), the
     CTC prefix beam search (--search ctc_stream_beam) or the frame-synchronous transducer beam search (--search
     transducer_stream_beam; these two fuse an LSTM LM under streaming) of one chunk-streaming model: refused, before anything
-    is loaded, with every other search, with LSTM-LM fusion elsewhere, ensembles and alignment output."""
+    is loaded, with every other search, with LSTM-LM fusion elsewhere, ensembles and alignment output.  --stream-endpoint
+    (endpointing) goes with the last two alone and with their 1-best."""
     if not args.streaming:
         for opt, v in (("--stream-chunk-ms", args.stream_chunk_ms), ("--streams", args.streams),
-                       ("--stream-partials", args.stream_partials or None)):
+                       ("--stream-partials", args.stream_partials or None), ("--stream-endpoint", getattr(args, "stream_endpoint", False) or None)):
             if v is not None:
                 raise ValueError(f"{opt} configures --streaming: give --streaming too")
         return
@@ -560,6 +585,14 @@ def check_streaming_args(args):
     if args.stream_partials and not (lexicon_beam or stream_beam):
         raise NotImplementedError("--stream-partials prints the partial results of --search ctc_beam --ngram-lm, of --search "
                                   "ctc_stream_beam and of --search transducer_stream_beam")
+    if getattr(args, "stream_endpoint", False):
+        if not stream_beam:
+            raise NotImplementedError("--stream-endpoint (endpointing) is implemented for --search ctc_stream_beam and --search "
+                                      f"transducer_stream_beam, not --search {args.search}" + " --ngram-lm" * bool(args.ngram_lm))
+        if args.nbest > 1:
+            raise NotImplementedError("--stream-endpoint joins the 1-best of consecutive segments: no --nbest > 1 with it")
+        if not args.endpoint_max_segment_s > 0:
+            raise ValueError("--endpoint-max-segment-s must be positive: it sizes the per-stream search state")
     if len(args.path.split(os.pathsep)) > 1:
         raise NotImplementedError("--streaming takes one model: ensembles (--path a.pt:b.pt) are not streamed")
     if (args.stream_chunk_ms is not None and args.stream_chunk_ms <= 0) or (args.streams is not None and args.streams <= 0):
@@ -568,19 +601,29 @@ def check_streaming_args(args):
 
 def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=400, streams=16, refs=None, out=sys.stdout,
                         quiet=False, scorer=None, summary_out=None, search="ctc", max_num_expansions_per_step=2, lexicon_beam=None,
-                        partials=False, stream_beam=None, ctc_stream_beam=None, ctm_hyps=None):
+                        partials=False, stream_beam=None, ctc_stream_beam=None, ctm_hyps=None, endpoint=None, seconds_per_frame=None):
     """The output of `recognize` from a streamed pass: every utterance is read in pieces of `chunk_ms`, `streams` of them in
     flight; a finished utterance frees its slot for the next one (wav.scp order).  search "ctc_beam": lexicon_beam holds the
     arguments of StreamingCTCLexiconBeamDecoder after `dictionary` (n-gram LM, lexicon) and its options; its prefix tables are
     sized for the longest utterance given.  search "transducer_stream_beam": stream_beam holds the options of
     StreamingTransducerFrameBeamDecoder (beam, n-best, LM, ...), search "ctc_stream_beam": ctc_stream_beam those of
     StreamingCTCPrefixBeamDecoder; their prefix tables are sized the same way.  partials: a `P-` line
-    per stream whenever its partial text changed.  ctm_hyps: a dict that gets utterance -> (its best hypothesis, the symbols stripped from the text) (--ctm)."""
+    per stream whenever its partial text changed.  ctm_hyps: a dict that gets utterance -> (its best hypothesis, the symbols stripped from the text) (--ctm).
+
+    endpoint (--stream-endpoint; search "ctc_stream_beam" / "transducer_stream_beam", 1-best): the EndpointRules, in encoder
+    frames, under which an utterance is decoded as consecutive segments.  A slot is then sized for segment_frames plus the most
+    frames one accept can bring, whatever the utterance lengths.  After every accept one `endpoint` readback names the streams
+    whose segment ends (silence / empty / length); a stream whose next piece would not fit ends its segment before that accept
+    ("room").  A closed segment prints `S-<utt>`, its start and end in seconds (seconds_per_frame per encoder frame; default:
+    the encoder's stride x the front-end's frame shift), the rule and its text; the segment the audio's end closes is "final".
+    Segments end on piece boundaries.  The utterance's hypothesis is the segments' joined: tokens concatenated, scores summed,
+    times shifted by each segment's first frame.  The stable field of a `P-` line starts with the closed segments' text."""
     from .models.transformer.streaming_encoder import StreamingEncoder
     from .tools.streaming_ctc_decoder import StreamingCTCDecoder
     from .tools.streaming_ctc_lexicon_beam_decoder import StreamingCTCLexiconBeamDecoder
     from .tools.streaming_ctc_prefix_beam_decoder import StreamingCTCPrefixBeamDecoder
     from .tools.streaming_transducer_frame_beam_decoder import StreamingTransducerFrameBeamDecoder
+    from .tools.beam_common import EndpointRules
     from .tools.streaming_transducer_greedy_decoder import StreamingTransducerGreedyDecoder
     from .tools.wer import Scorer
 
@@ -590,6 +633,20 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
     partial_of = None  # a decoder's partial -> (tokens of the best hypothesis, how many of them are stable)
     # the longest utterance's encoder frames: what a slot of the three beam searches is sized for
     max_frames = max([1] + [-(-task.frontend.num_frames(len(w)) // se.stride) for w in waves])
+    piece = max(1, int(16000 * chunk_ms / 1000))
+    if endpoint is not None:
+        if search not in ("ctc_stream_beam", "transducer_stream_beam"):
+            raise NotImplementedError("endpointing (--stream-endpoint) is implemented for --search ctc_stream_beam and --search "
+                                      f"transducer_stream_beam, not --search {search}")
+        opts = ctc_stream_beam if search == "ctc_stream_beam" else stream_beam
+        if opts.get("nbest", 1) != 1:
+            raise NotImplementedError("endpointing (--stream-endpoint) joins the 1-best of consecutive segments: no --nbest > 1 with it")
+        if endpoint.segment_frames > 0:  # a constant of the options: memory per stream no longer grows with the audio
+            max_frames = endpoint.segment_frames + se.max_rows_per_accept(piece)
+        opts = dict(opts, endpoint=endpoint)
+        ctc_stream_beam, stream_beam = (opts, stream_beam) if search == "ctc_stream_beam" else (ctc_stream_beam, opts)
+        if seconds_per_frame is None:
+            seconds_per_frame = se.stride * task.frontend.frame_shift / task.frontend.sample_rate
     if search == "ctc":
         dec = StreamingCTCDecoder(dictionary)
         strip = {dictionary.eos(), dictionary.pad()}
@@ -609,7 +666,6 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
     else:
         dec = StreamingTransducerGreedyDecoder(model, dictionary, max_num_expansions_per_step=max_num_expansions_per_step)
         strip = dec.symbols_to_strip_from_output
-    piece = max(1, int(16000 * chunk_ms / 1000))
     pending = list(range(len(utt_ids)))
     live = {}  # utterance index -> samples consumed
     hyps = {}
@@ -619,6 +675,29 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
     def text_of(toks):
         return dictionary.string(torch.tensor([t for t in toks if t not in strip], dtype=torch.long), bpe_symbol=None)
 
+    segs = {}  # endpointing: utterance index -> its closed segments (first frame, hypothesis, text)
+    seg_frames = {}  # utterance index -> [first frame of the open segment, its frames so far]
+
+    def end_segment(i, hypo, rule):
+        start, n = seg_frames[i]
+        text = text_of(hypo["tokens"].tolist())
+        segs.setdefault(i, []).append((start, hypo, text))
+        seg_frames[i] = [start + n, 0]
+        if not quiet:
+            print("S-{}\t{:.2f}\t{:.2f}\t{}\t{}".format(utt_ids[i], start * seconds_per_frame, (start + n) * seconds_per_frame, rule,
+                                                      text), file=out)
+
+    def joined(i):
+        """The utterance's hypothesis from its segments: tokens concatenated, scores summed, times shifted."""
+        parts = segs[i]
+        hypo = dict(parts[0][1])
+        hypo["tokens"] = torch.cat([h["tokens"] for _, h, _ in parts])
+        hypo["score"] = torch.stack([h["score"] for _, h, _ in parts]).sum()
+        if "times" in hypo:
+            hypo["times"] = torch.cat([h["times"] + s for s, h, _ in parts])
+            hypo["viterbi_score"] = torch.stack([h["viterbi_score"] for _, h, _ in parts]).sum()
+        return hypo
+
     t0 = time.perf_counter()
     while pending or live:
         while pending and len(live) < streams:
@@ -626,6 +705,7 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
             live[i] = 0
             se.open([i])
             dec.open([i])
+            seg_frames[i] = [0, 0]
         ids = list(live)
         pieces, final = [], []
         for i in ids:
@@ -636,11 +716,21 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
             final.append(b >= len(waves[i]))
         logits, counts = se.accept_waveform(ids, pieces, final)
         if logits is not None:
+            if endpoint is not None:  # rule 4: a piece that would not fit ends the segment first
+                for i in dec.room(ids, counts):
+                    end_segment(i, dec.end_segment(i)[0], EndpointRules.NAMES[EndpointRules.ROOM])
             dec.accept(ids, logits, counts)
+            if endpoint is not None:
+                for i, c, f, (rule, _, _, _) in zip(ids, counts, final, dec.endpoint(ids)):
+                    seg_frames[i][1] += c
+                    if rule and not f:  # (the audio's end closes the last segment below)
+                        end_segment(i, dec.end_segment(i)[0], EndpointRules.NAMES[rule])
         if partials:
             for i, part in zip(ids, dec.partial(ids)):
                 toks, k = partial_of(part)
                 texts = (text_of(toks[:k]), text_of(toks[k:]))
+                if i in segs:
+                    texts = (" ".join(t for t in [t for _, _, t in segs[i]] + [texts[0]] if t), texts[1])
                 if shown.get(i) != texts:
                     shown[i] = texts
                     print("P-{}\t{:.2f}\t{}\t{}".format(utt_ids[i], live[i] / 16000.0, *texts), file=out)
@@ -649,6 +739,10 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
                 se.close([i])
                 h = dec.close(i)
                 hyps[i] = h if isinstance(h, list) else [h]
+                if endpoint is not None:
+                    if seg_frames[i][1] > 0 or i not in segs:
+                        end_segment(i, hyps[i][0], "final")
+                    hyps[i] = [joined(i)]
                 del live[i]
     if torch.cuda.is_available():
         torch.cuda.synchronize()
@@ -874,10 +968,10 @@ def main(argv=None):
     stream = (collate(b, utt_ids, waves, dev) for b in batches)
     ctm_hyps = {} if args.ctm else None
 
+    from .tools.forced_aligner import frame_seconds
+
     def finish_ctm():
         if ctm_hyps is not None:
-            from .tools.forced_aligner import frame_seconds
-
             write_ctm(args.ctm, utt_ids, ctm_hyps, task.target_dictionary, args.ctm_unit,
                       frame_seconds(model, task.frontend.frame_shift / task.frontend.sample_rate))
 
@@ -888,6 +982,8 @@ def main(argv=None):
         kw = dict(chunk_ms=args.stream_chunk_ms or 400, streams=args.streams or 16, refs=refs, quiet=args.quiet, scorer=scorer,
                   search=args.search, max_num_expansions_per_step=args.max_num_expansions_per_step, partials=args.stream_partials,
                   ctm_hyps=ctm_hyps)
+        if getattr(args, "stream_endpoint", False):
+            kw.update(endpoint_options(args, frame_seconds(model, task.frontend.frame_shift / task.frontend.sample_rate)))
         if args.search == "ctc_beam":
             kw["lexicon_beam"] = (ngram, dict(beam_size=args.beam, nbest=args.nbest, beam_size_token=args.ctc_beam_size_token,
                                               lm_weight=args.lm_weight, word_score=args.word_score,

@@ -101,8 +101,42 @@ class BeamDecoderMixin:
         return tokens[:, 0, :U].to(torch.long), scores[:, 0], None
 
 
+class EndpointRules:
+    """When a streamed CTC / transducer beam search ends a segment ("Endpointing"): three thresholds in
+    encoder frames, each switched off when <= 0.  For a slot with F frames whose best live hypothesis has L tokens, the last of
+    them starting at frame E of its best alignment path (-1 when L == 0), the rule is the first that holds of
+      1 "silence": L > 0 and F - 1 - E >= silence_frames (that many frames after the last token's),
+      2 "empty":   L == 0 and F >= empty_frames,
+      3 "length":  F >= segment_frames,
+    else 0.  The endpoint kernels (ea_*_stream_endpoint) evaluate exactly this on the device; `decide` restates it on the host.
+    4 "room" is the caller's: a segment ended because the next piece would not fit the slot (`StreamSlots.room`)."""
+
+    NAMES = ("", "silence", "empty", "length", "room")
+    SILENCE, EMPTY, LENGTH, ROOM = 1, 2, 3, 4
+
+    def __init__(self, silence_frames=0, empty_frames=0, segment_frames=0):
+        self.silence_frames, self.empty_frames, self.segment_frames = int(silence_frames), int(empty_frames), int(segment_frames)
+
+    def frames(self):
+        return self.silence_frames, self.empty_frames, self.segment_frames
+
+    def decide(self, F, L, E) -> int:
+        if self.silence_frames > 0 and L > 0 and F - 1 - E >= self.silence_frames:
+            return self.SILENCE
+        if self.empty_frames > 0 and L == 0 and F >= self.empty_frames:
+            return self.EMPTY
+        if self.segment_frames > 0 and F >= self.segment_frames:
+            return self.LENGTH
+        return 0
+
+
 class StreamSlots:
-    """The slot pool of a streamed beam decoder: `streams` maps a stream id to [slot, frames consumed]."""
+    """The slot pool of a streamed beam decoder: `streams` maps a stream id to [slot, frames consumed].
+
+    Endpointing (the CTC prefix and the transducer frame beam decoders, built with `endpoint=EndpointRules(...)`): `endpoint`
+    reads the rule of every listed stream, `end_segment` returns what `finish` gives for a stream and restarts its slot, and
+    `room` names the streams whose next piece would not fit, whose segment the caller ends first.  Rules are read after an
+    `accept`, so a segment ends on a piece boundary; the thresholds themselves count frames and do not depend on the pieces."""
 
     def __init__(self, search_name, max_streams, max_frames):
         if max_streams < 1 or max_frames < 1:
@@ -112,6 +146,41 @@ class StreamSlots:
         self.streams: Dict[object, list] = {}
         self._unreset: List[int] = []  # slots opened since the last reset launch
         self.times_state = None  # the per-slot state of the time stamps, for a decoder asked for them
+        self.endpoint_rules = None  # EndpointRules of a decoder built with `endpoint`
+
+    def restart(self, sid):
+        """The stream starts a new segment in the slot it has: its frame count goes to 0 and the decoder's `_ensure` resets the
+        slot (search state, times state, LM / predictor rows) before the next launch that needs it."""
+        st = self.streams[sid]
+        st[1] = 0
+        if st[0] not in self._unreset:
+            self._unreset.append(st[0])
+
+    def room(self, stream_ids, counts):
+        """The streams whose next piece (`counts` encoder frames) would pass max_frames: the caller ends their segment before
+        that accept (rule 4, "room"), so an endpointed stream never raises for room.  A piece longer than max_frames itself
+        never fits."""
+        return [sid for sid, c in zip(stream_ids, counts) if self.streams[sid][1] > 0 and self.streams[sid][1] + int(c) > self.max_frames]
+
+    def _need_endpoint(self):
+        if self.endpoint_rules is None:
+            raise ValueError("this decoder was built without `endpoint` rules")
+
+    @torch.no_grad()
+    def endpoint(self, stream_ids):
+        """Per stream (rule, F, L, E) of EndpointRules, from one readback of `endpoint_tensors`."""
+        if not stream_ids:
+            return []
+        return [tuple(row) for row in self.endpoint_tensors(stream_ids).cpu().tolist()]
+
+    @torch.no_grad()
+    def end_segment(self, sid) -> List[Dict[str, torch.Tensor]]:
+        """Up to nbest finished hypotheses (with "times" and "viterbi_score", frames counted from the segment's first frame) of
+        the stream's current segment, as `close` returns them; the stream stays open and starts a new segment in its slot."""
+        self._need_endpoint()
+        hyps = self._finished(sid)  # the decoder's: what its `close` reads before it releases the slot
+        self.restart(sid)
+        return hyps
 
     def _allocate_times(self, make_state, beam, device):
         """The times state beside the search state (make_state: the K.*_stream_times_state of the search); the decoder's reset

@@ -25,7 +25,14 @@ the extension of one), so the stable tokens never change again.
 Time stamps: with `token_times=True` a slot also has a times slot (K.ctc_prefix_beam_stream_times_state), the reset, the steps and
 the finish are those of the times family (ea_ctc_prefix_beam_stream_times_*), `finish` also returns (times, vscores) with frames
 counted from the stream's first frame, and `close` puts "times" and "viterbi_score" into the hypotheses: what the offline
-decoder with token_times returns for the whole utterance.  `partial` carries no times."""
+decoder with token_times returns for the whole utterance.  `partial` carries no times.
+
+Endpointing: with `endpoint=EndpointRules(...)` (tools/beam_common.py) the decoder uses the times family and also has
+`endpoint_tensors` / `endpoint` (ea_ctc_prefix_beam_stream_endpoint: per stream (rule, F, L, E) of the hypothesis `partial` reports,
+read only), `end_segment` (the hypotheses of `finish`, then the slot restarts: search state, times state and LM rows start fresh)
+and `room`.  A segment's hypotheses are, bit for bit, what CTCPrefixBeamSearchDecoder with token_times returns for that segment's
+frames alone.  Rules are read after an `accept`, so segments end on piece boundaries; the thresholds count frames and do not
+depend on the pieces.  Without `endpoint` nothing changes: a stream that would pass `max_frames` raises."""
 from typing import Dict, List
 
 import torch
@@ -37,7 +44,7 @@ from .ctc_prefix_beam_search import CTCPrefixBeamSearchDecoder
 
 class StreamingCTCPrefixBeamDecoder(StreamSlots):
     def __init__(self, dictionary, max_streams, max_frames, beam_size=10, nbest=1, beam_size_token=None, lm_model=None, lm_weight=0.0,
-                 insertion_bonus=0.0, blank=None, context_graph=None, token_times=False):
+                 insertion_bonus=0.0, blank=None, context_graph=None, token_times=False, endpoint=None):
         # validation and defaults of the offline decoder
         o = CTCPrefixBeamSearchDecoder([None], dictionary, beam_size=beam_size, nbest=nbest, beam_size_token=beam_size_token,
                                        lm_model=lm_model, lm_weight=lm_weight, insertion_bonus=insertion_bonus, blank=blank,
@@ -51,7 +58,8 @@ class StreamingCTCPrefixBeamDecoder(StreamSlots):
         self._search = dict(max_frames=self.max_frames, V=o.vocab_size, beam=o.beam_size, K=o.beam_size_token, blank=o.blank,
                             ins_bonus=o.insertion_bonus)
         self.state = self.graph = self.lm = self.lm_rows = self._rows = None  # allocated on the device of the first frames
-        self.token_times = bool(token_times)
+        self.token_times = bool(token_times) or endpoint is not None  # the endpoint probe reads the times state
+        self.endpoint_rules = endpoint
 
     def state_bytes_per_stream(self) -> int:
         from .. import _lib
@@ -163,6 +171,15 @@ class StreamingCTCPrefixBeamDecoder(StreamSlots):
                                                 biased=self.graph is not None)
 
     @torch.no_grad()
+    def endpoint_tensors(self, stream_ids):
+        """Device tensor int32 [n][4] = (rule, F, L, E) of the streams under the decoder's EndpointRules; the state is read only."""
+        self._need_endpoint()
+        slots = self._slots_of(stream_ids, self._ensure(self._device()))
+        return K.ctc_prefix_beam_stream_endpoint(self.state, self.times_state, slots, self.max_frames, self.beam_size,
+                                                 *self.endpoint_rules.frames(), lm_weight=self.lm_weight if self.lm is not None else 0.0,
+                                                 ins_bonus=self.insertion_bonus, biased=self.graph is not None)
+
+    @torch.no_grad()
     def partial(self, stream_ids) -> List[Dict[str, object]]:
         """Per stream: `tokens` of the hypothesis the beam ranks first, its in-beam `score` and `stable`, the leading tokens
         that every later result starts with.  One readback."""
@@ -174,6 +191,9 @@ class StreamingCTCPrefixBeamDecoder(StreamSlots):
     @torch.no_grad()
     def close(self, sid) -> List[Dict[str, torch.Tensor]]:
         """Up to nbest finished hypotheses of a stream in the generators' format; its slot is free afterwards."""
-        hyps = hyps_from_tensors(*(t.cpu() for t in self.finish([sid])))[0]
+        hyps = self._finished(sid)
         self._release(sid)
         return hyps
+
+    def _finished(self, sid):
+        return hyps_from_tensors(*(t.cpu() for t in self.finish([sid])))[0]

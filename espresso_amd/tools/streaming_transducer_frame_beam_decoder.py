@@ -29,7 +29,14 @@ TransducerFrameBeamDecoder.search with the same graph returns.  The tables are u
 Time stamps: with `token_times=True` a slot also has a times slot (K.rnnt_frame_beam_stream_times_state), the reset, the steps and
 the finish are those of the times family (ea_rnnt_frame_beam_stream_times_*), `finish_tensors` also returns (times, vscores) with
 frames counted from the stream's first frame, and `finish` / `close` put "times" and "viterbi_score" into the hypotheses: what the
-offline decoder with token_times returns for the whole utterance.  `partial` carries no times."""
+offline decoder with token_times returns for the whole utterance.  `partial` carries no times.
+
+Endpointing: with `endpoint=EndpointRules(...)` (tools/beam_common.py) the decoder uses the times family and also has
+`endpoint_tensors` / `endpoint` (ea_rnnt_frame_beam_stream_endpoint: per stream (rule, F, L, E) of the hypothesis `partial` reports,
+read only), `end_segment` (the hypotheses of `finish`, then the slot restarts: search state, times state, predictor and LM rows
+start fresh) and `room`.  A segment's hypotheses are, bit for bit, what TransducerFrameBeamDecoder with token_times returns for
+that segment's frames alone.  Rules are read after an `accept`, so segments end on piece boundaries; the thresholds count frames
+and do not depend on the pieces.  Without `endpoint` nothing changes: a stream that would pass `max_frames` raises."""
 from typing import Dict, List
 
 import torch
@@ -41,7 +48,8 @@ from .transducer_frame_beam_decoder import TransducerFrameBeamDecoder
 
 class StreamingTransducerFrameBeamDecoder(StreamSlots):
     def __init__(self, model, dictionary, beam_size, max_streams, max_frames, nbest=1, beam_size_token=None, temperature=1.0,
-                 normalize_scores=True, lm_model=None, lm_weight=0.0, model_predicts_eos=False, context_graph=None, token_times=False):
+                 normalize_scores=True, lm_model=None, lm_weight=0.0, model_predicts_eos=False, context_graph=None, token_times=False,
+                 endpoint=None):
         # validation and defaults of the offline decoder
         o = TransducerFrameBeamDecoder(model, dictionary, beam_size=beam_size, nbest=nbest, beam_size_token=beam_size_token,
                                        temperature=temperature, normalize_scores=normalize_scores, lm_model=lm_model,
@@ -57,7 +65,8 @@ class StreamingTransducerFrameBeamDecoder(StreamSlots):
                           eos=o.eos if o.model_predicts_eos else -1, temperature=o.temperature, lm_weight=o.lm_weight,
                           lm_no_blank=o.no_blank_in_lm)
         self.state = self.graph = None
-        self.token_times = bool(token_times)
+        self.token_times = bool(token_times) or endpoint is not None  # the endpoint probe reads the times state
+        self.endpoint_rules = endpoint
         dev = next(self.model.parameters()).device if self.model is not None else None
         if dev is not None and dev.type == "cuda":
             self._allocate(dev)
@@ -171,6 +180,14 @@ class StreamingTransducerFrameBeamDecoder(StreamSlots):
         return partial(self.state, slots, self.max_frames, self.beam_size, self.pad, self._max_u(stream_ids) if max_u is None else max_u)
 
     @torch.no_grad()
+    def endpoint_tensors(self, stream_ids):
+        """Device tensor int32 [n][4] = (rule, F, L, E) of the streams under the decoder's EndpointRules; the state is read only."""
+        self._need_endpoint()
+        slots = self._slots_of(stream_ids, self._ensure(self._device()))
+        return K.rnnt_frame_beam_stream_endpoint(self.state, self.times_state, slots, self.max_frames, self.beam_size,
+                                                 *self.endpoint_rules.frames(), biased=self.graph is not None)
+
+    @torch.no_grad()
     def partial(self, stream_ids):
         """Per stream (tokens of the live hypothesis with the best score, stable_len, score): the first stable_len tokens are
         those every later result starts with.  One readback."""
@@ -189,3 +206,5 @@ class StreamingTransducerFrameBeamDecoder(StreamSlots):
         hyps = self.finish(sid)
         self._release(sid)
         return hyps
+
+    _finished = finish

@@ -569,6 +569,20 @@ int ea_ctc_prefix_beam_stream_times_finish(const void* state, const void* times_
                                            int cg_n_nodes, int max_streams, int max_frames, int beam, int nbest, int pad, int max_u,
                                            int* tokens, int* lengths, float* scores, int* nhyp, int* times, float* vscores,
                                            ea_stream_t stream);
+/* The endpoint probe of the streamed CTC prefix beam search with times (csrc/ctc_beam.hip): whether an utterance has ended in a
+ * slot, from state the kernels above already write.  state / times_state: those of ea_ctc_prefix_beam_stream_times_* (biased != 0:
+ * the searches ran with a graph); slots device int32 [n]; lm_weight / ins_bonus / biased as ea_ctc_prefix_beam_stream_partial takes
+ * them.  Per listed slot, with F = its frame counter: best = the live hypothesis ..._stream_partial reports (same score, tie rule
+ * and handling of non-finite scores; the empty hypothesis for F == 0 or no hypothesis), L = its length, E = the frame, counted
+ * from the slot's first frame, at which its last token starts on its best path: what ..._stream_times_finish writes as
+ * times[L - 1] for it (tfrm of the pointer of the larger of (vb, eb), (vnb, enb); tie: eb), -1 when L == 0.  rule = the first
+ * that holds of 1 "silence": L > 0 and F - 1 - E >= silence_frames; 2 "empty": L == 0 and F >= empty_frames; 3 "length":
+ * F >= segment_frames; else 0.  A threshold <= 0 switches its rule off.  out int32 [n][4] = (rule, F, L, E); a slot outside
+ * [0, max_streams) writes (0, 0, 0, -1).  Both states are read only.  Bad arguments (a NULL buffer, max_streams or max_frames < 1,
+ * beam outside [1, 64]) return -2 and launch nothing; n <= 0 returns 0. */
+int ea_ctc_prefix_beam_stream_endpoint(const void* state, const void* times_state, const int* slots, int n, float lm_weight,
+                                       float ins_bonus, int biased, int max_streams, int max_frames, int beam, int silence_frames,
+                                       int empty_frames, int segment_frames, int* out, ea_stream_t stream);
 /* Frame-synchronous transducer beam search (csrc/rnnt_beam.hip; at most one symbol per encoder frame and hypothesis, equal
  * token sequences merged — "modified beam search") with optional mass-preserving shallow fusion of one sub-word LM: the
  * transducer counterpart of ea_ctc_prefix_beam_*.  Hypotheses are distinct token sequences with a score (natural log), at most
@@ -718,6 +732,15 @@ int ea_rnnt_frame_beam_stream_times_finish(const void* state, const void* times_
                                            int max_frames, int beam, const int* cg_nodes, int cg_n_nodes, int nbest, int pad,
                                            int normalize, int max_u, int* tokens, int* lengths, float* scores, int* nhyp, int* times,
                                            float* vscores, ea_stream_t stream);
+/* The endpoint probe of the streamed transducer beam search with times (csrc/rnnt_beam.hip): ea_ctc_prefix_beam_stream_endpoint
+ * for state / times_state of ea_rnnt_frame_beam_stream_times_* (biased != 0: a bias state, as in ..._stream_times_reset).  best =
+ * the live hypothesis ..._stream_partial / _bias_partial reports (score s, biased: s + b; ties: the lower beam slot), L = its
+ * length, E = tfrm[e]: the frame at which its last token is emitted on its best path, what ..._stream_times_finish writes as
+ * times[L - 1] for it, -1 when L == 0.  Rules, thresholds, out int32 [n][4] = (rule, F, L, E), the row of a slot out of range
+ * and the refusals are those of the CTC probe.  Both states are read only. */
+int ea_rnnt_frame_beam_stream_endpoint(const void* state, const void* times_state, const int* slots, int n, int biased,
+                                       int max_streams, int max_frames, int beam, int silence_frames, int empty_frames,
+                                       int segment_frames, int* out, ea_stream_t stream);
 /* Word n-gram LM (ARPA) and lexicon-constrained CTC prefix beam search with its fusion (csrc/ctc_lexicon_beam.hip) — the
  * search the reference takes from Flashlight's KenLM lexicon decoder (espresso/tools/ctc_decoder.py:24-71).
  * ea_ngram_create: parses a plain-text ARPA file of order <= 6 at `path` into host tables and writes an opaque handle to

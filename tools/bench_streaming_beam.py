@@ -15,7 +15,12 @@ call, every stream ready in every call:
 with `--encoder`: enc_ms / dec_ms, the encoder (bench_streaming.py's model and loop) and the decoder of the same chunk timed
 apart, and dec_share = dec / (enc + dec) of the medians.
 
-Prints one JSON line per configuration, then one with the state bytes per stream."""
+Prints one JSON line per configuration, then one with the state bytes per stream.
+
+`--endpoint`: instead, the streamed CTC prefix beam search (StreamingCTCPrefixBeamDecoder, no LM) per piece without times (the
+baseline), with times, and endpointed (`accept` + the `endpoint` readback + the segment ends it asks for; rules of the command
+line's defaults: 0.8 s / 5 s / 20 s), the three decoders fed the same pieces in the same loop; endpoint_ms is the probe and its
+readback alone.  Then the bytes of device state per stream of a slot at the 20 s limit against one sized for 10 minutes."""
 import argparse
 import json
 import os
@@ -156,6 +161,68 @@ def run_with_encoder(streams, cs, args, dev, beam):
     return {"enc_ms_median": round(e, 3), "dec_ms_median": round(dd, 3), "dec_share": round(dd / (e + dd), 4), "chunks": len(enc)}
 
 
+def run_endpoint(streams, cs, args, dev):
+    from espresso_amd import kernels as K
+    from espresso_amd.data.asr_dictionary import AsrDictionary
+    from espresso_amd.tools.beam_common import EndpointRules
+    from espresso_amd.tools.streaming_ctc_prefix_beam_decoder import StreamingCTCPrefixBeamDecoder
+
+    T, V = args.frames, args.V
+    d = AsrDictionary.from_symbols([f"p{i}" for i in range(V - 5)], enable_bos=True)
+    assert len(d) == V
+    x = K.log_softmax(peaked_logits(streams, T, V, dev).view(streams * T, V), streams * T, V, V).view(streams, T, V)
+    ids = list(range(streams))
+    rules = EndpointRules(20, 125, 500)  # 0.8 s, 5 s, 20 s in frames of 40 ms
+    decs = {"step_ms": StreamingCTCPrefixBeamDecoder(d, streams, T, beam_size=args.beam),
+            "times_step_ms": StreamingCTCPrefixBeamDecoder(d, streams, T, beam_size=args.beam, token_times=True),
+            "endpointed_step_ms": StreamingCTCPrefixBeamDecoder(d, streams, rules.segment_frames + cs, beam_size=args.beam, endpoint=rules)}
+    ts = {k: [] for k in decs}
+    probe, ended = [], 0
+
+    def endpointed(dec, rows, counts):
+        n = 0
+        for i in dec.room(ids, counts):
+            dec.end_segment(i)
+            n += 1
+        dec.accept_lprobs(ids, rows, counts)
+        for i, (rule, _, _, _) in zip(ids, dec.endpoint(ids)):
+            if rule:
+                dec.end_segment(i)
+                n += 1
+        return n
+
+    for rnd in range(args.rounds + 1):  # round 0 warms every shape up
+        for dec in decs.values():
+            dec.open(ids)
+        for a in range(0, T, cs):
+            b = min(T, a + cs)
+            rows, counts = x[:, a:b].reshape(streams * (b - a), V), [b - a] * streams
+            for k, dec in decs.items():
+                t, n = _timed((lambda: endpointed(dec, rows, counts)) if k == "endpointed_step_ms" else (lambda: dec.accept_lprobs(ids, rows, counts)))
+                if rnd:
+                    ts[k].append(t)
+                    ended += n or 0
+            t, _ = _timed(lambda: decs["endpointed_step_ms"].endpoint(ids))
+            if rnd:
+                probe.append(t)
+        for dec in decs.values():
+            for i in ids:
+                dec.close(i)
+    res = {"mode": "endpoint", "streams": streams, "chunk_frames": cs, "frames": T, "beam": args.beam, "timed_accepts": len(probe),
+           "segments_ended": ended}
+    for k, v in ts.items():
+        res.update(_stats(v, k))
+    res.update(_stats(probe, "endpoint_ms"))
+    return res
+
+
+def endpoint_state_bytes(lib_state, lib_times, beams, cs):
+    """Device state per stream: a slot at the 20 s limit (500 frames + one piece, with its times slot) against the parent's slot
+    for a 10-minute utterance (15000 frames, no times)."""
+    return {"endpointed_20s_bytes_per_stream": {f"beam{b}": int(lib_state(500 + cs, b) + lib_times(500 + cs, b)) for b in beams},
+            "slot_10min_bytes_per_stream": {f"beam{b}": int(lib_state(15000, b)) for b in beams}}
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--streams", default="1,16,64")
@@ -166,6 +233,7 @@ def main():
     p.add_argument("--rounds", type=int, default=3, help="timed utterances per configuration, after one warm-up")
     p.add_argument("--calls", type=int, default=5, help="timed offline searches, after one warm-up")
     p.add_argument("--encoder", action="store_true", help="also time the decoder behind bench_streaming.py's encoder")
+    p.add_argument("--endpoint", action="store_true", help="the CTC prefix beam search with and without endpointing instead (see above)")
     p.add_argument("--words", type=int, default=100000)
     p.add_argument("--bigrams", type=int, default=1500000)
     p.add_argument("--trigrams", type=int, default=2000000)
@@ -173,6 +241,16 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_streaming_beam.py measures on the GPU: no device found")
     dev = torch.device("cuda:0")
+    if args.endpoint:
+        from espresso_amd import _lib
+
+        for cs in [int(x) for x in args.chunk_frames.split(",")]:
+            for s in [int(x) for x in args.streams.split(",")]:
+                print(json.dumps(run_endpoint(s, cs, args, dev)), flush=True)
+        L = _lib.lib()
+        print(json.dumps(endpoint_state_bytes(L.ea_ctc_prefix_beam_stream_state_bytes, L.ea_ctc_prefix_beam_stream_times_state_bytes,
+                                              (10, 64), 16)), flush=True)
+        return
     d, ngram, trie = tables(args, dev)
     print(json.dumps({"lexicon_words": trie.num_words, "lexicon_nodes": len(trie), "V": args.V}), flush=True)
     for cs in [int(x) for x in args.chunk_frames.split(",")]:

@@ -16,7 +16,12 @@ Per configuration (beam x streams x biased or not), one JSON line:
                             counted); the launches themselves are counted from a kernel trace, see DESIGN section 8.1;
   partial_ms, finish_ms     one `partial` / `finish_tensors` + readback for all streams, at the end of the utterance;
   tokens_per_audio_second   of the 1-best hypotheses.
-The last line gives the state bytes per stream for 30 s of audio."""
+The last line gives the state bytes per stream for 30 s of audio.
+
+`--endpoint`: instead, per configuration the beam decoder's `accept` without times (the baseline), with times, and endpointed
+(`accept` + the `endpoint` readback + the segment ends it asks for; rules of the command line's defaults: 0.8 s / 5 s / 20 s),
+the three decoders fed the same pieces in the same loop; endpoint_ms is the probe and its readback alone.  Then the bytes of
+device state per stream of a slot at the 20 s limit against one sized for 10 minutes."""
 import argparse
 import json
 import os
@@ -135,6 +140,54 @@ def run(model, d, rows, T, beam, streams, cs, args, biased):
     return res
 
 
+def run_endpoint(model, d, rows, T, beam, streams, cs, args):
+    from espresso_amd.tools.beam_common import EndpointRules
+    from espresso_amd.tools.streaming_transducer_frame_beam_decoder import StreamingTransducerFrameBeamDecoder
+
+    ids = list(range(streams))
+    rules = EndpointRules(20, 125, 500)  # 0.8 s, 5 s, 20 s in frames of 40 ms
+    mk = lambda mf, **kw: StreamingTransducerFrameBeamDecoder(model, d, beam, max_streams=streams, max_frames=mf, **kw)  # noqa: E731
+    decs = {"accept_ms": mk(T), "times_accept_ms": mk(T, token_times=True), "endpointed_accept_ms": mk(rules.segment_frames + cs, endpoint=rules)}
+    ts = {k: [] for k in decs}
+    probe, ended = [], 0
+
+    def endpointed(dec, x, counts):
+        n = 0
+        for i in dec.room(ids, counts):
+            dec.end_segment(i)
+            n += 1
+        dec.accept(ids, x, counts)
+        for i, (rule, _, _, _) in zip(ids, dec.endpoint(ids)):
+            if rule:
+                dec.end_segment(i)
+                n += 1
+        return n
+
+    for rnd in range(args.rounds + 1):  # round 0 warms every shape up
+        for dec in decs.values():
+            dec.open(ids)
+        for a in range(0, T, cs):
+            b = min(T, a + cs)
+            x, counts = rows[:, a:b].reshape(streams * (b - a), -1), [b - a] * streams
+            for k, dec in decs.items():
+                t, n = _timed((lambda: endpointed(dec, x, counts)) if k == "endpointed_accept_ms" else (lambda: dec.accept(ids, x, counts)))
+                if rnd:
+                    ts[k].append(t)
+                    ended += n or 0
+            t, _ = _timed(lambda: decs["endpointed_accept_ms"].endpoint(ids))
+            if rnd:
+                probe.append(t)
+        for dec in decs.values():
+            for i in ids:
+                dec.close(i)
+    res = {"mode": "endpoint", "beam": beam, "streams": streams, "chunk_frames": cs, "frames": T, "timed_accepts": len(probe),
+           "segments_ended": ended}
+    for k, v in ts.items():
+        res.update(_stats(v, k))
+    res.update(_stats(probe, "endpoint_ms"))
+    return res
+
+
 def calibrate(model, d, rows, T, rate, blank):
     """Bisection on the blank bias until the beam-1 search emits `rate` tokens per second of audio."""
     from espresso_amd.tools.streaming_transducer_frame_beam_decoder import StreamingTransducerFrameBeamDecoder
@@ -162,6 +215,7 @@ def main():
     p.add_argument("--chunk-frames", type=int, default=16, help="encoder frames per accept (and the encoder's chunk size)")
     p.add_argument("--frames", type=int, default=96, help="encoder frames per utterance (and max_frames of the decoder)")
     p.add_argument("--rounds", type=int, default=2, help="timed utterances per configuration, after one warm-up")
+    p.add_argument("--endpoint", action="store_true", help="the beam decoder with and without endpointing instead (see above)")
     p.add_argument("--emit-rate", type=float, default=4.5, help="also measure with the blank bias calibrated to this many tokens per audio second (0: skip)")
     args = p.parse_args()
     if not torch.cuda.is_available():
@@ -171,6 +225,19 @@ def main():
     blank = d.bos()
     streams = [int(x) for x in args.streams.split(",")]
     rows, T = encoder_rows(model, max(streams), args.frames, dev)
+    if args.endpoint:
+        from espresso_amd import _lib
+
+        for beam in [int(x) for x in args.beams.split(",")]:
+            for s in streams:
+                print(json.dumps(run_endpoint(model, d, rows[:s].contiguous(), T, beam, s, args.chunk_frames, args)), flush=True)
+        L, cs = _lib.lib(), args.chunk_frames
+        print(json.dumps({"endpointed_20s_bytes_per_stream": {f"beam{b}": int(L.ea_rnnt_frame_beam_stream_state_bytes(500 + cs, b) +
+                                                                                L.ea_rnnt_frame_beam_stream_times_state_bytes(500 + cs, b))
+                                                              for b in (1, 5, 10, 64)},
+                          "slot_10min_bytes_per_stream": {f"beam{b}": int(L.ea_rnnt_frame_beam_stream_state_bytes(15000, b))
+                                                          for b in (1, 5, 10, 64)}}), flush=True)
+        return
     for biased in ([False, True] if args.emit_rate > 0 else [False]):
         if biased:
             got = calibrate(model, d, rows, T, args.emit_rate, blank)
