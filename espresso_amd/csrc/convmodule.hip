@@ -959,7 +959,7 @@ extern "C" int ea_bn_act_bwd_fused(const void* Z, const void* dH, const float* m
 extern "C" int ea_conv1_bn_bwd(const float* X, const void* Z, const void* dH, const float* mean_rstd, const float* gamma,
                                const float* beta, float* red, float* dgamma, float* dbeta, float* dW, float* dbias, int B, int T,
                                int F, int CO, int sy, int sx, int act, int training, hipStream_t stream) {
-  if (B <= 0 || T <= 0) return 0;
+  if (B <= 0 || T <= 0 || F <= 0) return 0;
   if (CO % 64) return -2;
   const int To = (T - 1) / sy + 1, Fo = (F - 1) / sx + 1;
   const long npos = (long)B * To * Fo;

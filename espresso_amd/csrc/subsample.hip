@@ -280,7 +280,7 @@ static inline int egrid(long n) {
 
 extern "C" int ea_conv1_fwd(const float* X, const float* W, const float* bias, void* Z, double* stats, int B, int T, int F,
                             int CO, int sy, int sx, hipStream_t stream) {
-  if (B <= 0 || T <= 0) return 0;
+  if (B <= 0 || T <= 0 || F <= 0) return 0;
   if (CO % 64) return -2;
   const int To = (T - 1) / sy + 1, Fo = (F - 1) / sx + 1;
   const long npos = (long)B * To * Fo;
@@ -291,7 +291,7 @@ extern "C" int ea_conv1_fwd(const float* X, const float* W, const float* bias, v
 }
 extern "C" int ea_conv1_wgrad(const float* X, const void* dZ, float* dW, float* dbias, int B, int T, int F, int CO,
                               int sy, int sx, hipStream_t stream) {
-  if (B <= 0 || T <= 0) return 0;
+  if (B <= 0 || T <= 0 || F <= 0) return 0;
   if (CO % 64) return -2;
   const int To = (T - 1) / sy + 1, Fo = (F - 1) / sx + 1;
   const long npos = (long)B * To * Fo;
@@ -301,7 +301,7 @@ extern "C" int ea_conv1_wgrad(const float* X, const void* dZ, float* dW, float* 
   return EA_CHECK_LAUNCH();
 }
 extern "C" int ea_im2col3x3(const void* A, void* col, int B, int T, int F, int C, int sy, int sx, hipStream_t stream) {
-  if (B <= 0 || T <= 0) return 0;
+  if (B <= 0 || T <= 0 || F <= 0) return 0;
   if (C % 8) return -2;
   const int To = (T - 1) / sy + 1, Fo = (F - 1) / sx + 1;
   const long total = (long)B * To * Fo * 9 * (C / 8);
@@ -310,7 +310,7 @@ extern "C" int ea_im2col3x3(const void* A, void* col, int B, int T, int F, int C
   return EA_CHECK_LAUNCH();
 }
 extern "C" int ea_col2im3x3(const void* dcol, void* dA, int B, int T, int F, int C, int sy, int sx, hipStream_t stream) {
-  if (B <= 0 || T <= 0) return 0;
+  if (B <= 0 || T <= 0 || F <= 0) return 0;
   if (C % 8) return -2;
   const int To = (T - 1) / sy + 1, Fo = (F - 1) / sx + 1;
   const long total = (long)B * T * F * (C / 8);
