@@ -740,6 +740,99 @@ def ctc_prefix_beam_stream_partial(state, slots, max_frames, beam, pad, max_u, l
     return tokens, lengths, scores, stable
 
 
+def ctc_kws_state_bytes(K, Lmax, max_hits):
+    """Bytes per slot of the keyword spotter's state (ea_ctc_kws_state_bytes; 0 for sizes it does not take)."""
+    return int(_lib.lib().ea_ctc_kws_state_bytes(K, Lmax, max_hits))
+
+
+def ctc_kws_state(max_streams, K, Lmax, max_hits, device):
+    """(state uint8 [max_streams][bytes per slot], zero-filled; bytes per slot) of the keyword spotter."""
+    nbytes = ctc_kws_state_bytes(K, Lmax, max_hits)
+    assert nbytes > 0 and max_streams >= 1
+    return torch.zeros(max_streams, nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def _check_kws(state, keywords, max_hits):
+    """keywords = (tokens int32 [K][Lmax], lengths int32 [K], tau fp32 [K]) on the device of `state`; returns (K, Lmax)."""
+    tokens, lengths, tau = keywords
+    assert tokens.dtype == lengths.dtype == torch.int32 and tau.dtype == torch.float32 and tokens.dim() == 2
+    assert tokens.is_contiguous() and lengths.is_contiguous() and tau.is_contiguous()
+    Kk, Lmax = tokens.shape
+    assert lengths.numel() == tau.numel() == Kk and tokens.device == lengths.device == tau.device == state.device
+    assert state.dtype == torch.uint8 and state.is_contiguous() and state.dim() == 2
+    assert state.shape[1] == ctc_kws_state_bytes(Kk, Lmax, max_hits) > 0
+    return Kk, Lmax
+
+
+def ctc_kws_reset(state, slots, keywords, max_hits):
+    """The slots int32 [n] (device) of `state` get the spotter's state before frame 0 (ea_ctc_kws_reset)."""
+    Kk, Lmax = _check_kws(state, keywords, max_hits)
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
+    check(_lib.lib().ea_ctc_kws_reset(_p(state), _p(slots), slots.numel(), state.shape[0], Kk, Lmax, max_hits, _stream()),
+          "ea_ctc_kws_reset")
+
+
+def ctc_kws_step(x, meta, state, keywords, max_hits, V, blank, hold, rowmax=None, ld=None):
+    """The pieces of every listed stream through the keyword spotter (ea_ctc_kws_step).  x fp32 [rows][>= V] log-probs packed
+    stream by stream; meta int32 [3][n] = (slot, n_new, row_off) on the device; keywords as `_check_kws` takes them; rowmax: fp32
+    scratch [rows] (allocated when None).  Returns rowmax, the rows' maxima."""
+    ld = x.stride(0) if ld is None else ld
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(-1) == 1 and x.shape[1] >= V and ld >= V
+    assert meta.dtype == torch.int32 and meta.dim() == 2 and meta.shape[0] == 3 and meta.is_contiguous() and meta.device == x.device
+    Kk, Lmax = _check_kws(state, keywords, max_hits)
+    rows = x.shape[0]
+    if rowmax is None:
+        rowmax = torch.empty(max(rows, 1), dtype=torch.float32, device=x.device)
+    assert rowmax.dtype == torch.float32 and rowmax.is_contiguous() and rowmax.numel() >= rows and rowmax.device == x.device
+    tokens, lengths, tau = keywords
+    check(_lib.lib().ea_ctc_kws_step(_p(x), ld, rows, _p(rowmax), _p(meta[0]), _p(meta[1]), _p(meta[2]), meta.shape[1], _p(state),
+                                     _p(tokens), _p(lengths), _p(tau), state.shape[0], Kk, Lmax, max_hits, V, blank, int(hold),
+                                     _stream()), "ea_ctc_kws_step")
+    return rowmax
+
+
+def ctc_kws_hits(state, slots, keywords, max_hits, flush=False, clear=False):
+    """The hit lists of the slots int32 [n] (device), after emitting their open hits when `flush`; `clear` empties the lists
+    afterwards (ea_ctc_kws_hits).  Returns (starts int32 [n][K][max_hits] -1-filled, ends likewise, scores fp32 [n][K][max_hits],
+    counts int32 [n][K]) on the device."""
+    Kk, Lmax = _check_kws(state, keywords, max_hits)
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.device == state.device
+    n, dev = slots.numel(), state.device
+    starts = torch.empty(n, Kk, max_hits, dtype=torch.int32, device=dev)
+    ends = torch.empty_like(starts)
+    scores = torch.empty(n, Kk, max_hits, dtype=torch.float32, device=dev)
+    counts = torch.empty(n, Kk, dtype=torch.int32, device=dev)
+    check(_lib.lib().ea_ctc_kws_hits(_p(state), _p(slots), n, int(bool(flush)), int(bool(clear)), state.shape[0], Kk, Lmax, max_hits,
+                                     _p(starts), _p(ends), _p(scores), _p(counts), _stream()), "ea_ctc_kws_hits")
+    return starts, ends, scores, counts
+
+
+def ctc_kws_host(x, kw_tokens, kw_len, kw_tau, blank, hold, max_hits, V=None):
+    """The keyword spotter over one utterance on the host (ea_ctc_kws_host; no device): x fp32 [T][ld] numpy log-probs (V: the
+    columns that count, all by default), kw_tokens int32 [K][Lmax], kw_len int32 [K], kw_tau fp32 [K].  Returns numpy (starts
+    int32 [K][max_hits], ends, scores fp32 [K][max_hits], counts int32 [K]), flushed at the end."""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    assert x.ndim == 2
+    T, ld = x.shape
+    V = ld if V is None else V
+    tok = np.ascontiguousarray(kw_tokens, dtype=np.int32)
+    assert tok.ndim == 2
+    Kk, Lmax = tok.shape
+    ln = np.ascontiguousarray(kw_len, dtype=np.int32)
+    tau = np.ascontiguousarray(kw_tau, dtype=np.float32)
+    assert ln.shape == tau.shape == (Kk,)
+    starts = np.empty((Kk, max_hits), dtype=np.int32)
+    ends = np.empty_like(starts)
+    scores = np.empty((Kk, max_hits), dtype=np.float32)
+    counts = np.empty(Kk, dtype=np.int32)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    check(_lib.lib().ea_ctc_kws_host(vp(x), ld, T, V, vp(tok), vp(ln), vp(tau), Kk, Lmax, blank, int(hold), max_hits, vp(starts),
+                                     vp(ends), vp(scores), vp(counts)), "ea_ctc_kws_host")
+    return starts, ends, scores, counts
+
+
 def rnnt_frame_beam_workspace(B, T, beam, device):
     """Workspace of the frame-synchronous transducer beam search (ea_rnnt_frame_beam_workspace_bytes): the beams, prefix tables
     and per-row candidates of B utterances of at most T frames."""

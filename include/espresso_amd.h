@@ -1295,6 +1295,69 @@ int ea_ctc_prefix_posteriors(const void* x, long ld, int x_bf16, const int* targ
                              int blank, ea_stream_t stream);
 int ea_rnnt_prefix_posteriors(const float* lpb, const float* lpy, const int* logit_lengths, const int* target_lengths,
                               float* logc, float* total, float* psi, int B, int T, int U1, ea_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Keyword spotting on CTC log-probs, offline and streamed (csrc/kws.hip): where a list of phrases is spoken, and how sure the
+ * model is, from the per-frame log-probs alone -- no beam search, no transcript.  The reference has nothing of the kind.  The
+ * (stream, keyword) pairs are independent; each is a max-plus scan over the frames with a free start frame, its state carried
+ * across pieces in the stream's slot, so a stream fed in any pieces gives bit for bit the offline result.
+ *
+ * x: fp32 log-probs (the output of a log-softmax, finite) as rows [total_rows][ld], ld >= V.
+ *   g_t = max_{v < V} x_t[v], the score of the greedy path at frame t;
+ *   d_t(v) = x_t[v] - g_t, one fp32 subtraction: <= 0, and == 0 exactly on the frame's argmax.
+ * A keyword is a token sequence y_1 .. y_L, 1 <= L <= 64, no blank among the tokens.  LATTICE: 2L - 1 states tok_1, blk_1,
+ *   tok_2, ..., blk_{L-1}, tok_L -- no leading and no trailing blank, so a hit's bounds are tight.  Every state carries a pair
+ *   (e, b): e (fp32) is the best sum of d over the paths that entered tok_1 at frame b and occupy the state now; (-inf, -1)
+ *   means there is none.  Frames count from the stream's first frame.
+ * FRAME UPDATE of state s, from the pairs before the frame.  Candidates, in this order: 1. stay (s); 2. step (s-1); 3. skip
+ *   (s-2), only into a token state whose label differs from the token two states earlier; 4. for s == 0 only, a fresh start
+ *   (0, t).  TIE RULE: the largest e, on a tie the first in that order.  If the chosen e is -inf the state becomes (-inf, -1),
+ *   otherwise e' = e_chosen + d_t(label(s)) (one fp32 add; the label of a blk state is blank) and b' = b_chosen.  Every operation
+ *   is a max, one add or one subtract and no reduction is re-associated: the result has exactly one set of fp32 bits.
+ * DETECTION after the update of frame t, with tau_k = L_k * ln(theta_k) computed by the caller in fp32.  Per (stream, keyword):
+ *   an open hit (or none), last_end (-1 at first), a hit list and its count.  If e(tok_L) >= tau_k and b(tok_L) > last_end there
+ *   is a candidate (b, t, e): with no open hit it becomes the open hit; if b <= open.end it overlaps and replaces the open hit
+ *   iff e >= open.e (a tie goes to the later end, so the hit covers the last token's whole run); otherwise the open hit is
+ *   emitted and the candidate becomes the open hit.  Then, if there is an open hit and t - open.end > hold, it is emitted.  A
+ *   candidate with b <= last_end is dropped.
+ * EMIT appends (start, end, e) to the list if count < max_hits, increments count always (count > max_hits reports the overflow),
+ *   sets last_end = open.end and leaves no open hit.  end is inclusive.
+ * The confidence shown to users is exp(e / L): the geometric mean per token of p(keyword path) / p(greedy path), in (0, 1], and
+ *   1 when the keyword's path is the greedy path.
+ * A keyword is INACTIVE when its length is outside [1, Lmax] or it holds a token outside [0, V) or equal to blank: it never has a
+ *   candidate (its state is not touched).
+ *
+ * State: max_streams * ea_ctc_kws_state_bytes(K, Lmax, max_hits) bytes, slot-major.  Per slot, int32 words: [0] frames consumed,
+ *   [1] the stream frame of the first row of the slot's latest piece, then per keyword kw_words = 4 * Lmax + 6 + 3 * max_hits
+ *   rounded up to even: e fp32 [2 * Lmax] (tok_{u+1} at 2u, blk_{u+1} at 2u + 1; blk_L and the states past L stay -inf), b int32
+ *   [2 * Lmax], open.start (-1: no open hit), open.end, open.e (fp32), last_end, count, 0, then starts int32 [max_hits], ends
+ *   int32 [max_hits], scores fp32 [max_hits].  ..._state_bytes returns 0 for K < 1, Lmax outside [1, 64] or max_hits < 1.
+ * Conventions of ea_ctc_prefix_beam_stream_*: slots / slot_idx / n_new / row_off are device int32 [n]; a slot may be listed once
+ *   per call; no call synchronises with the host; bad arguments return -2 and launch nothing; n <= 0 returns 0.
+ * ..._reset: the listed slots get the state before frame 0; a slot outside [0, max_streams) is skipped.
+ * ..._step: entry i runs the frames of rows row_off[i] .. row_off[i] + n_new[i] - 1 of x through every active keyword and
+ *   advances its slot's frame counter by n_new[i].  It is skipped, its slot untouched, if its slot is out of range, if n_new[i]
+ *   <= 0 or if a row of its piece lies outside [0, total_rows).  rowmax: caller-provided fp32 scratch [total_rows], receives g of
+ *   every row of x.  kw_tokens int32 [K][Lmax], kw_len int32 [K], kw_tau fp32 [K], all on the device; hold >= 0 in frames.
+ *   Two launches: the row maxima (one wave per row) with the entries' frame bookkeeping, then the scan, 256-thread workgroups,
+ *   one keyword per wave, grid (ceil(K / 4), n).  The offline search is reset, one step over the whole utterances, then hits
+ *   with flush: one per-frame body for both.
+ * ..._hits: flush != 0 first emits the open hits of the listed slots (the audio's end).  Then the lists are copied into starts /
+ *   ends int32 [n][K][max_hits] (-1 past the list), scores fp32 [n][K][max_hits] (0 past the list) and counts int32 [n][K].
+ *   clear != 0 then empties the lists and zeroes the counts; the DP state, the open hits and last_end stay.  A slot out of range
+ *   gets empty lists and count 0.
+ * ea_ctc_kws_host: one utterance x_host [T][ld] on the host, flushed at the end, through the same __host__ __device__ update and
+ *   detection functions as the kernel: its yardstick.  All arrays are host arrays; starts / ends / scores [K][max_hits], counts
+ *   [K], filled as ..._hits fills them.  T == 0 gives empty lists. */
+long ea_ctc_kws_state_bytes(int K, int Lmax, int max_hits);
+int ea_ctc_kws_reset(void* state, const int* slots, int n, int max_streams, int K, int Lmax, int max_hits, ea_stream_t stream);
+int ea_ctc_kws_step(const float* x, long ld, long total_rows, float* rowmax, const int* slot_idx, const int* n_new,
+                    const int* row_off, int n, void* state, const int* kw_tokens, const int* kw_len, const float* kw_tau,
+                    int max_streams, int K, int Lmax, int max_hits, int V, int blank, int hold, ea_stream_t stream);
+int ea_ctc_kws_hits(void* state, const int* slots, int n, int flush, int clear, int max_streams, int K, int Lmax, int max_hits,
+                    int* starts, int* ends, float* scores, int* counts, ea_stream_t stream);
+int ea_ctc_kws_host(const float* x_host, long ld, int T, int V, const int* kw_tokens, const int* kw_len, const float* kw_tau, int K,
+                    int Lmax, int blank, int hold, int max_hits, int* starts, int* ends, float* scores, int* counts);
 /* Joint network element-wise stages (espresso/models/transformer/speech_transformer_transducer_base.py:276-299):
  * Z[b][t][u] = relu(E[b][t] + D[b][u]) (bf16, E [B*T][J], D [B*U1][J], Z [B*T*U1][J], J % 8 == 0) and its backward
  * reductions dE[b][t] = sum_u dZ[b][t][u], dD[b][u] = sum_t dZ[b][t][u] (either output may be NULL). */
