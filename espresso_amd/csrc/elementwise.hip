@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void scale_dropout_kernel(const bf16_t* __rest
       for (long j = i; j < n; ++j) {
         float k = 1.f;
         if (thr) k = ea_keep(seed, (uint64_t)j, thr, inv_keep);
-        out[j] = f2bf(a * bf2f(x[j]) * k + (y ? b * bf2f(y[j]) : 0.f));
+        out[j] = f2bf(a * bf2f(x[j]) * k + b * (y ? bf2f(y[j]) : 0.f));  // (a missing y is +0, as in the chunks: the same zero's sign)
       }
     }
   }

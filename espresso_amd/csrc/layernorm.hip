@@ -602,7 +602,7 @@ __global__ __launch_bounds__(256) void ln_bwd2_kernel(
 }
 
 // partial: [nrows][2C] -> dgamma[c] += sum partial[:, c], dbeta[c] += sum partial[:, C + c].
-// grid (2C/64, RSPLIT); block 256 = 4 row-lanes x 64 columns.
+// grid (ceil(2C/64), RSPLIT); block 256 = 4 row-lanes x 64 columns.
 __global__ __launch_bounds__(256) void ln_param_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dgamma,
                                                               float* __restrict__ dbeta, int nrows, int C) {
   __shared__ float sm[4][64];
@@ -611,10 +611,11 @@ __global__ __launch_bounds__(256) void ln_param_reduce_kernel(const float* __res
   const int per = (nrows + gridDim.y - 1) / gridDim.y;
   const int r0 = blockIdx.y * per, r1 = min(nrows, r0 + per);
   float a = 0.f;
-  for (int r = r0 + ry; r < r1; r += 4) a += partial[(long)r * 2 * C + col];
+  if (col < 2 * C)  // (2C is a multiple of 16, not of 64: the last column block may be ragged)
+    for (int r = r0 + ry; r < r1; r += 4) a += partial[(long)r * 2 * C + col];
   sm[ry][cx] = a;
   __syncthreads();
-  if (ry == 0) {
+  if (ry == 0 && col < 2 * C) {
     a = sm[0][cx] + sm[1][cx] + sm[2][cx] + sm[3][cx];
     if (col < C) atomicAdd(dgamma + col, a);
     else atomicAdd(dbeta + col - C, a);
@@ -769,7 +770,7 @@ extern "C" int ea_layernorm_param_reduce(const void* workspace, float* dgamma, f
   int rs = nblk / 32;
   if (rs < 1) rs = 1;
   if (rs > 32) rs = 32;
-  hipLaunchKernelGGL(ln_param_reduce_kernel, dim3(2 * C / 64, rs), dim3(256), 0, stream, (const float*)workspace, dgamma,
+  hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * C + 63) / 64, rs), dim3(256), 0, stream, (const float*)workspace, dgamma,
                      dbeta, nblk, C);
   return EA_CHECK_LAUNCH();
 }

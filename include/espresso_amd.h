@@ -232,7 +232,7 @@ int ea_audio_read_batch_i16(const char* const* paths, int n, int16_t* dst, const
  * (espresso/models/transformer/speech_transformer_encoder_model.py:207-208 fc_out, torch autograd of F.linear). */
 int ea_cast_f32_to_bf16_rows(const float* src, long ld_src, void* dst, long ld_dst, long M, int N, ea_stream_t stream);
 int ea_cast_bf16_to_f32(const void* src, float* dst, long n, ea_stream_t stream);
-/* out = a*x*keep(idx) + b*y  (bf16; y may be NULL) */
+/* out = a*x*keep(idx) + b*y  (bf16; y may be NULL: read as +0, which decides the sign of a zero result) */
 int ea_scale_dropout_bf16(const void* x, const void* y, void* out, long n, float a, float b, uint64_t seed,
                           uint32_t thr, float inv_keep, ea_stream_t stream);
 /* out[n] += sum_m X[m*ld+n]  (X bf16, out fp32) */
