@@ -196,8 +196,13 @@ static int fbank_launch(const TS* wav, const long* offsets, int B, const float* 
                         const int* mel_len, const int* mel_woff, const float* mel_w, const float* cmvn_mean, const float* cmvn_std,
                         float* feat, float* utt_sum, int* out_len, int Tmax, int nmel, int frame_len, int frame_shift, float preemph,
                         float log_floor, hipStream_t stream) {
-  if (B <= 0 || Tmax <= 0) return 0;
+  if (B <= 0) return 0;
   if (frame_len > NFFT || nmel > 128) return -2;
+  if (Tmax <= 0) {  // no frame of any utterance fits: nothing to launch, but out_len is an output and its readers (ea_specaugment)
+                    // use it as a loop bound — it holds 0, the number of rows each utterance has in the empty feature tensor
+    if (out_len && hipMemsetAsync(out_len, 0, (size_t)B * sizeof(int), stream) != hipSuccess) return -1;
+    return 0;
+  }
   const int fpb = 16;
   dim3 grid((Tmax + fpb - 1) / fpb, B);
   hipLaunchKernelGGL(fbank_kernel<TS>, grid, dim3(256), 0, stream, wav, offsets, window, (const float2*)twiddle, mel_start,

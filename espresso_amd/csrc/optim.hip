@@ -34,6 +34,9 @@ __global__ void clip_coef_kernel(const float* __restrict__ sumsq, float pre_scal
   const float norm = sqrtf(sumsq[0]) * pre_scale;
   float c = 1.f;
   if (max_norm > 0.f) c = fminf(1.f, max_norm / (norm + 1e-6f));
+  // a non-finite norm must reach adam_kernel as a non-finite coefficient (its skip test): max_norm / inf is 0 and fminf drops a
+  // NaN, either of which would turn the overflowed step into an ordinary update
+  if (!(fabsf(norm) < INFINITY)) c = norm;
   coef[0] = pre_scale * c;
   coef[1] = norm;
 }

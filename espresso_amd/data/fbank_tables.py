@@ -36,7 +36,10 @@ def build_mel_bank(num_bins=80, padded=512, sample_freq=16000.0, low_freq=20.0, 
 
 
 def build_tables(device, num_bins=80, frame_len=400, padded=512, sample_freq=16000.0):
-    win = torch.hann_window(frame_len, periodic=False, dtype=torch.float32).pow(0.85)
+    # Kaldi's own statement (feature-window.cc): the window in double, rounded to float once.  In fp32, 0.5 - 0.5 cos(x) cancels
+    # towards the frame's ends (up to 564 ulp at frame_len 400).
+    i = np.arange(frame_len, dtype=np.float64)
+    win = torch.from_numpy(((0.5 - 0.5 * np.cos(2 * math.pi * i / (frame_len - 1))) ** 0.85).astype(np.float32))
     k = np.arange(padded // 2, dtype=np.float64)
     tw = np.stack([np.cos(2 * math.pi * k / padded), -np.sin(2 * math.pi * k / padded)], axis=1).astype(np.float32)
     bank = build_mel_bank(num_bins, padded, sample_freq)

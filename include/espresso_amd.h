@@ -864,7 +864,11 @@ int ea_label_smoothed_ce(const void* logits, long ld, int logits_bf16, const int
  * wav: concatenated fp32 samples (int16 scale), offsets int64 [B+1]; feat fp32 [B][Tmax][nmel]
  * (rows >= n_frames(b) are written as 0); utt_sum fp32 [B] zeroed by caller (sum of features, for
  * the mean mask value); out_len int32 [B] = 1+(N-frame_len)/frame_shift.  window/twiddle/mel_* are
- * host-built tables (espresso_amd/data/fbank_tables.py).  Mask lists: int32 [B][n][2] = (start,width). */
+ * host-built tables (espresso_amd/data/fbank_tables.py).  Mask lists: int32 [B][n][2] = (start,width).
+ * Tmax below an utterance's frame count: rows >= Tmax are neither stored nor summed into utt_sum, out_len still holds
+ * the utterance's full count (not clamped: clamp it before it is used as a row bound).  Tmax <= 0: feat and utt_sum are
+ * untouched and out_len is set to 0.  B <= 0 returns 0, frame_len > 512 or nmel > 128 returns -2; no output is written.
+ * ea_specaugment clips nothing: lengths[b] <= Tmax and every mask inside [0, lengths[b]) x [0, nmel) are the caller's. */
 int ea_fbank_batch(const float* wav, const long* offsets, int B, const float* window, const float* twiddle,
                    const int* mel_start, const int* mel_len, const int* mel_woff, const float* mel_w,
                    const float* cmvn_mean, const float* cmvn_std, float* feat, float* utt_sum, int* out_len,
@@ -887,7 +891,11 @@ int ea_feature_stats(const float* feat, const int* lengths, double* acc, int B, 
 /* ------------------------------------------------------------------------------------------
  * Optimizer on flat fp32 buffers — fairseq/utils.py:347-397 (clip_grad_norm_),
  * fairseq/optim/adam.py:215-240.  coef[0] multiplies every gradient (pre_scale * clip), coef[1]
- * receives the (pre-scaled) gradient norm; both stay on the device. */
+ * receives the (pre-scaled) gradient norm; both stay on the device.  ea_grad_sumsq ADDS to out.
+ * A non-finite norm (sumsq inf or NaN, or a non-finite scale) gives a non-finite coef[0] as well.  ea_adam_step with a
+ * non-finite coef[0] skips the update: p, m, v keep their bits, p_bf16 (if given) is still written as bf16(p), and g is
+ * still zeroed when zero_grad is set (the overflowed gradient is discarded).  coef == NULL: the gradient is taken as is;
+ * max_norm <= 0: no clipping.  Weight decay is decoupled: p += p * (-weight_decay * lr) before the Adam update. */
 int ea_grad_sumsq(const float* g, long n, float* out, ea_stream_t stream);
 /* scale = pre_scale / denom_dev[0] (denom_dev: device fp32 scalar such as the all-reduced sample_size; may be NULL) */
 int ea_clip_coef(const float* sumsq, float pre_scale, const float* denom_dev, float max_norm, float* coef,
