@@ -16,6 +16,7 @@
 // and streaming exp(lprobs) once — no dense gradient-of-lprobs tensor, no global atomics.
 #include "common.h"
 #include "espresso_amd.h"
+#include "softmax_row.h"
 
 namespace {
 
@@ -27,27 +28,8 @@ __global__ __launch_bounds__(256) void log_softmax_kernel(const TIn* __restrict_
   __shared__ float sm[16];
   const long row = blockIdx.x;
   const TIn* x = in + row * ld_in;
-  float mx = -INFINITY;
-  for (int c = threadIdx.x; c < V; c += 256) {
-    float v;
-    if constexpr (sizeof(TIn) == 2) v = bf2f(x[c]); else v = x[c];
-    mx = fmaxf(mx, v);
-  }
-  mx = block_max(mx, sm);
-  float s = 0.f;
-  for (int c = threadIdx.x; c < V; c += 256) {
-    float v;
-    if constexpr (sizeof(TIn) == 2) v = bf2f(x[c]); else v = x[c];
-    s += expf(v - mx);
-  }
-  s = block_sum(s, sm);
-  const float lse = mx + logf(s);
-  float* o = out + row * (long)V;
-  for (int c = threadIdx.x; c < V; c += 256) {
-    float v;
-    if constexpr (sizeof(TIn) == 2) v = bf2f(x[c]); else v = x[c];
-    o[c] = v - lse;
-  }
+  const float lse = log_softmax_row_lse<TIn, false>(x, V, sm);  // softmax_row.h: shared with long_form.hip
+  log_softmax_row_write<TIn, false>(x, V, lse, out + row * (long)V);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1825,3 +1825,39 @@ def stream_glu_dwconv_bn_act(Y, w, mean_rstd, gamma, beta, carry, meta, B, chunk
 def stream_advance(frames, meta, B, chunk_size):
     check(_lib.lib().ea_stream_advance(_p(frames), _p(meta[0]), _p(meta[1]), B, chunk_size, frames.numel(), _stream()),
           "ea_stream_advance")
+
+
+LONGFORM_MAX_OVERLAP = 12288  # frames of one overlap that ea_longform_cuts holds in LDS
+
+
+def _longform_args(logits, counts, V):
+    assert logits.dim() == 3 and logits.is_contiguous() and logits.dtype in (torch.float32, torch.bfloat16)
+    Nw, Tw, ld = logits.shape
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == Nw and counts.device == logits.device
+    assert 1 <= V <= ld
+    return Nw, Tw, ld, int(logits.dtype == torch.bfloat16)
+
+
+def longform_cuts(logits, counts, V, Hf, blank, edge, guard):
+    """Long-form junction cuts (include/espresso_amd.h, "Long-form recognition").  logits [Nw][Tw][ld >= V] bf16 or fp32, counts
+    int32 [Nw] on the device -> (cuts int32 [Nw - 1], scores fp32 [Nw - 1])."""
+    Nw, Tw, ld, is_bf16 = _longform_args(logits, counts, V)
+    cuts = torch.empty(Nw - 1, dtype=torch.int32, device=logits.device)
+    scores = torch.empty(Nw - 1, dtype=torch.float32, device=logits.device)
+    check(_lib.lib().ea_longform_cuts(_p(logits), is_bf16, ld, _p(counts), Nw, Tw, V, Hf, blank, edge, guard, _p(cuts), _p(scores),
+                                      _stream()), "ea_longform_cuts")
+    return cuts, scores
+
+
+def longform_stitch(logits, counts, cuts, V, Hf, T, out=None):
+    """The stitched fp32 log-probs [T][V] of a recording (T = (Nw - 1) * Hf + the last window's frames, known to the caller):
+    row t is the log-softmax of frame t's row in the window that owns it under `cuts`.  `out` ([T][ldo >= V] fp32, rows
+    contiguous) is written in columns < V only."""
+    Nw, Tw, ld, is_bf16 = _longform_args(logits, counts, V)
+    assert Nw == 1 or (cuts.dtype == torch.int32 and cuts.is_contiguous() and cuts.numel() == Nw - 1)
+    if out is None:
+        out = torch.empty(T, V, dtype=torch.float32, device=logits.device)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == T and out.stride(1) == 1 and out.shape[1] >= V
+    check(_lib.lib().ea_longform_stitch(_p(logits), is_bf16, ld, _p(counts), _p(cuts) if Nw > 1 else None, Nw, Tw, V, Hf, T, _p(out),
+                                        out.stride(0), _stream()), "ea_longform_stitch")
+    return out

@@ -14,6 +14,10 @@ StreamingEncoder, as `speech_recognize --streaming` does, and a `K-<utt>` line g
 `K-utt<TAB>reported_s<TAB>start_s<TAB>end_s<TAB>confidence<TAB>keyword`, reported_s being the audio consumed when the hit was
 read, so the latency (hold after the hit's end, plus the piece) is visible.
 
+With `--long-form` every recording, of any length, goes through an offline model as overlapping windows whose logits are joined
+on the device into one log-prob matrix (tools/long_form.py; the window, overlap, edge and guard defaults are
+uncalibrated), and the offline scan runs over that: hits carry the recording's own times.
+
 Only encoder-only CTC models are taken: transducer and attention models are refused before anything is loaded.  The defaults
 0.5 and 500 ms are option defaults; their calibration on real speech is unmeasured."""
 import argparse
@@ -59,6 +63,9 @@ def get_parser():
                         "encoder) and print a K-<utt> line as soon as a hit is reported")
     p.add_argument("--stream-chunk-ms", type=int, default=None, help="--streaming: audio per piece (default 400)")
     p.add_argument("--streams", type=int, default=None, help="--streaming: concurrent utterances (default 16)")
+    from .tools.long_form import add_long_form_args
+
+    add_long_form_args(p)  # --long-form: recordings of any length through an offline CTC model, hits in global time
     return p
 
 
@@ -153,6 +160,9 @@ def spot_streaming(task, model, spotter, utt_ids, waves, seconds_per_frame, chun
 def main(argv=None):
     args = get_parser().parse_args(argv)
     chunk_ms, streams = check_args(args)
+    from .tools import long_form as LF
+
+    LF.check_long_form_args(args, tool="speech_kws")
     if args.model:  # refuse transducer and attention models before anything is loaded
         require_ctc(args.model)
     from .tasks.speech_recognition import SpeechRecognitionEspressoConfig, SpeechRecognitionEspressoTask
@@ -194,7 +204,15 @@ def main(argv=None):
                                 max_hits=args.max_hits)
 
     t0 = time.perf_counter()
-    if args.streaming:
+    if args.long_form:  # one recording at a time: its windows' stitched log-probs, then the offline scan
+        lf = LF.LongFormModel(model, LF.LongFormCTC(task, LF.plan_from_args(args, task.frontend, model), d.bos(), args.max_tokens,
+                                                    args.batch_size))
+        results = {}
+        for i in range(args.shard_id, len(utt_ids), args.num_shards):
+            out = lf(waves[i])
+            results[utt_ids[i]] = spotter.spot_lprobs(out["_lprobs"], out["src_lengths"][0])[0]
+        LF.log_worst(lf, sys.stderr)
+    elif args.streaming:
         mine = [i for i in range(len(utt_ids)) if i % args.num_shards == args.shard_id]
         results = spot_streaming(task, model, spotter, [utt_ids[i] for i in mine], [waves[i] for i in mine], spf, chunk_ms, streams)
     else:

@@ -9,7 +9,12 @@ Checkpoint management is fairseq's and stays out of this framework (SURVEY §2 o
 config mapping (`--model-config`, the `model:` block of the recipe YAML as JSON/YAML) and a `state_dict` file (`--path`:
 either a plain state_dict or a fairseq checkpoint dict whose `"model"` entry is the state_dict — reference checkpoints load
 because the parameter names are identical).  Audio comes from a Kaldi-style `wav.scp` (`utt_id path.wav`, 16-bit PCM read
-with the stdlib) and optional `text` (`utt_id tokens...`) files; the front-end (fbank + CMVN) runs on the GPU."""
+with the stdlib) and optional `text` (`utt_id tokens...`) files; the front-end (fbank + CMVN) runs on the GPU.
+
+`--long-form` (--search ctc / ctc_beam, an offline encoder-only CTC model) decodes every recording, of any length, as one
+utterance: overlapping windows are the batch of the offline forward, their logits are joined on the device into one log-prob
+matrix on the recording's own frame axis, and the search reads that (tools/long_form.py; the reference
+has no such path)."""
 import argparse
 import os
 import json
@@ -347,6 +352,9 @@ def get_parser():
                    help="--stream-endpoint: end every segment after this long; it sizes the per-stream search state (must be positive)")
     p.add_argument("--wer-output-filter", default=None, help="sed-style word filter applied before WER scoring")
     p.add_argument("--non-lang-syms", default=None, help="non-language symbols (one per line), ignored by WER / CER scoring")
+    from .tools.long_form import add_long_form_args
+
+    add_long_form_args(p)  # --long-form: recordings of any length through an offline CTC model (--search ctc / ctc_beam)
     return p
 
 
@@ -862,6 +870,9 @@ def main(argv=None):
     check_hotword_args(args)
     check_ngram_args(args)
     check_streaming_args(args)
+    from .tools import long_form as LF
+
+    LF.check_long_form_args(args)
     lm_mode = lm_fusion_mode(args)
     if args.search == "ctc_beam" and len(args.path.split(os.pathsep)) > 1:
         raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
@@ -881,6 +892,8 @@ def main(argv=None):
     paths = args.path.split(os.pathsep)  # `--path a.pt:b.pt` = an ensemble (fairseq utils.split_paths in speech_recognize.py:107)
     state = _load_file(paths[0])
     model_name, model_cfg = resolve_model_config(args.model, args.model_config, state)
+    if args.long_form:  # before the weights are loaded: an encoder-only CTC model
+        LF.require_ctc_model(model_name)
     autoregressive = args.search == "beam"
     # the criterion the checkpoint was trained with decides whether "<s>" is the blank (speech_recognition.py:324, 345-347)
     crit = {"beam": "label_smoothed_cross_entropy_v2", "ctc": "ctc_loss", "ctc_beam": "ctc_loss", "ctc_stream_beam": "ctc_loss"}.get(args.search, "transducer_loss")
@@ -951,7 +964,7 @@ def main(argv=None):
                 lm = TensorizedLookaheadLanguageModel(lm, task.target_dictionary, oov_penalty=args.oov_penalty,
                                                       open_vocab=not args.disable_open_vocab)
     gen = None  # (the streamed beam searches build their own decoders in recognize_streaming, which validates the same options)
-    if args.search not in ("transducer_stream_beam", "ctc_stream_beam"):
+    if args.search not in ("transducer_stream_beam", "ctc_stream_beam") and not args.long_form:
         gen = build_generator(args, members if len(members) > 1 else model, task.target_dictionary, lm, ngram, context_graph)
     scp = read_scp(args.wav_scp)
     utt_ids = list(scp.keys())
@@ -966,11 +979,20 @@ def main(argv=None):
 
     scorer = Scorer(task.target_dictionary, wer_output_filter=args.wer_output_filter)
     stream = (collate(b, utt_ids, waves, dev) for b in batches)
+    lf_model = None
+    if args.long_form:  # one recording at a time, its windows are the batch; the generator reads the stitched log-probs
+        lf_model = LF.LongFormModel(model, LF.LongFormCTC(task, LF.plan_from_args(args, task.frontend, model), task.target_dictionary.bos(),
+                                                          args.max_tokens, args.batch_size))
+        gen = build_generator(args, lf_model, task.target_dictionary, lm, ngram, context_graph)
+        batches = shard_batches([[i] for i in range(len(utt_ids))], args.num_shards, args.shard_id)
+        stream = ({"utt_ids": [utt_ids[i]], "num_samples": [len(waves[i])], "net_input": {"wave": waves[i]}} for (i,) in batches)
     ctm_hyps = {} if args.ctm else None
 
     from .tools.forced_aligner import frame_seconds
 
     def finish_ctm():
+        if lf_model is not None:
+            LF.log_worst(lf_model, sys.stderr)
         if ctm_hyps is not None:
             write_ctm(args.ctm, utt_ids, ctm_hyps, task.target_dictionary, args.ctm_unit,
                       frame_seconds(model, task.frontend.frame_shift / task.frontend.sample_rate))

@@ -1,0 +1,282 @@
+"""Long-form recognition for offline CTC models: a recording longer than the model was trained on is cut
+into overlapping windows on the encoder's frame grid, the existing offline encoder runs on batches of windows, and two kernels
+(csrc/long_form.hip) join the per-window logits on the device into one fp32 log-prob matrix on the recording's own frame axis.
+Everything downstream takes log-probs -- the greedy decoder, the prefix and lexicon beam searches, the keyword spotter -- and so
+works unchanged and in global time.  The reference has no long-form path.
+
+The plan (host, pure Python).  g = samples per encoder frame (frame shift x the sub-sampler's time stride; 640 for the recipes).
+Window W and overlap O are multiples of g, hop H = W - O; a recording of N samples gets Nw = max(1, ceil((N - O) / H)) windows,
+window n = samples [n * H, n * H + W), the last one running to the recording's end (its length lies in (O, W]).  With H a multiple
+of g, encoder frame j of window n is global frame n * Hf + j (Hf = H / g), a full window has W / g frames and
+(Nw - 1) * Hf + T_last is the recording's own frame count: `check_grid` verifies this arithmetic against the front-end and the
+model at hand and refuses what breaks it.
+
+The join.  At junction n the cut c in the overlap gives the frames < c to window n and the rest to window n + 1; it is put where
+both windows agree on blank for 2 * guard frames, `edge` frames off either end of the overlap (include/espresso_amd.h, "Long-form
+recognition").  The defaults of window, overlap, edge and guard are uncalibrated: no trained CTC model and no long corpus was at
+hand to measure WER with them."""
+import math
+import os
+from typing import List, Optional
+
+import torch
+
+from .. import kernels as K
+
+DEFAULT_WINDOW_S, DEFAULT_OVERLAP_S, DEFAULT_GUARD_FRAMES = 30.0, 6.0, 2
+UNCALIBRATED = "an option default, uncalibrated: no WER on real long recordings has been measured"
+
+
+class LongFormPlan:
+    """The windows of recordings: W, O, H in samples (multiples of g), Tw = W / g, Of = O / g, Hf = H / g in encoder frames."""
+
+    def __init__(self, g: int, window: int, overlap: int, edge_frames: Optional[int] = None, guard_frames: int = DEFAULT_GUARD_FRAMES):
+        if g < 1:
+            raise ValueError(f"long-form: {g} samples per encoder frame")
+        if window % g or overlap % g:
+            raise ValueError(f"long-form: window {window} and overlap {overlap} must be multiples of the {g} samples of an encoder frame")
+        if overlap < 2 * g:
+            raise ValueError(f"long-form: the overlap ({overlap} samples) must cover at least two encoder frames ({2 * g} samples)")
+        if 2 * overlap >= window:
+            raise ValueError(f"long-form: the overlap ({overlap} samples) must be less than half the window ({window} samples): a "
+                             "frame may lie in two windows, not in three")
+        self.g, self.W, self.O, self.H = g, window, overlap, window - overlap
+        self.Tw, self.Of, self.Hf = window // g, overlap // g, (window - overlap) // g
+        if self.Of > K.LONGFORM_MAX_OVERLAP:
+            raise ValueError(f"long-form: an overlap of {self.Of} encoder frames exceeds the {K.LONGFORM_MAX_OVERLAP} the cut kernel holds")
+        self.edge = self.Of // 4 if edge_frames is None else int(edge_frames)
+        self.guard = int(guard_frames)
+        if self.edge < 0 or self.guard < 0:
+            raise ValueError("long-form: edge and guard frames must not be negative")
+        if 2 * self.edge > self.Of:
+            raise ValueError(f"long-form: {self.edge} edge frames on either side leave no cut in an overlap of {self.Of} frames")
+
+    @classmethod
+    def from_seconds(cls, g, sample_rate, window_s=DEFAULT_WINDOW_S, overlap_s=DEFAULT_OVERLAP_S, edge_frames=None,
+                     guard_frames=DEFAULT_GUARD_FRAMES):
+        """Window and overlap in seconds, each rounded to a multiple of g."""
+        return cls(g, int(round(window_s * sample_rate / g)) * g, int(round(overlap_s * sample_rate / g)) * g, edge_frames, guard_frames)
+
+    def num_windows(self, n_samples: int) -> int:
+        return max(1, -(-(n_samples - self.O) // self.H))
+
+    def windows(self, n_samples: int) -> List[tuple]:
+        """(start, length) in samples of every window of a recording of n_samples."""
+        nw = self.num_windows(n_samples)
+        return [(n * self.H, self.W if n < nw - 1 else n_samples - n * self.H) for n in range(nw)]
+
+
+def samples_per_frame(frontend, model) -> int:
+    """g: the front-end's frame shift x the sub-sampler's total time stride."""
+    return int(frontend.frame_shift) * time_stride(model)
+
+
+def time_stride(model) -> int:
+    """The encoder's total time stride, read off `output_lengths`."""
+    probe = 1 << 12
+    out = int(model.output_lengths(probe))
+    if out < 1 or probe % out:
+        raise NotImplementedError(f"long-form: the encoder maps {probe} frames to {out}: no integer time stride")
+    return probe // out
+
+
+def check_grid(frontend, model, plan: LongFormPlan):
+    """Refuse, naming what breaks it, a front-end or model whose windows do not sit on the recording's frame grid."""
+    if getattr(frontend, "specaug", None) is not None and getattr(model, "training", False):
+        raise NotImplementedError("long-form: SpecAugment in training mode changes the features per utterance")
+    for name in ("dither", "utterance_cmvn", "per_utterance_norm"):
+        if getattr(frontend, name, 0):
+            raise NotImplementedError(f"long-form: the front-end's {name} makes a window's features differ from the recording's")
+    shift, flen = int(frontend.frame_shift), int(frontend.frame_len)
+    stride = time_stride(model)
+    if plan.g != shift * stride:
+        raise NotImplementedError(f"long-form: the plan's {plan.g} samples per encoder frame are not frame shift {shift} x stride {stride}")
+    enc = getattr(model, "encoder", model)
+    if getattr(getattr(enc, "cfg", None), "encoder", None) is not None and getattr(enc.cfg.encoder, "chunk_size", 0) > 0:
+        raise NotImplementedError("long-form runs offline encoders; a chunk-streaming encoder is decoded with --streaming --stream-endpoint")
+    pre = getattr(enc, "pre_encoder", None)
+    if pre is not None:
+        for ks in getattr(pre, "kernel_sizes", []):
+            ks = tuple(ks) if isinstance(ks, (list, tuple)) else (ks, ks)
+            if ks != (3, 3):
+                raise NotImplementedError(f"long-form: sub-sampler kernel size {ks} is not the recipes' 3x3; the frame grid is unverified for it")
+    # the arithmetic itself, on the functions as they stand
+    if plan.H % shift or frontend.num_frames(plan.H + flen) != plan.H // shift + 1:
+        raise NotImplementedError(f"long-form: a hop of {plan.H} samples is not a whole number of front-end frames (frame shift {shift})")
+    if int(model.output_lengths(frontend.num_frames(plan.W))) != plan.Tw:
+        raise NotImplementedError(f"long-form: a window of {plan.W} samples gives {int(model.output_lengths(frontend.num_frames(plan.W)))} "
+                                  f"encoder frames, not {plan.Tw} (frame length {flen}, frame shift {shift}, stride {stride})")
+    if (plan.H // shift) % stride:
+        raise NotImplementedError(f"long-form: a hop of {plan.H // shift} front-end frames is no multiple of the encoder's stride {stride}")
+    if flen > plan.O:
+        raise NotImplementedError(f"long-form: the overlap ({plan.O} samples) is shorter than one front-end frame ({flen})")
+
+
+def window_frames(frontend, model, plan: LongFormPlan, n_samples: int) -> List[int]:
+    """Encoder frames of every window of a recording (host arithmetic: `num_frames`, then `output_lengths`)."""
+    return [int(model.output_lengths(frontend.num_frames(ln))) for _, ln in plan.windows(n_samples)]
+
+
+class LongFormCTC:
+    """The front part of long-form recognition: `encode` turns one recording into stitched log-probs."""
+
+    def __init__(self, task, plan: LongFormPlan, blank: int, max_tokens: int = 15000, batch_size: int = 24):
+        self.task, self.plan, self.blank = task, plan, int(blank)
+        self.max_tokens, self.batch_size = max_tokens, batch_size
+        self._checked = None
+
+    @torch.no_grad()
+    def window_logits(self, model, wave):
+        """(logits [Nw][Tw][V] as the encoder wrote them (bf16, or fp32), counts: host list of frames per window).  The windows
+        go through the existing offline forward in length-sorted batches under the max_tokens / batch_size budget; one
+        recording's window logits stay on the device.  A recording of one window: Tw is that window's own frame count."""
+        from ..speech_recognize import collate, make_batches
+
+        if self._checked is not model:
+            check_grid(self.task.frontend, model, self.plan)
+            self._checked = model
+        dev = self.task.frontend.device
+        wins = self.plan.windows(len(wave))
+        counts = window_frames(self.task.frontend, model, self.plan, len(wave))
+        Nw = len(wins)
+        Tw = self.plan.Tw if Nw > 1 else counts[0]
+        pieces = [wave[a: a + ln] for a, ln in wins]
+        names = [str(n) for n in range(Nw)]
+        buf = None
+        for ids in make_batches(names, [ln for _, ln in wins], self.max_tokens, self.batch_size):
+            s = self.task.prepare_sample(collate(ids, names, pieces, dev), train=False)
+            out = model(**s["net_input"])
+            lg = out.get("_logits_bt")
+            if not lg:
+                raise NotImplementedError("long-form needs an encoder-only CTC model that returns its vocabulary logits")
+            B, Tp = out["encoder_padding_mask"][0].shape
+            logits = lg[0]
+            V = logits.shape[1]
+            if Tp > Tw or Tp != max(counts[i] for i in ids):
+                raise RuntimeError(f"long-form: a batch of windows has {Tp} encoder frames, the plan {max(counts[i] for i in ids)} (at most {Tw})")
+            if buf is None:
+                buf = torch.empty(Nw, max(Tw, 1), V, dtype=logits.dtype, device=logits.device)
+            src = logits.view(B, Tp, V) if logits.is_contiguous() else torch.as_strided(logits, (B, Tp, V), (Tp * logits.stride(0), logits.stride(0), 1))
+            buf[:, :Tp].index_copy_(0, torch.tensor(ids, dtype=torch.long, device=logits.device), src)
+        return buf, counts
+
+    @torch.no_grad()
+    def stitch(self, logits, counts: List[int]):
+        """logits [Nw][Tw][V], counts (host) -> (lprobs fp32 [1][T][V], in_len int32 [1], cuts int32 [Nw - 1], scores fp32
+        [Nw - 1]): the two kernels, once per recording."""
+        Nw, Tw, V = logits.shape
+        T = (Nw - 1) * self.plan.Hf + counts[-1]
+        cdev = torch.tensor(counts, dtype=torch.int32).to(logits.device)
+        cuts, scores = K.longform_cuts(logits, cdev, V, self.plan.Hf if Nw > 1 else max(Tw, 1), self.blank, self.plan.edge, self.plan.guard)
+        out = K.longform_stitch(logits, cdev, cuts, V, self.plan.Hf if Nw > 1 else max(Tw, 1), T)
+        return out.view(1, T, V), torch.tensor([T], dtype=torch.int32).to(logits.device), cuts, scores
+
+    @torch.no_grad()
+    def encode(self, model, wave):
+        """One recording (host samples) -> (lprobs fp32 [1][T][V], in_len, cuts, scores)."""
+        logits, counts = self.window_logits(model, wave)
+        return self.stitch(logits, counts)
+
+
+class LongFormModel:
+    """What the CTC decoders ask of a model -- a forward and `get_normalized_probs` -- answered from stitched log-probs, so that
+    `CTCDecoder`, `CTCPrefixBeamSearchDecoder` and `CTCLexiconBeamSearchDecoder` decode a recording as they decode an utterance.
+    A sample's net_input is {"wave": the recording's samples (host)}.  `junctions` collects (cuts, scores) per recording."""
+
+    def __init__(self, model, long_form: LongFormCTC):
+        self.model, self.long_form = model, long_form
+        self.junctions = []
+
+    def __call__(self, wave):
+        lprobs, in_len, cuts, scores = self.long_form.encode(self.model, wave)
+        self.junctions.append((cuts, scores))
+        return {"_lprobs": lprobs, "src_lengths": [in_len], "encoder_padding_mask": [torch.zeros(1, lprobs.shape[1], dtype=torch.bool,
+                                                                                                  device=lprobs.device)]}
+
+    def get_normalized_probs(self, net_output, log_probs, sample=None):
+        lp = net_output["_lprobs"]
+        return (lp if log_probs else lp.exp()).transpose(0, 1)  # T x 1 x V view of [1][T][V]
+
+    def output_lengths(self, in_lengths):
+        return self.model.output_lengths(in_lengths)
+
+    def cuda(self):
+        return self
+
+    def worst_score(self):
+        """The lowest junction score so far (None without junctions): a cut made through speech shows here."""
+        s = [sc for _, sc in self.junctions if sc.numel()]
+        return float(torch.cat(s).min()) if s else None
+
+
+def add_long_form_args(p):
+    p.add_argument("--long-form", action="store_true",
+                   help="decode every recording as overlapping windows of an offline encoder-only CTC model, joined on the device "
+                        "into one log-prob matrix on the recording's own frame axis (any length; times are global)")
+    p.add_argument("--long-form-window-s", type=float, default=None, help=f"--long-form: window in seconds (default {DEFAULT_WINDOW_S:g}; {UNCALIBRATED})")
+    p.add_argument("--long-form-overlap-s", type=float, default=None,
+                   help=f"--long-form: overlap of consecutive windows in seconds, less than half the window (default {DEFAULT_OVERLAP_S:g}; {UNCALIBRATED})")
+    p.add_argument("--long-form-edge-frames", type=int, default=None,
+                   help=f"--long-form: encoder frames at either end of an overlap where no cut is made (default: a quarter of the overlap; {UNCALIBRATED})")
+    p.add_argument("--long-form-guard-frames", type=int, default=None,
+                   help="--long-form: a cut is scored by the lowest blank log-prob either window gives within this many frames of it "
+                        f"(default {DEFAULT_GUARD_FRAMES}; {UNCALIBRATED})")
+
+
+def check_long_form_args(args, tool="speech_recognize"):
+    """Refused before anything is loaded: the options of --long-form without it, and --long-form with --streaming, with a search
+    that does not read CTC log-probs, with ensembles, alignments and --confidence."""
+    opts = (("--long-form-window-s", args.long_form_window_s), ("--long-form-overlap-s", args.long_form_overlap_s),
+            ("--long-form-edge-frames", args.long_form_edge_frames), ("--long-form-guard-frames", args.long_form_guard_frames))
+    if not args.long_form:
+        for opt, v in opts:
+            if v is not None:
+                raise ValueError(f"{opt} configures --long-form: give --long-form too")
+        return
+    if args.streaming:
+        raise NotImplementedError("--long-form windows an offline encoder: no --streaming with it (a chunk-streaming model decodes audio "
+                                  "of any length with --streaming --stream-endpoint)")
+    if tool == "speech_recognize":
+        if args.search not in ("ctc", "ctc_beam"):
+            raise NotImplementedError("--long-form joins CTC log-probs: it is implemented for --search ctc and --search ctc_beam, not "
+                                      f"--search {args.search} (transducer and encoder-decoder models merge token sequences, a different mechanism)")
+        if getattr(args, "confidence", False):
+            raise NotImplementedError("--long-form is not implemented with --confidence: the posterior kernel holds at most 1023 tokens "
+                                      "per hypothesis, fewer than a long recording's transcript")
+        if args.print_alignment is not None:
+            raise NotImplementedError("--long-form is not implemented with --print-alignment")
+        if len(args.path.split(os.pathsep)) > 1:
+            raise NotImplementedError("--long-form takes one model")
+    for opt, v in opts[:2]:
+        if v is not None and not v > 0:
+            raise ValueError(f"{opt} must be positive")
+
+
+def plan_from_args(args, frontend, model) -> LongFormPlan:
+    return LongFormPlan.from_seconds(
+        samples_per_frame(frontend, model), frontend.sample_rate,
+        DEFAULT_WINDOW_S if args.long_form_window_s is None else args.long_form_window_s,
+        DEFAULT_OVERLAP_S if args.long_form_overlap_s is None else args.long_form_overlap_s,
+        args.long_form_edge_frames, DEFAULT_GUARD_FRAMES if args.long_form_guard_frames is None else args.long_form_guard_frames)
+
+
+def require_ctc_model(model_name: str):
+    """--long-form reads CTC logits: transducer and encoder-decoder models are refused before anything is loaded."""
+    from ..speech_align import model_kind
+
+    try:
+        kind = model_kind(model_name)
+    except NotImplementedError:
+        kind = "attention"
+    if kind != "ctc":
+        raise NotImplementedError(f"--long-form is implemented for encoder-only CTC models, not for the {kind} model '{model_name}': "
+                                  "joining windows of a transducer or encoder-decoder model means merging token sequences by time")
+
+
+def log_worst(model: LongFormModel, file):
+    cuts = [c for c, _ in model.junctions if c.numel()]
+    if not cuts:
+        return
+    worst = model.worst_score()
+    print("| long-form: {} junctions, lowest cut score {:.3f} (log-prob of blank around the cut; near 0 = silence in both windows{})".format(
+        sum(c.numel() for c in cuts), worst, ", this low: a cut through speech" if worst < math.log(0.5) else ""), file=file)

@@ -1366,6 +1366,33 @@ int ea_ctc_kws_hits(void* state, const int* slots, int n, int flush, int clear, 
                     int* starts, int* ends, float* scores, int* counts, ea_stream_t stream);
 int ea_ctc_kws_host(const float* x_host, long ld, int T, int V, const int* kw_tokens, const int* kw_len, const float* kw_tau, int K,
                     int Lmax, int blank, int hold, int max_hits, int* starts, int* ends, float* scores, int* counts);
+
+/* ------------------------------------------------------------------------------------------
+ * Long-form recognition for offline CTC models (csrc/long_form.hip): the join of the logits of one recording's overlapping
+ * windows into one fp32 log-prob matrix on the recording's own frame axis.  The reference has no long-form path (its recognizer
+ * takes a recording as one utterance), so these two entry points replace nothing of it; what they spare is a host loop of
+ * slices, log-softmaxes and index copies per junction.
+ *
+ * logits: [Nw][Tw][ld >= V], bf16 (is_bf16 != 0) or fp32, as the encoder wrote them; counts int32 [Nw] (device): the frames of
+ * each window, in [0, Tw]; window n holds global frames n * Hf + [0, counts[n]), 1 <= Hf <= Tw.
+ * ea_longform_cuts: per junction n (windows n and n + 1, n < Nw - 1) the overlap is the global frames [lo, hi), lo = (n + 1) * Hf,
+ *   hi = min(n * Hf + counts[n], lo + counts[n + 1]).  b(j) = min over the two windows of the log-softmax of frame j at column
+ *   `blank` (the bits ea_log_softmax_* writes there).  A cut c gives the frames < c to window n and the frames >= c to window
+ *   n + 1; the candidates are lo + edge <= c <= hi - edge, score(c) = min of b(j) over j in [c - guard, c + guard) within [lo, hi),
+ *   or, that range being empty, b at the overlap frame nearest c (c, or hi - 1 for c == hi).  cuts[n] = the candidate with the
+ *   largest score, ties to the smallest |2c - (lo + hi)|, then to the smallest c; without candidates floor((lo + hi) / 2);
+ *   scores[n] = its score.  An empty overlap (hi <= lo) gives cuts[n] = lo, scores[n] = 0.  Nw == 1 launches nothing.
+ *   Tw - Hf <= 12288 (the b(j) of an overlap live in LDS).
+ * ea_longform_stitch: out fp32 [T][ldo >= V], T <= (Nw - 1) * Hf + Tw; row t = the log-softmax of frame t's row in the window
+ *   that owns it under `cuts` (window 0 before cuts[0], window n from cuts[n - 1] up to cuts[n], the last window after), bit for
+ *   bit what ea_log_softmax_* writes for that row; columns >= V of out are not written, rows of other windows are not read.
+ *   Needs Tw < 2 * Hf for Nw > 1 (a frame lies in at most two windows, so the cuts increase).  cuts may be NULL for Nw == 1.
+ *   A frame whose owner under `cuts` does not hold it is left unwritten.
+ * Bad arguments return -2 and launch nothing. */
+int ea_longform_cuts(const void* logits, int is_bf16, long ld, const int* counts, int Nw, int Tw, int V, int Hf, int blank, int edge,
+                     int guard, int* cuts, float* scores, ea_stream_t stream);
+int ea_longform_stitch(const void* logits, int is_bf16, long ld, const int* counts, const int* cuts, int Nw, int Tw, int V, int Hf,
+                       long T, float* out, long ldo, ea_stream_t stream);
 /* Joint network element-wise stages (espresso/models/transformer/speech_transformer_transducer_base.py:276-299):
  * Z[b][t][u] = relu(E[b][t] + D[b][u]) (bf16, E [B*T][J], D [B*U1][J], Z [B*T*U1][J], J % 8 == 0) and its backward
  * reductions dE[b][t] = sum_u dZ[b][t][u], dD[b][u] = sum_t dZ[b][t][u] (either output may be NULL). */
