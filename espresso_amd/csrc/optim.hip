@@ -28,10 +28,12 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
 }
 
 // coef[0] = pre_scale * min(1, max_norm / (norm + 1e-6)),  coef[1] = norm = sqrt(sumsq) * pre_scale
-__global__ void clip_coef_kernel(const float* __restrict__ sumsq, float pre_scale, const float* __restrict__ denom,
-                                 float max_norm, float* __restrict__ coef) {
+// clear: sumsq[0] = 0 afterwards (ea_clip_coef_clear: the accumulator is ready for the next step's ea_grad_sumsq without a fill)
+__global__ void clip_coef_kernel(float* __restrict__ sumsq, float pre_scale, const float* __restrict__ denom, float max_norm,
+                                 float* __restrict__ coef, int clear) {
   if (denom) pre_scale = pre_scale / denom[0];
   const float norm = sqrtf(sumsq[0]) * pre_scale;
+  if (clear) sumsq[0] = 0.f;
   float c = 1.f;
   if (max_norm > 0.f) c = fminf(1.f, max_norm / (norm + 1e-6f));
   // a non-finite norm must reach adam_kernel as a non-finite coefficient (its skip test): max_norm / inf is 0 and fminf drops a
@@ -106,19 +108,39 @@ extern "C" int ea_grad_sumsq(const float* g, long n, float* out /*zeroed by call
 }
 extern "C" int ea_clip_coef(const float* sumsq, float pre_scale, const float* denom_dev, float max_norm,
                             float* coef /*[2]*/, hipStream_t stream) {
-  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1), 0, stream, sumsq, pre_scale, denom_dev, max_norm, coef);
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1), 0, stream, const_cast<float*>(sumsq), pre_scale, denom_dev, max_norm,
+                     coef, 0);
   return EA_CHECK_LAUNCH();
 }
-extern "C" int ea_adam_step(float* p, float* g, float* m, float* v, void* p_bf16, long n, const float* coef,
-                            float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                            int zero_grad, hipStream_t stream) {
+extern "C" int ea_clip_coef_clear(float* sumsq, float pre_scale, const float* denom_dev, float max_norm, float* coef /*[2]*/,
+                                  hipStream_t stream) {
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1), 0, stream, sumsq, pre_scale, denom_dev, max_norm, coef, 1);
+  return EA_CHECK_LAUNCH();
+}
+// One kernel for both entry points: the grid-stride loop gives the same bits from any grid (an element is always the same lane of
+// the same float4), which two differently shaped kernels do not — the compiler contracts a * b + c into an fma per lane position.
+static int adam_launch(float* p, float* g, float* m, float* v, void* p_bf16, long n, const float* coef, float lr, float beta1,
+                       float beta2, float eps, float weight_decay, int step, int zero_grad, long max_blocks, hipStream_t stream) {
   if (n <= 0) return 0;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   const float step_size = (float)((double)lr * sqrt(bc2) / bc1);
   long blocks = (n + 1023) / 1024;
-  if (blocks > 4096) blocks = 4096;
+  if (blocks > max_blocks) blocks = max_blocks;
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n, coef, lr,
                      beta1, beta2, eps, weight_decay, step_size, zero_grad);
   return EA_CHECK_LAUNCH();
+}
+extern "C" int ea_adam_step(float* p, float* g, float* m, float* v, void* p_bf16, long n, const float* coef,
+                            float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                            int zero_grad, hipStream_t stream) {
+  return adam_launch(p, g, m, v, p_bf16, n, coef, lr, beta1, beta2, eps, weight_decay, step, zero_grad, 4096, stream);
+}
+// The same update from a persistent grid of at most max_blocks workgroups: the launch that runs on a side queue beside the next
+// step's first kernels must not fill the device (a sub-range of the buffers: offset the five pointers alike).
+extern "C" int ea_adam_step_capped(float* p, float* g, float* m, float* v, void* p_bf16, long n, const float* coef,
+                                   float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                   int zero_grad, int max_blocks, hipStream_t stream) {
+  if (max_blocks < 1) return n <= 0 ? 0 : -1;
+  return adam_launch(p, g, m, v, p_bf16, n, coef, lr, beta1, beta2, eps, weight_decay, step, zero_grad, max_blocks, stream);
 }

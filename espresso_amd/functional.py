@@ -813,7 +813,7 @@ class _ConvSubsample(torch.autograd.Function):
     params: flat list [w_1, b_1, g_1, beta_1, ..., w_L, b_L, g_L, beta_L]; bufs: [rm_1, rv_1, ...]."""
 
     @staticmethod
-    def forward(ctx, X, row_zero, strides, bufs, p_drop, training, bn_eps, bn_momentum, *params):
+    def forward(ctx, X, row_zero, strides, bufs, p_drop, training, bn_eps, bn_momentum, after_first_layer, *params):
         B, T, F = X.shape
         L = len(params) // 4
         saved = []
@@ -847,6 +847,8 @@ class _ConvSubsample(torch.autograd.Function):
             n = B * To * Fo
             mr = K.bn_finalize(stats, Co, n, bn_eps, bn_momentum, rm, rv) if training else K.bn_from_running(rm, rv, bn_eps)
             A = K.bn_act_fwd(Zi, mr, g, beta, "relu")
+            if i == 0 and after_first_layer is not None:
+                after_first_layer()  # (host callback between two launches: the encoder starts a deferred optimizer pass here)
             saved += [Zi, mr, col, w16, g, beta]
             cfgs.append((Tc, Fc, Cc, To, Fo, Co, sy, sx))
             Tc, Fc, Cc = To, Fo, Co
@@ -963,11 +965,14 @@ class _ConvSubsample(torch.autograd.Function):
                 grads[4 * i + 3] = dbeta
         cur.wait_stream(side)
         del keep
-        return (None,) * 8 + tuple(grads)
+        return (None,) * 9 + tuple(grads)
 
 
-def conv_subsample(X, row_zero, strides, params, bufs, p_drop=0.0, training=True, bn_eps=1e-5, bn_momentum=0.1):
-    return _ConvSubsample.apply(X, row_zero, tuple(strides), list(bufs), p_drop, training, bn_eps, bn_momentum, *params)
+def conv_subsample(X, row_zero, strides, params, bufs, p_drop=0.0, training=True, bn_eps=1e-5, bn_momentum=0.1,
+                   after_first_layer=None):
+    """`after_first_layer`: called on the host once the first layer (conv 1 + BatchNorm + ReLU) has been launched."""
+    return _ConvSubsample.apply(X, row_zero, tuple(strides), list(bufs), p_drop, training, bn_eps, bn_momentum, after_first_layer,
+                                *params)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -535,6 +535,21 @@ def adam_step(p, g, m, v, p_bf16, coef, lr, beta1, beta2, eps, weight_decay, ste
     )
 
 
+def clip_coef_clear(sumsq, pre_scale, max_norm, coef, denom_dev=None):
+    """clip_coef that leaves sumsq[0] = 0 for the next grad_sumsq."""
+    check(_lib.lib().ea_clip_coef_clear(_p(sumsq), pre_scale, _p(denom_dev), max_norm, _p(coef), _stream()), "ea_clip_coef_clear")
+    return coef
+
+
+def adam_step_capped(p, g, m, v, p_bf16, coef, lr, beta1, beta2, eps, weight_decay, step, max_blocks, stream, zero_grad=True):
+    """adam_step from at most `max_blocks` workgroups on `stream` (a torch stream; not the current one: the caller orders it)."""
+    check(
+        _lib.lib().ea_adam_step_capped(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), p.numel(), _p(coef), lr, beta1, beta2, eps,
+                                       weight_decay, step, int(zero_grad), int(max_blocks), ctypes.c_void_p(stream.cuda_stream)),
+        "ea_adam_step_capped",
+    )
+
+
 def ctc_greedy_decode(x, in_len, B, T, V, blank, pad, ld=None, want_align=True):
     """x: [B*T][V] fp32/bf16 log-probs (batch-major).  Returns tokens [B][T] (pad filled), lengths [B], scores [B], align [B][T]."""
     dev = x.device

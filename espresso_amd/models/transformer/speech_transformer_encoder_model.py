@@ -87,9 +87,23 @@ class SpeechTransformerEncoderBase(nn.Module):
             self.layer_norm = None
         self.transformer_context = speech_utils.eval_str_nested_list_or_tuple(cfg.encoder.transformer_context, type=int)
         self.num_updates = 0
+        # a deferred optimizer pass (optim.adam.PendingUpdate): started behind the sub-sampler's first layer — the front-end, conv 1
+        # and its BatchNorm + ReLU are HBM-bound like the pass itself, the gather convolutions that follow are not — and waited for
+        # in front of the first encoder layer
+        self.pending_update = None
+        if pre_encoder is not None:
+            pre_encoder.after_first_layer = self.start_pending_update
 
     def set_num_updates(self, num_updates):
         self.num_updates = num_updates
+
+    def start_pending_update(self):
+        if self.pending_update is not None:
+            self.pending_update.start()
+
+    def early_modules(self):
+        """The modules whose parameters `encode` reads before its first layer."""
+        return [self.pre_encoder, self.fc0, self.embed_positions, self.layernorm_embedding]
 
     def output_lengths(self, in_lengths):
         return in_lengths if self.pre_encoder is None else self.pre_encoder.output_lengths(in_lengths)
@@ -199,6 +213,11 @@ class SpeechTransformerEncoderBase(nn.Module):
             native = [l for i, l in enumerate(self.layers) if (keep is None or bool(keep[i])) and _native_conformer(l)]
             if native:  # transposed weight copies of the backward pass: refreshed off the compute stream, under this forward pass
                 wt_event = F.refresh_layer_transposes(native, B, Tp)
+        if self.pending_update is not None:
+            # the trainer left the optimizer pass over the layers' and fc_out's parameters running on the side stream, under the
+            # front-end and the sub-sampler above (Trainer.train_step): from here on this stream reads what it writes
+            self.pending_update.wait(torch.cuda.current_stream(x.device))
+            self.pending_update = None
         kept = [l for i, l in enumerate(self.layers) if keep is None or bool(keep[i])]
         if (not return_all_hiddens and x.is_cuda and all(_native_conformer(l) for l in kept) and F.conformer_stack_supported(kept, x)):
             # the whole layer loop as one C call per direction (same launches; host time at small batches: functional.py)
@@ -322,6 +341,22 @@ class SpeechTransformerEncoderModel(nn.Module):
     def set_num_updates(self, num_updates):
         self.num_updates = num_updates
         self.encoder.set_num_updates(num_updates)
+
+    def early_update_modules(self):
+        """Declares to the trainer that the optimizer pass over every OTHER module's parameters may still be running when the
+        next forward call starts (`defer_update`): the encoder waits for it by itself, in front of its first layer."""
+        return self.encoder.early_modules()
+
+    def defer_update(self, pending):
+        """`pending`: the optimizer pass outside `early_update_modules()` (optim.adam.PendingUpdate), or None."""
+        self.encoder.pending_update = pending
+
+    def state_dict(self, *args, **kwargs):
+        if self.encoder.pending_update is not None:  # (a held optimizer pass: the weights outside the early modules are a step behind)
+            dev = next(self.parameters()).device
+            self.encoder.pending_update.wait(torch.cuda.current_stream(dev))
+            self.encoder.pending_update = None
+        return super().state_dict(*args, **kwargs)
 
     def forward(self, src_tokens, src_lengths, **kwargs):
         return self.encoder(src_tokens, src_lengths, **kwargs)

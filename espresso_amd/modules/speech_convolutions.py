@@ -67,7 +67,7 @@ class ConvBNReLU(nn.Module):
             bufs += [bn.running_mean, bn.running_var]
         x = F.conv_subsample(src.contiguous().float(), row_zero, [self._stride2(s) for s in self.strides], params, bufs,
                              p_drop=p_drop, training=self.training, bn_eps=self.batchnorms[0].eps,
-                             bn_momentum=self.batchnorms[0].momentum)
+                             bn_momentum=self.batchnorms[0].momentum, after_first_layer=getattr(self, "after_first_layer", None))
         if self.training and not getattr(self, "_counters_managed", False):
             for bn in self.batchnorms:
                 bn.num_batches_tracked += 1

@@ -13,6 +13,7 @@ import torch
 from .. import kernels as K
 
 _ALIGN = 64  # elements; keeps every parameter 256-byte (fp32) / 128-byte (bf16) aligned
+_EARLY_MAX_SHARE = 0.25  # the early range's update stays on the critical path: above this share of the buffer the pass is not split
 
 
 class FlatParams:
@@ -62,7 +63,27 @@ class FlatParams:
             o = self.offsets[id(grp[0])]
             n = grp[0].numel()
             grp[0]._ea_fused_qkv = self.p16[o:o + 3 * n].view(3 * grp[0].shape[0], grp[0].shape[1])
+        declared = getattr(module, "early_update_modules", None)
+        self.early_range = self.range_of(declared()) if callable(declared) else None
         self.sync_bf16()
+
+    def range_of(self, modules, max_share=_EARLY_MAX_SHARE):
+        """(lo, hi): the smallest element range of the flat buffers that holds every parameter of `modules` — or None when
+        a parameter of another module lies inside it (the flat order is the fused QKV groups, then `parameters()` order: nothing
+        here assumes where a module's parameters ended up), when it is empty, or when it holds more than `max_share` of the buffer.
+        `early_range` is this range for the modules a model runs before its first encoder layer (`model.early_update_modules()`):
+        the only parameters the next step reads before that layer, hence all of the optimizer pass that cannot be deferred."""
+        inside = {id(p) for m in modules if m is not None for p in m.parameters() if id(p) in self.offsets}
+        if not inside:
+            return None
+        span = lambda p: (self.offsets[id(p)], self.offsets[id(p)] + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN)
+        lo = min(span(p)[0] for p in self.params if id(p) in inside)
+        hi = max(span(p)[1] for p in self.params if id(p) in inside)
+        if any(id(p) not in inside and span(p)[0] < hi and span(p)[1] > lo for p in self.params):
+            return None
+        if hi - lo > max_share * self.numel:
+            return None
+        return lo, hi
 
     def sync_bf16(self):
         """Refresh the bf16 shadow from the fp32 master (after init / checkpoint load).  The shadow only

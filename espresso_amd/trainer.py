@@ -27,25 +27,26 @@ def grad_norms_inconsistent(norms: torch.Tensor) -> torch.Tensor:
 
 class Trainer:
     def __init__(self, task, model, criterion, device, clip_norm=2.0, lr=5.0, warmup_steps=25000, adam_betas=(0.9, 0.98),
-                 adam_eps=1e-8, weight_decay=0.0, final_lr=1e-6, seed=1, bucket_mb=64.0, lr_scheduler=None):
-        """`lr_scheduler`: optional `(name, kwargs)` resolved through the registry (default: the headline recipe's `noam`)."""
+                 adam_eps=1e-8, weight_decay=0.0, final_lr=1e-6, seed=1, bucket_mb=64.0, lr_scheduler=None, defer_update=True):
+        """`lr_scheduler`: optional `(name, kwargs)` resolved through the registry (default: the headline recipe's `noam`).
+        `defer_update`: run most of the optimizer pass under the next step's sub-sampler when the model allows it (below)."""
         self.task, self.criterion, self.device = task, criterion, device
         self.model = model.to(device)
-        self.flat = FlatParams(self.model, device)
-        self.optimizer = FlatAdam(self.flat, lr=lr, betas=adam_betas, eps=adam_eps, weight_decay=weight_decay)
+        self._flat = FlatParams(self.model, device)
+        self._optimizer = FlatAdam(self._flat, lr=lr, betas=adam_betas, eps=adam_eps, weight_decay=weight_decay)
         if lr_scheduler is None:
-            self.lr_scheduler = NoamSchedule(self.optimizer, lr=lr, warmup_steps=warmup_steps,
+            self.lr_scheduler = NoamSchedule(self._optimizer, lr=lr, warmup_steps=warmup_steps,
                                              model_size=model.cfg.encoder.embed_dim, final_lr=final_lr)
         else:
             from . import registry
             from .optim import lr_schedulers  # noqa: F401  (registers tri_stage / polynomial_decay_v2 / reduce_lr_on_plateau_v2)
 
             name, kw = lr_scheduler
-            self.lr_scheduler = registry.LR_SCHEDULER_REGISTRY[name](self.optimizer, lr=lr, **kw)
+            self.lr_scheduler = registry.LR_SCHEDULER_REGISTRY[name](self._optimizer, lr=lr, **kw)
         self.cfg = None
         self._optim_history = []
         self.world_size = dist.get_world_size() if dist.is_initialized() else 1
-        self.ddp = OverlappedDistributedDataParallel(self.model, self.flat, bucket_mb=bucket_mb)
+        self.ddp = OverlappedDistributedDataParallel(self.model, self._flat, bucket_mb=bucket_mb)
         self.clip_norm = clip_norm
         self.seed = seed
         self.num_updates = 0
@@ -55,10 +56,41 @@ class Trainer:
         self.last_coef = None
         self.ooms = 0  # updates skipped after an out-of-memory error (fairseq/trainer.py:797,850)
         self._train_mode_checked = False
+        # defer_update: the optimizer pass over everything the model does not read before its first encoder layer (98 % of the
+        # Conformer-CTC model) is HELD at the end of train_step and started by the model's next forward pass on the Python-side
+        # stream, behind the sub-sampler's first layer, so that it runs beside the MFMA-bound gather convolutions; the model waits
+        # for it in front of its first encoder layer (model.defer_update).  Until then the buffers outside the early range hold the
+        # previous step's values: every other reader goes through flush_update() — the methods below, and the `flat` /
+        # `optimizer` attributes themselves.  A model that does not declare its early modules, or a CPU run, keeps the single launch.
+        self._split_update = (bool(defer_update) and torch.device(device).type == "cuda" and self._flat.early_range is not None
+                              and hasattr(self.model, "defer_update"))
+        self._pending_update = None
+
+    @property
+    def flat(self):
+        """The flat parameter / gradient buffers, complete: reading this attribute (or `optimizer`) finishes a deferred update."""
+        self.flush_update()
+        return self._flat
+
+    @property
+    def optimizer(self):
+        self.flush_update()
+        return self._optimizer
+
+    def flush_update(self):
+        """The compute stream waits for a deferred optimizer pass (no-op when none is pending).  Called before anything but the
+        model's own training forward touches parameters, gradients or optimizer state."""
+        pending, self._pending_update = self._pending_update, None
+        if pending is not None:
+            pending.wait(torch.cuda.current_stream(self._flat.p32.device))
+            if hasattr(self.model, "defer_update"):
+                self.model.defer_update(None)
 
     def train_step(self, samples):
         """One optimizer update over a list of micro-batches (update_freq = len(samples))."""
         F.set_dropout_seed(self.seed + self.num_updates)  # trainer.py:782 _set_seed
+        if not self._split_update:
+            self.flush_update()
         if not self.model.training or not self._train_mode_checked:
             # nn.Module.train() walks every sub-module (2 300 of them: 1.1 ms of host time per update); once the whole tree is
             # in training mode the root flag tells (eval() / train() always set the tree as a whole)
@@ -104,7 +136,12 @@ class Trainer:
                 self._gnorm_mismatch += grad_norms_inconsistent(self._stats[4:])
         self.ddp.all_reduce_grads()
         F.end_step()
-        self.last_coef = self.optimizer.clip_and_step(pre_scale=1.0, max_norm=self.clip_norm, denom_dev=self._stats[0:1])
+        if self._split_update:
+            self.last_coef, self._pending_update = self._optimizer.clip_and_step_split(
+                F._side_stream(self._flat.p32.device), pre_scale=1.0, max_norm=self.clip_norm, denom_dev=self._stats[0:1], hold=True)
+            self.model.defer_update(self._pending_update)
+        else:
+            self.last_coef = self._optimizer.clip_and_step(pre_scale=1.0, max_norm=self.clip_norm, denom_dev=self._stats[0:1])
         self.num_updates += 1
         if hasattr(self.model, "set_num_updates"):
             self.model.set_num_updates(self.num_updates)
@@ -133,7 +170,8 @@ class Trainer:
                 b.saved_busy = False
             m.__dict__.pop("_ea_chain_in", None)  # (a chained layer call whose successor never ran: drop its token and the tensors it holds)
             m.__dict__.pop("_ea_wt_fresh", None)
-        self.flat.zero_grad()
+        self.flush_update()
+        self._flat.zero_grad()
         self._stats.zero_()
         if self._stats.is_cuda:
             torch.cuda.synchronize(self._stats.device)
@@ -154,6 +192,7 @@ class Trainer:
         batch shapes that will be seen: one forward + backward over each given sample with gradient reduction disabled,
         gradients and BatchNorm statistics restored afterwards; no optimizer update.  Called once at start-up (the reference's
         trainer does the same for the CUDA caching allocator with its dummy-batch / OOM-recovery logic, trainer.py:803-855)."""
+        self.flush_update()
         bn = {n: b.clone() for n, b in self.model.named_buffers()}
         self.model.train()
         with self.ddp.no_sync():
@@ -162,7 +201,7 @@ class Trainer:
                 loss, _, _ = self.criterion(self.ddp, sample)
                 with F.accumulating_backward():
                     loss.backward()
-        self.flat.zero_grad()
+        self._flat.zero_grad()
         with torch.no_grad():
             for n, b in self.model.named_buffers():
                 b.copy_(bn[n])
@@ -170,6 +209,7 @@ class Trainer:
             torch.cuda.synchronize()
 
     def valid_step(self, sample):
+        self.flush_update()
         return self.task.valid_step(sample, self.model, self.criterion)
 
     # ---- configuration, learning-rate bookkeeping, checkpoints (fairseq/trainer.py:387-640, checkpoint_utils.py) ----
@@ -198,7 +238,7 @@ class Trainer:
         return t
 
     def get_lr(self):
-        return self.optimizer.get_lr()
+        return self._optimizer.get_lr()
 
     def lr_step_begin_epoch(self, epoch):
         if hasattr(self.lr_scheduler, "step_begin_epoch"):
@@ -214,7 +254,8 @@ class Trainer:
     def _optimizer_state(self):
         """torch.optim.Adam layout over `model.parameters()` order — what fairseq's FairseqAdam writes as
         `last_optimizer_state` (fairseq/optim/adam.py:159-240), so either side can resume the other's checkpoint."""
-        f, o = self.flat, self.optimizer
+        self.flush_update()
+        f, o = self._flat, self._optimizer
         state, ids = {}, []
         for i, p in enumerate(q for q in self.model.parameters() if q.requires_grad):
             off, n = f.offsets[id(p)], p.numel()
@@ -225,7 +266,8 @@ class Trainer:
         return {"state": state, "param_groups": [group]}
 
     def _load_optimizer_state(self, sd):
-        f, o = self.flat, self.optimizer
+        self.flush_update()
+        f, o = self._flat, self._optimizer
         params = [q for q in self.model.parameters() if q.requires_grad]
         if len(sd["state"]) not in (0, len(params)):
             raise ValueError(f"optimizer state holds {len(sd['state'])} parameters, the model has {len(params)}")
@@ -242,6 +284,7 @@ class Trainer:
 
     def state_dict(self, extra_state=None):
         """Checkpoint dictionary with the reference's top-level keys (fairseq/trainer.py:387-431)."""
+        self.flush_update()
         sched = self.lr_scheduler.state_dict() if hasattr(self.lr_scheduler, "state_dict") else {}
         extra = {"previous_training_time": 0.0}
         extra.update(extra_state or {})
@@ -252,7 +295,7 @@ class Trainer:
             "model": {k: v.detach().clone().cpu() for k, v in self.model.state_dict().items()},
             "criterion": None,
             "optimizer_history": self._optim_history + [{
-                "criterion_name": type(self.criterion).__name__, "optimizer_name": type(self.optimizer).__name__,
+                "criterion_name": type(self.criterion).__name__, "optimizer_name": type(self._optimizer).__name__,
                 "lr_scheduler_state": sched, "num_updates": self.num_updates}],
             "task_state": {},
             "extra_state": extra,
@@ -265,6 +308,7 @@ class Trainer:
         """Rank 0 writes (data-parallel replicas hold identical state); atomically, like checkpoint_utils.torch_persistent_save."""
         import os
 
+        self.flush_update()
         if dist.is_initialized() and dist.get_rank() != 0:
             return
         tmp = filename + ".tmp"
@@ -276,6 +320,7 @@ class Trainer:
         does not exist.  The bf16 shadow copies of the weights are refreshed from the restored fp32 masters."""
         import os
 
+        self.flush_update()
         if not os.path.exists(filename):
             return None
         state = torch.load(filename, map_location="cpu", weights_only=False)
@@ -290,7 +335,7 @@ class Trainer:
                 raise RuntimeError(f"checkpoint does not match the model: missing {missing[:5]}, unexpected {unexpected[:5]}")
             for k, v in own.items():
                 v.copy_(sd[k])
-        self.flat.sync_bf16()
+        self._flat.sync_bf16()
         hist = state.get("optimizer_history") or []
         self._optim_history = hist[:-1]
         last = hist[-1] if hist else None

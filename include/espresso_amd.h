@@ -900,9 +900,19 @@ int ea_grad_sumsq(const float* g, long n, float* out, ea_stream_t stream);
 /* scale = pre_scale / denom_dev[0] (denom_dev: device fp32 scalar such as the all-reduced sample_size; may be NULL) */
 int ea_clip_coef(const float* sumsq, float pre_scale, const float* denom_dev, float max_norm, float* coef,
                  ea_stream_t stream);
+/* ea_clip_coef, and sumsq[0] = 0 afterwards: the accumulator is ready for the next ea_grad_sumsq without a fill launch */
+int ea_clip_coef_clear(float* sumsq, float pre_scale, const float* denom_dev, float max_norm, float* coef,
+                       ea_stream_t stream);
 int ea_adam_step(float* p, float* g, float* m, float* v, void* p_bf16, long n, const float* coef, float lr,
                  float beta1, float beta2, float eps, float weight_decay, int step, int zero_grad,
                  ea_stream_t stream);
+/* ea_adam_step from a persistent grid of at most max_blocks (>= 1) workgroups, for a launch that shares the device with
+ * another queue's kernels: same arguments, same kernel, bit-identical p, g, m, v and p_bf16.  A sub-range of the flat
+ * buffers is addressed by offsetting the five pointers alike (by a multiple of 4 elements: 16-byte loads, and the bits
+ * of an element depend on its lane of the float4). */
+int ea_adam_step_capped(float* p, float* g, float* m, float* v, void* p_bf16, long n, const float* coef, float lr,
+                        float beta1, float beta2, float eps, float weight_decay, int step, int zero_grad,
+                        int max_blocks, ea_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Native layer runtime (csrc/engine.hip): a whole Conformer encoder layer per call —

@@ -1,5 +1,5 @@
 """GPU idle-gap analysis of a rocprofv3 kernel trace (rocpd sqlite): busy time vs wall per training step (steps are
-delimited by the adam kernel), histogram of the idle gaps and the largest ones.  Usage: gap_analysis.py <db> [nsteps]"""
+delimited by the gradient-norm kernel), histogram of the idle gaps and the largest ones.  Usage: gap_analysis.py <db> [nsteps]"""
 import sqlite3, sys
 import numpy as np
 
@@ -7,9 +7,10 @@ db = sys.argv[1]
 nsteps = int(sys.argv[2]) if len(sys.argv) > 2 else 6
 c = sqlite3.connect(db)
 rows = c.execute("select start, end, name from kernels order by start").fetchall()
+step_ends = [r for r in rows if "sumsq_kernel" in r[2]]  # one launch per step (Adam is up to three, on two queues)
 adam = [r for r in rows if "adam_kernel" in r[2]]
-if len(adam) > nsteps:
-    t0, t1 = adam[-nsteps - 1][1], adam[-1][1]
+if len(step_ends) > nsteps:
+    t0, t1 = step_ends[-nsteps - 1][1], step_ends[-1][1]
 else:  # not a training trace (e.g. the decode block): the whole trace after the first tenth (start-up) as ONE "step"
     nsteps = 1
     t0, t1 = rows[len(rows) // 10][0], rows[-1][1]

@@ -1,7 +1,7 @@
 """Per-queue view of a rocprofv3 kernel trace (rocpd sqlite) of the training step: for each HIP stream (hardware queue) the busy
 time per step, and for the busiest queue (the main stream) its idle gaps split by whether another queue was busy during the gap
 (= the main stream waited for side-stream work or for a cross-stream event) or the whole device was idle (= host / launch latency).
-Steps are delimited by the adam kernel.   Usage: stream_analysis.py <db> [nsteps]"""
+Steps are delimited by the gradient-norm kernel (one launch per step; Adam is up to three, on two queues).   Usage: stream_analysis.py <db> [nsteps]"""
 import sqlite3
 import sys
 
@@ -14,7 +14,7 @@ print("kernels view columns:", cols)
 if qcol is None:
     sys.exit("no queue / stream column in this trace")
 rows = c.execute(f"select start, end, name, {qcol} from kernels order by start").fetchall()
-adam = [r for r in rows if "adam_kernel" in r[2]]
+adam = [r for r in rows if "sumsq_kernel" in r[2]]  # (the step's delimiter)
 t0, t1 = adam[-nsteps - 1][1], adam[-1][1]
 sel = [r for r in rows if r[0] >= t0 and r[1] <= t1]
 queues = {}
