@@ -1279,6 +1279,43 @@ def ctc_viterbi_align(x, targets, in_len, tgt_len, B, T, V, blank, ld=None):
     return tok_start, tok_end, frame_label, score
 
 
+def ctc_viterbi_long_tile():
+    """(frames, states) of one tile of ea_ctc_viterbi_long_align (compile-time constants of csrc/align_long.hip)."""
+    frames, states = ctypes.c_int(0), ctypes.c_int(0)
+    check(_lib.lib().ea_ctc_viterbi_long_tile(ctypes.byref(frames), ctypes.byref(states)), "ea_ctc_viterbi_long_tile")
+    return frames.value, states.value
+
+
+def ctc_viterbi_align_long(x, targets, T, V, blank, ld=None):
+    """Forced alignment of ONE sequence of any length: targets int32 [U] to x [T][V] fp32/bf16 log-probs (row pitch ld), tiled
+    over the device (ea_ctc_viterbi_long_align).  Returns (tok_start int32 [U], tok_end int32 [U], frame_label int32 [T], frame_lp
+    fp32 [T], score fp32 [1]), all on the device.  The backpointers take 2 bits per frame and state; a workspace larger than the
+    device's free memory is refused with a ValueError (there is no banded or pruned search)."""
+    if ld is None:
+        ld = x.stride(0) if T > 1 else V  # (the strides of a tensor of no or one row say nothing)
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 2 and x.shape[0] == T and x.shape[1] == V
+    assert T == 0 or x.stride(-1) == 1
+    assert targets.dtype == torch.int32 and targets.is_contiguous() and targets.dim() == 1
+    U = targets.numel()
+    dev = x.device
+    need = int(_lib.lib().ea_ctc_viterbi_long_workspace_bytes(T, U))
+    free = int(torch.cuda.mem_get_info(dev)[0])
+    if need > free:
+        raise ValueError(f"long-form alignment of T = {T} frames to U = {U} tokens needs a workspace of {need} bytes, the device has "
+                         f"{free} bytes free (2 bits per frame and state; there is no banded search)")
+    ws = torch.empty(max(1, need), dtype=torch.uint8, device=dev)
+    tok_start = torch.empty(U, dtype=torch.int32, device=dev)
+    tok_end = torch.empty(U, dtype=torch.int32, device=dev)
+    frame_label = torch.empty(T, dtype=torch.int32, device=dev)
+    frame_lp = torch.empty(T, dtype=torch.float32, device=dev)
+    score = torch.empty(1, dtype=torch.float32, device=dev)
+    check(_lib.lib().ea_ctc_viterbi_long_align(_p(x), ld, int(x.dtype == torch.bfloat16), _p(targets) if U else None, _p(ws),
+                                               _p(tok_start) if U else None, _p(tok_end) if U else None,
+                                               _p(frame_label) if T else None, _p(frame_lp) if T else None, _p(score), T, V, U, blank,
+                                               _stream()), "ea_ctc_viterbi_long_align")
+    return tok_start, tok_end, frame_label, frame_lp, score
+
+
 def rnnt_viterbi_align(lpb, lpy, logit_lengths, target_lengths):
     """Forced alignment over a transducer lattice lpb / lpy fp32 [B][T][U1] (ea_rnnt_scan's meaning).  Returns (emit_frame int32
     [B][U1 - 1], score fp32 [B]) on the device."""

@@ -8,7 +8,14 @@ space-separated tokens).  The model kind decides the aligner: an encoder-only CT
 frame = the front-end's frame shift x the model's sub-sampling factor.  `--scores` gets one line per utterance (id, encoder
 frames, tokens, Viterbi log-prob, log-prob per frame); utterances whose transcript cannot be aligned (too few frames) are
 marked `infeasible` there and left out of the CTM.  With `--confidence` the last CTM column is the acoustic model's posterior of
-the unit (tools/token_posteriors.py) instead of 1.00."""
+the unit (tools/token_posteriors.py) instead of 1.00.
+
+With `--long-form` every `wav.scp` entry is one recording of any length and its `--text` line the whole transcript: the recording
+goes through an offline CTC model as overlapping windows joined on the device (tools/long_form.py) and the
+transcript is aligned to all of it by the tiled Viterbi kernel (csrc/align_long.hip); the CTM carries times on
+the recording's own axis.  `--segments-dir` then cuts every recording at its silences into utterance-sized segments (`segments`,
+`text`, `scores`: Kaldi-style data for training; a segment whose text does not match its audio shows a low mean log-prob per
+frame in `scores`).  The segment defaults are uncalibrated."""
 import argparse
 import math
 import os
@@ -19,6 +26,8 @@ from typing import Dict, List
 import torch
 
 from .speech_recognize import _load_file, collate, load_member, make_batches, read_scp, read_wav, resolve_model_config, shard_batches
+
+DEFAULT_SEGMENT_MAX_S, DEFAULT_SEGMENT_MIN_SILENCE_S = 20.0, 0.3  # option defaults, uncalibrated
 
 
 def get_parser():
@@ -46,7 +55,43 @@ def get_parser():
     p.add_argument("--confidence", action="store_true",
                    help="the CTM's last column carries the model's posterior of the unit given the audio and the transcript before it "
                         "(tools/token_posteriors.py; a word: the product over its tokens) instead of 1.00: transcript verification")
+    from .tools.long_form import UNCALIBRATED, add_long_form_args
+
+    add_long_form_args(p)  # --long-form: one recording of any length per wav.scp entry, aligned to its whole transcript
+    p.add_argument("--segments-dir", default=None,
+                   help="--long-form: cut every aligned recording at its silences into segments and write `segments` (<rec>_<k> <rec> "
+                        "start_s end_s), `text` and `scores` (<rec>_<k> frames words mean-log-prob-per-frame [overlong]) there")
+    p.add_argument("--segment-max-s", type=float, default=None,
+                   help=f"--segments-dir: split segments longer than this many seconds (default {DEFAULT_SEGMENT_MAX_S:g}; {UNCALIBRATED})")
+    p.add_argument("--segment-min-silence-s", type=float, default=None,
+                   help="--segments-dir: split only at gaps between words of at least this many seconds "
+                        f"(default {DEFAULT_SEGMENT_MIN_SILENCE_S:g}; {UNCALIBRATED})")
     return p
+
+
+def check_args(args):
+    """Refused before anything is loaded: the long-form and segment options without --long-form, --long-form --confidence."""
+    from .tools.long_form import check_long_form_args
+
+    check_long_form_args(args, tool="speech_align")
+    opts = (("--segments-dir", args.segments_dir), ("--segment-max-s", args.segment_max_s),
+            ("--segment-min-silence-s", args.segment_min_silence_s))
+    if not args.long_form:
+        for opt, v in opts:
+            if v is not None:
+                raise ValueError(f"{opt} cuts a --long-form alignment into segments: give --long-form too")
+        return
+    if args.segments_dir is None:
+        for opt, v in opts[1:]:
+            if v is not None:
+                raise ValueError(f"{opt} configures --segments-dir: give --segments-dir too")
+    if args.confidence:
+        raise NotImplementedError("--long-form is not implemented with --confidence: the posterior kernel holds at most 1023 tokens "
+                                  "per transcript, fewer than a long recording's")
+    if args.segment_max_s is not None and not args.segment_max_s > 0:
+        raise ValueError("--segment-max-s must be positive")
+    if args.segment_min_silence_s is not None and args.segment_min_silence_s < 0:
+        raise ValueError("--segment-min-silence-s must not be negative")
 
 
 def model_kind(name: str) -> str:
@@ -84,16 +129,43 @@ def tokenize(dictionary, text: str, blank: int) -> List[int]:
     return ids
 
 
+def write_segments(out_dir, aligned, dictionary, spf, max_frames, min_gap_frames):
+    """`segments`, `text` and `scores` of the aligned recordings [(id, result of LongFormCTCAligner.align)] under out_dir: every
+    recording cut by `cut_segments` on its word spans; a segment's score is the mean of frame_lp over its frames."""
+    from .tools.forced_aligner import cut_segments, utterance_units
+
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "segments"), "w", encoding="utf-8") as f_seg, \
+            open(os.path.join(out_dir, "text"), "w", encoding="utf-8") as f_text, \
+            open(os.path.join(out_dir, "scores"), "w", encoding="utf-8") as f_sc:
+        for rec, r in aligned:
+            words = utterance_units(r, dictionary, "word")
+            for k, (a, b, s, e, overlong) in enumerate(cut_segments(words, r["frames"], max_frames, min_gap_frames)):
+                name = "{}_{:04d}".format(rec, k)
+                mean = float(r["frame_lp"][s:e].mean()) if e > s else 0.0
+                print("{} {} {:.3f} {:.3f}".format(name, rec, s * spf, e * spf), file=f_seg)
+                print("{} {}".format(name, " ".join(w for w, _, _ in words[a:b])), file=f_text)
+                print("{} {} {} {:.4f}{}".format(name, e - s, b - a, mean, " overlong" if overlong else ""), file=f_sc)
+
+
 def main(argv=None):
     args = get_parser().parse_args(argv)
-    if args.model:  # refuse attention models before anything is loaded
+    check_args(args)
+    from .tools import long_form as LF
+
+    if args.model:  # refuse attention models (--long-form: everything but CTC models) before anything is loaded
+        if args.long_form:
+            LF.require_ctc_model(args.model)
         model_kind(args.model)
     from .tasks.speech_recognition import SpeechRecognitionEspressoConfig, SpeechRecognitionEspressoTask
-    from .tools.forced_aligner import CTCForcedAligner, TransducerForcedAligner, ctm_lines, frame_seconds, utterance_units
+    from .tools.forced_aligner import (CTCForcedAligner, LongFormCTCAligner, TransducerForcedAligner, ctm_lines, frame_seconds,
+                                       utterance_units)
     from .tools.token_posteriors import unit_confidences
 
     state = _load_file(args.path)
     model_name, model_cfg = resolve_model_config(args.model, args.model_config, state)
+    if args.long_form:
+        LF.require_ctc_model(model_name)
     kind = model_kind(model_name)
     dev = torch.device(args.device or "cuda:{}".format(int(os.environ.get("LOCAL_RANK", "0"))))
     if dev.type == "cuda":
@@ -106,7 +178,10 @@ def main(argv=None):
         sentencepiece_model=args.sentencepiece_model))
     d = task.target_dictionary
     model = load_member(state, model_name, model_cfg, task, dev)
-    aligner = (CTCForcedAligner if kind == "ctc" else TransducerForcedAligner)([model], d, token_posteriors=args.confidence)
+    aligner = None
+    if not args.long_form:
+        aligner = (CTCForcedAligner if kind == "ctc" else TransducerForcedAligner)([model], d, token_posteriors=args.confidence)
+    blank = d.bos() if aligner is None else aligner.blank
 
     scp = read_scp(args.wav_scp)
     texts = read_text(args.text)
@@ -114,14 +189,27 @@ def main(argv=None):
     missing = [u for u in utt_ids if u not in texts]
     if missing:
         raise ValueError(f"--text has no transcript for {len(missing)} utterance(s), e.g. {missing[0]}")
-    targets = {u: tokenize(d, texts[u], aligner.blank) for u in utt_ids}
+    targets = {u: tokenize(d, texts[u], blank) for u in utt_ids}
     waves = [read_wav(scp[u]) for u in utt_ids]
     task.build_frontend(dev)
     spf = frame_seconds(model, task.frontend.frame_shift / task.frontend.sample_rate)
-    batches = shard_batches(make_batches(utt_ids, [len(w) for w in waves], args.max_tokens, args.batch_size), args.num_shards,
-                            args.shard_id)
-
     results, t_align, audio_s = {}, 0.0, 0.0
+    if args.long_form:  # one recording at a time: its windows' stitched log-probs, then the tiled Viterbi search
+        aligner = LongFormCTCAligner(task, model, LF.plan_from_args(args, task.frontend, model), d, max_tokens=args.max_tokens,
+                                     batch_size=args.batch_size)
+        junctions = LF.LongFormModel(model, aligner.long_form)  # (for `log_worst`: the cuts of every recording)
+        for i in range(args.shard_id, len(utt_ids), args.num_shards):
+            t0 = time.perf_counter()
+            r = aligner.align(waves[i], targets[utt_ids[i]])  # (one host copy per recording)
+            t_align += time.perf_counter() - t0
+            audio_s += len(waves[i]) / float(task.frontend.sample_rate)
+            results[utt_ids[i]] = r
+            junctions.junctions.append((torch.from_numpy(r["cuts"]), torch.from_numpy(r["cut_scores"])))
+        LF.log_worst(junctions, sys.stderr)
+        batches = []
+    else:
+        batches = shard_batches(make_batches(utt_ids, [len(w) for w in waves], args.max_tokens, args.batch_size), args.num_shards,
+                                args.shard_id)
     for ids in batches:
         sample = collate(ids, utt_ids, waves, dev)
         t0 = time.perf_counter()
@@ -153,6 +241,11 @@ def main(argv=None):
                 per = r["score"] / r["frames"] if r["feasible"] and r["frames"] > 0 else (0.0 if r["feasible"] else -math.inf)
                 print("{} {} {} {:.4f} {:.4f}{}".format(u, r["frames"], len(r["tokens"]), r["score"], per,
                                                        "" if r["feasible"] else " infeasible"), file=f)
+    if args.segments_dir:
+        max_s = DEFAULT_SEGMENT_MAX_S if args.segment_max_s is None else args.segment_max_s
+        min_sil = DEFAULT_SEGMENT_MIN_SILENCE_S if args.segment_min_silence_s is None else args.segment_min_silence_s
+        write_segments(args.segments_dir, [(u, results[u]) for u in order if results[u]["feasible"]], d, spf,
+                       max(1, int(round(max_s / spf))), int(round(min_sil / spf)))
     n_bad = sum(not results[u]["feasible"] for u in order)
     print("| aligned {} utterances ({} infeasible) in {:.1f}s, RTF {:.4f}".format(len(order), n_bad, t_align,
                                                                                t_align / max(audio_s, 1e-9)), file=sys.stderr)

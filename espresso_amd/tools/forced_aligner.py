@@ -100,6 +100,79 @@ class CTCForcedAligner:
         return out
 
 
+class LongFormCTCAligner:
+    """Viterbi alignment of ONE recording of any length to its whole transcript with an offline encoder-only CTC model: the
+    recording goes through `LongFormCTC.encode` (overlapping windows, joined on the device into one fp32 log-prob matrix on the
+    recording's own frame axis, tools/long_form.py), the transcript's lattice through the tiled kernel of csrc/align_long.hip
+    (`kernels.ctc_viterbi_align_long`), whatever its length: the one-workgroup kernel of
+    `CTCForcedAligner` and its 1023-token cap are not involved."""
+
+    def __init__(self, task, model, plan, dictionary, blank=None, max_tokens=15000, batch_size=24):
+        from .long_form import LongFormCTC
+
+        self.model = model
+        self.dictionary = dictionary
+        self.blank = dictionary.bos() if blank is None else blank
+        self.long_form = LongFormCTC(task, plan, self.blank, max_tokens, batch_size)
+
+    @torch.no_grad()
+    def align(self, wave, tokens) -> Dict:
+        """wave: the recording's samples (host); tokens: its transcript's ids.  Returns the keys of an entry of
+        `CTCForcedAligner.align` (tokens, start / end in the recording's encoder frames, score, frames, feasible) and frame_lp
+        (host fp32 [T]: the log-prob of the chosen label in every frame, 0 when nothing was aligned), cuts and cut_scores (the
+        junctions of `LongFormCTC.encode`).  One host copy."""
+        lprobs, _, cuts, cut_scores = self.long_form.encode(self.model, wave)
+        T, V = lprobs.shape[1], lprobs.shape[2]
+        tg = torch.as_tensor(list(tokens), dtype=torch.int32).to(lprobs.device)
+        U, J = tg.numel(), cuts.numel()
+        ts, te, _, flp, score = K.ctc_viterbi_align_long(lprobs[0], tg, T, V, self.blank)
+        host = torch.cat([ts, te, cuts.to(torch.int32), score.view(torch.int32), flp.view(torch.int32),
+                          cut_scores.view(torch.int32)]).cpu().numpy()
+        sc = float(host[2 * U + J: 2 * U + J + 1].view(np.float32)[0])
+        feasible = bool(np.isfinite(sc))
+        return {"tokens": np.asarray(list(tokens), dtype=np.int64),
+                "start": host[:U].astype(np.int64) if feasible else np.full(U, -1),
+                "end": host[U: 2 * U].astype(np.int64) if feasible else np.full(U, -1), "score": sc, "frames": T,
+                "feasible": feasible, "frame_lp": host[2 * U + J + 1: 2 * U + J + 1 + T].view(np.float32).copy(),
+                "cuts": host[2 * U: 2 * U + J].astype(np.int64), "cut_scores": host[2 * U + J + 1 + T:].view(np.float32).copy()}
+
+
+def cut_segments(words, n_frames: int, max_frames: int, min_gap_frames: int):
+    """Cut an aligned recording into utterance-sized segments at its silences.  words: `word_spans` output [(word, start, end)] in
+    encoder frames, in order; n_frames: the recording's frames.
+    The rule.  Start from one segment holding every word.  While a segment is longer than max_frames, split it at its longest
+    inter-word gap (next.start - prev.end) among the gaps of at least min_gap_frames; ties go to the gap nearest the segment's
+    middle (|prev.end + next.start - segment start - segment end| smallest), then to the earlier gap; the cut frame is
+    prev.end + gap // 2, which ends the left part and starts the right one.  The recording's first segment starts
+    min_gap_frames // 2 before its first word and its last one ends as much after its last word, clamped to [0, n_frames].  A
+    segment that is too long but has no eligible gap stays whole and is flagged `overlong`.
+    Returns [(first_word, end_word, start_frame, end_frame, overlong)] in order: segment k holds words[first_word:end_word]."""
+    if not words:
+        return []
+    pad = min_gap_frames // 2
+    todo = [(0, len(words), max(0, min(int(words[0][1]) - pad, n_frames)), max(0, min(int(words[-1][2]) + pad, n_frames)))]
+    done = []
+    while todo:
+        a, b, s, e = todo.pop()
+        best = None
+        if e - s > max_frames:
+            for k in range(a, b - 1):
+                left, right = int(words[k][2]), int(words[k + 1][1])
+                gap = right - left
+                if gap < min_gap_frames:
+                    continue
+                key = (-gap, abs(left + right - s - e), k)
+                if best is None or key < best[0]:
+                    best = (key, k, left + gap // 2)
+        if best is None:
+            done.append((a, b, s, e, e - s > max_frames))
+        else:
+            _, k, c = best
+            todo.append((k + 1, b, c, e))  # (popped last: the left part first)
+            todo.append((a, k + 1, s, c))
+    return sorted(done)
+
+
 @torch.no_grad()
 def joint_lattice(m, E, enc_len, tg, tl, bos, pad, blank, fused=True):
     """The transducer lattice of targets tg int32 [B][U] (lengths tl int32 [B]) from the joint network's encoder branch E

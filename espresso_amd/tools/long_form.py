@@ -233,7 +233,7 @@ def check_long_form_args(args, tool="speech_recognize"):
             if v is not None:
                 raise ValueError(f"{opt} configures --long-form: give --long-form too")
         return
-    if args.streaming:
+    if getattr(args, "streaming", False):  # (speech_align has no --streaming)
         raise NotImplementedError("--long-form windows an offline encoder: no --streaming with it (a chunk-streaming model decodes audio "
                                   "of any length with --streaming --stream-endpoint)")
     if tool == "speech_recognize":

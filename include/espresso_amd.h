@@ -1287,6 +1287,35 @@ int ea_rnnt_viterbi_align(const float* lpb, const float* lpy, const int* logit_l
                           void* workspace, int* emit_frame, float* score, int B, int T, int U1, ea_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Long-form forced alignment (csrc/align_long.hip): ea_ctc_viterbi_align's search for ONE sequence whose lattice does not fit a
+ * workgroup -- a recording's stitched log-probs (ea_longform_stitch) against its whole transcript.  The reference has no forced
+ * aligner of its own.  The lattice is cut into tiles of `frames` x `states` (ea_ctc_viterbi_long_tile); the tiles of one
+ * anti-diagonal run in one launch, and launch boundaries are the only ordering between workgroups (no grid barrier, no
+ * cooperative launch, no flag one workgroup waits on): ceil(T / frames) + ceil(S / states) + 1 launches per call, no device
+ * allocation and no synchronisation inside.
+ *
+ * ea_ctc_viterbi_long_align: x fp32 or bf16 (x_bf16) [T][ld] log-probs (ld >= V), targets int32 [U] (may be NULL for U == 0),
+ *   workspace: ea_ctc_viterbi_long_workspace_bytes(T, U) bytes, any contents (backpointers 2 bits per frame and state, the score
+ *   vector alpha [S] and the tile edges [ceil(S / states)][T][2]).
+ *   Lattice: blank y1 blank ... yU blank (S = 2U + 1 states); moves stay, +1, +2 (+2 only into a non-blank state whose label
+ *   differs from the label two states earlier); frame 0 admits states 0 and 1, a path ends in state S-1 or S-2.
+ *   TIE RULE: stay over +1 over +2; at the end S-1 over S-2.  Scores are fp32 sums in frame order: every output equals, BIT FOR
+ *   BIT, what ea_ctc_viterbi_align gives for B = 1, in_len = T, tgt_len = Lmax = U wherever that call accepts the problem.
+ *   Outputs (device): tok_start / tok_end int32 [U] = first frame of token u's non-blank run and one past its last frame;
+ *   frame_label int32 [T] = u on a frame of token u, -1 on blank frames; frame_lp fp32 [T] = x[t][label of the chosen state]
+ *   (their sum over a stretch of frames is that stretch's share of the score); score fp32 [1] (U == 0: the all-blank path;
+ *   T == U == 0: 0).
+ *   Infeasible (T < U + number of equal adjacent targets, or no finite path): score = -inf, tok_start = tok_end = -1,
+ *   frame_label = -2, frame_lp = 0.  A target id outside [0, V) or equal to blank: score = NaN and the same fill, not aligned.
+ *   Returns -2 for T < 0, U < 0, V < 1, blank outside [0, V), ld < V, T > 2^30 or U > 2^28 (ea_ctc_viterbi_long_workspace_bytes
+ *   returns 0 for such T, U). */
+int ea_ctc_viterbi_long_tile(int* frames, int* states);
+long ea_ctc_viterbi_long_workspace_bytes(long T, long U);
+int ea_ctc_viterbi_long_align(const void* x, long ld, int x_bf16, const int* targets, void* workspace, int* tok_start, int* tok_end,
+                              int* frame_label, float* frame_lp, float* score, long T, int V, long U, int blank,
+                              ea_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-token posteriors of a given label sequence (csrc/prefix_posterior.hip): the sum-product twins of the two aligners.  The
  * reference has them for attention-decoder hypotheses only (positional_scores); CTC and transducer hypotheses get them here.
  *   Psi_i = log P(the model's output starts with y1 .. yi | x), summed over all continuations and all alignments (Psi_0 = 0);
