@@ -1351,6 +1351,33 @@ def ctc_prefix_posteriors(x, targets, utt, in_len, tgt_len, B, T, V, blank, ld=N
     return (logc, total, psi) if want_psi else (logc, total)
 
 
+def ctc_prefix_posteriors_long(x, targets, T, V, blank, ld=None, want_psi=False):
+    """Per-token posteriors of ONE sequence of any length: targets int32 [U] under x [T][V] fp32/bf16 log-probs (row pitch ld),
+    tiled over the device (ea_ctc_prefix_long_posteriors).  Returns (logc fp32 [U + 1], total fp32 [1]) and, with want_psi, psi
+    fp32 [U], all on the device.  The workspace holds two scores per frame and state tile and no backpointers; one larger than
+    the device's free memory is refused with a ValueError."""
+    if ld is None:
+        ld = x.stride(0) if T > 1 else V  # (the strides of a tensor of no or one row say nothing)
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 2 and x.shape[0] == T and x.shape[1] == V
+    assert T == 0 or x.stride(-1) == 1
+    assert targets.dtype == torch.int32 and targets.is_contiguous() and targets.dim() == 1
+    U = targets.numel()
+    dev = x.device
+    need = int(_lib.lib().ea_ctc_prefix_long_workspace_bytes(T, U))
+    free = int(torch.cuda.mem_get_info(dev)[0])
+    if need > free:
+        raise ValueError(f"long-form posteriors of U = {U} tokens over T = {T} frames need a workspace of {need} bytes, the device has "
+                         f"{free} bytes free (two scores per frame and tile of states)")
+    ws = torch.empty(max(1, need), dtype=torch.uint8, device=dev)
+    logc = torch.empty(U + 1, dtype=torch.float32, device=dev)
+    total = torch.empty(1, dtype=torch.float32, device=dev)
+    psi = torch.empty(U, dtype=torch.float32, device=dev) if want_psi else None
+    check(_lib.lib().ea_ctc_prefix_long_posteriors(_p(x), ld, int(x.dtype == torch.bfloat16), _p(targets) if U else None, _p(ws),
+                                                   _p(logc), _p(total), _p(psi) if want_psi and U else None, T, V, U, blank,
+                                                   _stream()), "ea_ctc_prefix_long_posteriors")
+    return (logc, total, psi) if want_psi else (logc, total)
+
+
 def rnnt_prefix_posteriors(lpb, lpy, logit_lengths, target_lengths, want_psi=False):
     """Per-token posteriors (ea_rnnt_prefix_posteriors) over transducer lattices lpb / lpy fp32 [B][T][U1] (ea_rnnt_scan's
     meaning).  Returns (logc fp32 [B][U1], total fp32 [B]) and, with want_psi, psi fp32 [B][U1 - 1], all on the device."""

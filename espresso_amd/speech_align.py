@@ -15,7 +15,10 @@ goes through an offline CTC model as overlapping windows joined on the device (t
 transcript is aligned to all of it by the tiled Viterbi kernel (csrc/align_long.hip); the CTM carries times on
 the recording's own axis.  `--segments-dir` then cuts every recording at its silences into utterance-sized segments (`segments`,
 `text`, `scores`: Kaldi-style data for training; a segment whose text does not match its audio shows a low mean log-prob per
-frame in `scores`).  The segment defaults are uncalibrated."""
+frame in `scores`).  The segment defaults are uncalibrated.  `--long-form-posteriors` adds the acoustic model's posterior of every
+token of the transcript, whatever its length (csrc/prefix_posterior_long.hip): the CTM's last column
+carries the unit's probability and `--segments-dir` gets a fourth file, `confidence`, which says which segment holds a word
+the model does not hear; `--confidence` itself keeps its 1023-token cap and stays refused with `--long-form`."""
 import argparse
 import math
 import os
@@ -58,6 +61,12 @@ def get_parser():
     from .tools.long_form import UNCALIBRATED, add_long_form_args
 
     add_long_form_args(p)  # --long-form: one recording of any length per wav.scp entry, aligned to its whole transcript
+    p.add_argument("--long-form-posteriors", action="store_true",
+                   help="--long-form: the CTM's last column carries the model's posterior of the unit given the audio and the "
+                        "transcript before it, computed for a transcript of any length by the tiled kernel of "
+                        "csrc/prefix_posterior_long.hip (a word: the product over its tokens); --segments-dir also gets `confidence` "
+                        "(<rec>_<k> mean-token-log-posterior lowest-word-probability words).  How the probabilities relate to word "
+                        "correctness has not been measured")
     p.add_argument("--segments-dir", default=None,
                    help="--long-form: cut every aligned recording at its silences into segments and write `segments` (<rec>_<k> <rec> "
                         "start_s end_s), `text` and `scores` (<rec>_<k> frames words mean-log-prob-per-frame [overlong]) there")
@@ -77,6 +86,8 @@ def check_args(args):
     opts = (("--segments-dir", args.segments_dir), ("--segment-max-s", args.segment_max_s),
             ("--segment-min-silence-s", args.segment_min_silence_s))
     if not args.long_form:
+        if args.long_form_posteriors:
+            raise ValueError("--long-form-posteriors configures --long-form: give --long-form too")
         for opt, v in opts:
             if v is not None:
                 raise ValueError(f"{opt} cuts a --long-form alignment into segments: give --long-form too")
@@ -148,6 +159,24 @@ def write_segments(out_dir, aligned, dictionary, spf, max_frames, min_gap_frames
                 print("{} {} {} {:.4f}{}".format(name, e - s, b - a, mean, " overlong" if overlong else ""), file=f_sc)
 
 
+def write_confidence(out_dir, aligned, dictionary, max_frames, min_gap_frames):
+    """`confidence` next to the files of `write_segments`, for the same recordings (results with "token_posteriors") and the same
+    cuts: one line per segment, `<rec>_<k> mean-token-log-posterior lowest-word-probability words` (`segment_confidence` over
+    the segment's words)."""
+    from .tools.forced_aligner import cut_segments, utterance_units
+    from .tools.token_posteriors import segment_confidence, word_log_factors
+
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "confidence"), "w", encoding="utf-8") as f:
+        for rec, r in aligned:
+            words = utterance_units(r, dictionary, "word")
+            rows = word_log_factors([dictionary[int(t)] for t in r["tokens"]], r["token_posteriors"],
+                                    space=getattr(dictionary, "space_word", "<space>"))
+            assert len(rows) == len(words), (len(rows), len(words))
+            for k, (a, b, _, _, _) in enumerate(cut_segments(words, r["frames"], max_frames, min_gap_frames)):
+                print("{}_{:04d} {:.4f} {:.4f} {}".format(rec, k, *segment_confidence(rows[a:b])), file=f)
+
+
 def main(argv=None):
     args = get_parser().parse_args(argv)
     check_args(args)
@@ -196,7 +225,7 @@ def main(argv=None):
     results, t_align, audio_s = {}, 0.0, 0.0
     if args.long_form:  # one recording at a time: its windows' stitched log-probs, then the tiled Viterbi search
         aligner = LongFormCTCAligner(task, model, LF.plan_from_args(args, task.frontend, model), d, max_tokens=args.max_tokens,
-                                     batch_size=args.batch_size)
+                                     batch_size=args.batch_size, token_posteriors=args.long_form_posteriors)
         junctions = LF.LongFormModel(model, aligner.long_form)  # (for `log_worst`: the cuts of every recording)
         for i in range(args.shard_id, len(utt_ids), args.num_shards):
             t0 = time.perf_counter()
@@ -226,7 +255,7 @@ def main(argv=None):
             r = results[u]
             if r["feasible"]:
                 conf = None
-                if args.confidence:
+                if args.confidence or args.long_form_posteriors:
                     conf = unit_confidences([d[int(t)] for t in r["tokens"]], r["token_posteriors"], args.unit,
                                             space=getattr(d, "space_word", "<space>"))
                 for line in ctm_lines(u, utterance_units(r, d, args.unit), spf, confidences=conf):
@@ -244,8 +273,11 @@ def main(argv=None):
     if args.segments_dir:
         max_s = DEFAULT_SEGMENT_MAX_S if args.segment_max_s is None else args.segment_max_s
         min_sil = DEFAULT_SEGMENT_MIN_SILENCE_S if args.segment_min_silence_s is None else args.segment_min_silence_s
-        write_segments(args.segments_dir, [(u, results[u]) for u in order if results[u]["feasible"]], d, spf,
-                       max(1, int(round(max_s / spf))), int(round(min_sil / spf)))
+        aligned = [(u, results[u]) for u in order if results[u]["feasible"]]
+        max_frames, min_gap_frames = max(1, int(round(max_s / spf))), int(round(min_sil / spf))
+        write_segments(args.segments_dir, aligned, d, spf, max_frames, min_gap_frames)
+        if args.long_form_posteriors:
+            write_confidence(args.segments_dir, aligned, d, max_frames, min_gap_frames)
     n_bad = sum(not results[u]["feasible"] for u in order)
     print("| aligned {} utterances ({} infeasible) in {:.1f}s, RTF {:.4f}".format(len(order), n_bad, t_align,
                                                                                t_align / max(audio_s, 1e-9)), file=sys.stderr)

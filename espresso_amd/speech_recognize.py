@@ -355,7 +355,24 @@ def get_parser():
     from .tools.long_form import add_long_form_args
 
     add_long_form_args(p)  # --long-form: recordings of any length through an offline CTC model (--search ctc / ctc_beam)
+    p.add_argument("--long-form-posteriors", action="store_true",
+                   help="--long-form (ctc / ctc_beam without --ngram-lm): after every `H-<utt>` line print `C-<utt>` as --confidence "
+                        "does, computed after the search for hypotheses of any length by the tiled kernel of "
+                        "csrc/prefix_posterior_long.hip on the log-probs the search read; --ctm then carries the unit's probability.  "
+                        "How the probabilities relate to word correctness has not been measured")
     return p
+
+
+def check_long_form_posteriors_args(args):
+    """--long-form-posteriors belongs to --long-form and, like --confidence, scores the model's sub-word tokens: refused, before
+    anything is loaded, without --long-form and with the lexicon + n-gram search."""
+    if not getattr(args, "long_form_posteriors", False):
+        return
+    if not args.long_form:
+        raise ValueError("--long-form-posteriors configures --long-form: give --long-form too")
+    if args.ngram_lm:
+        raise NotImplementedError("--long-form-posteriors scores the model's sub-word tokens: no --ngram-lm with it (the units of the "
+                                  "lexicon search are words)")
 
 
 def check_ngram_args(args):
@@ -873,6 +890,7 @@ def main(argv=None):
     from .tools import long_form as LF
 
     LF.check_long_form_args(args)
+    check_long_form_posteriors_args(args)
     lm_mode = lm_fusion_mode(args)
     if args.search == "ctc_beam" and len(args.path.split(os.pathsep)) > 1:
         raise NotImplementedError("ensembles are implemented for the attention decoder's beam search (--search beam)")
@@ -984,6 +1002,8 @@ def main(argv=None):
         lf_model = LF.LongFormModel(model, LF.LongFormCTC(task, LF.plan_from_args(args, task.frontend, model), task.target_dictionary.bos(),
                                                           args.max_tokens, args.batch_size))
         gen = build_generator(args, lf_model, task.target_dictionary, lm, ngram, context_graph)
+        if args.long_form_posteriors:  # after the search, per hypothesis, on the matrix the search read
+            gen = LF.LongFormPosteriors(gen, lf_model, task.target_dictionary)
         batches = shard_batches([[i] for i in range(len(utt_ids))], args.num_shards, args.shard_id)
         stream = ({"utt_ids": [utt_ids[i]], "num_samples": [len(waves[i])], "net_input": {"wave": waves[i]}} for (i,) in batches)
     ctm_hyps = {} if args.ctm else None

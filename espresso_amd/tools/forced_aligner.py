@@ -105,36 +105,50 @@ class LongFormCTCAligner:
     recording goes through `LongFormCTC.encode` (overlapping windows, joined on the device into one fp32 log-prob matrix on the
     recording's own frame axis, tools/long_form.py), the transcript's lattice through the tiled kernel of csrc/align_long.hip
     (`kernels.ctc_viterbi_align_long`), whatever its length: the one-workgroup kernel of
-    `CTCForcedAligner` and its 1023-token cap are not involved."""
+    `CTCForcedAligner` and its 1023-token cap are not involved.  With `token_posteriors` the tiled sum-product kernel of
+    csrc/prefix_posterior_long.hip (`kernels.ctc_prefix_posteriors_long`) scores the same transcript on
+    the same matrix."""
 
-    def __init__(self, task, model, plan, dictionary, blank=None, max_tokens=15000, batch_size=24):
+    def __init__(self, task, model, plan, dictionary, blank=None, max_tokens=15000, batch_size=24, token_posteriors=False):
         from .long_form import LongFormCTC
 
         self.model = model
         self.dictionary = dictionary
         self.blank = dictionary.bos() if blank is None else blank
         self.long_form = LongFormCTC(task, plan, self.blank, max_tokens, batch_size)
+        self.token_posteriors = bool(token_posteriors)
 
     @torch.no_grad()
     def align(self, wave, tokens) -> Dict:
         """wave: the recording's samples (host); tokens: its transcript's ids.  Returns the keys of an entry of
         `CTCForcedAligner.align` (tokens, start / end in the recording's encoder frames, score, frames, feasible) and frame_lp
         (host fp32 [T]: the log-prob of the chosen label in every frame, 0 when nothing was aligned), cuts and cut_scores (the
-        junctions of `LongFormCTC.encode`).  One host copy."""
+        junctions of `LongFormCTC.encode`); with token_posteriors also the three keys of tools/token_posteriors.py for the
+        transcript.  One host copy."""
         lprobs, _, cuts, cut_scores = self.long_form.encode(self.model, wave)
         T, V = lprobs.shape[1], lprobs.shape[2]
         tg = torch.as_tensor(list(tokens), dtype=torch.int32).to(lprobs.device)
         U, J = tg.numel(), cuts.numel()
         ts, te, _, flp, score = K.ctc_viterbi_align_long(lprobs[0], tg, T, V, self.blank)
-        host = torch.cat([ts, te, cuts.to(torch.int32), score.view(torch.int32), flp.view(torch.int32),
-                          cut_scores.view(torch.int32)]).cpu().numpy()
+        parts = [ts, te, cuts.to(torch.int32), score.view(torch.int32), flp.view(torch.int32), cut_scores.view(torch.int32)]
+        if self.token_posteriors:  # (appended: the other keys read the same words of the copy as without it)
+            logc, total = K.ctc_prefix_posteriors_long(lprobs[0], tg, T, V, self.blank)
+            parts += [logc.view(torch.int32), total.view(torch.int32)]
+        host = torch.cat(parts).cpu().numpy()
         sc = float(host[2 * U + J: 2 * U + J + 1].view(np.float32)[0])
         feasible = bool(np.isfinite(sc))
-        return {"tokens": np.asarray(list(tokens), dtype=np.int64),
-                "start": host[:U].astype(np.int64) if feasible else np.full(U, -1),
-                "end": host[U: 2 * U].astype(np.int64) if feasible else np.full(U, -1), "score": sc, "frames": T,
-                "feasible": feasible, "frame_lp": host[2 * U + J + 1: 2 * U + J + 1 + T].view(np.float32).copy(),
-                "cuts": host[2 * U: 2 * U + J].astype(np.int64), "cut_scores": host[2 * U + J + 1 + T:].view(np.float32).copy()}
+        n = 2 * U + 2 * J + 1 + T  # the words of the copy without the posteriors
+        out = {"tokens": np.asarray(list(tokens), dtype=np.int64),
+               "start": host[:U].astype(np.int64) if feasible else np.full(U, -1),
+               "end": host[U: 2 * U].astype(np.int64) if feasible else np.full(U, -1), "score": sc, "frames": T,
+               "feasible": feasible, "frame_lp": host[2 * U + J + 1: 2 * U + J + 1 + T].view(np.float32).copy(),
+               "cuts": host[2 * U: 2 * U + J].astype(np.int64), "cut_scores": host[2 * U + J + 1 + T: n].view(np.float32).copy()}
+        if self.token_posteriors:
+            post = host[n:].view(np.float32)
+            out["token_posteriors"] = post[:U].copy()
+            out["end_posterior"] = float(post[U])
+            out["posterior_score"] = float(post[U + 1])
+        return out
 
 
 def cut_segments(words, n_frames: int, max_frames: int, min_gap_frames: int):

@@ -186,10 +186,12 @@ class LongFormModel:
     def __init__(self, model, long_form: LongFormCTC):
         self.model, self.long_form = model, long_form
         self.junctions = []
+        self.lprobs = None  # the last recording's matrix [1][T][V] (what `LongFormPosteriors` scores the hypotheses on)
 
     def __call__(self, wave):
         lprobs, in_len, cuts, scores = self.long_form.encode(self.model, wave)
         self.junctions.append((cuts, scores))
+        self.lprobs = lprobs
         return {"_lprobs": lprobs, "src_lengths": [in_len], "encoder_padding_mask": [torch.zeros(1, lprobs.shape[1], dtype=torch.bool,
                                                                                                   device=lprobs.device)]}
 
@@ -207,6 +209,39 @@ class LongFormModel:
         """The lowest junction score so far (None without junctions): a cut made through speech shows here."""
         s = [sc for _, sc in self.junctions if sc.numel()]
         return float(torch.cat(s).min()) if s else None
+
+
+class LongFormPosteriors:
+    """A generator around a CTC generator that decodes a `LongFormModel`: after the search, every hypothesis of the n-best gets
+    the three keys of tools/token_posteriors.py, computed by the tiled kernel (`kernels.ctc_prefix_posteriors_long`, DESIGN.md
+    section 3.10) on the matrix the search read, whatever the hypothesis' length.  Blank and pad are no labels (factor 0), as in
+    `token_posteriors.score_rows`.  Tokens, scores, order and times are the inner generator's.  One host copy per hypothesis."""
+
+    def __init__(self, generator, model: LongFormModel, dictionary, blank=None):
+        self.generator, self.model = generator, model
+        self.blank = dictionary.bos() if blank is None else blank
+        self.pad = dictionary.pad()
+
+    def __getattr__(self, name):  # (symbols_to_strip_from_output and the like: the inner generator's)
+        return getattr(self.generator, name)
+
+    @torch.no_grad()
+    def generate(self, models, sample, **kwargs):
+        hyps = self.generator.generate(models, sample, **kwargs)
+        lprobs = self.model.lprobs
+        assert len(hyps) == 1 and lprobs is not None and lprobs.shape[0] == 1, "one recording per sample"
+        T, V = lprobs.shape[1], lprobs.shape[2]
+        for h in hyps[0]:
+            toks = h["tokens"].tolist()
+            keep = [k for k, t in enumerate(toks) if t != self.blank and t != self.pad]
+            labels = torch.tensor([toks[k] for k in keep], dtype=torch.int32).to(lprobs.device)
+            logc, total = K.ctc_prefix_posteriors_long(lprobs[0], labels, T, V, self.blank)
+            host = torch.cat([logc, total]).cpu()
+            tok = torch.zeros(len(toks), dtype=torch.float32)
+            tok[keep] = host[: len(keep)]
+            h["token_posteriors"], h["end_posterior"], h["posterior_score"] = tok, host[len(keep)], host[len(keep) + 1]
+        self.model.lprobs = None
+        return hyps
 
 
 def add_long_form_args(p):

@@ -184,6 +184,36 @@ def unit_confidences(symbols: Sequence[str], log_factors: Sequence[float], unit:
     return [math.exp(f) for w, f in words if w]
 
 
+def word_log_factors(symbols: Sequence[str], log_factors: Sequence[float], space: str = "<space>") -> List[List[float]]:
+    """The log factors of every word's own tokens, words grouped and ordered as `unit_confidences(..., "word")` groups them (the
+    exp of a row's sum is that word's probability there)."""
+    from .forced_aligner import SP_SPACE
+
+    words, cur = [], None
+    for sym, f in zip(symbols, log_factors):
+        if sym == space:
+            cur = None
+            continue
+        if sym.startswith(SP_SPACE) or cur is None:
+            cur = [sym.lstrip(SP_SPACE), [float(f)]]
+            words.append(cur)
+        else:
+            cur[0] += sym
+            cur[1].append(float(f))
+    return [fs for w, fs in words if w]
+
+
+def segment_confidence(word_factors: Sequence[Sequence[float]]):
+    """(mean token log-posterior, lowest word probability, words) of a stretch of words given as rows of `word_log_factors`:
+    the mean runs over the words' own tokens, a word's probability is the product over its tokens.  No word: (0.0, 1.0, 0)."""
+    import math
+
+    flat = [f for fs in word_factors for f in fs]
+    if not flat:
+        return 0.0, 1.0, 0
+    return sum(flat) / len(flat), min(math.exp(sum(fs)) for fs in word_factors), len(word_factors)
+
+
 def confidence_line(utt: str, token_log_factors: Sequence[float], end_log_factor: float) -> str:
     """`C-<utt>\\t` + the token probabilities and the end probability, space-separated, 4 decimals."""
     import math

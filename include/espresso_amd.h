@@ -1344,6 +1344,33 @@ int ea_rnnt_prefix_posteriors(const float* lpb, const float* lpy, const int* log
                               float* logc, float* total, float* psi, int B, int T, int U1, ea_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-token posteriors of ONE label sequence of any length (csrc/prefix_posterior_long.hip): ea_ctc_prefix_posteriors'
+ * quantities for a recording's stitched log-probs (ea_longform_stitch) against its whole transcript, the sum-product twin of
+ * ea_ctc_viterbi_long_align.  Definitions, lattice, move rules and conventions are those of ea_ctc_prefix_posteriors, and both
+ * kernels do the same fp32 operations in the same order (csrc/prefix_math.h).  The tiles are those of the long-form aligner
+ * (ea_ctc_viterbi_long_tile); the tiles of one anti-diagonal run in one launch and launch boundaries are the only ordering
+ * between workgroups: ceil(T / frames) + ceil(S / states) + 1 launches per call (2 for T == 0), no device allocation and no
+ * synchronisation inside.  A tile whose first state no alignment reaches by its last frame computes nothing; every other tile
+ * is computed (Psi counts prefixes whether or not they can still reach the end).
+ *
+ * ea_ctc_prefix_long_posteriors: x fp32 or bf16 (x_bf16) [T][ld] log-probs (ld >= V), targets int32 [U] (may be NULL for
+ *   U == 0), workspace: ea_ctc_prefix_long_workspace_bytes(T, U) bytes, any contents (the score vector alpha [S], the tile edges
+ *   [ceil(S / states)][T][2], the accumulators Psi [U] and 8 KiB of flags; no backpointers).
+ *   Outputs (device): logc fp32 [U + 1]: position i < U holds log c_{i+1}, position U holds log c_end (U == 0: logc[0] = total,
+ *   the all-blank path); total fp32 [1]; psi fp32 [U] or NULL: Psi_{i+1}.  Every logc entry is clamped to <= 0.  Zero probability
+ *   or an infeasible sequence (T < U + number of equal adjacent targets): from the first i with Psi_i = -inf on every factor and
+ *   total are -inf, never NaN.  T == 0: total = 0 for U == 0, else -inf.  A target id outside [0, V) or equal to blank: every
+ *   output is NaN.
+ *   Psi and total have the magnitude of the path score (thousands for an hour of audio) and carry fp32 rounding of that size;
+ *   log c_i is the difference of two neighbours whose errors are strongly correlated; log c_end = total - Psi_U is not such a
+ *   difference (DESIGN.md sections 3.10 and 8.6 have the figures).
+ *   Returns -2 for T < 0, U < 0, V < 1, blank outside [0, V), ld < V, T > 2^30 or U > 2^28 (ea_ctc_prefix_long_workspace_bytes
+ *   returns 0 for such T, U). */
+long ea_ctc_prefix_long_workspace_bytes(long T, long U);
+int ea_ctc_prefix_long_posteriors(const void* x, long ld, int x_bf16, const int* targets, void* workspace, float* logc,
+                                  float* total, float* psi, long T, int V, long U, int blank, ea_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Keyword spotting on CTC log-probs, offline and streamed (csrc/kws.hip): where a list of phrases is spoken, and how sure the
  * model is, from the per-frame log-probs alone -- no beam search, no transcript.  The reference has nothing of the kind.  The
  * (stream, keyword) pairs are independent; each is a max-plus scan over the frames with a free start frame, its state carried
