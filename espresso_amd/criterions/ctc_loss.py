@@ -6,7 +6,17 @@ import math
 import torch
 
 from .. import functional as F
+from .. import kernels as K
 from ..registry import register_criterion
+
+
+def targets_and_lengths(target, pad_idx, eos_idx):
+    """(labels int32 [B][L], label counts int32 [B], pad / eos excluded) of int64 targets: one launch on the device, the torch
+    expressions (espresso/criterions/ctc_loss.py:66-68) elsewhere."""
+    if target.is_cuda and target.dtype == torch.int64 and target.dim() == 2:
+        return K.ctc_targets(target.contiguous(), pad_idx, eos_idx)
+    pad_mask = (target != pad_idx) & (target != eos_idx)
+    return target.to(torch.int32).contiguous(), pad_mask.sum(-1).to(torch.int32).contiguous()
 
 
 @register_criterion("ctc_loss")
@@ -41,8 +51,9 @@ class CtcLossCriterion:
         net_output = model(**sample["net_input"], **({"epoch": self.epoch} if False else {}))
         input_lengths = net_output["src_lengths"][0]
         target = sample["target"]
-        pad_mask = (target != self.pad_idx) & (target != self.eos_idx)
-        target_lengths = pad_mask.sum(-1)
+        targets32, target_lengths = targets_and_lengths(target, self.pad_idx, self.eos_idx)
+        lens32 = net_output.get("_src_lengths_i32")
+        in_len32 = lens32[0] if lens32 and lens32[0] is not None else input_lengths.to(torch.int32).contiguous()
         lg = net_output.get("_logits_bt")
         if lg:
             logits = lg[0]
@@ -52,11 +63,9 @@ class CtcLossCriterion:
             Tp, B, V = e.shape
             logits = e.transpose(0, 1).reshape(B * Tp, V)
         # left-aligned labels per row (pad/eos only trail the labels in AsrDataset.collater output)
-        nll, lprobs = F.ctc_loss(logits, target.to(torch.int32).contiguous(), input_lengths.to(torch.int32).contiguous(),
-                                 target_lengths.to(torch.int32).contiguous(), B, Tp, blank=self.blank_idx,
-                                 zero_infinity=self.zero_infinity)
-        if self.zero_infinity:
-            nll = torch.where(torch.isinf(nll), torch.zeros_like(nll), nll)
+        # (clean: with zero_infinity the loss kernel itself hands back 0 for an infeasible utterance)
+        nll, lprobs = F.ctc_loss(logits, targets32, in_len32, target_lengths, B, Tp,
+                                 blank=self.blank_idx, zero_infinity=self.zero_infinity, clean=self.zero_infinity)
         loss = nll.sum()
         ntokens = sample["ntokens"] if "ntokens" in sample else int(target_lengths.sum())
         nsentences = target.size(0)

@@ -165,6 +165,83 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const int* __restric
   for (int c = (threadIdx.x & 63); c < C; c += 64) atomicAdd(w + c, scale * bf2f(dy[(long)row * C + c]));
 }
 
+// ---- per-step bookkeeping that used to be a handful of ATen launches each ----------------------------------------------------
+// Sub-sampler lengths and masks: x_len[b] = floor((src_len[b] + total - 1) / total), key_len the same as int32,
+// pad_mask[b][t] = row_zero[b*Tp + t] = t >= x_len[b] (one byte each, 0 / 1).
+__global__ __launch_bounds__(256) void subsample_lengths_kernel(const long* __restrict__ src_len, long* __restrict__ x_len,
+                                                                int* __restrict__ key_len, uint8_t* __restrict__ pad_mask,
+                                                                uint8_t* __restrict__ row_zero, int B, int Tp, long total) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  auto out_len = [&](int b) {
+    const long a = src_len[b] + (total - 1);
+    long q = a / total;
+    if ((a % total != 0) && ((a < 0) != (total < 0))) --q;  // floor, as torch.div(rounding_mode="floor")
+    return q;
+  };
+  if (i < B) {
+    const long q = out_len((int)i);
+    x_len[i] = q;
+    key_len[i] = (int)q;
+  }
+  if (i < (long)B * Tp) {
+    const int b = (int)(i / Tp), t = (int)(i % Tp);
+    const uint8_t m = (long)t >= out_len(b) ? 1 : 0;
+    pad_mask[i] = m;
+    row_zero[i] = m;
+  }
+}
+// The trainer's four running sums: stats[0] += a0, stats[1] += loss[0], stats[2] += a2, stats[3] += a3 (fp32, one add each).
+__global__ void stats_add4_kernel(float* __restrict__ stats, float a0, const float* __restrict__ loss, float a2, float a3) {
+  const int i = threadIdx.x;
+  if (i >= 4) return;
+  const float v = i == 0 ? a0 : i == 1 ? loss[0] : i == 2 ? a2 : a3;
+  stats[i] = stats[i] + v;
+}
+// dst[c][r] = src[r][c] for r < R, 0 for R <= r < ld_dst (src dense [R][Cc], dst [Cc][ld_dst]); 64x64 LDS tile as above.
+__global__ __launch_bounds__(256) void transpose_pad_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int R, int Cc,
+                                                            long ld_dst) {
+  __shared__ bf16_t tile[64][66];
+  const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  for (int i = ty; i < 64; i += 4)
+    if (r0 + i < R && c0 + tx < Cc) tile[i][tx] = src[(long)(r0 + i) * Cc + c0 + tx];
+  __syncthreads();
+  for (int i = ty; i < 64; i += 4)
+    if (c0 + i < Cc && r0 + tx < ld_dst) dst[(long)(c0 + i) * ld_dst + r0 + tx] = r0 + tx < R ? tile[tx][i] : (bf16_t)0;
+}
+// Input-axis permutation of a [N][C*F] weight between the reference's (c*F + f) order and the channels-last sub-sampler's
+// (f*C + c): dst[n][f*C + c] = src[n][c*F + f] (bf16), and the way back for the gradient, dst[n][c*F + f] += src[n][f*C + c].
+// (64x64 LDS tile; dst_t, when given, also receives the permuted weight transposed, dst_t[f*C + c][n]: the k-contiguous operand
+// of the data gradient)
+__global__ __launch_bounds__(256) void permute_k_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst,
+                                                        bf16_t* __restrict__ dst_t, int N, int C, int F) {
+  __shared__ bf16_t tile[64][66];
+  const int CF = C * F;
+  const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int j = c0 + tx;  // column of dst: f*C + c
+  const int f = j / C, c = j % C;
+  for (int i = ty; i < 64; i += 4)
+    if (r0 + i < N && j < CF) {
+      const bf16_t v = src[(long)(r0 + i) * CF + (long)c * F + f];
+      tile[i][tx] = v;
+      dst[(long)(r0 + i) * CF + j] = v;
+    }
+  if (!dst_t) return;
+  __syncthreads();
+  for (int i = ty; i < 64; i += 4)
+    if (c0 + i < CF && r0 + tx < N) dst_t[(long)(c0 + i) * N + r0 + tx] = tile[tx][i];
+}
+__global__ __launch_bounds__(256) void unpermute_k_add_kernel(const float* __restrict__ src, float* __restrict__ dst, long n, int C, int F) {
+  const int CF = C * F;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long row = i / CF;
+    const int j = (int)(i % CF), f = j / C, c = j % C;
+    float* d = dst + row * CF + (long)c * F + f;
+    *d = *d + src[i];
+  }
+}
+
 }  // namespace
 
 static inline int grid_for(long n, int per_thread) {
@@ -219,6 +296,39 @@ extern "C" int ea_transpose_bf16_batch(const void* const* src, void* const* dst,
   tb.n = n;
   if (tot == 0) return 0;
   hipLaunchKernelGGL(transpose_batch_kernel, dim3(tot), dim3(256), 0, stream, tb);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_subsample_lengths(const long* src_len, long* x_len, int* key_len, void* pad_mask, void* row_zero, int B, int Tp,
+                                    int total, hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (Tp < 0 || total < 1) return -2;
+  const long n = (long)B * Tp > B ? (long)B * Tp : B;
+  hipLaunchKernelGGL(subsample_lengths_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src_len, x_len, key_len,
+                     (uint8_t*)pad_mask, (uint8_t*)row_zero, B, Tp, (long)total);
+  return EA_CHECK_LAUNCH();
+}
+extern "C" int ea_stats_add4(float* stats, float a0, const float* loss, float a2, float a3, hipStream_t stream) {
+  hipLaunchKernelGGL(stats_add4_kernel, dim3(1), dim3(64), 0, stream, stats, a0, loss, a2, a3);
+  return EA_CHECK_LAUNCH();
+}
+extern "C" int ea_transpose_pad_bf16(const void* src, void* dst, int rows, int cols, long ld_dst, hipStream_t stream) {
+  if (rows <= 0 || cols <= 0) return 0;
+  if (ld_dst < rows) return -2;
+  hipLaunchKernelGGL(transpose_pad_kernel, dim3((cols + 63) / 64, (unsigned)((ld_dst + 63) / 64)), dim3(256), 0, stream,
+                     (const bf16_t*)src, (bf16_t*)dst, rows, cols, ld_dst);
+  return EA_CHECK_LAUNCH();
+}
+extern "C" int ea_permute_k_bf16(const void* src, void* dst, void* dst_t, int N, int C, int F, hipStream_t stream) {
+  if (N <= 0 || C <= 0 || F <= 0) return 0;
+  hipLaunchKernelGGL(permute_k_kernel, dim3((C * F + 63) / 64, (N + 63) / 64), dim3(256), 0, stream, (const bf16_t*)src, (bf16_t*)dst,
+                     (bf16_t*)dst_t, N, C, F);
+  return EA_CHECK_LAUNCH();
+}
+extern "C" int ea_unpermute_k_add_f32(const float* src, float* dst, int N, int C, int F, hipStream_t stream) {
+  if (N <= 0 || C <= 0 || F <= 0) return 0;
+  const long n = (long)N * C * F;
+  hipLaunchKernelGGL(unpermute_k_add_kernel, dim3(grid_for(n, 2)), dim3(256), 0, stream, src, dst, n, C, F);
   return EA_CHECK_LAUNCH();
 }
 

@@ -37,6 +37,22 @@ __global__ __launch_bounds__(256) void log_softmax_kernel(const TIn* __restrict_
 // lattice buffers G, A(lpha), Bt(beta): [B][T][Smax] fp32, Smax = 2*Lmax+1
 __device__ __forceinline__ int ctc_label(const int* tg, int s, int blank) { return (s & 1) ? tg[s >> 1] : blank; }
 
+// Criterion bookkeeping: tgt32[b][l] = (int)target[b][l] and tgt_len[b] = #{l : target[b][l] != pad and != eos} (exact integer
+// count, one wave per row) — what `target.to(int32)` and `((target != pad) & (target != eos)).sum(-1)` compute.
+__global__ __launch_bounds__(64) void ctc_targets_kernel(const long* __restrict__ target, int* __restrict__ tgt32,
+                                                         int* __restrict__ tgt_len, int L, long pad, long eos) {
+  const int b = blockIdx.x;
+  const long* tg = target + (long)b * L;
+  int cnt = 0;
+  for (int l = threadIdx.x; l < L; l += 64) {
+    const long v = tg[l];
+    tgt32[(long)b * L + l] = (int)v;
+    cnt += (v != pad && v != eos) ? 1 : 0;
+  }
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+  if (threadIdx.x == 0) tgt_len[b] = cnt;
+}
+
 __global__ __launch_bounds__(256) void ctc_gather_kernel(const float* __restrict__ lprobs, const int* __restrict__ targets,
                                                          const int* __restrict__ in_len, const int* __restrict__ tgt_len,
                                                          float* __restrict__ G, int T, int V, int Lmax, int blank) {
@@ -57,7 +73,7 @@ __global__ __launch_bounds__(256) void ctc_gather_kernel(const float* __restrict
 __global__ void ctc_scan_kernel(const float* __restrict__ G, const int* __restrict__ targets,
                                 const int* __restrict__ in_len, const int* __restrict__ tgt_len,
                                 float* __restrict__ A, float* __restrict__ Bt, float* __restrict__ nll_out,
-                                int T, int Lmax, int blank, int SP) {
+                                float* __restrict__ nll_clean, int T, int Lmax, int blank, int SP) {
   extern __shared__ float sh[];  // [2 buf][SP + 2]
   const int b = blockIdx.x;
   const int Tb = in_len[b], L = tgt_len[b];
@@ -68,7 +84,10 @@ __global__ void ctc_scan_kernel(const float* __restrict__ G, const int* __restri
   float* buf1 = sh + 1 * (SP + 2) + (dir ? 0 : 2);
   const int* tg = targets + (long)b * Lmax;
   if (Tb <= 0) {
-    if (threadIdx.x == 0 && dir == 0) nll_out[b] = (L == 0) ? 0.f : INFINITY;
+    if (threadIdx.x == 0 && dir == 0) {
+      nll_out[b] = (L == 0) ? 0.f : INFINITY;
+      if (nll_clean) nll_clean[b] = 0.f;
+    }
     return;
   }
   // skip transition allowed?  alpha: from s-2 if label(s) != blank and != label(s-2)
@@ -150,7 +169,10 @@ __global__ void ctc_scan_kernel(const float* __restrict__ G, const int* __restri
     const float l1 = rd[S - 1];
     const float l2 = S >= 2 ? rd[S - 2] : -INFINITY;
     const float m = fmaxf(l1, l2);
-    nll_out[b] = (m == -INFINITY) ? INFINITY : -(m + logf(expf(l1 - m) + expf(l2 - m)));
+    const float v = (m == -INFINITY) ? INFINITY : -(m + logf(expf(l1 - m) + expf(l2 - m)));
+    nll_out[b] = v;
+    // (zero_infinity: what `where(isinf(nll), 0, nll)` gives; the raw value stays for the backward pass, which tests it)
+    if (nll_clean) nll_clean[b] = (v == INFINITY || v == -INFINITY) ? 0.f : v;
   }
 }
 
@@ -383,9 +405,16 @@ extern "C" long ea_ctc_workspace_bytes(int B, int T, int Lmax) {
   return 3L * B * T * (2L * Lmax + 1) * (long)sizeof(float);
 }
 
-extern "C" int ea_ctc_loss(const float* lprobs, const int* targets, const int* in_len, const int* tgt_len,
-                           float* nll /*[B]*/, void* workspace, int B, int T, int V, int Lmax, int blank,
-                           hipStream_t stream) {
+extern "C" int ea_ctc_targets(const long* target, int* tgt32, int* tgt_len, int B, int L, int pad, int eos, hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (L < 0) return -2;
+  hipLaunchKernelGGL(ctc_targets_kernel, dim3(B), dim3(64), 0, stream, target, tgt32, tgt_len, L, (long)pad, (long)eos);
+  return EA_CHECK_LAUNCH();
+}
+
+extern "C" int ea_ctc_loss_clean(const float* lprobs, const int* targets, const int* in_len, const int* tgt_len,
+                                 float* nll /*[B]*/, float* nll_clean /*[B] or NULL*/, void* workspace, int B, int T, int V,
+                                 int Lmax, int blank, hipStream_t stream) {
   if (B <= 0) return 0;
   if (T <= 0 || V <= 0 || Lmax < 0) return -2;
   const int Smax = 2 * Lmax + 1;
@@ -397,8 +426,13 @@ extern "C" int ea_ctc_loss(const float* lprobs, const int* targets, const int* i
   hipLaunchKernelGGL(ctc_gather_kernel, dim3(T, B), dim3(256), 0, stream, lprobs, targets, in_len, tgt_len, G, T, V,
                      Lmax, blank);
   hipLaunchKernelGGL(ctc_scan_kernel, dim3(B, 2), dim3(SP), (size_t)2 * (SP + 2) * sizeof(float), stream, G, targets,
-                     in_len, tgt_len, A, Bt, nll, T, Lmax, blank, SP);
+                     in_len, tgt_len, A, Bt, nll, nll_clean, T, Lmax, blank, SP);
   return EA_CHECK_LAUNCH();
+}
+extern "C" int ea_ctc_loss(const float* lprobs, const int* targets, const int* in_len, const int* tgt_len,
+                           float* nll /*[B]*/, void* workspace, int B, int T, int V, int Lmax, int blank,
+                           hipStream_t stream) {
+  return ea_ctc_loss_clean(lprobs, targets, in_len, tgt_len, nll, nullptr, workspace, B, T, V, Lmax, blank, stream);
 }
 
 extern "C" int ea_ctc_grad(const float* lprobs, const void* workspace, const float* nll, const int* targets,

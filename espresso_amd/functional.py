@@ -342,7 +342,10 @@ def branch_overlap() -> bool:
 # ------------------------------------------------------------------------------------------------
 class _Linear(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, w16, out_f32):
+    def forward(ctx, x, w, b, w16, out_f32, wt_kc=None, k_perm=None):
+        """wt_kc: a current k-contiguous copy [K_in][pad64(N)] of w16 for the data gradient (`refresh_dgrad_weight`), or None.
+        k_perm = (C, F): x carries its K_in = C*F features in (f*C + c) order while the weight's input axis is (c*F + f); w16
+        arrives already permuted (`linear`), the weight gradient is un-permuted on its way into `w.grad`."""
         M, Kin = x.shape
         N = w.shape[0]
         # rows are padded to a multiple of 8 elements so that every later 16-byte access (dgrad /
@@ -353,6 +356,7 @@ class _Linear(torch.autograd.Function):
         ctx.save_for_backward(x, w16)
         ctx.has_bias = b is not None
         ctx.params = (w, b)
+        ctx.wt_kc, ctx.k_perm = wt_kc, k_perm
         return buf if ld == N else buf[:, :N]
 
     @staticmethod
@@ -360,15 +364,18 @@ class _Linear(torch.autograd.Function):
         x, w16 = ctx.saved_tensors
         M, Kin = x.shape
         N = w16.shape[0]
+        zero_pad = getattr(dy, "_ea_zero_pad", 0)  # (the loss kernel's promise: columns [N, zero_pad) of every row hold zeros)
         if dy.dtype != torch.bfloat16:
             # fp32 output (vocabulary logits): one pass to bf16 at a row pitch of a multiple of 8 elements
+            zero_pad = 0
             if dy.stride(1) != 1:
                 dy = dy.contiguous()
             dy = K.cast_f32_to_bf16_rows(dy, _pad8(N)) if M <= 65535 else K.cast_f32_to_bf16(dy.contiguous())
         if dy.stride(1) != 1 or dy.stride(0) % 8 != 0:
-            dy = dy.contiguous()
+            dy, zero_pad = dy.contiguous(), 0
         ld = dy.stride(0)
         pw, pb = ctx.params
+        perm = ctx.k_perm
         sW = _grad_sink(pw, N * Kin)
         sb = _grad_sink(pb, N) if ctx.has_bias else None
         if sW is not None and (sb is not None or not ctx.has_bias):
@@ -377,36 +384,84 @@ class _Linear(torch.autograd.Function):
             # GEMM per update step were on the compute stream, in front of the data gradient the backward chain waits for);
             # `end_step()` / the data-parallel wrapper join that stream before the gradients are used.
             side = _side_stream(dy.device) if (dy.is_cuda and 2.0 * M * N * Kin >= 4e9) else None
+
+            def products():
+                if perm is None:
+                    _wgrad(dy, x, M, N, Kin, ld_dy=ld, out=sW.view(N, Kin), accumulate=True)
+                else:  # (f*C + c)-ordered product, added into the (c*F + f)-ordered gradient: same sums, same single add
+                    K.unpermute_k_add(_wgrad(dy, x, M, N, Kin, ld_dy=ld), sW, N, perm[0], perm[1])
+                if ctx.has_bias:
+                    K.colsum(dy, sb, M, N, ld)
+
             if side is not None:
                 cur = torch.cuda.current_stream(dy.device)
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):
-                    _wgrad(dy, x, M, N, Kin, ld_dy=ld, out=sW.view(N, Kin), accumulate=True)
-                    if ctx.has_bias:
-                        K.colsum(dy, sb, M, N, ld)
+                    products()
                 dy.record_stream(side)
                 x.record_stream(side)
                 _side_pending[str(dy.device)] = True
             else:
-                _wgrad(dy, x, M, N, Kin, ld_dy=ld, out=sW.view(N, Kin), accumulate=True)
-                if ctx.has_bias:
-                    K.colsum(dy, sb, M, N, ld)
+                products()
             dW, db = None, None
         else:
             dW = _wgrad(dy, x, M, N, Kin, ld_dy=ld)
+            if perm is not None:
+                dW = dW.view(N, perm[1], perm[0]).permute(0, 2, 1).reshape(N, Kin)
             db = None
             if ctx.has_bias:
                 db = K.colsum(dy, _zeros_f32(N, dy), M, N, ld)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = _new((M, Kin), torch.bfloat16, x)
-            K.gemm(dy, w16, dx, M, Kin, N, lda=ld, ldb=Kin, ldc=Kin, b_kstrided=True)
-        return dx, dW, db, None, None
+            wt = ctx.wt_kc
+            if wt is not None and ld % _DGRAD_PITCH == 0 and tuple(wt.shape) == (Kin, ld) and (zero_pad == ld or ld == N):
+                # both operands k-contiguous, the reduction padded to a multiple of 64 with zeros on BOTH sides (0 x NaN is NaN)
+                K.gemm(dy, wt, dx, M, Kin, ld, lda=ld, ldb=ld, ldc=Kin)
+            else:
+                K.gemm(dy, w16, dx, M, Kin, N, lda=ld, ldb=Kin, ldc=Kin, b_kstrided=True)
+        return dx, dW, db, None, None, None, None
 
 
-def linear(x, w, b=None, out_f32=False):
-    """y = x w^T + b ; x bf16 [M][K], w fp32 [N][K] (bf16 shadow used on the MFMA)."""
-    return _Linear.apply(x, w, b, bf16_weight(w), out_f32)
+_DGRAD_PITCH = 64  # row pitch granule of the loss gradient and of the k-contiguous output-projection copy
+
+
+def _pad_dgrad(n):
+    return (n + _DGRAD_PITCH - 1) // _DGRAD_PITCH * _DGRAD_PITCH
+
+
+def refresh_dgrad_weight(w):
+    """Before a TRAINING forward pass: the k-contiguous bf16 copy Wt[K_in][pad64(N)] (pad columns zero) of an output projection's
+    weight [N][K_in], read by its data gradient, is refreshed from the bf16 shadow on the Python-side stream (where the optimizer
+    pass that writes the shadow runs, and in front of `refresh_layer_transposes`, whose event the compute stream waits for
+    before the projection).  The next `linear(x, w)` call consumes it.  False: nothing done (no shadow, not on a device)."""
+    sh = getattr(w, "_ea_bf16", None)
+    if sh is None or not sh.is_cuda or w.dim() != 2:
+        return False
+    N, Kin = w.shape
+    ldk = _pad_dgrad(N)
+    buf = w.__dict__.get("_ea_wt_kc")
+    if buf is None or tuple(buf.shape) != (Kin, ldk) or buf.device != sh.device:
+        buf = w.__dict__["_ea_wt_kc"] = torch.empty(Kin, ldk, dtype=torch.bfloat16, device=sh.device)
+    cur, side = torch.cuda.current_stream(sh.device), _side_stream(sh.device)
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        K.transpose_pad(sh.view(N, Kin), buf, N, Kin, ldk)
+    w.__dict__["_ea_wt_kc_fresh"] = buf
+    return True
+
+
+def linear(x, w, b=None, out_f32=False, k_perm=None):
+    """y = x w^T + b ; x bf16 [M][K], w fp32 [N][K] (bf16 shadow used on the MFMA).  k_perm: see _Linear.forward."""
+    w16 = bf16_weight(w)
+    wt_kc = w.__dict__.pop("_ea_wt_kc_fresh", None) if torch.is_grad_enabled() else None
+    if k_perm is not None:
+        if torch.is_grad_enabled() and x.requires_grad and w.shape[0] % _DGRAD_PITCH == 0:
+            # (the data gradient reduces over N: the transposed copy comes out of the same launch, no pad columns needed)
+            w16, wt_kc = K.permute_k(w16.view(w.shape[0], -1), k_perm[0], k_perm[1], transposed=True)
+        else:
+            w16 = K.permute_k(w16.view(w.shape[0], -1), k_perm[0], k_perm[1])
+    return _Linear.apply(x, w, b, w16, out_f32, wt_kc, k_perm)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -712,18 +767,24 @@ class _CTCLoss(torch.autograd.Function):
     alpha/beta lattice kept in the workspace."""
 
     @staticmethod
-    def forward(ctx, logits, targets, in_len, tgt_len, B, T, blank, zero_infinity):
+    def forward(ctx, logits, targets, in_len, tgt_len, B, T, blank, zero_infinity, clean=False):
+        """clean: the first output is the zero_infinity value (0 where the loss is infinite) from the loss kernel itself; the
+        raw per-utterance loss is kept for the backward pass either way."""
         M, V = logits.shape
         assert M == B * T
         if logits.stride(1) != 1:
             logits = logits.contiguous()
         Lmax = targets.shape[1]
         lprobs = K.log_softmax(logits, M, V, logits.stride(0))
-        nll, ws = K.ctc_loss_fwd(lprobs, targets, in_len, tgt_len, B, T, V, Lmax, blank)
+        if clean:
+            nll, ws, out = K.ctc_loss_fwd(lprobs, targets, in_len, tgt_len, B, T, V, Lmax, blank, clean=True)
+        else:
+            nll, ws = K.ctc_loss_fwd(lprobs, targets, in_len, tgt_len, B, T, V, Lmax, blank)
+            out = nll
         ctx.save_for_backward(lprobs, ws, nll, targets, in_len, tgt_len)
         ctx.cfg = (B, T, V, Lmax, blank, zero_infinity, logits.dtype)
         ctx.mark_non_differentiable(lprobs)
-        return nll, lprobs
+        return out, lprobs
 
     @staticmethod
     def backward(ctx, dnll, _dlp):
@@ -731,18 +792,23 @@ class _CTCLoss(torch.autograd.Function):
         B, T, V, Lmax, blank, zero_infinity, dt = ctx.cfg
         # The criterion reduces nll with a plain sum, so dnll is one scalar broadcast over B; it is
         # applied on the device from dnll[0] (no host sync).
-        scale_dev = dnll.float().contiguous()
+        scale_dev = dnll.float()[:1].contiguous()  # (one element of the sum's expanded gradient: a view, no copy launch)
         bf = dt == torch.bfloat16
-        ld = _pad8(V) if bf else V
+        # bf16: rows at a pitch of a multiple of 64 with zeros behind column V, so that the output projection's data gradient
+        # can reduce over the padded pitch with both operands k-contiguous (_Linear.backward)
+        ld = _pad_dgrad(V) if bf else V
         dl = K.ctc_loss_grad(lprobs, ws, nll, targets, in_len, tgt_len, B, T, V, Lmax, blank, ld_out=ld, grad_bf16=bf,
                              grad_scale=1.0, grad_scale_dev=scale_dev, zero_infinity=zero_infinity)
-        return (dl if ld == V else dl[:, :V]), None, None, None, None, None, None, None
+        g = dl if ld == V else dl[:, :V]
+        if bf:
+            g._ea_zero_pad = ld
+        return g, None, None, None, None, None, None, None, None
 
 
-def ctc_loss(logits, targets, in_len, tgt_len, B, T, blank=0, zero_infinity=True):
+def ctc_loss(logits, targets, in_len, tgt_len, B, T, blank=0, zero_infinity=True, clean=False):
     """(nll [B], lprobs [B*T][V]).  NOTE: backward assumes a uniform upstream weight over utterances
-    (reduction='sum' as in espresso/criterions/ctc_loss.py:85-94)."""
-    return _CTCLoss.apply(logits, targets, in_len, tgt_len, B, T, blank, zero_infinity)
+    (reduction='sum' as in espresso/criterions/ctc_loss.py:85-94).  clean: nll holds 0 where the loss is infinite."""
+    return _CTCLoss.apply(logits, targets, in_len, tgt_len, B, T, blank, zero_infinity, clean)
 
 
 class _LabelSmoothedCE(torch.autograd.Function):

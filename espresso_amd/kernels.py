@@ -431,19 +431,81 @@ def log_softmax(x, M, V, ld):
     return out
 
 
-def ctc_loss_fwd(lprobs, targets, in_len, tgt_len, B, T, V, Lmax, blank):
-    """lprobs fp32 [B][T][V] -> (nll[B], workspace holding the gathered lattice + alpha + beta)."""
+def ctc_loss_fwd(lprobs, targets, in_len, tgt_len, B, T, V, Lmax, blank, clean=False):
+    """lprobs fp32 [B][T][V] -> (nll[B], workspace holding the gathered lattice + alpha + beta); with `clean` also
+    nll_clean[B] = 0 where nll is infinite, else nll (the criterion's zero_infinity value): (nll, ws, nll_clean)."""
     assert lprobs.dtype == torch.float32 and lprobs.is_contiguous()
     assert targets.dtype == torch.int32 and in_len.dtype == torch.int32 and tgt_len.dtype == torch.int32
+    assert targets.is_contiguous() and in_len.is_contiguous() and tgt_len.is_contiguous()
+    assert targets.numel() >= B * Lmax and in_len.numel() >= B and tgt_len.numel() >= B
     dev = lprobs.device
     nll = torch.empty(B, dtype=torch.float32, device=dev)
+    nll_clean = torch.empty(B, dtype=torch.float32, device=dev) if clean else None
     ws = torch.empty(int(_lib.lib().ea_ctc_workspace_bytes(B, T, Lmax)), dtype=torch.uint8, device=dev)
     check(
-        _lib.lib().ea_ctc_loss(_p(lprobs), _p(targets), _p(in_len), _p(tgt_len), _p(nll), _p(ws), B, T, V, Lmax, blank,
-                               _stream()),
-        "ea_ctc_loss",
+        _lib.lib().ea_ctc_loss_clean(_p(lprobs), _p(targets), _p(in_len), _p(tgt_len), _p(nll), _p(nll_clean), _p(ws), B, T, V,
+                                     Lmax, blank, _stream()),
+        "ea_ctc_loss_clean",
     )
-    return nll, ws
+    return (nll, ws, nll_clean) if clean else (nll, ws)
+
+
+def ctc_targets(target, pad, eos):
+    """target int64 [B][L] -> (int32 [B][L] copy, int32 [B] count of the entries that are neither pad nor eos), one launch."""
+    assert target.dtype == torch.int64 and target.dim() == 2 and target.is_contiguous()
+    B, L = target.shape
+    tgt32 = torch.empty(B, L, dtype=torch.int32, device=target.device)
+    tgt_len = torch.empty(B, dtype=torch.int32, device=target.device)
+    check(_lib.lib().ea_ctc_targets(_p(target), _p(tgt32), _p(tgt_len), B, L, int(pad), int(eos), _stream()), "ea_ctc_targets")
+    return tgt32, tgt_len
+
+
+def subsample_lengths(src_lengths, total, Tp):
+    """src_lengths int64 [B] -> (x_lengths int64 [B] = ceil(src / total), key_len int32 [B], padding_mask bool [B][Tp],
+    row_zero uint8 [B*Tp]), one launch."""
+    assert src_lengths.dtype == torch.int64 and src_lengths.dim() == 1 and src_lengths.is_contiguous()
+    B, dev = src_lengths.numel(), src_lengths.device
+    x_len = torch.empty(B, dtype=torch.int64, device=dev)
+    key_len = torch.empty(B, dtype=torch.int32, device=dev)
+    mask = torch.empty(B, Tp, dtype=torch.bool, device=dev)
+    row_zero = torch.empty(B * Tp, dtype=torch.uint8, device=dev)
+    check(_lib.lib().ea_subsample_lengths(_p(src_lengths), _p(x_len), _p(key_len), _p(mask), _p(row_zero), B, Tp, int(total),
+                                          _stream()), "ea_subsample_lengths")
+    return x_len, key_len, mask, row_zero
+
+
+def stats_add4(stats, a0, loss, a2, a3):
+    """stats[0:4] += (a0, loss[0], a2, a3) in fp32, one launch; `loss` is a one-element fp32 device tensor."""
+    assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() >= 4
+    assert loss.dtype == torch.float32 and loss.numel() == 1
+    check(_lib.lib().ea_stats_add4(_p(stats), float(a0), _p(loss), float(a2), float(a3), _stream()), "ea_stats_add4")
+    return stats
+
+
+def transpose_pad(src, dst, rows, cols, ld_dst):
+    """dst bf16 [cols][ld_dst]: dst[c][r] = src[r][c] for r < rows, zero for rows <= r < ld_dst (src dense [rows][cols])."""
+    assert src.dtype == torch.bfloat16 and dst.dtype == torch.bfloat16 and src.is_contiguous() and dst.is_contiguous()
+    assert src.numel() == rows * cols and dst.numel() == cols * ld_dst and ld_dst >= rows
+    check(_lib.lib().ea_transpose_pad_bf16(_p(src), _p(dst), rows, cols, ld_dst, _stream()), "ea_transpose_pad_bf16")
+    return dst
+
+
+def permute_k(src, C, F, transposed=False):
+    """bf16 [N][C*F] with the input axis in (c*F + f) order -> the same weight in (f*C + c) order; with `transposed` also its
+    transpose [F*C][N] from the same launch: (permuted, transposed)."""
+    assert src.dtype == torch.bfloat16 and src.is_contiguous() and src.dim() == 2 and src.shape[1] == C * F
+    dst = torch.empty_like(src)
+    dst_t = torch.empty(C * F, src.shape[0], dtype=torch.bfloat16, device=src.device) if transposed else None
+    check(_lib.lib().ea_permute_k_bf16(_p(src), _p(dst), _p(dst_t), src.shape[0], C, F, _stream()), "ea_permute_k_bf16")
+    return (dst, dst_t) if transposed else dst
+
+
+def unpermute_k_add(src, dst, N, C, F):
+    """dst fp32 [N][C*F] ((c*F + f) order) += src fp32 [N][F*C] ((f*C + c) order)."""
+    assert src.dtype == torch.float32 and dst.dtype == torch.float32 and src.is_contiguous() and dst.is_contiguous()
+    assert src.numel() == N * C * F and dst.numel() == N * C * F
+    check(_lib.lib().ea_unpermute_k_add_f32(_p(src), _p(dst), N, C, F, _stream()), "ea_unpermute_k_add_f32")
+    return dst
 
 
 def ctc_loss_grad(lprobs, ws, nll, targets, in_len, tgt_len, B, T, V, Lmax, blank, ld_out=None, grad_bf16=True,

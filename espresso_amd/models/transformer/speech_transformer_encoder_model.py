@@ -173,6 +173,11 @@ class SpeechTransformerEncoderBase(nn.Module):
             table = self._sin_table
         return F.add_positions(x, table, pos, self.embed_scale)
 
+    def _refresh_output_transpose(self, train):
+        """Hook of encoders with an output projection (below): True when a copy was refreshed on the Python-side stream (only
+        for a training pass; any other pass drops a copy left over from one that never reached the projection)."""
+        return False
+
     def _fc0_weight(self):
         """fc0 consumes (c*F' + f)-ordered features in the reference; the channels-last sub-sampler
         emits f*C + c, so the weight's input axis is permuted once per call (autograd un-permutes)."""
@@ -192,7 +197,12 @@ class SpeechTransformerEncoderBase(nn.Module):
         x, x_lengths, padding_mask, row_zero = self.pre_encoder(src_tokens, src_lengths, p_drop=p if self.fc0 is not None else 0.0)
         Tp = padding_mask.shape[1]
         if self.fc0 is not None:
-            x = F.linear(x, self._fc0_weight(), self.fc0.bias)
+            if x.is_cuda:
+                # (the weight stays the leaf: one native launch permutes its bf16 shadow, the gradient is un-permuted into place)
+                C0 = self.pre_encoder.out_channels[-1]
+                x = F.linear(x, self.fc0.weight, self.fc0.bias, k_perm=(C0, self.fc0.weight.shape[1] // C0))
+            else:
+                x = F.linear(x, self._fc0_weight(), self.fc0.bias)
         if self.abs_positions or self.embed_scale != 1.0:
             x = self._add_positions(x, padding_mask)
         if self.layernorm_embedding is not None:
@@ -202,17 +212,28 @@ class SpeechTransformerEncoderBase(nn.Module):
                 x = F.dropout(x, p)
             if row_zero is not None:
                 x = F.zero_rows(x, row_zero)
-        key_len = x_lengths.to(torch.int32).contiguous()
+        key_len = getattr(self.pre_encoder, "_key_len", None)  # (int32 lengths from the sub-sampler's own bookkeeping launch)
+        if key_len is None:
+            key_len = x_lengths.to(torch.int32).contiguous()
+        self._key_len = key_len
         attn_mask = self.get_attn_mask(Tp, x.device, in_lengths=x_lengths)
         states = [x] if return_all_hiddens else []
         # LayerDrop (fairseq/modules/layer_drop.py:38-44: one uniform draw per layer per forward, layer kept when the draw exceeds p)
         ld = float(getattr(cfg.encoder, "layerdrop", 0.0) or 0.0)
         keep = torch.empty(len(self.layers)).uniform_() > ld if (tr and ld > 0) else None
         wt_event = None
-        if tr and torch.is_grad_enabled() and x.is_cuda:
+        train_pass = bool(tr and torch.is_grad_enabled() and x.is_cuda)
+        if not train_pass:
+            self._refresh_output_transpose(False)
+        if train_pass:
             native = [l for i, l in enumerate(self.layers) if (keep is None or bool(keep[i])) and _native_conformer(l)]
-            if native:  # transposed weight copies of the backward pass: refreshed off the compute stream, under this forward pass
+            # transposed weight copies of the backward pass: refreshed off the compute stream, under this forward pass (first the
+            # output projection's, so that the layers' event covers it)
+            out_fresh = self._refresh_output_transpose(True)
+            if native:
                 wt_event = F.refresh_layer_transposes(native, B, Tp)
+            if wt_event is None and out_fresh:
+                wt_event = F._side_stream(x.device).record_event()
         if self.pending_update is not None:
             # the trainer left the optimizer pass over the layers' and fc_out's parameters running on the side stream, under the
             # front-end and the sub-sampler above (Trainer.train_step): from here on this stream reads what it writes
@@ -271,6 +292,7 @@ class SpeechTransformerEncoderBase(nn.Module):
         out["src_lengths"] = [l.index_select(0, new_order) for l in encoder_out["src_lengths"]]
         out["encoder_states"] = [s.index_select(1, new_order) for s in encoder_out["encoder_states"]]
         out.pop("_x_bt", None)
+        out.pop("_src_lengths_i32", None)
         return out
 
 
@@ -288,6 +310,15 @@ class SpeechTransformerEncoderForPrediction(SpeechTransformerEncoderBase):
         super().__init__(cfg, pre_encoder=pre_encoder, input_size=input_size)
         self.fc_out = LinearParams(cfg.encoder.embed_dim, vocab_size) if vocab_size is not None else None
 
+    def _refresh_output_transpose(self, train):
+        if self.fc_out is None:
+            return False
+        self.fc_out.weight.__dict__.pop("_ea_wt_kc_fresh", None)  # (a copy no forward call consumed is not current any more)
+        if not train:
+            return False
+        self.start_pending_update()  # (a held optimizer pass writes the weight's bf16 shadow on the same stream: it goes first)
+        return F.refresh_dgrad_weight(self.fc_out.weight)
+
     def forward(self, src_tokens, src_lengths, return_all_hiddens=False):
         out = super().forward(src_tokens, src_lengths, return_all_hiddens=return_all_hiddens)
         if self.fc_out is not None:
@@ -302,6 +333,7 @@ class SpeechTransformerEncoderForPrediction(SpeechTransformerEncoderBase):
             V = logits.shape[1]
             out["encoder_out"] = [logits.view(B, Tp, V).transpose(0, 1)]  # T x B x V
             out["_logits_bt"] = [logits]
+            out["_src_lengths_i32"] = [self._key_len]  # (the criterion's input lengths, already int32: no cast launch there)
         return out
 
 

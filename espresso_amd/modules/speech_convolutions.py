@@ -4,6 +4,7 @@ import torch
 import torch.nn as nn
 
 from .. import functional as F
+from .. import kernels as K
 from .params import BatchNormParams, ConvParams
 
 
@@ -44,6 +45,18 @@ class ConvBNReLU(nn.Module):
                 out = (out + s - 1) // s
         return out
 
+    def lengths_and_masks(self, src_lengths, Tp):
+        """(lengths' int64 [B], the same as int32 or None, padding_mask bool [B][T'], row_zero uint8 [B*T']): one launch for device
+        lengths, the torch expressions (None for the int32 copy) elsewhere."""
+        if src_lengths.is_cuda and src_lengths.dtype == torch.int64 and src_lengths.dim() == 1:
+            total = 1
+            for stride in self.strides:
+                total *= self._stride2(stride)[0]
+            return K.subsample_lengths(src_lengths.contiguous(), total, Tp)
+        x_lengths = self.output_lengths(src_lengths)
+        padding_mask = torch.arange(Tp, device=src_lengths.device).unsqueeze(0) >= x_lengths.unsqueeze(1)
+        return x_lengths, None, padding_mask, padding_mask.reshape(-1).to(torch.uint8).contiguous()
+
     def output_feat_dim(self, feat_dim):
         f = feat_dim
         for stride in self.strides:
@@ -54,13 +67,12 @@ class ConvBNReLU(nn.Module):
     def forward(self, src, src_lengths, p_drop=0.0):
         """src fp32 [B][T][F]; returns (x bf16 [B*T'][F'*C] (feature index f*C + c), lengths', padding_mask [B][T'])."""
         B, T, _ = src.shape
-        x_lengths = self.output_lengths(src_lengths)
         Tp = (T + 0)
         for stride in self.strides:
             s = self._stride2(stride)[0]
             Tp = (Tp + s - 1) // s
-        padding_mask = torch.arange(Tp, device=src.device).unsqueeze(0) >= x_lengths.unsqueeze(1)
-        row_zero = padding_mask.reshape(-1).to(torch.uint8).contiguous()
+        # (_key_len: the int32 lengths, picked up by the encoder for the attention and loss kernels)
+        x_lengths, self._key_len, padding_mask, row_zero = self.lengths_and_masks(src_lengths, Tp)
         params, bufs = [], []
         for conv, bn in zip(self.convolutions, self.batchnorms):
             params += [conv.weight, conv.bias, bn.weight, bn.bias]

@@ -10,6 +10,7 @@ import torch
 import torch.distributed as dist
 
 from . import functional as F
+from . import kernels as K
 from .distributed.overlapped_ddp import OverlappedDistributedDataParallel
 from .optim.adam import FlatAdam
 from .optim.flat import FlatParams
@@ -117,11 +118,16 @@ class Trainer:
                 return None
             if dummy:
                 continue
-            # (in-place adds on one-element views: `stats[i] += x` would be view + add + copy-back, two launches each)
-            self._stats[0:1].add_(float(sample_size))
-            self._stats[1:2].add_(loss.detach().reshape(1))
-            self._stats[2:3].add_(float(log["ntokens"]))
-            self._stats[3:4].add_(float(log["nsentences"]))
+            if self._stats.is_cuda:
+                # the four running sums in one launch (the loss is read from its device tensor: no host read)
+                K.stats_add4(self._stats, float(sample_size), loss.detach().reshape(1).float(), float(log["ntokens"]),
+                             float(log["nsentences"]))
+            else:
+                # (in-place adds on one-element views: `stats[i] += x` would be view + add + copy-back, two launches each)
+                self._stats[0:1].add_(float(sample_size))
+                self._stats[1:2].add_(loss.detach().reshape(1))
+                self._stats[2:3].add_(float(log["ntokens"]))
+                self._stats[3:4].add_(float(log["nsentences"]))
         if self.ddp.active:
             if self.world_size > 1 and self.last_coef is not None:
                 # fairseq/trainer.py:1451-1488 _check_grad_norms: every rank must have clipped the SAME gradient norm (they

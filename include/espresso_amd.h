@@ -232,6 +232,22 @@ int ea_audio_read_batch_i16(const char* const* paths, int n, int16_t* dst, const
  * (espresso/models/transformer/speech_transformer_encoder_model.py:207-208 fc_out, torch autograd of F.linear). */
 int ea_cast_f32_to_bf16_rows(const float* src, long ld_src, void* dst, long ld_dst, long M, int N, ea_stream_t stream);
 int ea_cast_bf16_to_f32(const void* src, float* dst, long n, ea_stream_t stream);
+/* Per-step bookkeeping of the training step, one launch each instead of a handful of framework element-wise launches.
+ * ea_subsample_lengths: src_len int64 [B] -> x_len int64 [B] = floor((src_len + total - 1) / total) (the sub-sampler's output
+ *   lengths, total = product of its time strides), key_len int32 [B] the same numbers, pad_mask [B][Tp] and row_zero [B*Tp]
+ *   one byte each = (t >= x_len[b]).
+ * ea_stats_add4: stats[0] += a0, stats[1] += loss[0] (device scalar), stats[2] += a2, stats[3] += a3 (fp32).
+ * ea_transpose_pad_bf16: dst[c][r] = src[r][c] for r < rows and 0 for rows <= r < ld_dst (src dense [rows][cols], dst
+ *   [cols][ld_dst]): the k-contiguous copy of the output projection's weight with the reduction axis padded with zeros.
+ * ea_permute_k_bf16: dst[n][f*C + c] = src[n][c*F + f] and, when dst_t is not NULL, dst_t[f*C + c][n] the same (the k-contiguous
+ *   operand of the data gradient); ea_unpermute_k_add_f32: dst[n][c*F + f] += src[n][f*C + c] (the input
+ *   axis of fc0 between the reference's channel-major order and the channels-last sub-sampler's, and its gradient back). */
+int ea_subsample_lengths(const long* src_len, long* x_len, int* key_len, void* pad_mask, void* row_zero, int B, int Tp, int total,
+                         ea_stream_t stream);
+int ea_stats_add4(float* stats, float a0, const float* loss, float a2, float a3, ea_stream_t stream);
+int ea_transpose_pad_bf16(const void* src, void* dst, int rows, int cols, long ld_dst, ea_stream_t stream);
+int ea_permute_k_bf16(const void* src, void* dst, void* dst_t, int N, int C, int F, ea_stream_t stream);
+int ea_unpermute_k_add_f32(const float* src, float* dst, int N, int C, int F, ea_stream_t stream);
 /* out = a*x*keep(idx) + b*y  (bf16; y may be NULL: read as +0, which decides the sign of a zero result) */
 int ea_scale_dropout_bf16(const void* x, const void* y, void* out, long n, float a, float b, uint64_t seed,
                           uint32_t thr, float inv_keep, ea_stream_t stream);
@@ -409,6 +425,13 @@ int ea_log_softmax_bf16(const void* in, long ld_in, float* out, long M, int V, e
 long ea_ctc_workspace_bytes(int B, int T, int Lmax);
 int ea_ctc_loss(const float* lprobs, const int* targets, const int* in_len, const int* tgt_len, float* nll,
                 void* workspace, int B, int T, int V, int Lmax, int blank, ea_stream_t stream);
+/* ea_ctc_loss with a second per-utterance output (may be NULL): nll_clean[b] = 0 where nll[b] is infinite, else nll[b] — the
+ * criterion's zero_infinity value; nll keeps the raw value, which ea_ctc_grad tests.
+ * ea_ctc_targets: target int64 [B][L] -> tgt32 int32 [B][L] (same values) and tgt_len int32 [B] = entries that are neither pad
+ * nor eos (espresso/criterions/ctc_loss.py:66-68). */
+int ea_ctc_loss_clean(const float* lprobs, const int* targets, const int* in_len, const int* tgt_len, float* nll,
+                      float* nll_clean, void* workspace, int B, int T, int V, int Lmax, int blank, ea_stream_t stream);
+int ea_ctc_targets(const long* target, int* tgt32, int* tgt_len, int B, int L, int pad, int eos, ea_stream_t stream);
 /* backward of ea_ctc_loss: reads the lattice left in `workspace`; grad_scale_dev (device fp32 scalar,
  * may be NULL) multiplies grad_scale — the autograd grad_output, without a host sync. */
 int ea_ctc_grad(const float* lprobs, const void* workspace, const float* nll, const int* targets,
