@@ -4,45 +4,23 @@
 // workgroup per utterance, workgroups never talk to each other.
 //
 // ctc_viterbi_kernel: the lattice of ea_ctc_loss (blank y1 blank ... yU blank, S = 2U + 1 states), max instead of logsumexp.
-//   Thread i owns states 16i .. 16i + 15; the score vector lives in LDS, double-buffered, one barrier per frame.  The U + 1
-//   columns a frame needs (blank + the thread's 8 target labels) are requested four frames ahead into four register sets, every
-//   lane loading from a clamped frame / column (no load in a divergent branch: hipcc would wait vmcnt(0) for it).
-//   Backpointers: 2 bits per state (0 stay, 1 from s-1, 2 from s-2), 16 states per 32-bit word, one vector store per thread and
-//   frame into the workspace.  The backtrace streams blocks of frames' backpointer rows into LDS with coalesced loads and one
-//   lane walks them there.
+//   Thread layout, prefetch and the max-plus frame update (viterbi_frame) are ctc_lattice.h's.  This kernel's own: the
+//   backpointers, 2 bits per state (0 stay, 1 from s-1, 2 from s-2), 16 states per 32-bit word, one vector store per thread and
+//   frame into the workspace, and the backtrace, which streams blocks of frames' backpointer rows into LDS with coalesced loads
+//   while one lane walks them there.
 // rnnt_viterbi_kernel: the (t,u) lattice of ea_rnnt_scan, swept backwards (best score FROM each node) along anti-diagonals, one
 //   lane per u, so that the decision at a node is about its successor: 1 bit per node (1 = emit, 0 = blank), ballot-packed per
 //   wave, one row per diagonal.  The walk then goes forwards from (0,0) through blocks of rows staged in LDS the same way.
 #include "common.h"
+#include "ctc_lattice.h"
 #include "espresso_amd.h"
 
 namespace {
 
-constexpr int kCtcMaxS = 2048;    // states per utterance (Lmax <= 1023)
 constexpr int kCtcMaxW = kCtcMaxS / 16;
 constexpr int kCtcBlk = 32;       // backpointer rows staged per backtrace block
 constexpr int kRnntMaxU1 = 1024;  // lanes (one per u)
 constexpr int kRnntBlk = 64;      // diagonals staged per walk block
-
-__host__ __device__ __forceinline__ int ctc_words(int Lmax) {  // backpointer words per frame row (pitch, a multiple of 64)
-  const int w = (2 * Lmax + 1 + 15) / 16;
-  return (w + 63) & ~63;
-}
-
-template <typename TX>
-__device__ __forceinline__ float ldx(const TX* p, long i) {
-  if constexpr (sizeof(TX) == 2) return bf2f(p[i]); else return p[i];
-}
-
-// the columns one thread needs in one frame: blank and the labels of its 8 odd states
-struct Emis {
-  float b, y[8];
-};
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the LDS hand-off only: prefetched global loads stay in flight
-  __builtin_amdgcn_s_barrier();
-}
 
 template <typename TX>
 __global__ __launch_bounds__(128) void ctc_viterbi_kernel(const TX* __restrict__ x, long ld, const int* __restrict__ targets,
@@ -63,21 +41,9 @@ __global__ __launch_bounds__(128) void ctc_viterbi_kernel(const TX* __restrict__
   int* ts = tok_start + (long)b * Lmax;
   int* te = tok_end + (long)b * Lmax;
 
-  // labels of this thread's odd states 16i + 2k + 1 (token u = 8i + k), clamped to a valid column; bit k of `skip`: the +2 move
-  // into that state is allowed (its label differs from the one two states earlier)
   int col[8];
-  unsigned skip = 0u;
-  int bad = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int u = 8 * i + k;
-    const int uc = min(u, max(U - 1, 0));
-    const int y = tg[uc], yp = tg[max(uc - 1, 0)];
-    const bool real = u < U;
-    bad |= real && (y < 0 || y >= V || y == blank);
-    col[k] = (real && y >= 0 && y < V) ? y : blank;
-    if (real && u > 0 && y != yp) skip |= 1u << k;
-  }
+  unsigned skip;
+  const int bad = ctc_labels(tg, i, U, V, blank, col, skip);
   for (int u = i; u < Lmax; u += nt) { ts[u] = -1; te[u] = -1; }
   for (int t = i; t < T; t += nt) fl[t] = -2;
   if (__syncthreads_or(bad)) {  // a target id outside [0, V) or equal to blank: reported (score NaN), not aligned
@@ -90,49 +56,19 @@ __global__ __launch_bounds__(128) void ctc_viterbi_kernel(const TX* __restrict__
   }
 
   const TX* xb = x + (long)b * T * ld;
-  auto fetch = [&](int t, Emis& e) {
-    const TX* r = xb + (long)min(t, L - 1) * ld;
-    e.b = ldx(r, blank);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) e.y[k] = ldx(r, col[k]);
-  };
+  auto fetch = [&](int t, Emis& e) { ctc_fetch(xb + (long)min(t, L - 1) * ld, blank, col, e); };
   float* prev = s_a[0];
   float* cur = s_a[1];
   const int s0 = 16 * i;
   uint32_t* bprow = bp + (long)b * (T + 3) * Wp + i;
 
-  // one frame: new[s] = max(stay, +1, +2) + x[t][label(s)]; ties prefer stay, then +1.  The loop runs L rounded up to 4 frames
-  // without a branch (a branch here costs the prefetch: hipcc then moves the pending registers, i.e. waits for them); frames
-  // from L on keep the scores (their backpointer rows L .. L+2 are padding rows of the workspace)
+  // one frame.  The loop runs L rounded up to 4 frames; frames from L on keep the scores (their backpointer rows L .. L+2 are
+  // padding rows of the workspace)
   auto step = [&](int t, Emis& q) {
-    const bool live = t < L;
-    const Emis& e = q;
-    float p[18];
-#pragma unroll
-    for (int j = 0; j < 18; j += 2) {
-      const float2 v = *reinterpret_cast<const float2*>(prev + s0 + j);
-      p[j] = v.x; p[j + 1] = v.y;
-    }
-    uint32_t word = 0u;
     float o[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int s = s0 + j;
-      const float st = p[j + 2], m1 = p[j + 1];
-      const float m2 = ((j & 1) && ((skip >> (j >> 1)) & 1u)) ? p[j] : -INFINITY;
-      float best = st;
-      uint32_t c = 0u;
-      if (m1 > best) { best = m1; c = 1u; }
-      if (m2 > best) { best = m2; c = 2u; }
-      float v;
-      if (t == 0) v = s == 0 ? e.b : (s == 1 && S > 1 ? e.y[0] : -INFINITY);
-      else v = best + ((j & 1) ? e.y[j >> 1] : e.b);
-      o[j] = live ? (s < S ? v : -INFINITY) : st;
-      word |= c << (2 * j);
-    }
-    fetch(t + 4, q);  // (after the last use of the set: the load can then take the same registers, no copy that waits for it)
-#pragma unroll
-    for (int j = 0; j < 16; j += 2) *reinterpret_cast<float2*>(cur + s0 + 2 + j) = make_float2(o[j], o[j + 1]);
+    const uint32_t word = viterbi_frame(prev + s0, q, skip, s0, S, t, t < L, o);
+    fetch(t + 4, q);
+    ctc_store(cur + s0 + 2, o);
     bprow[(long)t * Wp] = word;
     lds_barrier();
     float* tmp = prev; prev = cur; cur = tmp;
@@ -141,10 +77,7 @@ __global__ __launch_bounds__(128) void ctc_viterbi_kernel(const TX* __restrict__
   // frame -1: every state -inf (frame 0 does not use it, but reads it)
   for (int s = i; s < kCtcMaxS + 2; s += nt) { s_a[0][s] = -INFINITY; s_a[1][s] = -INFINITY; }
   Emis q0, q1, q2, q3;
-  fetch(0, q0);
-  fetch(1, q1);
-  fetch(2, q2);
-  fetch(3, q3);
+  ctc_prefetch(fetch, 0, q0, q1, q2, q3);
   __syncthreads();
   for (int t = 0; t < L; t += 4) {
     step(t, q0);
@@ -287,7 +220,7 @@ __global__ __launch_bounds__(1024) void rnnt_viterbi_kernel(const float* __restr
 
 extern "C" long ea_ctc_viterbi_workspace_bytes(int B, int T, int Lmax) {
   if (B <= 0 || T < 0 || Lmax < 1 || 2 * Lmax + 1 > kCtcMaxS) return 0;
-  return 4L * B * (T + 3) * ctc_words(Lmax);  // (3 padding rows per utterance, see step)
+  return 4L * B * (T + 3) * ctc_threads(Lmax);  // (3 padding rows per utterance, see step)
 }
 
 extern "C" int ea_ctc_viterbi_align(const void* x, long ld, int x_bf16, const int* targets, const int* in_len, const int* tgt_len,
@@ -295,7 +228,7 @@ extern "C" int ea_ctc_viterbi_align(const void* x, long ld, int x_bf16, const in
                                     int V, int Lmax, int blank, hipStream_t stream) {
   if (B <= 0) return 0;
   if (T < 0 || V < 1 || ld < V || Lmax < 1 || 2 * Lmax + 1 > kCtcMaxS || blank < 0 || blank >= V) return -2;
-  const int Wp = ctc_words(Lmax);  // = threads per workgroup (64 or 128)
+  const int Wp = ctc_threads(Lmax);  // backpointer words per frame row = threads per workgroup
   if (x_bf16)
     hipLaunchKernelGGL(ctc_viterbi_kernel<bf16_t>, dim3(B), dim3(Wp), 0, stream, (const bf16_t*)x, ld, targets, in_len, tgt_len,
                        (uint32_t*)workspace, tok_start, tok_end, frame_label, score, T, V, Lmax, blank, Wp);

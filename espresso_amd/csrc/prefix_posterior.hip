@@ -7,44 +7,20 @@
 // total - Psi_U that of stopping, and the factors add up to total = log P(y | x) = -(CTC / RNN-T loss).  Both kernels are
 // latency chains: one workgroup per hypothesis, workgroups never talk to each other, no workspace (alpha is not stored).
 //
-// ctc_prefix_kernel: the lattice and the layout of ctc_viterbi_kernel (thread i owns states 16i .. 16i + 15, double-buffered LDS
-//   score vector, one barrier per frame, the U + 1 columns of a frame requested four frames ahead from clamped cells), log-add-exp
-//   where the aligner takes the max.  Every odd state (token u) keeps one more accumulator in a register: the log-sum over frames
-//   of the mass ENTERING the state (from the blank before it and, where the labels differ, from the token before it) times the
-//   frame's emission — the self-loop is left out, so that every alignment of the prefix is counted once, at the frame where its
-//   last token starts.  Hypothesis n reads the log-probs of utterance utt[n]: an n-best list shares its utterance's rows.
+// ctc_prefix_kernel: the lattice, thread layout and prefetch of ctc_viterbi_kernel (ctc_lattice.h), log-add-exp where the aligner
+//   takes the max: the sum-product frame update is prefix_frame there.  Every odd state (token u) keeps one more accumulator in a
+//   register: the log-sum over frames of the mass ENTERING the state times the frame's emission, the self-loop left out.  This
+//   kernel's own: the early exits and the factors from Psi.  Hypothesis n reads the log-probs of utterance utt[n]: an n-best list
+//   shares its utterance's rows.
 // rnnt_prefix_kernel: the forward half of rnnt_scan_kernel along anti-diagonals, one lane per u.  Lane u holds alpha(t,u), hands
 //   alpha(t,u) + lpy(t,u) to lane u + 1 through LDS and adds the same value to its accumulator: Psi_{u+1} = lse_t of it.
 #include "common.h"
+#include "ctc_lattice.h"
 #include "espresso_amd.h"
-#include "prefix_math.h"
 
 namespace {
 
-constexpr int kCtcMaxS = 2048;    // states per hypothesis (Lmax <= 1023)
 constexpr int kRnntMaxU1 = 1024;  // lanes (one per u)
-
-__host__ __device__ __forceinline__ int ctc_threads(int Lmax) {  // one thread per 16 states, whole waves
-  const int w = (2 * Lmax + 1 + 15) / 16;
-  return (w + 63) & ~63;
-}
-
-template <typename TX>
-__device__ __forceinline__ float ldx(const TX* p, long i) {
-  if constexpr (sizeof(TX) == 2) return bf2f(p[i]); else return p[i];
-}
-
-// the columns one thread needs in one frame: blank and the labels of its 8 odd states
-struct Emis {
-  float b, y[8];
-};
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the LDS hand-off only: prefetched global loads stay in flight
-  __builtin_amdgcn_s_barrier();
-}
-
-// lse2, factor and quiet_nan: prefix_math.h, shared with the tiled kernel of prefix_posterior_long.hip
 
 template <typename TX>
 __global__ __launch_bounds__(128) void ctc_prefix_kernel(const TX* __restrict__ x, long ld, const int* __restrict__ targets,
@@ -63,21 +39,9 @@ __global__ __launch_bounds__(128) void ctc_prefix_kernel(const TX* __restrict__ 
   float* lc = logc + (long)n * (Lmax + 1);
   float* po = psi_out ? psi_out + (long)n * Lmax : nullptr;
 
-  // labels of this thread's odd states 16i + 2k + 1 (token u = 8i + k), clamped to a valid column; bit k of `skip`: the +2 move
-  // into that state is allowed (its label differs from the one two states earlier)
   int col[8];
-  unsigned skip = 0u;
-  int bad = bad_utt;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int u = 8 * i + k;
-    const int uc = min(u, max(U - 1, 0));
-    const int y = tg[uc], yp = tg[max(uc - 1, 0)];
-    const bool real = u < U;
-    bad |= real && (y < 0 || y >= V || y == blank);
-    col[k] = (real && y >= 0 && y < V) ? y : blank;
-    if (real && u > 0 && y != yp) skip |= 1u << k;
-  }
+  unsigned skip;
+  const int bad = ctc_labels(tg, i, U, V, blank, col, skip) || bad_utt;
   if (__syncthreads_or(bad)) {  // an id outside [0, V) or equal to blank, or a row outside [0, B): reported as NaN
     for (int u = i; u <= Lmax; u += nt) lc[u] = quiet_nan();
     if (po) for (int u = i; u < Lmax; u += nt) po[u] = quiet_nan();
@@ -93,12 +57,7 @@ __global__ __launch_bounds__(128) void ctc_prefix_kernel(const TX* __restrict__ 
   }
 
   const TX* xb = x + (long)b * T * ld;
-  auto fetch = [&](int t, Emis& e) {
-    const TX* r = xb + (long)min(t, L - 1) * ld;
-    e.b = ldx(r, blank);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) e.y[k] = ldx(r, col[k]);
-  };
+  auto fetch = [&](int t, Emis& e) { ctc_fetch(xb + (long)min(t, L - 1) * ld, blank, col, e); };
   float* prev = s_a[0];
   float* cur = s_a[1];
   const int s0 = 16 * i;
@@ -106,40 +65,12 @@ __global__ __launch_bounds__(128) void ctc_prefix_kernel(const TX* __restrict__ 
 #pragma unroll
   for (int k = 0; k < 8; ++k) psi[k] = -INFINITY;
 
-  // one frame: new[s] = lse(stay, +1, +2) + x[t][label(s)], and for an odd state psi += (+1, +2 mass) * x[t][label].  The loop
-  // runs L rounded up to 4 frames without a branch (a branch here costs the prefetch, see ctc_viterbi_kernel); frames from L on
-  // keep the scores and add nothing
+  // one frame.  The loop runs L rounded up to 4 frames; frames from L on keep the scores and add nothing
   auto step = [&](int t, Emis& q) {
-    const bool live = t < L;
-    const Emis& e = q;
-    float p[18];
-#pragma unroll
-    for (int j = 0; j < 18; j += 2) {
-      const float2 v = *reinterpret_cast<const float2*>(prev + s0 + j);
-      p[j] = v.x; p[j + 1] = v.y;
-    }
     float o[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int s = s0 + j;
-      const float st = p[j + 2], m1 = p[j + 1];
-      float v;
-      if (j & 1) {
-        const int k = j >> 1;
-        const float m2 = ((skip >> k) & 1u) ? p[j] : -INFINITY;
-        float enter = lse2(m1, m2) + e.y[k];
-        v = lse2(st + e.y[k], enter);
-        if (t == 0) { enter = (s == 1 && S > 1) ? e.y[0] : -INFINITY; v = enter; }
-        if (live && s < S) psi[k] = lse2(psi[k], enter);
-      } else {
-        v = lse2(st, m1) + e.b;
-        if (t == 0) v = s == 0 ? e.b : -INFINITY;
-      }
-      o[j] = live ? (s < S ? v : -INFINITY) : st;
-    }
-    fetch(t + 4, q);  // (after the last use of the set: the load can then take the same registers, no copy that waits for it)
-#pragma unroll
-    for (int j = 0; j < 16; j += 2) *reinterpret_cast<float2*>(cur + s0 + 2 + j) = make_float2(o[j], o[j + 1]);
+    prefix_frame(prev + s0, q, skip, s0, S, t, t < L, psi, o);
+    fetch(t + 4, q);
+    ctc_store(cur + s0 + 2, o);
     lds_barrier();
     float* tmp = prev; prev = cur; cur = tmp;
   };
@@ -147,10 +78,7 @@ __global__ __launch_bounds__(128) void ctc_prefix_kernel(const TX* __restrict__ 
   // frame -1: every state -inf (frame 0 does not use it, but reads it)
   for (int s = i; s < kCtcMaxS + 2; s += nt) { s_a[0][s] = -INFINITY; s_a[1][s] = -INFINITY; }
   Emis q0, q1, q2, q3;
-  fetch(0, q0);
-  fetch(1, q1);
-  fetch(2, q2);
-  fetch(3, q3);
+  ctc_prefetch(fetch, 0, q0, q1, q2, q3);
   __syncthreads();
   for (int t = 0; t < L; t += 4) {
     step(t, q0);

@@ -1348,6 +1348,16 @@ def ctc_viterbi_long_tile():
     return frames.value, states.value
 
 
+def _long_workspace(workspace_bytes, T, U, dev, refusal):
+    """The uint8 workspace of a tiled (long-form) CTC entry point, or a ValueError made from `refusal` (a format string over need,
+    free, T and U) when it is larger than the device's free memory."""
+    need = int(workspace_bytes(T, U))
+    free = int(torch.cuda.mem_get_info(dev)[0])
+    if need > free:
+        raise ValueError(refusal.format(need=need, free=free, T=T, U=U))
+    return torch.empty(max(1, need), dtype=torch.uint8, device=dev)
+
+
 def ctc_viterbi_align_long(x, targets, T, V, blank, ld=None):
     """Forced alignment of ONE sequence of any length: targets int32 [U] to x [T][V] fp32/bf16 log-probs (row pitch ld), tiled
     over the device (ea_ctc_viterbi_long_align).  Returns (tok_start int32 [U], tok_end int32 [U], frame_label int32 [T], frame_lp
@@ -1360,12 +1370,9 @@ def ctc_viterbi_align_long(x, targets, T, V, blank, ld=None):
     assert targets.dtype == torch.int32 and targets.is_contiguous() and targets.dim() == 1
     U = targets.numel()
     dev = x.device
-    need = int(_lib.lib().ea_ctc_viterbi_long_workspace_bytes(T, U))
-    free = int(torch.cuda.mem_get_info(dev)[0])
-    if need > free:
-        raise ValueError(f"long-form alignment of T = {T} frames to U = {U} tokens needs a workspace of {need} bytes, the device has "
-                         f"{free} bytes free (2 bits per frame and state; there is no banded search)")
-    ws = torch.empty(max(1, need), dtype=torch.uint8, device=dev)
+    ws = _long_workspace(_lib.lib().ea_ctc_viterbi_long_workspace_bytes, T, U, dev,
+                         "long-form alignment of T = {T} frames to U = {U} tokens needs a workspace of {need} bytes, the device has "
+                         "{free} bytes free (2 bits per frame and state; there is no banded search)")
     tok_start = torch.empty(U, dtype=torch.int32, device=dev)
     tok_end = torch.empty(U, dtype=torch.int32, device=dev)
     frame_label = torch.empty(T, dtype=torch.int32, device=dev)
@@ -1425,12 +1432,9 @@ def ctc_prefix_posteriors_long(x, targets, T, V, blank, ld=None, want_psi=False)
     assert targets.dtype == torch.int32 and targets.is_contiguous() and targets.dim() == 1
     U = targets.numel()
     dev = x.device
-    need = int(_lib.lib().ea_ctc_prefix_long_workspace_bytes(T, U))
-    free = int(torch.cuda.mem_get_info(dev)[0])
-    if need > free:
-        raise ValueError(f"long-form posteriors of U = {U} tokens over T = {T} frames need a workspace of {need} bytes, the device has "
-                         f"{free} bytes free (two scores per frame and tile of states)")
-    ws = torch.empty(max(1, need), dtype=torch.uint8, device=dev)
+    ws = _long_workspace(_lib.lib().ea_ctc_prefix_long_workspace_bytes, T, U, dev,
+                         "long-form posteriors of U = {U} tokens over T = {T} frames need a workspace of {need} bytes, the device has "
+                         "{free} bytes free (two scores per frame and tile of states)")
     logc = torch.empty(U + 1, dtype=torch.float32, device=dev)
     total = torch.empty(1, dtype=torch.float32, device=dev)
     psi = torch.empty(U, dtype=torch.float32, device=dev) if want_psi else None

@@ -85,7 +85,7 @@ def _peaked_lprobs(rng, T, V, sharp=3.0):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("U", [0, 1, 7, 1023])
+@pytest.mark.parametrize("U", [0, 1, 7, 511, 512, 1023])  # (511, 512: S one state short of a state tile, one state into the second)
 def test_bit_identical_to_the_one_workgroup_kernel(U, dtype):
     """Real-valued log-probs: max-plus in fp32 in the same order gives the same bits, so every common output is `torch.equal`
     to ea_ctc_viterbi_align's at B = 1; also from a padded matrix (ld > V) whose pad columns hold NaN."""

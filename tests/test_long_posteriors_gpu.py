@@ -192,7 +192,7 @@ def test_against_the_float64_oracle(frames, dtype_name):
 @pytest.mark.parametrize("frames", ["TB-1", "3TB+5", "10TB+3"])
 @pytest.mark.parametrize("U", [0, 1, 7, 511, 512, 1023])
 def test_bit_identical_to_the_one_workgroup_kernel(U, frames, dtype_name):
-    """Both kernels include csrc/prefix_math.h and do the same fp32 operations in the same order: logc, total and psi are
+    """Both kernels call prefix_frame of csrc/ctc_lattice.h and so do the same fp32 operations in the same order: logc, total and psi are
     `torch.equal` to ea_ctc_prefix_posteriors' at one hypothesis.  U = 512 and 1023 put the +1 / +2 moves and the hand-over of
     the accumulators across the first state-tile border, T = 3 TB + 5 the scores and accumulators across three frame blocks;
     up to T = 3 TB + 5 the frames do not hold 511 tokens and more (early factors finite, the rest -inf in both) and no alignment
