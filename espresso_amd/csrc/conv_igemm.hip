@@ -25,9 +25,6 @@
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 struct ConvGatherArgs {
   const bf16_t* src;   // gathered tensor [RB][ST][SF][SC]
   const bf16_t* W;     // [N][ldw] k-contiguous: k = koff[tap] + channel
@@ -95,11 +92,10 @@ __global__ __launch_bounds__(256, 2) void conv_gather_kernel(const ConvGatherArg
       const int st = rowt[i] + dt, sf = rowf[i] + df;
       const bool ok = rowb[i] >= 0 && (unsigned)st < (unsigned)a.ST && (unsigned)sf < (unsigned)a.SF;
       const bf16_t* s = ok ? a.src + (((long)(rowb[i] + st)) * a.SF + sf) * a.SC + chunk * BK + cs[i] * 8 : a.zero + cs[i] * 8;
-      __builtin_amdgcn_global_load_lds((gptr_t)s, (lptr_t)(base + i * 4096), 16, 0, 0);
+      glds16(s, base + i * 4096);
     }
 #pragma unroll
-    for (int i = 0; i < NB; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(bp[i] + ko), (lptr_t)(base + A_BYTES + i * 4096), 16, 0, 0);
+    for (int i = 0; i < NB; ++i) glds16(bp[i] + ko, base + A_BYTES + i * 4096);
   };
 
   f32x4_t acc[4][NJ];
@@ -119,25 +115,11 @@ __global__ __launch_bounds__(256, 2) void conv_gather_kernel(const ConvGatherArg
   if (nk > 0) issue(0, 0);
   int stage = 0;
   for (int kt = 0; kt < nk; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();  // step kt complete in LDS; everyone is done reading the other stage
     if (kt + 1 < nk) issue(stage ^ 1, kt + 1);
     const char* st = dsm + stage * STAGE;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8_t af[4], bfr[NJ];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const bf16x8_t*>(st + a_off[ks][i]);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bfr[j] = *reinterpret_cast<const bf16x8_t*>(st + b_off[ks][j]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, af[i]),
-              __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, bfr[j]), acc[i][j], 0, 0, 0);
-    }
+    tile_step<NJ>(st, st, a_off, b_off, acc);
     stage ^= 1;
   }
 
@@ -241,7 +223,7 @@ int launch_gather(const ConvGatherArgs& a, hipStream_t stream) {
 // down the rows of a row-major [k][64 channels] image, so both operand tiles go global -> LDS with global_load_lds exactly as
 // they lie in HBM (position rows of 128 bytes; the tap's source rows gathered like in the forward kernel) — no register
 // transposes, no im2col matrix.  Bank swizzle for the transposing reads: 32-byte chunk c of row r is stored at chunk
-// c ^ (r & 3) ^ ((r >> 3) & 1), which makes the 8 rows x 32 bytes one 32-lane read cycle touches hit 64 distinct banks.
+// c ^ tr_sw_rows128(r) (wave_prims.h), which makes the 8 rows x 32 bytes one 32-lane read cycle touches hit 64 distinct banks.
 // Workgroup = 64 cout x 64 cin x all taps over a slice of the positions (split-K): the dZ tile of a 64-position chunk is
 // loaded once and its fragments are kept in registers for the nine tap tiles.  Partial sums go to fp32 slabs, a small second
 // kernel folds them into dW (fp32 atomics: 19 M of them per layer would cost more than the whole product).
@@ -255,20 +237,6 @@ struct ConvWgradArgs {
   int bt[9], bf[9];
   int chunks_per_wg;   // 64-position chunks per workgroup
 };
-
-__device__ __forceinline__ int tr_sw(int r) { return (r & 3) ^ ((r >> 3) & 1); }
-// Eight transposing reads + their wait in ONE asm statement: hipcc does not track the completion of loads issued from inline
-// asm, so the destinations must not be visible to it (copied, spilled) before the data has landed
-// (/opt/skills/guides/cdna_hip_programming.md 5.7 item 1, form (i)).
-__device__ __forceinline__ void ds_read_tr16_x8(const uint32_t (&ad)[8], uint2 (&o)[8]) {
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8\n\tds_read_b64_tr_b16 %1, %9\n\tds_read_b64_tr_b16 %2, %10\n\tds_read_b64_tr_b16 %3, %11\n\t"
-      "ds_read_b64_tr_b16 %4, %12\n\tds_read_b64_tr_b16 %5, %13\n\tds_read_b64_tr_b16 %6, %14\n\tds_read_b64_tr_b16 %7, %15\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(o[6]), "=&v"(o[7])
-      : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]), "v"(ad[4]), "v"(ad[5]), "v"(ad[6]), "v"(ad[7])
-      : "memory");
-}
 
 // A workgroup owns the three taps of one kernel row of its 64 x 64 channel tile (blockIdx.z % 3 picks the row): 48 accumulator
 // registers, four workgroups per CU (round 6, see the launcher)
@@ -302,7 +270,7 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_kernel(const ConvWgradArgs 
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     rr[i] = (wave + 4 * i) * 8 + (lane >> 3);
-    cs[i] = (lane & 7) ^ (tr_sw(rr[i]) << 1);
+    cs[i] = (lane & 7) ^ (tr_sw_rows128(rr[i]) << 1);
   }
   int rowb[2], rowt[2], rowf[2];  // this chunk's two rows: b * ST (or -1), rt * at, rf * af
   long rowp[2];
@@ -326,7 +294,7 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_kernel(const ConvWgradArgs 
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const bf16_t* s = rowb[i] >= 0 ? a.dZ + rowp[i] * a.Cout + co0 + cs[i] * 8 : a.zero + cs[i] * 8;
-      __builtin_amdgcn_global_load_lds((gptr_t)s, (lptr_t)(lds + abuf * TILE + (wave + 4 * i) * 1024), 16, 0, 0);
+      glds16(s, lds + abuf * TILE + (wave + 4 * i) * 1024);
     }
   };
   auto issue_B = [&](int buf, int tap) {  // X rows the decoded chunk's positions read through `tap`
@@ -335,13 +303,13 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_kernel(const ConvWgradArgs 
       const int st = rowt[i] + a.bt[tap0 + tap], sf = rowf[i] + a.bf[tap0 + tap];
       const bool ok = rowb[i] >= 0 && (unsigned)st < (unsigned)a.ST && (unsigned)sf < (unsigned)a.SF;
       const bf16_t* s = ok ? a.X + (((long)(rowb[i] + st)) * a.SF + sf) * a.Cin + ci0 + cs[i] * 8 : a.zero + cs[i] * 8;
-      __builtin_amdgcn_global_load_lds((gptr_t)s, (lptr_t)(lds + (2 + buf) * TILE + (wave + 4 * i) * 1024), 16, 0, 0);
+      glds16(s, lds + (2 + buf) * TILE + (wave + 4 * i) * 1024);
     }
   };
   // transposing fragment reads: tile at byte offset tile_off, the wave's 32 channels [c0, c0 + 32) (two 16-channel tiles) x 64
   // positions (two 32-deep halves) -> fr[ks][tile] = 8 bf16 per lane (k = ks*32 + 8*(lane>>4) + e, channel c0 + 16*tile + (lane&15))
   const uint32_t lds0 = (uint32_t)(uintptr_t)lds;
-  auto read_frags = [&](int tile_off, int c0, uint4 (&fr)[2][2]) {
+  auto read_frags = [&](int tile_off, int c0, bf16x8_t (&fr)[2][2]) {
     const int g = lane >> 4, i = lane & 15;
     uint32_t ad[8];
     uint2 o[8];
@@ -353,13 +321,13 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_kernel(const ConvWgradArgs 
         for (int h = 0; h < 2; ++h) {
           const int r = ks * 32 + 8 * g + (i >> 2) + 4 * h;
           const int chunk = (c0 >> 4) + t;
-          ad[(ks * 2 + t) * 2 + h] = lds0 + tile_off + r * ROW_BYTES + ((chunk ^ tr_sw(r)) << 5) + (i & 3) * 8;
+          ad[(ks * 2 + t) * 2 + h] = lds0 + tile_off + r * ROW_BYTES + ((chunk ^ tr_sw_rows128(r)) << 5) + (i & 3) * 8;
         }
-    ds_read_tr16_x8(ad, o);
+    trr8x1(ad, o);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-      for (int t = 0; t < 2; ++t) fr[ks][t] = make_uint4(o[(ks * 2 + t) * 2].x, o[(ks * 2 + t) * 2].y, o[(ks * 2 + t) * 2 + 1].x, o[(ks * 2 + t) * 2 + 1].y);
+      for (int t = 0; t < 2; ++t) fr[ks][t] = cat2(o[(ks * 2 + t) * 2], o[(ks * 2 + t) * 2 + 1]);
   };
 
   const int nsteps = (int)nch * NT;
@@ -378,14 +346,14 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_kernel(const ConvWgradArgs 
     if (++itap == NT) { itap = 0; ++ich; }
   };
   issue_next();
-  uint4 fa[2][2];  // dZ fragments of the current chunk: [ksub][cout tile]
+  bf16x8_t fa[2][2];  // dZ fragments of the current chunk: [ksub][cout tile]
   long ch = 0;
   int tap = 0;
   for (int s = 0; s < nsteps; ++s) {
     const int tap1 = tap + 1 == NT ? 0 : tap + 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // nothing is issued after this step's X tile
+    wait_vmcnt<0>();  // nothing is issued after this step's X tile
     __builtin_amdgcn_s_barrier();  // this step's tiles are complete in every wavefront's part; everyone is done with step s - 1's X tile
-    uint4 fb[2][2];
+    bf16x8_t fb[2][2];
     if (tap == 0) read_frags((int)(ch & 1) * TILE, wr * 32, fa);
     read_frags((2 + (s & (NBUF - 1))) * TILE, wc * 32, fb);
     __builtin_amdgcn_sched_barrier(0);
@@ -402,9 +370,7 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_kernel(const ConvWgradArgs 
           for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
-              acc[t][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                  __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, fa[ks][i]),
-                  __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, fb[ks][j]), acc[t][i][j], 0, 0, 0);
+              acc[t][i][j] = mfma32(fa[ks][i], fb[ks][j], acc[t][i][j]);
       }
     }
     tap = tap1;

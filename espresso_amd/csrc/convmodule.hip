@@ -10,6 +10,7 @@
 #include "common.h"
 #include "convmodule_math.h"
 #include "espresso_amd.h"
+#include "wave_prims.h"
 
 namespace {
 
@@ -769,17 +770,8 @@ namespace {
 // step (the scalar version spent ~300 VALU operations per position and lane group: 380 us; this one is bound by reading Z and
 // dH once): a wave stages its 32 x 64 dZ block in LDS as it lies in memory ([position][channel]) and reads the A fragments with
 // ds_read_b64_tr_b16 (k = position runs down the rows); the B operand is the tap value of X for (position, tap), split into
-// bf16 hi + lo parts (two MFMAs into one accumulator) so that the fp32 features lose nothing.
-__device__ __forceinline__ int c1_sw(int r) { return (r & 3) ^ ((r >> 3) & 1); }
-__device__ __forceinline__ void c1_tr_read8(const uint32_t (&ad)[8], uint2 (&o)[8]) {
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8\n\tds_read_b64_tr_b16 %1, %9\n\tds_read_b64_tr_b16 %2, %10\n\tds_read_b64_tr_b16 %3, %11\n\t"
-      "ds_read_b64_tr_b16 %4, %12\n\tds_read_b64_tr_b16 %5, %13\n\tds_read_b64_tr_b16 %6, %14\n\tds_read_b64_tr_b16 %7, %15\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(o[6]), "=&v"(o[7])
-      : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]), "v"(ad[4]), "v"(ad[5]), "v"(ad[6]), "v"(ad[7])
-      : "memory");
-}
+// bf16 hi + lo parts (two MFMAs into one accumulator) so that the fp32 features lose nothing.  The tile is the 128-byte-row image
+// of wave_prims.h (tr_sw_rows128).
 __global__ __launch_bounds__(256) void conv1_bn_bwd_wgrad_kernel(const float* __restrict__ X, const bf16_t* __restrict__ Z,
                                                                  const bf16_t* __restrict__ dH, const float* __restrict__ mean_rstd,
                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -860,7 +852,7 @@ __global__ __launch_bounds__(256) void conv1_bn_bwd_wgrad_kernel(const float* __
           o.x = pack_bf2(d[0], d[1]); o.y = pack_bf2(d[2], d[3]); o.z = pack_bf2(d[4], d[5]); o.w = pack_bf2(d[6], d[7]);
         }
         if (p >= npos) o = make_uint4(0, 0, 0, 0);
-        *reinterpret_cast<uint4*>(&tile[wave][r * 128 + (((c8 >> 1) ^ c1_sw(r)) << 5) + (c8 & 1) * 16]) = o;
+        *reinterpret_cast<uint4*>(&tile[wave][r * 128 + (((c8 >> 1) ^ tr_sw_rows128(r)) << 5) + (c8 & 1) * 16]) = o;
       }
       // ---- B operand: X tap values of (position 8 g4 + j, column li) as bf16 hi / lo ----
       uint32_t bh[4], bl[4];
@@ -874,9 +866,7 @@ __global__ __launch_bounds__(256) void conv1_bn_bwd_wgrad_kernel(const float* __
         if (j & 1) { bh[j >> 1] |= hi << 16; bl[j >> 1] |= lo << 16; }
         else { bh[j >> 1] = hi; bl[j >> 1] = lo; }
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       // ---- A fragments: channels 16 mt + li, positions 8 g4 .. + 7 (two transposing reads of 4 positions each) ----
       uint32_t ad[8];
       uint2 o8[8];
@@ -885,18 +875,16 @@ __global__ __launch_bounds__(256) void conv1_bn_bwd_wgrad_kernel(const float* __
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int r = 8 * g4 + 4 * h + (li >> 2);
-          ad[mt * 2 + h] = lds0 + r * 128 + ((mt ^ c1_sw(r)) << 5) + (li & 3) * 8;
+          ad[mt * 2 + h] = lds0 + r * 128 + ((mt ^ tr_sw_rows128(r)) << 5) + (li & 3) * 8;
         }
-      c1_tr_read8(ad, o8);
+      trr8x1(ad, o8);
       const bf16x8_t vbh = __builtin_bit_cast(bf16x8_t, make_uint4(bh[0], bh[1], bh[2], bh[3]));
       const bf16x8_t vbl = __builtin_bit_cast(bf16x8_t, make_uint4(bl[0], bl[1], bl[2], bl[3]));
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) {
-        const bf16x8_t a8 = __builtin_bit_cast(bf16x8_t, make_uint4(o8[mt * 2].x, o8[mt * 2].y, o8[mt * 2 + 1].x, o8[mt * 2 + 1].y));
-        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, a8),
-                                                          __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, vbh), acc[mt], 0, 0, 0);
-        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, a8),
-                                                          __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, vbl), acc[mt], 0, 0, 0);
+        const bf16x8_t a8 = cat2(o8[mt * 2], o8[mt * 2 + 1]);
+        acc[mt] = mfma32(a8, vbh, acc[mt]);
+        acc[mt] = mfma32(a8, vbl, acc[mt]);
       }
       __builtin_amdgcn_wave_barrier();  // the tile is rewritten in the next iteration
     }

@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "wave_prims.h"
 
 constexpr int kCtcMaxS = 2048;  // states of a one-workgroup kernel (Lmax <= 1023)
 
@@ -39,7 +40,7 @@ struct Emis {  // the columns one thread needs in one frame: blank and the label
 };
 
 __device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the LDS hand-off only: prefetched global loads stay in flight
+  wait_lgkmcnt0();  // the LDS hand-off only: prefetched global loads stay in flight
   __builtin_amdgcn_s_barrier();
 }
 

@@ -28,8 +28,6 @@
 
 namespace {
 
-typedef short bf16x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int DH = 64;           // head dim
 constexpr int TQ = 64, TK = 64;  // query rows per workgroup, keys per step
 constexpr int ROWB = DH * 2;     // 128-byte LDS rows
@@ -38,14 +36,6 @@ constexpr int BDP = 18;          // pitch (floats) of the per-wavefront BD^T bou
 // k-contiguous [row][64] bf16 tile: 16-byte chunk c of row r at chunk c ^ (r & 7)   (conflict-free ds_read_b128)
 __device__ __forceinline__ uint32_t off16(int row, int chunk) { return (uint32_t)(row * ROWB + ((chunk ^ (row & 7)) << 4)); }
 
-
-
-
-// bijective XCD-aware remap of a 1-D grid (8 XCDs, round-robin dispatch): consecutive virtual ids stay on one XCD
-__device__ __forceinline__ int xcd_remap(int id, int total) {
-  const int xcd = id & 7, q = total >> 3, r = total & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-}
 
 // ---- register-staged tile movers: global -> registers (issued one tile ahead) -> LDS ------------------------
 // k-contiguous image: a thread owns NP 16-byte chunks (rows (tid>>3) + 32p, chunk tid&7); rows outside [0, limit) read 0
@@ -100,14 +90,6 @@ __device__ __forceinline__ void store_blk_t(char* s, const BlkRegs& r, int t) {
 template <int NR>
 __device__ __forceinline__ bf16x4_t read_t(const char* s, int d, int chunk) {
   return *reinterpret_cast<const bf16x4_t*>(s + d * (NR * 2) + ((chunk ^ (d & 15)) << 3));
-}
-
-__device__ __forceinline__ f32x4_t mfma32(bf16x8_t a, bf16x8_t b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, a),
-                                                 __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4_t mfma16(bf16x4_t a, bf16x4_t b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
 }
 
 template <bool RELPOS>
@@ -283,18 +265,6 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(const FlashFwdArgs a)
 //                                     the un-skewed (T x 2T-1) layout for the pos_proj weight gradient, and D.
 //   KV kernel (grid: key tiles)    -> dK = dS^T Qu, dV = Pd^T dO accumulated in registers over the query tiles.
 // Both recompute the scores on MFMA (cheap next to moving T x S tensors through HBM).
-
-__device__ __forceinline__ bf16x4_t pack4(float a, float b, float c, float d) {
-  uint2 pk;
-  pk.x = pack_bf2(a, b);
-  pk.y = pack_bf2(c, d);
-  return __builtin_bit_cast(bf16x4_t, pk);
-}
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 
 template <bool RELPOS>

@@ -2,6 +2,7 @@
 // encoder self-attention hot path, relative positions, T == S, no causal mask).
 #pragma once
 #include "common.h"
+#include "wave_prims.h"
 
 struct FlashFwdArgs {
   const bf16_t* qu; const bf16_t* qv; long ldq;

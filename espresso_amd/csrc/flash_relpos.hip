@@ -26,9 +26,6 @@
 
 namespace {
 
-typedef short bf16x4_t __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 typedef __attribute__((address_space(3))) bf16x4_t* lds_b4_t;
 
 constexpr int DH = 64, TQ = 64, TK = 64;
@@ -46,88 +43,13 @@ constexpr float LOG2E = 1.4426950408889634f;
 // ds_read_b64_tr_b16 patterns (tools/lds_layout_check.py)
 __device__ __forceinline__ int swz(int r) { return ((r >> 2) & 1) | (((r >> 1) & 1) << 1) | ((((r >> 2) ^ (r >> 3)) & 1) << 2); }
 
-__device__ __forceinline__ int xcd_remap(int id, int total) {
-  const int xcd = id & 7, q = total >> 3, r = total & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-}
-__device__ __forceinline__ f32x4_t mfma32(bf16x8_t a, bf16x8_t b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, a),
-                                                 __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4_t mfma16(bf16x4_t a, bf16x4_t b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ bf16x8_t cat(bf16x4_t lo, bf16x4_t hi) { return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7); }
-__device__ __forceinline__ bf16x4_t pack4(float a, float b, float c, float d) {
-  uint2 pk;
-  pk.x = pack_bf2(a, b);
-  pk.y = pack_bf2(c, d);
-  return __builtin_bit_cast(bf16x4_t, pk);
-}
-// transposing read (ds_read_b64_tr_b16): lane (g = lane>>4, i = lane&15) passes the address of element
-// [k0(g) + (i>>2)][m0 + 4*(i&3)] of a row-major image and receives the four elements [k0(g) + e][m0 + i], e = 0..3.
-// Issued from inline asm in batches with their own wait: through the builtin, hipcc puts `s_waitcnt vmcnt(0)` in front of
-// the first transposing read of every tile (it cannot tell them from the global_load_lds writes in flight), which drains
-// the operand prefetch in the middle of the tile it should overlap with.  The compiler does not track loads issued from
-// asm, so the results must not be visible to it before the wait inside the same statement (cdna_hip_programming.md 5.7).
-__device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)p; }
-// 4 addresses x 4 immediate offsets -> o[a*4 + q] = image at ad[a] + OFFq
-template <int O0, int O1, int O2, int O3>
-__device__ __forceinline__ void trr16(const uint32_t (&ad)[4], uint2 (&o)[16]) {
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %16 offset:%20\n\tds_read_b64_tr_b16 %1, %16 offset:%21\n\t"
-      "ds_read_b64_tr_b16 %2, %16 offset:%22\n\tds_read_b64_tr_b16 %3, %16 offset:%23\n\t"
-      "ds_read_b64_tr_b16 %4, %17 offset:%20\n\tds_read_b64_tr_b16 %5, %17 offset:%21\n\t"
-      "ds_read_b64_tr_b16 %6, %17 offset:%22\n\tds_read_b64_tr_b16 %7, %17 offset:%23\n\t"
-      "ds_read_b64_tr_b16 %8, %18 offset:%20\n\tds_read_b64_tr_b16 %9, %18 offset:%21\n\t"
-      "ds_read_b64_tr_b16 %10, %18 offset:%22\n\tds_read_b64_tr_b16 %11, %18 offset:%23\n\t"
-      "ds_read_b64_tr_b16 %12, %19 offset:%20\n\tds_read_b64_tr_b16 %13, %19 offset:%21\n\t"
-      "ds_read_b64_tr_b16 %14, %19 offset:%22\n\tds_read_b64_tr_b16 %15, %19 offset:%23\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(o[6]), "=&v"(o[7]), "=&v"(o[8]),
-        "=&v"(o[9]), "=&v"(o[10]), "=&v"(o[11]), "=&v"(o[12]), "=&v"(o[13]), "=&v"(o[14]), "=&v"(o[15])
-      : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]), "i"(O0), "i"(O1), "i"(O2), "i"(O3)
-      : "memory");
-}
-// 2 addresses x 4 immediate offsets
-template <int O0, int O1, int O2, int O3>
-__device__ __forceinline__ void trr8(const uint32_t (&ad)[2], uint2 (&o)[8]) {
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8 offset:%10\n\tds_read_b64_tr_b16 %1, %8 offset:%11\n\t"
-      "ds_read_b64_tr_b16 %2, %8 offset:%12\n\tds_read_b64_tr_b16 %3, %8 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %4, %9 offset:%10\n\tds_read_b64_tr_b16 %5, %9 offset:%11\n\t"
-      "ds_read_b64_tr_b16 %6, %9 offset:%12\n\tds_read_b64_tr_b16 %7, %9 offset:%13\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(o[6]), "=&v"(o[7])
-      : "v"(ad[0]), "v"(ad[1]), "i"(O0), "i"(O1), "i"(O2), "i"(O3)
-      : "memory");
-}
-// 20 addresses, no offsets (the five 16-row blocks of a wave's positional window x four 16-column tiles)
-__device__ __forceinline__ void trr20(const uint32_t (&ad)[20], uint2 (&o)[20]) {
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %20\n\tds_read_b64_tr_b16 %1, %21\n\tds_read_b64_tr_b16 %2, %22\n\tds_read_b64_tr_b16 %3, %23\n\t"
-      "ds_read_b64_tr_b16 %4, %24\n\tds_read_b64_tr_b16 %5, %25\n\tds_read_b64_tr_b16 %6, %26\n\tds_read_b64_tr_b16 %7, %27\n\t"
-      "ds_read_b64_tr_b16 %8, %28\n\tds_read_b64_tr_b16 %9, %29\n\tds_read_b64_tr_b16 %10, %30\n\tds_read_b64_tr_b16 %11, %31\n\t"
-      "ds_read_b64_tr_b16 %12, %32\n\tds_read_b64_tr_b16 %13, %33\n\tds_read_b64_tr_b16 %14, %34\n\tds_read_b64_tr_b16 %15, %35\n\t"
-      "ds_read_b64_tr_b16 %16, %36\n\tds_read_b64_tr_b16 %17, %37\n\tds_read_b64_tr_b16 %18, %38\n\tds_read_b64_tr_b16 %19, %39\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(o[6]), "=&v"(o[7]), "=&v"(o[8]),
-        "=&v"(o[9]), "=&v"(o[10]), "=&v"(o[11]), "=&v"(o[12]), "=&v"(o[13]), "=&v"(o[14]), "=&v"(o[15]), "=&v"(o[16]),
-        "=&v"(o[17]), "=&v"(o[18]), "=&v"(o[19])
-      : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]), "v"(ad[4]), "v"(ad[5]), "v"(ad[6]), "v"(ad[7]), "v"(ad[8]), "v"(ad[9]),
-        "v"(ad[10]), "v"(ad[11]), "v"(ad[12]), "v"(ad[13]), "v"(ad[14]), "v"(ad[15]), "v"(ad[16]), "v"(ad[17]), "v"(ad[18]),
-        "v"(ad[19])
-      : "memory");
-}
 // 8 bytes of the un-skew buffer as two SCALAR float loads (merged into one ds_read_b64 / ds_read2 by the compiler): hipcc
 // puts `s_waitcnt vmcnt(0)` in front of vector-typed LDS loads that follow a global_load_lds (type-based alias analysis
 // cannot separate them from the in-flight LDS writes), which would drain the next tile's prefetch in mid-tile
 __device__ __forceinline__ uint2 lds_u2(const char* p) {
   const float* f = reinterpret_cast<const float*>(p);
   return make_uint2(__float_as_uint(f[0]), __float_as_uint(f[1]));
-}
-__device__ __forceinline__ bf16x8_t cat2(uint2 lo, uint2 hi) {
-  return __builtin_bit_cast(bf16x8_t, make_uint4(lo.x, lo.y, hi.x, hi.y));
 }
 // the [64 d] x [64 keys / rows] transposed operand of an image as eight 16x32 fragments: f[dt*2 + kb], keys kb*32 .. +31 in the
 // permuted order (rows 4g..4g+3 of the block's first 16, then of its second 16)
@@ -143,11 +65,6 @@ __device__ __forceinline__ void tr_image(const char* img, const uint32_t (&tro)[
   }
 }
 __device__ __forceinline__ bf16x8_t ldf(const char* p) { return *reinterpret_cast<const bf16x8_t*>(p); }
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 struct LaneK {
@@ -199,13 +116,13 @@ __device__ __forceinline__ void issue_img(char* dst, const ImgSrc& s, int row0, 
     const long off = (long)row0 * s.ld;
 #pragma unroll
     for (int n = 0; n < 2; ++n)
-      __builtin_amdgcn_global_load_lds((gptr_t)(s.p[n] + off), (lptr_t)(dst + (w + 4 * n) * 1024), 16, 0, 0);
+      glds16(s.p[n] + off, dst + (w + 4 * n) * 1024);
   } else {
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
       const int r = (w + 4 * n) * 8 + (lane >> 3);
       const int g = min(max(row0 + r, 0), s.rmax);
-      __builtin_amdgcn_global_load_lds((gptr_t)(s.p[n] + (long)(g - r) * s.ld), (lptr_t)(dst + (w + 4 * n) * 1024), 16, 0, 0);
+      glds16(s.p[n] + (long)(g - r) * s.ld, dst + (w + 4 * n) * 1024);
     }
   }
 }
@@ -336,7 +253,7 @@ __global__ __launch_bounds__(256, 2) void rp_fwd_kernel(const FlashFwdArgs a) {
   int slot_lo = 0;  // ring slot of positional block t
   for (int t = 0; t < nt; ++t) {
     const int j0 = t * TK;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();  // tile t is in LDS (every wave's part); everyone is done with tile t-1
     const int slot_hi = slot_lo == 2 ? 0 : slot_lo + 1;
     const int slot_nx = slot_hi == 2 ? 0 : slot_hi + 1;
@@ -575,7 +492,7 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_q_kernel(const FlashBwdArgs a) 
   for (int t = 0; t < nt; ++t) {
     const int j0 = t * TK;
     jcov = min(T, j0 + TK);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     store_dbd();  // previous tile's rows
     const int slot_hi = slot_lo == 2 ? 0 : slot_lo + 1;
@@ -823,7 +740,7 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_kv_kernel(const FlashBwdArgs a)
   int slot_lo = 0;  // ring slot of block `it` (window rows 0..63); block it-1 (rows 64..127) sits one slot below
   for (int it = 0; it < nq; ++it) {
     const int i0 = it * TQ;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();  // tile `it` landed; everyone is done with the exchange tiles of tile it-1
     const int slot_hi = slot_lo == 0 ? 2 : slot_lo - 1;
     const int slot_nx = slot_lo == 2 ? 0 : slot_lo + 1;
@@ -877,7 +794,7 @@ __global__ __launch_bounds__(256, 2) void rp_bwd_kv_kernel(const FlashBwdArgs a)
       *reinterpret_cast<bf16x4_t*>(exw + (exo ^ (jt << 5))) = dsb[jt];
       *reinterpret_cast<bf16x4_t*>(exw + 2048 + (exo ^ (jt << 5))) = pdb[jt];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // not __syncthreads(): that also waits for the prefetch (vmcnt)
+    wait_lgkmcnt0();  // not __syncthreads(): that also waits for the prefetch (vmcnt)
     __builtin_amdgcn_s_barrier();
     // phase 2: this wave's 16 keys, all 64 rows:  dK^T[d][j] += sum_i Qu^T[d][i] dS[i][j],  dV^T[d][j] += sum_i dO^T[d][i] Pd[i][j]
     {

@@ -282,8 +282,7 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16_kernel(const EaGemmParams p,
     // then share their operand rows in ONE L2 (bijective for any grid size)
     const int gx = gridDim.x, gxy = gridDim.x * gridDim.y, total = gxy * gridDim.z;
     const int lin = (blockIdx.z * gridDim.y + blockIdx.y) * gx + blockIdx.x;
-    const int xcd = lin & 7, q = total >> 3, r = total & 7;
-    const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
+    const int v = xcd_remap(lin, total);
     tile_z = FAST ? 0 : v / gxy;  // (FAST launches have gridDim.z == 1: no batch / split-K index arithmetic at all)
     const int rem = v - tile_z * gxy;
     tile_y = rem / gx;
@@ -358,23 +357,8 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16_kernel(const EaGemmParams p,
   }
 
   auto storeB = [&](const uint4 (&rb)[4]) { if (B_KS) store_ks(sB, tid, rb); else store_kc(sB, tid, rb); };
-  auto compute = [&]() {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8_t af[4], bfr[NJ];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const bf16x8_t*>(sA + a_off[ks][i]);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bfr[j] = *reinterpret_cast<const bf16x8_t*>(sB + b_off[ks][j]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, af[i]),
-              __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, bfr[j]), acc[i][j], 0, 0, 0);
-    }
-  };
+  // (through a lambda like the movers above: called directly, three k-strided instantiations schedule their loops differently)
+  auto compute = [&]() { tile_step<NJ>(sA, sB, a_off, b_off, acc); };
   for (int kt = 0; kt < nk; ++kt) {
     __syncthreads();
     storeA(ra);
@@ -419,8 +403,7 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(const EaGemmParams p,
     // then share their operand rows in ONE L2 (bijective for any grid size)
     const int gx = gridDim.x, gxy = gridDim.x * gridDim.y, total = gxy * gridDim.z;
     const int lin = (blockIdx.z * gridDim.y + blockIdx.y) * gx + blockIdx.x;
-    const int xcd = lin & 7, q = total >> 3, r = total & 7;
-    const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
+    const int v = xcd_remap(lin, total);
     tile_z = FAST ? 0 : v / gxy;  // (FAST launches have gridDim.z == 1: no batch / split-K index arithmetic at all)
     const int rem = v - tile_z * gxy;
     tile_y = rem / gx;
@@ -458,16 +441,12 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(const EaGemmParams p,
     const int c = (lane & 7) ^ (r & 7) ^ ((r >> 4) & 7);
     bp[i] = B + (long)min(n0 + r, p.N - 1) * p.ldb + kbeg + c * 8;
   }
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   auto issue = [&](int stage, int kt) {
     char* base = dsm + stage * STAGE + wave * 1024;
 #pragma unroll
-    for (int i = 0; i < NA; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(ap[i] + (long)kt * BK), (lptr_t)(base + i * 4096), 16, 0, 0);
+    for (int i = 0; i < NA; ++i) glds16(ap[i] + (long)kt * BK, base + i * 4096);
 #pragma unroll
-    for (int i = 0; i < NB; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(bp[i] + (long)kt * BK), (lptr_t)(base + A_BYTES + i * 4096), 16, 0, 0);
+    for (int i = 0; i < NB; ++i) glds16(bp[i] + (long)kt * BK, base + A_BYTES + i * 4096);
   };
   uint32_t a_off[2][4], b_off[2][NJ];
 #pragma unroll
@@ -484,35 +463,13 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(const EaGemmParams p,
   int stage = 0, fill = NST - 1;  // stage holding tile kt ; stage that tile kt+NST-1 goes to
   for (int kt = 0; kt < nk; ++kt) {
     // tile kt has landed once at most NST-2 younger tiles (NA+NB instructions each) are still outstanding
-    if (kt + NST - 2 < nk) {
-      if (NST == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else if ((NST - 2) * (NA + NB) == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else if ((NST - 2) * (NA + NB) == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else if ((NST - 2) * (NA + NB) == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-      else if ((NST - 2) * (NA + NB) == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    if (kt + NST - 2 < nk) wait_vmcnt<(NST - 2) * (NA + NB)>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();  // every wave's part of tile kt is in LDS; everyone is done reading tile kt-1's stage
     if (kt == 0) EA_STAMP(1);
     if (kt + NST - 1 < nk) issue(fill, kt + NST - 1);
     const char* st = dsm + stage * STAGE;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8_t af[4], bfr[NJ];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const bf16x8_t*>(st + a_off[ks][i]);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bfr[j] = *reinterpret_cast<const bf16x8_t*>(st + b_off[ks][j]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, af[i]),
-              __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, bfr[j]), acc[i][j], 0, 0, 0);
-    }
+    tile_step<NJ>(st, st, a_off, b_off, acc);
     stage = stage + 1 == NST ? 0 : stage + 1;
     fill = fill + 1 == NST ? 0 : fill + 1;
   }
@@ -588,8 +545,7 @@ __global__ __launch_bounds__(256) void wgrad_group_kernel(const EaWgradGroup g, 
   // workgroups are dealt round-robin to the 8 XCDs: hand every XCD one contiguous range of the (problem, row block, column
   // block) tile list instead, so that the tiles that walk the same dy / x columns share ONE L2 (PMC: 601 MB of L2 fills per
   // launch against 207 MB of operands when neighbouring tiles sat on 8 different XCDs)
-  const int total = gridDim.x, xcd = blockIdx.x & 7, xq = total >> 3, xr = total & 7;
-  const int bid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (blockIdx.x >> 3);
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   while (pi + 1 < g.count && bid >= tb.start[pi + 1]) ++pi;
   const EaWgradProblem P = g.p[pi];
   const int local = bid - tb.start[pi];
@@ -658,21 +614,7 @@ __global__ __launch_bounds__(256) void wgrad_group_kernel(const EaWgradGroup g, 
     store_ks(sB, tid, rb);
     __syncthreads();
     if (kt + 1 < nk) { loadA((kt + 1) * BK); loadB((kt + 1) * BK); }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8_t af[4], bfr[NJ];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const bf16x8_t*>(sA + a_off[ks][i]);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bfr[j] = *reinterpret_cast<const bf16x8_t*>(sB + b_off[ks][j]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, af[i]),
-              __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, bfr[j]), acc[i][j], 0, 0, 0);
-    }
+    tile_step<NJ>(sA, sB, a_off, b_off, acc);
   }
 
   float* sC = reinterpret_cast<float*>(smem);
@@ -739,42 +681,8 @@ __global__ __launch_bounds__(256) void wgrad_group_kernel(const EaWgradGroup g, 
 // are fetched from a zero page.  The bias gradient is one more MFMA per A fragment against a fragment of ones.
 __device__ __attribute__((aligned(256))) unsigned char g_wgrad_zero_page[256];
 
-__device__ __forceinline__ int wg_f256(int r) { return ((r & 3) | ((r >> 1) & 4)) << 1; }
+// slot swizzle of the 128-byte-pitch A image (BM_ = 64); the 256-byte-pitch images use tr_sw_rows256 (wave_prims.h)
 __device__ __forceinline__ int wg_f128(int r) { return (((r >> 1) & 1) | ((r >> 2) & 2)) << 1; }
-// transposing reads from inline asm with their own wait (through the builtin hipcc drains vmcnt — the prefetch — first)
-template <int O0, int O1, int O2, int O3>
-__device__ __forceinline__ void wg_trr16(const uint32_t (&ad)[4], uint2 (&o)[16]) {
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %16 offset:%20\n\tds_read_b64_tr_b16 %1, %16 offset:%21\n\t"
-      "ds_read_b64_tr_b16 %2, %16 offset:%22\n\tds_read_b64_tr_b16 %3, %16 offset:%23\n\t"
-      "ds_read_b64_tr_b16 %4, %17 offset:%20\n\tds_read_b64_tr_b16 %5, %17 offset:%21\n\t"
-      "ds_read_b64_tr_b16 %6, %17 offset:%22\n\tds_read_b64_tr_b16 %7, %17 offset:%23\n\t"
-      "ds_read_b64_tr_b16 %8, %18 offset:%20\n\tds_read_b64_tr_b16 %9, %18 offset:%21\n\t"
-      "ds_read_b64_tr_b16 %10, %18 offset:%22\n\tds_read_b64_tr_b16 %11, %18 offset:%23\n\t"
-      "ds_read_b64_tr_b16 %12, %19 offset:%20\n\tds_read_b64_tr_b16 %13, %19 offset:%21\n\t"
-      "ds_read_b64_tr_b16 %14, %19 offset:%22\n\tds_read_b64_tr_b16 %15, %19 offset:%23\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(o[6]), "=&v"(o[7]), "=&v"(o[8]),
-        "=&v"(o[9]), "=&v"(o[10]), "=&v"(o[11]), "=&v"(o[12]), "=&v"(o[13]), "=&v"(o[14]), "=&v"(o[15])
-      : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]), "i"(O0), "i"(O1), "i"(O2), "i"(O3)
-      : "memory");
-}
-template <int O0, int O1, int O2, int O3>
-__device__ __forceinline__ void wg_trr8(const uint32_t (&ad)[2], uint2 (&o)[8]) {
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8 offset:%10\n\tds_read_b64_tr_b16 %1, %8 offset:%11\n\t"
-      "ds_read_b64_tr_b16 %2, %8 offset:%12\n\tds_read_b64_tr_b16 %3, %8 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %4, %9 offset:%10\n\tds_read_b64_tr_b16 %5, %9 offset:%11\n\t"
-      "ds_read_b64_tr_b16 %6, %9 offset:%12\n\tds_read_b64_tr_b16 %7, %9 offset:%13\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(o[6]), "=&v"(o[7])
-      : "v"(ad[0]), "v"(ad[1]), "i"(O0), "i"(O1), "i"(O2), "i"(O3)
-      : "memory");
-}
-__device__ __forceinline__ bf16x8_t wg_cat(uint2 lo, uint2 hi) {
-  const uint4 u = make_uint4(lo.x, lo.y, hi.x, hi.y);
-  return __builtin_bit_cast(bf16x8_t, u);
-}
 
 template <int BM_, int NST>
 __global__ __launch_bounds__(256, BM_ == 64 ? 3 : 2) void wgrad_group_tr_kernel(const EaWgradGroup g, const WgradTable tb) {
@@ -790,8 +698,7 @@ __global__ __launch_bounds__(256, BM_ == 64 ? 3 : 2) void wgrad_group_tr_kernel(
   const int wcol = BM_ == 128 ? (wave & 1) * 64 : wave * 32;
 
   int pi = 0;
-  const int total = gridDim.x, xcd = blockIdx.x & 7, xq = total >> 3, xr = total & 7;
-  const int bid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (blockIdx.x >> 3);  // see wgrad_group_kernel
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);  // see wgrad_group_kernel
   while (pi + 1 < g.count && bid >= tb.start[pi + 1]) ++pi;
   const EaWgradProblem P = g.p[pi];
   const int local = bid - tb.start[pi];
@@ -819,34 +726,28 @@ __global__ __launch_bounds__(256, BM_ == 64 ? 3 : 2) void wgrad_group_tr_kernel(
   for (int i = 0; i < NA; ++i) {
     const int row = (wave + 4 * i) * RPI_A + lane / SPR_A, slot = lane % SPR_A;
     arow[i] = row;
-    ap[i] = reinterpret_cast<const bf16_t*>(P.dy) + (long)row * lda + m0 + 8 * (slot ^ (BM_ == 128 ? wg_f256(row) : wg_f128(row)));
+    ap[i] = reinterpret_cast<const bf16_t*>(P.dy) + (long)row * lda + m0 + 8 * (slot ^ (BM_ == 128 ? tr_sw_rows256(row) : wg_f128(row)));
   }
 #pragma unroll
   for (int i = 0; i < NB; ++i) {
     const int row = (wave + 4 * i) * 4 + (lane >> 4), slot = lane & 15;
     brow[i] = row;
-    bp[i] = reinterpret_cast<const bf16_t*>(P.x) + (long)row * ldb + n0 + 8 * (slot ^ wg_f256(row));
+    bp[i] = reinterpret_cast<const bf16_t*>(P.x) + (long)row * ldb + n0 + 8 * (slot ^ tr_sw_rows256(row));
   }
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_wgrad_zero_page) + (lane & 15) * 8;
   auto issue = [&](int stage, int kt) {
     char* base = dsm + stage * STAGE + wave * 1024;
     const long roff = (long)kt * BK;
     if ((kt + 1) * BK <= Kr) {
 #pragma unroll
-      for (int i = 0; i < NA; ++i) __builtin_amdgcn_global_load_lds((gptr_t)(ap[i] + roff * lda), (lptr_t)(base + i * 4096), 16, 0, 0);
+      for (int i = 0; i < NA; ++i) glds16(ap[i] + roff * lda, base + i * 4096);
 #pragma unroll
-      for (int i = 0; i < NB; ++i)
-        __builtin_amdgcn_global_load_lds((gptr_t)(bp[i] + roff * ldb), (lptr_t)(base + A_BYTES + i * 4096), 16, 0, 0);
+      for (int i = 0; i < NB; ++i) glds16(bp[i] + roff * ldb, base + A_BYTES + i * 4096);
     } else {  // last, partial stage: rows past M contribute zeros
 #pragma unroll
-      for (int i = 0; i < NA; ++i)
-        __builtin_amdgcn_global_load_lds((gptr_t)(kt * BK + arow[i] < Kr ? ap[i] + roff * lda : zero), (lptr_t)(base + i * 4096), 16, 0, 0);
+      for (int i = 0; i < NA; ++i) glds16(kt * BK + arow[i] < Kr ? ap[i] + roff * lda : zero, base + i * 4096);
 #pragma unroll
-      for (int i = 0; i < NB; ++i)
-        __builtin_amdgcn_global_load_lds((gptr_t)(kt * BK + brow[i] < Kr ? bp[i] + roff * ldb : zero), (lptr_t)(base + A_BYTES + i * 4096), 16,
-                                         0, 0);
+      for (int i = 0; i < NB; ++i) glds16(kt * BK + brow[i] < Kr ? bp[i] + roff * ldb : zero, base + A_BYTES + i * 4096);
     }
   };
   // fragment addresses inside a stage (the swizzle term does not depend on the +4-row / +32-row immediates)
@@ -855,10 +756,10 @@ __global__ __launch_bounds__(256, BM_ == 64 ? 3 : 2) void wgrad_group_tr_kernel(
   uint32_t adA[4], adB[NJ];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    adA[i] = lds0 + row0 * PA + (((((wm * 64 + 16 * i) >> 3) + (lq >> 1)) ^ (BM_ == 128 ? wg_f256(row0) : wg_f128(row0))) << 4) + (lq & 1) * 8;
+    adA[i] = lds0 + row0 * PA + (((((wm * 64 + 16 * i) >> 3) + (lq >> 1)) ^ (BM_ == 128 ? tr_sw_rows256(row0) : wg_f128(row0))) << 4) + (lq & 1) * 8;
 #pragma unroll
   for (int j = 0; j < NJ; ++j)
-    adB[j] = lds0 + A_BYTES + row0 * PB + (((((wcol + 16 * j) >> 3) + (lq >> 1)) ^ wg_f256(row0)) << 4) + (lq & 1) * 8;
+    adB[j] = lds0 + A_BYTES + row0 * PB + (((((wcol + 16 * j) >> 3) + (lq >> 1)) ^ tr_sw_rows256(row0)) << 4) + (lq & 1) * 8;
   const uint4 ones_u = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
   const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, ones_u);
 
@@ -871,13 +772,8 @@ __global__ __launch_bounds__(256, BM_ == 64 ? 3 : 2) void wgrad_group_tr_kernel(
   constexpr bool DO_BIAS = decltype(bias_tag)::value;
   int stage = 0, fill = NST - 1;
   for (int kt = 0; kt < nk; ++kt) {
-    if (NST > 2 && kt + NST - 2 < nk) {
-      if ((NST - 2) * (NA + NB) == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else if ((NST - 2) * (NA + NB) == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    if (NST > 2 && kt + NST - 2 < nk) wait_vmcnt<(NST - 2) * (NA + NB)>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();  // tile kt is in LDS for every wave; everyone is done reading the stage that is refilled next
     if (kt + NST - 1 < nk) issue(fill, kt + NST - 1);
     const uint32_t so = (uint32_t)(stage * STAGE);
@@ -885,41 +781,36 @@ __global__ __launch_bounds__(256, BM_ == 64 ? 3 : 2) void wgrad_group_tr_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) a4[i] = adA[i] + so;
     uint2 oa[16];
-    wg_trr16<0, 4 * PA, 32 * PA, 36 * PA>(a4, oa);
+    trr16<0, 4 * PA, 32 * PA, 36 * PA>(a4, oa);
     bf16x8_t bfr[2][NJ];
     if constexpr (BM_ == 128) {
       uint32_t b4[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) b4[j] = adB[j] + so;
       uint2 ob[16];
-      wg_trr16<0, 4 * PB, 32 * PB, 36 * PB>(b4, ob);
+      trr16<0, 4 * PB, 32 * PB, 36 * PB>(b4, ob);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) bfr[ks][j] = wg_cat(ob[j * 4 + 2 * ks], ob[j * 4 + 2 * ks + 1]);
+        for (int j = 0; j < 4; ++j) bfr[ks][j] = cat2(ob[j * 4 + 2 * ks], ob[j * 4 + 2 * ks + 1]);
     } else {
       uint32_t b2[2] = {adB[0] + so, adB[1] + so};
       uint2 ob[8];
-      wg_trr8<0, 4 * PB, 32 * PB, 36 * PB>(b2, ob);
+      trr8<0, 4 * PB, 32 * PB, 36 * PB>(b2, ob);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) bfr[ks][j] = wg_cat(ob[j * 4 + 2 * ks], ob[j * 4 + 2 * ks + 1]);
+        for (int j = 0; j < 2; ++j) bfr[ks][j] = cat2(ob[j * 4 + 2 * ks], ob[j * 4 + 2 * ks + 1]);
     }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const bf16x8_t af = wg_cat(oa[i * 4 + 2 * ks], oa[i * 4 + 2 * ks + 1]);
+        const bf16x8_t af = cat2(oa[i * 4 + 2 * ks], oa[i * 4 + 2 * ks + 1]);
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, af),
-              __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, bfr[ks][j]), acc[i][j], 0, 0, 0);
-        if constexpr (DO_BIAS)
-          accb[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, af),
-                                                            __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, ones), accb[i], 0, 0,
-                                                            0);
+          acc[i][j] = mfma32(af, bfr[ks][j], acc[i][j]);
+        if constexpr (DO_BIAS) accb[i] = mfma32(af, ones, accb[i]);
       }
     }
     stage = stage + 1 == NST ? 0 : stage + 1;

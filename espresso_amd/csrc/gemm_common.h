@@ -1,8 +1,10 @@
 // Pieces shared by the GEMM kernels (gemm.hip: register-staged / direct-to-LDS / grouped weight-gradient kernels;
-// conv_igemm.hip: implicit-GEMM convolutions): the LDS tile image and the activation functions of the fused epilogues.
+// conv_igemm.hip: implicit-GEMM convolutions): the LDS tile image, the k-tile step of the 4-wavefront kernels and the activation
+// functions of the fused epilogues.
 #pragma once
 #include "common.h"
 #include "espresso_amd.h"
+#include "wave_prims.h"
 
 // Development probe (tools/probes/gemm_timing.hip compiles gemm.hip / gemm_w8.hip with -DEA_GEMM_TIMING): thread 0 of every workgroup stamps the
 // 100 MHz device clock at entry / first tile in LDS / end of the k loop / end of the epilogue.  Compiled out of the library.
@@ -38,6 +40,29 @@ constexpr int ROW_BYTES = BK * 2;  // 128 B per LDS row
 // whose 16 lanes hit rows 8 apart (same r&7), over 8 different bank slots instead of one.
 __device__ __forceinline__ uint32_t lds_off(int row, int chunk) {
   return (uint32_t)(row * ROW_BYTES + ((chunk ^ (row & 7) ^ ((row >> 4) & 7)) << 4));
+}
+
+// The k-tile step of the 4-wavefront kernels (64 rows x NJ*16 columns per wavefront, BK = 64: two 16x16x32 MFMAs per accumulator).
+// acc += A tile x B tile^T: per k-half the 4 + NJ fragment reads, then the 4 x NJ MFMAs.  a_off[ks][i] / b_off[ks][j] are the byte
+// offsets of this lane's fragments from sA / sB: lds_off(first row of the 16-row group + (lane & 15), ks * 4 + (lane >> 4)).  The
+// callers fill them in their own loops: filled through array references inside a helper (tried in four forms), hipcc's address
+// arithmetic and register allocation come out differently in most kernels, conv_gather_kernel<128> with 32 more VALU instructions
+// per k-tile.
+template <int NJ>
+__device__ __forceinline__ void tile_step(const char* sA, const char* sB, const uint32_t (&a_off)[2][4], const uint32_t (&b_off)[2][NJ],
+                                          f32x4_t (&acc)[4][NJ]) {
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    bf16x8_t af[4], bfr[NJ];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const bf16x8_t*>(sA + a_off[ks][i]);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) bfr[j] = *reinterpret_cast<const bf16x8_t*>(sB + b_off[ks][j]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[i][j] = mfma32(af[i], bfr[j], acc[i][j]);
+  }
 }
 
 __device__ __forceinline__ float apply_act(float v, int act) {

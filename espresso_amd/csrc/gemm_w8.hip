@@ -215,25 +215,19 @@ __device__ __forceinline__ void w8_reg_epilogue(const EaGemmParams& p, const f32
 }
 
 // grid: 1-D, one workgroup per output tile (tiles_n fastest); flags bit 0: XCD-aware tile order, bit 1: non-temporal stores
-template <int BM_, int BN_, int WM_, int WN_, int NST, int PIPE, int KIND>
+template <int BM_, int BN_, int WM_, int WN_, int NST, int KIND>
 __global__ __launch_bounds__(512, 2) void gemm_w8_kernel(const EaGemmParams p, const int tiles_n, const int flags) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];  // the ONLY LDS object: ring of operand stages
   constexpr int TM = BM_ / WM_, TN = BN_ / WN_, MI = TM / 16, NJ = TN / 16;
-  constexpr int A_BYTES = BM_ * 128, STAGE = (BM_ + BN_) * 128;
-  constexpr int NA = BM_ / 64, NB = BN_ / 64;  // load instructions per wavefront and stage (one instruction = 8 rows of 128 B)
-  static_assert(WM_ * WN_ == 8 && NST >= 2, "eight wavefronts");
   EA_STAMP(0);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN_, wn = wave % WN_;
   int tile = blockIdx.x;
-  if (flags & 1) {
-    // workgroups go round-robin to the 8 XCDs in dispatch order: give every XCD one contiguous range of the (row block, n-tile)
-    // order instead, so that the n-tiles of a row block share their operand rows in ONE L2 (bijective for any grid size)
-    const int total = gridDim.x, xcd = tile & 7, q = total >> 3, r = total & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (tile >> 3);
-  }
+  // workgroups go round-robin to the 8 XCDs in dispatch order: give every XCD one contiguous range of the (row block, n-tile)
+  // order instead, so that the n-tiles of a row block share their operand rows in ONE L2 (bijective for any grid size)
+  if (flags & 1) tile = xcd_remap(tile, gridDim.x);
   const int tile_y = tile / tiles_n, tile_x = tile - tile_y * tiles_n;
   const int m0 = tile_y * BM_, n0 = tile_x * BN_;
   const bf16_t* A = reinterpret_cast<const bf16_t*>(p.A);
@@ -246,6 +240,9 @@ __global__ __launch_bounds__(512, 2) void gemm_w8_kernel(const EaGemmParams p, c
 #pragma unroll
     for (int j = 0; j < NJ; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
+  constexpr int A_BYTES = BM_ * 128, STAGE = (BM_ + BN_) * 128;
+  constexpr int NA = BM_ / 64, NB = BN_ / 64;  // load instructions per wavefront and stage (one instruction = 8 rows of 128 B)
+  static_assert(WM_ * WN_ == 8 && NST >= 2, "eight wavefronts");
   // per-lane source pointers: lane l of load instruction i fills row (wave + 8 i) * 8 + (l >> 3), slot l & 7, which holds k-chunk
   // slot ^ (row & 7); rows past M / N re-read the last valid row (their products are never stored)
   const int src_chunk = (lane & 7) ^ (lane >> 3);
@@ -255,15 +252,12 @@ __global__ __launch_bounds__(512, 2) void gemm_w8_kernel(const EaGemmParams p, c
   for (int i = 0; i < NA; ++i) ap[i] = A + (long)min(m0 + (wave + 8 * i) * 8 + (lane >> 3), p.M - 1) * p.lda + src_chunk * 8;
 #pragma unroll
   for (int i = 0; i < NB; ++i) bp[i] = B + (long)min(n0 + (wave + 8 * i) * 8 + (lane >> 3), p.N - 1) * p.ldb + src_chunk * 8;
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   auto issue = [&](int stage, int kt) {
     char* base = dsm + stage * STAGE + wave * 1024;
 #pragma unroll
-    for (int i = 0; i < NA; ++i) __builtin_amdgcn_global_load_lds((gptr_t)(ap[i] + (long)kt * BK), (lptr_t)(base + i * 8192), 16, 0, 0);
+    for (int i = 0; i < NA; ++i) glds16(ap[i] + (long)kt * BK, base + i * 8192);
 #pragma unroll
-    for (int i = 0; i < NB; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(bp[i] + (long)kt * BK), (lptr_t)(base + A_BYTES + i * 8192), 16, 0, 0);
+    for (int i = 0; i < NB; ++i) glds16(bp[i] + (long)kt * BK, base + A_BYTES + i * 8192);
   };
   // fragment base addresses inside a stage: row (lane & 15) of the wavefront's first 16-row group, k-chunk ks * 4 + (lane >> 4); the
   // other 16-row groups are +2048-byte immediates
@@ -280,64 +274,43 @@ __global__ __launch_bounds__(512, 2) void gemm_w8_kernel(const EaGemmParams p, c
   int stage = 0, fill = NST - 1;  // stage holding tile kt ; stage that tile kt + NST - 1 goes to
   for (int kt = 0; kt < nk; ++kt) {
     // tile kt has landed once at most NST - 2 younger tiles (NA + NB instructions each) are outstanding
-    if (kt + NST - 2 < nk) w8_wait_vmcnt<(NST - 2) * (NA + NB)>();
-    else w8_wait_vmcnt<0>();
+    if (kt + NST - 2 < nk) wait_vmcnt<(NST - 2) * (NA + NB)>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();  // every wavefront's part of tile kt is in LDS; everyone is done reading tile kt - 1's stage
     if (kt == 0) EA_STAMP(1);
     if (kt == 4) EA_STAMP(7);
     if (kt + NST - 1 < nk) issue(fill, kt + NST - 1);
     const char* st = dsm + stage * STAGE;
-    if constexpr (PIPE == 0) {
+    // Software pipeline inside the k-tile: the MFMAs are cut into groups of eight (AG A fragments x NJ B fragments); the
+    // fragment reads of group g + 1 are issued before the MFMAs of group g (hipcc on its own reads two A fragments, waits for
+    // them, issues eight MFMAs, reads the next two ...: every group then pays one LDS round trip in the open).  The order is
+    // pinned with sched_group_barrier; the compiler still counts lgkmcnt itself.
+    constexpr int AG = NJ >= 4 ? 2 : (MI >= 4 ? 4 : MI);
+    constexpr int GPK = MI / AG, NG = 2 * GPK;
+    bf16x8_t bq[2][NJ], aq[2][AG];
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        bf16x8_t af[MI], bfr[NJ];
+    for (int j = 0; j < NJ; ++j) bq[0][j] = *reinterpret_cast<const bf16x8_t*>(st + b_base[0] + j * 2048);
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) bfr[j] = *reinterpret_cast<const bf16x8_t*>(st + b_base[ks] + j * 2048);
+    for (int a = 0; a < AG; ++a) aq[0][a] = *reinterpret_cast<const bf16x8_t*>(st + a_base[0] + a * 2048);
 #pragma unroll
-        for (int i = 0; i < MI; ++i) af[i] = *reinterpret_cast<const bf16x8_t*>(st + a_base[ks] + i * 2048);
+    for (int g = 0; g < NG; ++g) {
+      if (g + 1 < NG) {
+        const int ks1 = (g + 1) / GPK, gi = (g + 1) % GPK;
+        if (gi == 0) {
 #pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, bfr[j]),
-                __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, af[i]), acc[i][j], 0, 0, 0);
-      }
-    } else {
-      // Software pipeline inside the k-tile: the MFMAs are cut into groups of eight (AG A fragments x NJ B fragments); the
-      // fragment reads of group g + 1 are issued before the MFMAs of group g (hipcc on its own reads two A fragments, waits for
-      // them, issues eight MFMAs, reads the next two ...: every group then pays one LDS round trip in the open).  The order is
-      // pinned with sched_group_barrier; the compiler still counts lgkmcnt itself.
-      constexpr int AG = NJ >= 4 ? 2 : (MI >= 4 ? 4 : MI);
-      constexpr int GPK = MI / AG, NG = 2 * GPK;
-      bf16x8_t bq[2][NJ], aq[2][AG];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bq[0][j] = *reinterpret_cast<const bf16x8_t*>(st + b_base[0] + j * 2048);
-#pragma unroll
-      for (int a = 0; a < AG; ++a) aq[0][a] = *reinterpret_cast<const bf16x8_t*>(st + a_base[0] + a * 2048);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        if (g + 1 < NG) {
-          const int ks1 = (g + 1) / GPK, gi = (g + 1) % GPK;
-          if (gi == 0) {
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) bq[ks1][j] = *reinterpret_cast<const bf16x8_t*>(st + b_base[ks1] + j * 2048);
-          }
-#pragma unroll
-          for (int a = 0; a < AG; ++a) aq[(g + 1) & 1][a] = *reinterpret_cast<const bf16x8_t*>(st + a_base[ks1] + (gi * AG + a) * 2048);
+          for (int j = 0; j < NJ; ++j) bq[ks1][j] = *reinterpret_cast<const bf16x8_t*>(st + b_base[ks1] + j * 2048);
         }
-        const int ks = g / GPK, gi0 = g % GPK;
 #pragma unroll
-        for (int a = 0; a < AG; ++a)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            acc[gi0 * AG + a][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, bq[ks][j]),
-                __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, aq[g & 1][a]), acc[gi0 * AG + a][j], 0, 0, 0);
+        for (int a = 0; a < AG; ++a) aq[(g + 1) & 1][a] = *reinterpret_cast<const bf16x8_t*>(st + a_base[ks1] + (gi * AG + a) * 2048);
       }
-      __builtin_amdgcn_sched_group_barrier(0x100, NJ + AG, 0);
-      w8_sched_groups<NG, GPK, AG, NJ>();
+      const int ks = g / GPK, gi0 = g % GPK;
+#pragma unroll
+      for (int a = 0; a < AG; ++a)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[gi0 * AG + a][j] = mfma32(bq[ks][j], aq[g & 1][a], acc[gi0 * AG + a][j]);
     }
+    __builtin_amdgcn_sched_group_barrier(0x100, NJ + AG, 0);
+    w8_sched_groups<NG, GPK, AG, NJ>();
     stage = stage + 1 == NST ? 0 : stage + 1;
     fill = fill + 1 == NST ? 0 : fill + 1;
   }
@@ -346,14 +319,14 @@ __global__ __launch_bounds__(512, 2) void gemm_w8_kernel(const EaGemmParams p, c
   EA_STAMP(3);
 }
 
-template <int BM_, int BN_, int WM_, int WN_, int NST, int PIPE, int KIND>
+template <int BM_, int BN_, int WM_, int WN_, int NST, int KIND>
 bool w8_launch_kind(const EaGemmParams& q, int flags, hipStream_t stream) {
   constexpr int bytes = NST * (BM_ + BN_) * 128;
-  static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_w8_kernel<BM_, BN_, WM_, WN_, NST, PIPE, KIND>),
+  static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_w8_kernel<BM_, BN_, WM_, WN_, NST, KIND>),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
   if (!attr_ok) return false;
   const int tiles_n = (q.N + BN_ - 1) / BN_, tiles_m = (q.M + BM_ - 1) / BM_;
-  hipLaunchKernelGGL((gemm_w8_kernel<BM_, BN_, WM_, WN_, NST, PIPE, KIND>), dim3(tiles_n * tiles_m), dim3(512), bytes, stream, q, tiles_n, flags);
+  hipLaunchKernelGGL((gemm_w8_kernel<BM_, BN_, WM_, WN_, NST, KIND>), dim3(tiles_n * tiles_m), dim3(512), bytes, stream, q, tiles_n, flags);
   return true;
 }
 // which specialisation of the register epilogue a (FAST) launch takes; -1: a combination none of them covers
@@ -368,14 +341,14 @@ int w8_kind(const EaGemmParams& q) {
   if (q.aux) return q.resid ? -1 : W8_AUX;
   return q.resid ? W8_RESID : W8_PLAIN;
 }
-template <int BM_, int BN_, int WM_, int WN_, int NST, int PIPE>
+template <int BM_, int BN_, int WM_, int WN_, int NST>
 bool w8_launch(const EaGemmParams& q, int flags, hipStream_t stream) {
   switch (w8_kind(q)) {
-    case W8_PLAIN: return w8_launch_kind<BM_, BN_, WM_, WN_, NST, PIPE, W8_PLAIN>(q, flags, stream);
-    case W8_QSPLIT: return w8_launch_kind<BM_, BN_, WM_, WN_, NST, PIPE, W8_QSPLIT>(q, flags, stream);
-    case W8_ACT2: return w8_launch_kind<BM_, BN_, WM_, WN_, NST, PIPE, W8_ACT2>(q, flags, stream);
-    case W8_AUX: return w8_launch_kind<BM_, BN_, WM_, WN_, NST, PIPE, W8_AUX>(q, flags, stream);
-    case W8_RESID: return w8_launch_kind<BM_, BN_, WM_, WN_, NST, PIPE, W8_RESID>(q, flags, stream);
+    case W8_PLAIN: return w8_launch_kind<BM_, BN_, WM_, WN_, NST, W8_PLAIN>(q, flags, stream);
+    case W8_QSPLIT: return w8_launch_kind<BM_, BN_, WM_, WN_, NST, W8_QSPLIT>(q, flags, stream);
+    case W8_ACT2: return w8_launch_kind<BM_, BN_, WM_, WN_, NST, W8_ACT2>(q, flags, stream);
+    case W8_AUX: return w8_launch_kind<BM_, BN_, WM_, WN_, NST, W8_AUX>(q, flags, stream);
+    case W8_RESID: return w8_launch_kind<BM_, BN_, WM_, WN_, NST, W8_RESID>(q, flags, stream);
     default: return false;
   }
 }
@@ -416,10 +389,10 @@ int ea_gemm_w8_try(const EaGemmParams& q, int nt_flag, hipStream_t stream, int* 
   const int flags = 1 | nt_flag;
   bool ok = false;
   switch (cfg) {
-    case 2: ok = w8_launch<256, 256, 2, 4, 2, 1>(q, flags, stream); break;
-    case 3: ok = w8_launch<128, 128, 2, 4, 4, 1>(q, flags, stream); break;
-    case 4: ok = w8_launch<256, 128, 4, 2, 3, 1>(q, flags, stream); break;
-    case 5: ok = w8_launch<128, 256, 2, 4, 3, 1>(q, flags, stream); break;
+    case 2: ok = w8_launch<256, 256, 2, 4, 2>(q, flags, stream); break;
+    case 3: ok = w8_launch<128, 128, 2, 4, 4>(q, flags, stream); break;
+    case 4: ok = w8_launch<256, 128, 4, 2, 3>(q, flags, stream); break;
+    case 5: ok = w8_launch<128, 256, 2, 4, 3>(q, flags, stream); break;
     default: return 0;
   }
   if (ok && cfg_out) *cfg_out = cfg;

@@ -14,7 +14,7 @@
 //             it as bf16 [n][pitch] (pad columns zero): the operand of the joint's data- and weight-gradient GEMMs.
 // One more GEMM pass (0.36 TFLOP at the recipe size) instead of 2.1 GB of HBM traffic and two bf16 roundings of every logit.
 //
-// The k loop is gemm_w8_kernel<256, 256, 2, 4, 2, 1> (same ring, same fragment order, same accumulation order along k): the
+// The k loop is gemm_w8_kernel<256, 256, 2, 4, 2>'s (same ring, same fragment order, same accumulation order along k): the
 // fp32 accumulators are bit-identical to what the unfused path rounds to bf16.
 #include "common.h"
 #include "espresso_amd.h"
@@ -73,17 +73,13 @@ __device__ __forceinline__ float xor32_sum(float v) {
 template <int KIND>
 __global__ __launch_bounds__(512, 2) void joint_rnnt_kernel(const JointArgs a, const int tiles_n) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
-  constexpr int A_BYTES = JBM * 128, STAGE = (JBM + JBN) * 128;
-  constexpr int NA = JBM / 64, NB = JBN / 64;
+  constexpr int STAGE = (JBM + JBN) * 128;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / JWN, wn = wave % JWN;
-  int tile = blockIdx.x;
-  {  // XCD-aware order (gemm_w8_kernel, flags bit 0): the vocabulary tiles of a row block share Z's rows in ONE L2
-    const int total = gridDim.x, xcd = tile & 7, q = total >> 3, r = total & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (tile >> 3);
-  }
+  // XCD-aware order (gemm_w8_kernel, flags bit 0): the vocabulary tiles of a row block share Z's rows in ONE L2
+  const int tile = xcd_remap(blockIdx.x, gridDim.x);
   const int tile_y = tile / tiles_n, tile_x = tile - tile_y * tiles_n;
   const int m0 = tile_y * JBM, n0 = tile_x * JBN;
   const int nk = a.K / BK;
@@ -115,6 +111,11 @@ __global__ __launch_bounds__(512, 2) void joint_rnnt_kernel(const JointArgs a, c
   float scale = a.scale;
   if (KIND == J_GRAD && a.scale_dev) scale *= a.scale_dev[0];
 
+  constexpr int A_BYTES = JBM * 128;
+  constexpr int NA = JBM / 64, NB = JBN / 64;  // load instructions per wavefront and stage (one instruction = 8 rows of 128 B)
+  static_assert(JWM * JWN == 8 && JNST >= 2, "eight wavefronts");
+  // per-lane source pointers: lane l of load instruction i fills row (wave + 8 i) * 8 + (l >> 3), slot l & 7, which holds k-chunk
+  // slot ^ (row & 7); rows past M / N re-read the last valid row (their products are never stored)
   const int src_chunk = (lane & 7) ^ (lane >> 3);
   const bf16_t* ap[NA];
   const bf16_t* bp[NB];
@@ -122,16 +123,15 @@ __global__ __launch_bounds__(512, 2) void joint_rnnt_kernel(const JointArgs a, c
   for (int i = 0; i < NA; ++i) ap[i] = a.Z + (long)min(m0 + (wave + 8 * i) * 8 + (lane >> 3), a.M - 1) * a.K + src_chunk * 8;
 #pragma unroll
   for (int i = 0; i < NB; ++i) bp[i] = a.W + (long)min(n0 + (wave + 8 * i) * 8 + (lane >> 3), a.V - 1) * a.K + src_chunk * 8;
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   auto issue = [&](int stage, int kt) {
     char* base = dsm + stage * STAGE + wave * 1024;
 #pragma unroll
-    for (int i = 0; i < NA; ++i) __builtin_amdgcn_global_load_lds((gptr_t)(ap[i] + (long)kt * BK), (lptr_t)(base + i * 8192), 16, 0, 0);
+    for (int i = 0; i < NA; ++i) glds16(ap[i] + (long)kt * BK, base + i * 8192);
 #pragma unroll
-    for (int i = 0; i < NB; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(bp[i] + (long)kt * BK), (lptr_t)(base + A_BYTES + i * 8192), 16, 0, 0);
+    for (int i = 0; i < NB; ++i) glds16(bp[i] + (long)kt * BK, base + A_BYTES + i * 8192);
   };
+  // fragment base addresses inside a stage: row (lane & 15) of the wavefront's first 16-row group, k-chunk ks * 4 + (lane >> 4); the
+  // other 16-row groups are +2048-byte immediates
   uint32_t a_base[2], b_base[2];
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
@@ -141,19 +141,25 @@ __global__ __launch_bounds__(512, 2) void joint_rnnt_kernel(const JointArgs a, c
 #pragma unroll
   for (int s = 0; s < JNST - 1; ++s)
     if (s < nk) issue(s, s);
-  int stage = 0, fill = JNST - 1;
+  int stage = 0, fill = JNST - 1;  // stage holding tile kt ; stage that tile kt + JNST - 1 goes to
   for (int kt = 0; kt < nk; ++kt) {
-    if (kt + JNST - 2 < nk) w8_wait_vmcnt<(JNST - 2) * (NA + NB)>();
-    else w8_wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
+    // tile kt has landed once at most JNST - 2 younger tiles (NA + NB instructions each) are outstanding
+    if (kt + JNST - 2 < nk) wait_vmcnt<(JNST - 2) * (NA + NB)>();
+    else wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();  // every wavefront's part of tile kt is in LDS; everyone is done reading tile kt - 1's stage
     if (kt + JNST - 1 < nk) issue(fill, kt + JNST - 1);
     const char* st = dsm + stage * STAGE;
-    constexpr int AG = 2, GPK = JMI / AG, NG = 2 * GPK;
+    // Software pipeline inside the k-tile: the MFMAs are cut into groups of eight (AG A fragments x JNJ B fragments); the
+    // fragment reads of group g + 1 are issued before the MFMAs of group g (hipcc on its own reads two A fragments, waits for
+    // them, issues eight MFMAs, reads the next two ...: every group then pays one LDS round trip in the open).  The order is
+    // pinned with sched_group_barrier; the compiler still counts lgkmcnt itself.
+    constexpr int AG = JNJ >= 4 ? 2 : (JMI >= 4 ? 4 : JMI);
+    constexpr int GPK = JMI / AG, NG = 2 * GPK;
     bf16x8_t bq[2][JNJ], aq[2][AG];
 #pragma unroll
     for (int j = 0; j < JNJ; ++j) bq[0][j] = *reinterpret_cast<const bf16x8_t*>(st + b_base[0] + j * 2048);
 #pragma unroll
-    for (int q = 0; q < AG; ++q) aq[0][q] = *reinterpret_cast<const bf16x8_t*>(st + a_base[0] + q * 2048);
+    for (int a = 0; a < AG; ++a) aq[0][a] = *reinterpret_cast<const bf16x8_t*>(st + a_base[0] + a * 2048);
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
       if (g + 1 < NG) {
@@ -163,16 +169,13 @@ __global__ __launch_bounds__(512, 2) void joint_rnnt_kernel(const JointArgs a, c
           for (int j = 0; j < JNJ; ++j) bq[ks1][j] = *reinterpret_cast<const bf16x8_t*>(st + b_base[ks1] + j * 2048);
         }
 #pragma unroll
-        for (int q = 0; q < AG; ++q) aq[(g + 1) & 1][q] = *reinterpret_cast<const bf16x8_t*>(st + a_base[ks1] + (gi * AG + q) * 2048);
+        for (int a = 0; a < AG; ++a) aq[(g + 1) & 1][a] = *reinterpret_cast<const bf16x8_t*>(st + a_base[ks1] + (gi * AG + a) * 2048);
       }
       const int ks = g / GPK, gi0 = g % GPK;
 #pragma unroll
-      for (int q = 0; q < AG; ++q)
+      for (int a = 0; a < AG; ++a)
 #pragma unroll
-        for (int j = 0; j < JNJ; ++j)
-          acc[gi0 * AG + q][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, bq[ks][j]),
-              __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, aq[g & 1][q]), acc[gi0 * AG + q][j], 0, 0, 0);
+        for (int j = 0; j < JNJ; ++j) acc[gi0 * AG + a][j] = mfma32(bq[ks][j], aq[g & 1][a], acc[gi0 * AG + a][j]);
     }
     __builtin_amdgcn_sched_group_barrier(0x100, JNJ + AG, 0);
     w8_sched_groups<NG, GPK, AG, JNJ>();

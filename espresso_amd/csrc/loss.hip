@@ -17,6 +17,7 @@
 #include "common.h"
 #include "espresso_amd.h"
 #include "softmax_row.h"
+#include "wave_prims.h"
 
 namespace {
 
@@ -152,7 +153,7 @@ __global__ void ctc_scan_kernel(const float* __restrict__ G, const int* __restri
     v = (live && m > -INFINITY) ? v : -INFINITY;
     if (live) *op = v;  // (a store under a branch only makes the wait-count pass assume it was issued: the loads stay counted)
     wr[s] = v;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this lane's hand-off is in LDS (global requests stay in flight)
+    wait_lgkmcnt0();  // this lane's hand-off is in LDS (global requests stay in flight)
     __builtin_amdgcn_s_barrier();
     float* tmp = rd; rd = wr; wr = tmp;
   };

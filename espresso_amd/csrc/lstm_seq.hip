@@ -16,6 +16,7 @@
 // All workgroups of a launch must be resident at once: at most 64 workgroups of 256 threads are launched (256 CUs).
 #include "common.h"
 #include "espresso_amd.h"
+#include "wave_prims.h"
 
 namespace {
 
@@ -118,9 +119,7 @@ __global__ __launch_bounds__(256) void lstm_seq_fwd_kernel(const LstmSeqFwdArgs 
         for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt)
-            acc[mt][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, wf[mt][ks]),
-                __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, hb[ks]), acc[mt][g], 0, 0, 0);
+            acc[mt][g] = mfma32(wf[mt][ks], hb[ks], acc[mt][g]);
       }
     }
 #pragma unroll
@@ -221,9 +220,7 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_kernel(const LstmSeqBwdArgs 
         for (int ks = 0; ks < KS; ++ks) gb[ks] = *reinterpret_cast<const bf16x8_t*>(gr + ks * 32);
         f32x4_t acc = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, wf[ks]),
-                                                        __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, gb[ks]), acc, 0, 0, 0);
+        for (int ks = 0; ks < KS; ++ks) acc = mfma32(wf[ks], gb[ks], acc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) part[pb][wave][g][q * 4 + r][col] = acc[r];
       }

@@ -17,6 +17,7 @@
 // the path for logits that exist (criterion called on a tensor, shapes the fused kernels do not take) and the test reference.
 #include "common.h"
 #include "espresso_amd.h"
+#include "wave_prims.h"
 
 namespace {
 
@@ -187,7 +188,7 @@ __global__ void rnnt_scan_kernel(const float* __restrict__ lpb, const float* __r
       own_prev = val;
     }
     curbuf[u] = val;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this lane's hand-off is in LDS (global requests are NOT waited for)
+    wait_lgkmcnt0();  // this lane's hand-off is in LDS (global requests are NOT waited for)
     __builtin_amdgcn_s_barrier();
     float* tmp = prevbuf; prevbuf = curbuf; curbuf = tmp;
   };

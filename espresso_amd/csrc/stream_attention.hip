@@ -15,6 +15,7 @@
 // n*W*dh*3 FMAs on <= 24 KiB of cache: bound by the cache bytes and the launch, not by the VALU (DESIGN.md kernel table).
 #include "common.h"
 #include "espresso_amd.h"
+#include "wave_prims.h"
 
 namespace {
 
@@ -31,13 +32,6 @@ __device__ __forceinline__ void unpack8(const uint4 u, float (&f)[8]) {
     f[2 * e] = __uint_as_float(w[e] << 16);
     f[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u);
   }
-}
-
-// LDS written by some lanes of this wave, read by others (no other wave touches the wave's slab)
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 struct RingGeom {

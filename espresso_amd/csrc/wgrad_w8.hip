@@ -31,52 +31,15 @@ struct W8WgradTable {
 
 __device__ __attribute__((aligned(256))) unsigned char g_wgrad_w8_zero_page[256];
 
-// image rows are 512 B (256 bf16 columns); the 16-byte slot s of row r holds source slot s ^ f(r).  A half-wave of a transposing
-// read touches rows {8g + e : g in a pair, e < 4} x 32 bytes: f gives those 8 rows 8 different 32-byte positions of a 256-byte
-// bank window, and does not change under the +4-row / +32-row immediates (same function as the 256-byte-pitch image of gemm.hip)
-__device__ __forceinline__ int wg8_f(int r) { return ((r & 3) | ((r >> 1) & 4)) << 1; }
+// image rows are 512 B (256 bf16 columns); the 16-byte slot s of row r holds source slot s ^ tr_sw_rows256(r) (wave_prims.h)
 
-// eight transposing reads (4 addresses x 2 row offsets), NOT waited for: o[2 a + h] = address a at offset h
-template <int O0, int O1>
-__device__ __forceinline__ void wg8_read8(const uint32_t (&ad)[4], uint2 (&o)[8]) {
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8 offset:%12\n\tds_read_b64_tr_b16 %1, %8 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %2, %9 offset:%12\n\tds_read_b64_tr_b16 %3, %9 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %4, %10 offset:%12\n\tds_read_b64_tr_b16 %5, %10 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %6, %11 offset:%12\n\tds_read_b64_tr_b16 %7, %11 offset:%13"
-      : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(o[6]), "=&v"(o[7])
-      : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]), "i"(O0), "i"(O1)
-      : "memory");
-}
-// the wait for every outstanding LDS read; the registers of the reads it completes are tied to it so that no consumer is
-// scheduled above it (the compiler does not count lgkmcnt for reads issued from inline asm)
-__device__ __forceinline__ void wg8_wait8(uint2 (&o)[8]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]), "+v"(o[4]), "+v"(o[5]), "+v"(o[6]), "+v"(o[7])
-               :
-               : "memory");
-}
-__device__ __forceinline__ void wg8_wait16(uint2 (&o)[8], uint2 (&q)[8]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]), "+v"(o[4]), "+v"(o[5]), "+v"(o[6]), "+v"(o[7]), "+v"(q[0]), "+v"(q[1]),
-                 "+v"(q[2]), "+v"(q[3]), "+v"(q[4]), "+v"(q[5]), "+v"(q[6]), "+v"(q[7])
-               :
-               : "memory");
-}
-__device__ __forceinline__ bf16x8_t wg8_cat(uint2 lo, uint2 hi) {
-  const uint4 u = make_uint4(lo.x, lo.y, hi.x, hi.y);
-  return __builtin_bit_cast(bf16x8_t, u);
-}
-__device__ __forceinline__ bf16x8_t wg8_sel(bool c, bf16x8_t a, bf16x8_t b) {
+// c ? a : b on whole fragments (c is wave-uniform)
+__device__ __forceinline__ bf16x8_t sel8(bool c, bf16x8_t a, bf16x8_t b) {
   const uint4 x = __builtin_bit_cast(uint4, a), y = __builtin_bit_cast(uint4, b);
   return __builtin_bit_cast(bf16x8_t, make_uint4(c ? x.x : y.x, c ? x.y : y.y, c ? x.z : y.z, c ? x.w : y.w));
 }
-#define WG8_MFMA(A_, B_, C_)                                                                                              \
-  __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, A_),              \
-                                          __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, B_), C_, 0, 0, 0)
-
 // one 256 x 256 tile: `vb` = position of the tile in the launch's virtual 1-D grid of `total` tiles
-__device__ __forceinline__ void wg8_tile(const EaWgradGroup& g, const W8WgradTable& tb, const int vb, const int total, char* dsm) {
+__device__ __forceinline__ void wgrad_w8_tile(const EaWgradGroup& g, const W8WgradTable& tb, const int vb, const int total, char* dsm) {
   constexpr int PITCH = 512, A_BYTES = 64 * PITCH, STAGE = 2 * A_BYTES;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -84,10 +47,9 @@ __device__ __forceinline__ void wg8_tile(const EaWgradGroup& g, const W8WgradTab
   const int wm = wave >> 2, wn = wave & 3;  // wavefront tile: rows wm * 128 .. + 128 (columns of dy), columns wn * 64 .. + 64 (of x)
 
   int pi = 0;
-  const int xcd = vb & 7, xq = total >> 3, xr = total & 7;
   // workgroups go round-robin to the 8 XCDs: give every XCD a contiguous range, so that the column tiles of a row block (same dy
   // columns) and neighbouring row blocks (same x rows) of one slab meet in ONE L2
-  const int bid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (vb >> 3);
+  const int bid = xcd_remap(vb, total);
   while (pi + 1 < g.count && bid >= tb.start[pi + 1]) ++pi;
   const EaWgradProblem P = g.p[pi];
   const int local = bid - tb.start[pi];
@@ -107,7 +69,7 @@ __device__ __forceinline__ void wg8_tile(const EaWgradGroup& g, const W8WgradTab
   const bool do_bias = P.dbias != nullptr && tile_x == 0;
 
   // per-lane sources of this wavefront's load instructions: instruction i fills image rows lrow0 + 16 i, slot lane & 31 <- source
-  // slot (lane & 31) ^ f(row).  32-bit byte offsets from the (uniform) operand bases.  A column past the row pitch re-reads the
+  // slot (lane & 31) ^ tr_sw_rows256(row).  32-bit byte offsets from the (uniform) operand bases.  A column past the row pitch re-reads the
   // row's last 16 bytes: such columns are >= N / >= K, their products only reach outputs that are never stored
   const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_wgrad_w8_zero_page) + (lane & 15) * 8;
   const char* abase = reinterpret_cast<const char*>(P.dy);
@@ -118,29 +80,25 @@ __device__ __forceinline__ void wg8_tile(const EaWgradGroup& g, const W8WgradTab
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int row = lrow0 + 16 * i, slot = lane & 31;
-    const int ca = min(m0 + 8 * (slot ^ wg8_f(row)), (int)lda - 8), cb = min(n0 + 8 * (slot ^ wg8_f(row)), (int)ldb - 8);
+    const int ca = min(m0 + 8 * (slot ^ tr_sw_rows256(row)), (int)lda - 8), cb = min(n0 + 8 * (slot ^ tr_sw_rows256(row)), (int)ldb - 8);
     aoff[i] = ((uint32_t)row * (uint32_t)lda + (uint32_t)ca) * 2u;
     boff[i] = ((uint32_t)row * (uint32_t)ldb + (uint32_t)cb) * 2u;
   }
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   // loads of stage kt; the offsets walk forward one stage per call (stages are issued in order, each exactly once)
   auto issue = [&](int stage, int kt) {
     char* base = dsm + stage * STAGE + wave * 1024;
     if ((kt + 1) * BK <= Kr) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) __builtin_amdgcn_global_load_lds((gptr_t)(abase + aoff[i]), (lptr_t)(base + i * 8192), 16, 0, 0);
+      for (int i = 0; i < 4; ++i) glds16(abase + aoff[i], base + i * 8192);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) __builtin_amdgcn_global_load_lds((gptr_t)(bbase + boff[i]), (lptr_t)(base + A_BYTES + i * 8192), 16, 0, 0);
+      for (int i = 0; i < 4; ++i) glds16(bbase + boff[i], base + A_BYTES + i * 8192);
     } else {  // last, partial stage: rows past M contribute zeros
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds((gptr_t)(kt * BK + lrow0 + 16 * i < Kr ? abase + aoff[i] : reinterpret_cast<const char*>(zero)),
-                                         (lptr_t)(base + i * 8192), 16, 0, 0);
+        glds16(kt * BK + lrow0 + 16 * i < Kr ? abase + aoff[i] : reinterpret_cast<const char*>(zero), base + i * 8192);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds((gptr_t)(kt * BK + lrow0 + 16 * i < Kr ? bbase + boff[i] : reinterpret_cast<const char*>(zero)),
-                                         (lptr_t)(base + A_BYTES + i * 8192), 16, 0, 0);
+        glds16(kt * BK + lrow0 + 16 * i < Kr ? bbase + boff[i] : reinterpret_cast<const char*>(zero), base + A_BYTES + i * 8192);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -156,12 +114,12 @@ __device__ __forceinline__ void wg8_tile(const EaWgradGroup& g, const W8WgradTab
   uint32_t adAlo[4], adAhi[4], adB[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    adAlo[i] = lds0 + row0 * PITCH + (((((wm * 128 + 16 * i) >> 3) + (lq >> 1)) ^ wg8_f(row0)) << 4) + (lq & 1) * 8;
-    adAhi[i] = lds0 + row0 * PITCH + (((((wm * 128 + 64 + 16 * i) >> 3) + (lq >> 1)) ^ wg8_f(row0)) << 4) + (lq & 1) * 8;
+    adAlo[i] = lds0 + row0 * PITCH + (((((wm * 128 + 16 * i) >> 3) + (lq >> 1)) ^ tr_sw_rows256(row0)) << 4) + (lq & 1) * 8;
+    adAhi[i] = lds0 + row0 * PITCH + (((((wm * 128 + 64 + 16 * i) >> 3) + (lq >> 1)) ^ tr_sw_rows256(row0)) << 4) + (lq & 1) * 8;
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j)
-    adB[j] = lds0 + A_BYTES + row0 * PITCH + (((((wn * 64 + 16 * j) >> 3) + (lq >> 1)) ^ wg8_f(row0)) << 4) + (lq & 1) * 8;
+    adB[j] = lds0 + A_BYTES + row0 * PITCH + (((((wn * 64 + 16 * j) >> 3) + (lq >> 1)) ^ tr_sw_rows256(row0)) << 4) + (lq & 1) * 8;
   const uint4 ones_u = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
   const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, ones_u);
 
@@ -170,7 +128,7 @@ __device__ __forceinline__ void wg8_tile(const EaWgradGroup& g, const W8WgradTab
     constexpr bool DO_BIAS = decltype(bias_tag)::value;
     int stage = 0;
     for (int kt = 0; kt < nk; ++kt) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();  // stage kt is in LDS for every wavefront; everyone is done reading the other stage
       if (kt + 1 < nk) issue(stage ^ 1, kt + 1);
       // (the fragment addresses themselves flip between the stages at the bottom of the loop: no per-stage copies)
@@ -179,47 +137,47 @@ __device__ __forceinline__ void wg8_tile(const EaWgradGroup& g, const W8WgradTab
       uint32_t(&aHi)[4] = adAhi;
       // [B0, A0lo] wait | [A0hi] MFMA(A0lo) wait | [B1, A1lo] MFMA(A0hi) wait | [A1hi] MFMA(A1lo) wait | MFMA(A1hi)
       uint2 ob0[8], ob1[8], oal[8], oah[8];
-      wg8_read8<0, 4 * PITCH>(bA, ob0);
-      wg8_read8<0, 4 * PITCH>(aLo, oal);
-      wg8_wait16(ob0, oal);
+      read8<0, 4 * PITCH>(bA, ob0);
+      read8<0, 4 * PITCH>(aLo, oal);
+      wait16(ob0, oal);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         uint2(&ob)[8] = ks == 0 ? ob0 : ob1;
-        if (ks == 0) wg8_read8<0, 4 * PITCH>(aHi, oah);
-        else wg8_read8<32 * PITCH, 36 * PITCH>(aHi, oah);
+        if (ks == 0) read8<0, 4 * PITCH>(aHi, oah);
+        else read8<32 * PITCH, 36 * PITCH>(aHi, oah);
         __builtin_amdgcn_sched_barrier(0);  // (the reads stay ABOVE the MFMAs they hide under; hipcc sinks them to their wait otherwise)
         bf16x8_t bfr[4], af[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) bfr[j] = wg8_cat(ob[2 * j], ob[2 * j + 1]);
+        for (int j = 0; j < 4; ++j) bfr[j] = cat2(ob[2 * j], ob[2 * j + 1]);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) af[i] = wg8_cat(oal[2 * i], oal[2 * i + 1]);
+        for (int i = 0; i < 4; ++i) af[i] = cat2(oal[2 * i], oal[2 * i + 1]);
         bf16x8_t sb0 = af[0];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = WG8_MFMA(bfr[j], af[i], acc[i][j]);
-          if (DO_BIAS && i > 0) sb0 = wg8_sel(wn == i, af[i], sb0);
+          for (int j = 0; j < 4; ++j) acc[i][j] = mfma32(bfr[j], af[i], acc[i][j]);
+          if (DO_BIAS && i > 0) sb0 = sel8(wn == i, af[i], sb0);
         }
-        if (DO_BIAS) accb[0] = WG8_MFMA(ones, sb0, accb[0]);
+        if (DO_BIAS) accb[0] = mfma32(ones, sb0, accb[0]);
         __builtin_amdgcn_sched_barrier(0);
-        wg8_wait8(oah);
+        wait8(oah);
         if (ks == 0) {
-          wg8_read8<32 * PITCH, 36 * PITCH>(bA, ob1);
-          wg8_read8<32 * PITCH, 36 * PITCH>(aLo, oal);
+          read8<32 * PITCH, 36 * PITCH>(bA, ob1);
+          read8<32 * PITCH, 36 * PITCH>(aLo, oal);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) af[i] = wg8_cat(oah[2 * i], oah[2 * i + 1]);
+        for (int i = 0; i < 4; ++i) af[i] = cat2(oah[2 * i], oah[2 * i + 1]);
         bf16x8_t sb1 = af[0];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) acc[4 + i][j] = WG8_MFMA(bfr[j], af[i], acc[4 + i][j]);
-          if (DO_BIAS && i > 0) sb1 = wg8_sel(wn == i, af[i], sb1);
+          for (int j = 0; j < 4; ++j) acc[4 + i][j] = mfma32(bfr[j], af[i], acc[4 + i][j]);
+          if (DO_BIAS && i > 0) sb1 = sel8(wn == i, af[i], sb1);
         }
-        if (DO_BIAS) accb[1] = WG8_MFMA(ones, sb1, accb[1]);
+        if (DO_BIAS) accb[1] = mfma32(ones, sb1, accb[1]);
         __builtin_amdgcn_sched_barrier(0);
-        if (ks == 0) wg8_wait16(ob1, oal);
+        if (ks == 0) wait16(ob1, oal);
       }
       stage ^= 1;
       const uint32_t flip = stage ? (uint32_t)STAGE : (uint32_t)-STAGE;
@@ -268,7 +226,7 @@ __device__ __forceinline__ void wg8_tile(const EaWgradGroup& g, const W8WgradTab
 // grid: 1-D, 512 threads, 128 KB of dynamic LDS (two stages).  gridDim.x == tb.start[EA_WGRAD_MAX] (the tile count): one tile per workgroup.
 __global__ __launch_bounds__(512, 2) void wgrad_w8_kernel(const EaWgradGroup g, const W8WgradTable tb) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
-  wg8_tile(g, tb, blockIdx.x, tb.start[EA_WGRAD_MAX], dsm);
+  wgrad_w8_tile(g, tb, blockIdx.x, tb.start[EA_WGRAD_MAX], dsm);
 }
 
 }  // namespace

@@ -1,18 +1,18 @@
 """Lane-level CPU model of csrc/gemm.hip `wgrad_group_tr_kernel` (weight gradients dW[n][k] += sum_m dy[m][n] x[m][k] with both
 operand tiles brought global -> LDS by global_load_lds as they lie in memory — reduction index m along the ROWS — and read
 as MFMA fragments by ds_read_b64_tr_b16): the kernel's index arithmetic transcribed, so that the 16-byte-slot swizzles, the
-fragment addresses / immediate offsets and the operand order are checked on the CPU (tests/test_kernel_models.py) against
+fragment addresses / immediate offsets (csrc/wave_prims.h: trr16 / trr8) and the operand order are checked on the CPU (tests/test_kernel_models.py) against
 dy^T x in float64, together with the LDS bank rules.   python tools/emu_wgrad_tr.py"""
 import numpy as np
 
 from lds_layout_check import HALF_GROUPS, worst
 
 
-def f256(r):  # slot swizzle of a 256-byte-pitch image (16 slots per row)
+def f256(r):  # tr_sw_rows256 (csrc/wave_prims.h): slot swizzle of a 256-byte-pitch image (16 slots per row)
     return ((r & 3) | ((r >> 1) & 4)) << 1
 
 
-def f128(r):  # 128-byte pitch (8 slots per row)
+def f128(r):  # wg_f128 (csrc/gemm.hip): 128-byte pitch (8 slots per row)
     return (((r >> 1) & 1) | ((r >> 2) & 2)) << 1
 
 

@@ -1,7 +1,8 @@
 """Lane-level CPU model of csrc/wgrad_w8.hip `wgrad_w8_kernel` (8 wavefronts, 256 x 256 output tile; both operand tiles are
 [64 reduction rows][256 columns] as they lie in memory, moved by global_load_lds and read as MFMA fragments by
-ds_read_b64_tr_b16): the kernel's index arithmetic transcribed — load-instruction rows / slots with the source-side swizzle, the
-column clamp at the row pitch, zero-page rows past M, fragment addresses and their +4-row / +32-row immediates, the SWAPPED MFMA
+ds_read_b64_tr_b16): the kernel's index arithmetic transcribed — load-instruction rows / slots with the source-side swizzle
+(tr_sw_rows256, csrc/wave_prims.h), the column clamp at the row pitch, zero-page rows past M, fragment addresses and their +4-row /
++32-row immediates (read8<O0, O1>), the SWAPPED MFMA
 operand order (a lane ends up with four consecutive output columns of one row), the bias sums routed to wavefront wn for row
 tiles wn and 4 + wn — checked against dy^T x in float64, together with the LDS bank rules (tests/test_kernel_models.py).
     python tools/emu_wgrad_w8.py"""

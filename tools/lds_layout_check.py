@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""LDS bank-conflict model for the 128-byte-row bf16 tile images of the fused attention kernels (gfx950 rules from
-/opt/skills/guides/MI355X_MICROARCH.md, LDS section): ds_read_b128 is served in four fixed 16-lane groups, ds_read_b64 and
+"""LDS bank-conflict model for the 128-byte-row bf16 tile images of the fused attention kernels (gfx950 rules: the LDS
+section of the MI355X micro-architecture notes): ds_read_b128 is served in four fixed 16-lane groups, ds_read_b64 and
 ds_read_b64_tr_b16 in two 32-lane groups, bank = (byte/4) mod 64.  A 16-byte slot s of row r is stored at slot s ^ f(r);
 the search below finds the linear f (3 output bits, each an XOR of row bits) for which every fragment-read pattern the
 kernels use is conflict free.  Run with no arguments to re-derive csrc/flash_relpos.hip's `swz` (bit0 = r>>2, bit1 = r>>1, bit2 = (r>>2)^(r>>3)).
+The swizzles of the images that several kernels share (tr_sw_rows128, tr_sw_rows256) are in csrc/wave_prims.h.
 """
 import itertools
 import sys
