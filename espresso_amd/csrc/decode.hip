@@ -65,7 +65,8 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(const bf16_t* __r
   float acc = 0.f;
   if (lane < dh)
     for (int j = 0; j < L; ++j) acc += pr[j] * bf2f(Vb[(long)j * ldkv + lane]);
-  if (lane < dh) out[(long)n * ldq + h * dh + lane] = f2bf(acc / sum);
+  // an empty row (L == 0: sum == 0) attends to nothing: its output is 0, not 0 / 0
+  if (lane < dh) out[(long)n * ldq + h * dh + lane] = f2bf(sum > 0.f ? acc / sum : 0.f);
 }
 
 // The same for head dims 16 / 32 / 64 with 16-byte aligned rows (every recipe): the kernel above moves ONE bf16 per lane and key
@@ -168,7 +169,7 @@ __global__ __launch_bounds__(256) void decode_attention_vec_kernel(const bf16_t*
 #pragma unroll
     for (int e = 0; e < E; ++e) acc[e] += __shfl_xor(acc[e], m, 64);
   if (kg == 0) {
-    const float inv = 1.f / sum;
+    const float inv = sum > 0.f ? 1.f / sum : 0.f;  // an empty row (L == 0) gives 0, not 0 * inf
     bf16_t* o = out + (long)n * ldq + h * DH + cq * E;
 #pragma unroll
     for (int e = 0; e < E; e += 2) *reinterpret_cast<uint32_t*>(o + e) = pack_bf2(acc[e] * inv, acc[e + 1] * inv);

@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void bahdanau_fwd_kernel(const bf16_t* __restr
     sum += e;
   }
   sum = block_sum(sum, sm);
-  const float inv = 1.f / sum;
+  const float inv = sum > 0.f ? 1.f / sum : 0.f;  // len == 0: every key is masked, p = 0 (not 0 * inf)
   for (int t = threadIdx.x; t < T; t += 256) {
     const float pr = sc[t] * inv;
     sc[t] = pr;

@@ -14,6 +14,12 @@
 //   backward: rows are hidden units, the 4H-long reduction is split over the 4 waves of a workgroup (wave w = gate w's rows),
 //             partial sums meet in LDS, then thread (unit, batch row) runs the cell backward.
 // All workgroups of a launch must be resident at once: at most 64 workgroups of 256 threads are launched (256 CUs).
+//
+// Contract for `frozen` (padded steps of a packed sequence): it comes with frozen_out_zero = 1 and a zero initial state
+// (h0 = c0 = null), as functional.py's _LSTMLayer uses it.  A frozen step keeps c, emits hs = 0 and carries h = 0 forward, which
+// is the packed-sequence result only because a row's frozen steps all lie on one side of its valid ones.  `frozen` with
+// frozen_out_zero = 0 is outside the contract: the per-step cell kernel (lstm.hip) passes h_prev through there, this kernel
+// does not, and nothing in the library combines the two that way.
 #include "common.h"
 #include "espresso_amd.h"
 #include "wave_prims.h"

@@ -2042,14 +2042,17 @@ class _LSTMLayer(torch.autograd.Function):
         h_last = torch.empty(B, H, dtype=torch.float32, device=dev)
         h0_16 = K.cast_f32_to_bf16(h0.float().contiguous()) if h0 is not None else None
         c0 = c0.float().contiguous() if c0 is not None else None
+        # frozen (padded steps) always comes with frozen_out_zero and the zero initial state: the only combination in the contract of
+        # the persistent kernels (csrc/lstm_seq.hip), which carry h = 0 through a frozen step where the cell kernel passes h_prev on
         assert frozen is None or (h0 is None and c0 is None), "packed sequences start from the zero state"
+        frozen_out_zero = frozen is not None
         order = range(U - 1, -1, -1) if reverse else range(U)
         prev = None
         persistent = _LSTM_PERSISTENT and K.lstm_seq_supported(B, H)
         if persistent:  # the whole time loop in one launch (csrc/lstm_seq.hip)
             counter = torch.empty(2, dtype=torch.int32, device=dev)
             K.lstm_seq_fwd(gx, w_hh16, h0_16, c0, frozen, hs, cs, act, h_last, counter, B, U, H, reverse=reverse,
-                           frozen_out_zero=frozen is not None)
+                           frozen_out_zero=frozen_out_zero)
             prev = 0 if reverse else U - 1
             order = ()
             _lstm_counters.append(counter)

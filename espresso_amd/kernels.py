@@ -1832,6 +1832,8 @@ def lstm_seq_supported(B, H):
 
 
 def lstm_seq_fwd(gx, w_hh16, h0_16, c0, frozen, hs, cs, act, h_last, counter, B, U, H, reverse=False, frozen_out_zero=False):
+    # the persistent kernels' contract (csrc/lstm_seq.hip): frozen steps emit zeros and start from the zero state
+    assert frozen is None or (frozen_out_zero and h0_16 is None and c0 is None), "lstm_seq_fwd: frozen needs frozen_out_zero and no h0 / c0"
     check(_lib.lib().ea_lstm_seq_fwd(_p(gx), _p(w_hh16), _p(h0_16), _p(c0), _p(frozen), _p(hs), _p(cs), _p(act), _p(h_last),
                                      _p(counter), B, U, H, int(reverse), int(frozen_out_zero), _stream()), "ea_lstm_seq_fwd")
 

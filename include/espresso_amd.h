@@ -1194,7 +1194,7 @@ int ea_lstm_seq_bwd(const void* dhs, const float* dh_last, const float* dc_last,
  *
  * Bahdanau attention of one decoder step — espresso/modules/speech_attention.py:38-87 (normalize=True):
  *   score[t][b] = sum_a nv[a] tanh(qp[b][a] + key[t][b][a] + bias[a]), nv = g v/||v|| (caller), softmax over t < len[b],
- *   ctx[b] = sum_t p[t][b] value[t][b].  qp bf16 [B][A]; key bf16 [T][B][A]; value bf16 [T][B][Cv]; p fp32 [T][B]; ctx bf16 [B][ldc].
+ *   ctx[b] = sum_t p[t][b] value[t][b] (len[b] == 0: p = 0, ctx = 0).  qp bf16 [B][A]; key bf16 [T][B][A]; value bf16 [T][B][Cv]; p fp32 [T][B]; ctx bf16 [B][ldc].
  * bwd (one step): dqp bf16 [B][A]; dkey_acc fp32 [T][B][A] and dvalue_acc fp32 [T][B][Cv] are accumulated in place over the
  * decoder steps; dnv_acc / dbias_acc fp32 [A] by atomics. */
 int ea_bahdanau_fwd(const void* qp, const void* key, const void* value, const float* nv, const float* bias, const int* len,
@@ -1212,6 +1212,7 @@ int ea_gather_rows(const void* in, void* out, const int* parent, int N, int W, i
  * fairseq/modules/multihead_attention.py:716-760,878-897,964-989.
  * ea_decode_attention: out[n] = softmax(q[n] . K[r]^T) V[r], r = kv_row ? kv_row[n] : n, over len ? len[r] : max_len keys;
  *   q/out bf16 [N][ldq] (q pre-scaled), K/V bf16 rows of `row_stride` elements, key j at j*ldkv + koff/voff + h*dh.
+ *   len[r] <= max_len; a row with len[r] == 0 attends to nothing: out[n] = 0 (and probs = 0).
  * ea_kv_append_reorder: new[n][0:L] = old[parent[n]][0:L], new[n][L] = kv_new[n]  (rows of W bf16, capacity Lmax).
  * ea_beam_mask_rows: sequence_generator.py:395-424 on fp32 lprobs [N][V] in place.
  * ea_beam_topk: per sentence the k (<=128) best of lprobs[(s*beam+b)][v] + prev_scores[s*beam+b], b < nbeam_used. */
