@@ -22,6 +22,7 @@ import torch
 from ..tools.utils import collate_frames
 from . import audio_utils, kaldi_io
 from .data_utils import collate_tokens
+from .resample import resampled_length
 
 FRAME_LEN, FRAME_SHIFT = 400, 160  # 25 ms / 10 ms at 16 kHz (espresso/tools/utils.py:478-486)
 
@@ -52,8 +53,9 @@ class _AudioBase:
 
 
 class AudioWaveDataset(_AudioBase):
-    """Raw waveforms: WAV paths, `cmd |` pipes, or in-memory float arrays.  `sizes` are frame counts (what
-    `--max-tokens` budgets), from `utt2num_frames` when given, else from the WAV headers."""
+    """Raw waveforms: WAV paths, `cmd |` pipes, or in-memory float arrays (those at `sample_rate`).  `sizes` are frame counts (what
+    `--max-tokens` budgets), from `utt2num_frames` when given, else from the WAV headers: the frames of the audio once it is at
+    `sample_rate` (a file at another rate is resampled by the front-end, data/resample.py, and carries its rate there)."""
 
     is_wave = True
 
@@ -62,12 +64,12 @@ class AudioWaveDataset(_AudioBase):
         assert len(utt_ids) == len(rxfiles)
         self.utt_ids, self.rxfiles, self.size = list(utt_ids), list(rxfiles), len(utt_ids)
         self.feat_dim, self.sample_rate, self.epoch = feat_dim, sample_rate, 1
-        self._nsamp = {}  # sample counts read from the file headers (lazy mode needs them before the files are decoded)
+        self._nsamp = {}  # (sample count, rate) read from the file headers (lazy mode needs them before the files are decoded)
         if utt2num_frames is not None and len(utt2num_frames) > 0:
             assert len(utt2num_frames) == self.size
             sizes = utt2num_frames
         else:
-            sizes = [samples_to_frames(len(r) if isinstance(r, np.ndarray) else audio_utils.num_samples(r)) for r in self.rxfiles]
+            sizes = [samples_to_frames(resampled_length(*self.samples_and_rate(i), sample_rate)) for i in range(self.size)]
         self.sizes = np.array(sizes, dtype=np.int32)
 
     # lazy mode (set by the training loop): file entries are returned as `audio_utils.LazyWave` placeholders and the collater
@@ -75,13 +77,16 @@ class AudioWaveDataset(_AudioBase):
     lazy = False
     num_workers = 1
 
-    def num_samples(self, i) -> int:
-        n = self._nsamp.get(i)
-        if n is None:
+    def samples_and_rate(self, i):
+        nr = self._nsamp.get(i)
+        if nr is None:
             r = self.rxfiles[i]
-            n = len(r) if isinstance(r, np.ndarray) else audio_utils.num_samples(r)
-            self._nsamp[i] = n
-        return n
+            nr = (len(r), self.sample_rate) if isinstance(r, np.ndarray) else audio_utils.samples_and_rate(r)
+            self._nsamp[i] = nr
+        return nr
+
+    def num_samples(self, i) -> int:
+        return self.samples_and_rate(i)[0]
 
     def __getitem__(self, i):
         self.check_index(i)
@@ -89,10 +94,9 @@ class AudioWaveDataset(_AudioBase):
         if isinstance(r, np.ndarray):
             return r.astype(np.float32, copy=False)
         if self.lazy and audio_utils._is_file(r):
-            return audio_utils.LazyWave(r, self.num_samples(i))
+            return audio_utils.LazyWave(r, *self.samples_and_rate(i))
         x, sr = audio_utils.get_waveform(r)
-        assert sr == self.sample_rate, f"{self.utt_ids[i]}: {sr} Hz, the front-end tables are built for {self.sample_rate} Hz"
-        return x
+        return x if sr == self.sample_rate else audio_utils.RatedWave(x, sr)
 
 
 class AudioFeatDataset(_AudioBase):
@@ -155,7 +159,9 @@ class AsrTextDataset:
 def collate(samples, pad_idx, eos_idx, left_pad_source=False, left_pad_target=False, input_feeding=True, maybe_bos_idx=None,
             pad_to_length=None, pad_to_multiple=1, pin_memory=False, wave_workers=1, sample_rate=16000):
     """espresso/data/asr_dataset.py:17-136.  `source` is either a `(T, F)` feature tensor (reference path) or a 1-D
-    float waveform (raw-audio path, see the module docstring)."""
+    float waveform (raw-audio path, see the module docstring).  A waveform at another rate than `sample_rate` (a `RatedWave`, or
+    a `LazyWave` whose header says so) is sorted and counted by the frames it has once resampled, and the batch then carries
+    `wav_rates` for the front-end; a batch whose audio is all at `sample_rate` has exactly the keys it always had."""
     if len(samples) == 0:
         return {}
     is_wave = isinstance(samples[0]["source"], (np.ndarray, audio_utils.LazyWave)) and samples[0]["source"].ndim == 1
@@ -166,7 +172,9 @@ def collate(samples, pad_idx, eos_idx, left_pad_source=False, left_pad_target=Fa
 
     id = torch.LongTensor([s["id"] for s in samples])
     if is_wave:
-        src_lengths = torch.IntTensor([samples_to_frames(len(s["source"])) for s in samples])
+        wav_rates = [int(getattr(s["source"], "sample_rate", None) or sample_rate) for s in samples]
+        src_lengths = torch.IntTensor([samples_to_frames(resampled_length(len(s["source"]), r, sample_rate))
+                                       for s, r in zip(samples, wav_rates)])
     else:
         src_frames = collate_frames([s["source"] for s in samples], 0.0, left_pad_source,
                                     pad_to_length=pad_to_length["source"] if pad_to_length is not None else None,
@@ -213,8 +221,9 @@ def collate(samples, pad_idx, eos_idx, left_pad_source=False, left_pad_target=Fa
             # every file decoded straight into its slot, `wave_workers` files at a time, outside the interpreter lock
             wav = torch.empty(int(offsets[-1]), dtype=torch.int16, pin_memory=pin_memory)
             rates = audio_utils.read_batch_i16([samples[i]["source"].path for i in order], wav.numpy(), offsets, wave_workers)
-            assert all(r == sample_rate for r in rates), f"sample rates {sorted(set(rates))}: the front-end tables are built for {sample_rate} Hz"
+            wav_rates = [int(r) for r in rates]  # (the decoder's word; the headers said the same)
         else:
+            wav_rates = [wav_rates[i] for i in order]
             wav = torch.empty(int(offsets[-1]), dtype=torch.float32, pin_memory=pin_memory)
             wnp = wav.numpy()
             for k, i in enumerate(order):
@@ -222,6 +231,8 @@ def collate(samples, pad_idx, eos_idx, left_pad_source=False, left_pad_target=Fa
                 wnp[offsets[k]:offsets[k + 1]] = audio_utils.get_waveform(src.path)[0] if lazy[k] else src
         batch.update(wav=wav, wav_offsets=torch.from_numpy(offsets), num_samples=lens, id_list=id.tolist(),
                      audio_seconds=float(offsets[-1]) / 16000.0)
+        if any(r != sample_rate for r in wav_rates):
+            batch.update(wav_rates=wav_rates, audio_seconds=sum(n / float(r) for n, r in zip(lens, wav_rates)))
     else:
         net_input["src_tokens"] = src_frames.index_select(0, sort_order)
     if prev_output_tokens is not None:

@@ -18,14 +18,29 @@ class LazyWave:
     """A waveform file that has not been read yet: what `AudioWaveDataset` hands the collater in lazy mode, so that the files of
     a whole batch are decoded in parallel straight into the pinned staging buffer (`read_batch_i16`)."""
 
-    __slots__ = ("path", "num_samples")
+    __slots__ = ("path", "num_samples", "sample_rate")
     ndim = 1
 
-    def __init__(self, path: str, num_samples: int):
+    def __init__(self, path: str, num_samples: int, sample_rate=None):
         self.path, self.num_samples = path, int(num_samples)
+        self.sample_rate = sample_rate  # from the header (None: not probed; the front-end's rate is assumed)
 
     def __len__(self):
         return self.num_samples
+
+
+class RatedWave(np.ndarray):
+    """Decoded samples that are NOT at the front-end's rate: a float32 array that carries its `sample_rate` to the collater."""
+
+    sample_rate = None
+
+    def __new__(cls, samples: np.ndarray, sample_rate: int):
+        obj = np.asarray(samples, dtype=np.float32).view(cls)
+        obj.sample_rate = int(sample_rate)
+        return obj
+
+    def __array_finalize__(self, obj):
+        self.sample_rate = getattr(obj, "sample_rate", None)
 
 
 def _is_file(source) -> bool:
@@ -121,6 +136,15 @@ def num_samples(source: str) -> int:
     if source.rstrip().endswith("|"):
         return len(get_waveform(source)[0])
     return probe(source)[0]
+
+
+def samples_and_rate(source: str) -> Tuple[int, int]:
+    """(sample count, sample rate) from the header only (a `cmd |` pipe is decoded)."""
+    if source.rstrip().endswith("|"):
+        x, sr = get_waveform(source)
+        return len(x), sr
+    n, sr, _, _ = probe(source)
+    return n, sr
 
 
 def write_wav(path: str, samples: np.ndarray, sample_rate: int = 16000):

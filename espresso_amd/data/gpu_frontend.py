@@ -11,6 +11,7 @@ import torch
 
 from .. import kernels as K
 from .fbank_tables import build_tables
+from .resample import Resampler
 from .feature_transforms import AdaptiveSpecAugmentTransform, GlobalCMVN, numpy_seed_value
 
 
@@ -41,6 +42,7 @@ class GpuFbankFrontend:
             self.cmvn_std = torch.tensor(cmvn.std, dtype=torch.float32, device=device)
         self.specaug = specaug
         self.seed = seed
+        self.resampler = Resampler(device, sample_rate)
 
     def num_frames(self, n_samples: int) -> int:
         return 0 if n_samples < self.frame_len else 1 + (n_samples - self.frame_len) // self.frame_shift
@@ -83,10 +85,14 @@ class GpuFbankFrontend:
         return pinned.to(self.device, non_blocking=True)
 
     def __call__(self, wav: torch.Tensor, offsets: torch.Tensor, n_samples: Sequence[int], train=False, epoch=1,
-                 indices: Optional[Sequence[int]] = None):
+                 indices: Optional[Sequence[int]] = None, rates: Optional[Sequence[int]] = None):
         """wav: device fp32 concatenated samples; offsets: device int64 [B+1]; n_samples: host lengths.
+        rates: the sample rate of each utterance (None: all at `sample_rate`); utterances at another rate are resampled on the
+        device first (data/resample.py), and the frame counts are those of the resampled audio.
         Returns (feat fp32 [B][Tmax][nmel], lengths int32 [B] on device, host frame counts)."""
         B = len(n_samples)
+        if rates is not None:
+            wav, offsets, n_samples = self.resampler(wav, offsets, n_samples, rates)
         frames = [self.num_frames(int(n)) for n in n_samples]
         Tmax = max(frames) if frames else 0
         use_sa = train and self.specaug is not None

@@ -559,6 +559,23 @@ def fbank_batch(wav, offsets, B, tables, cmvn_mean, cmvn_std, Tmax, nmel=80, fra
     return feat, out_len, utt_sum
 
 
+def resample_batch(wav, in_offsets, out, out_offsets, B, taps, first, in_unit, max_out, in_base=None, out_base=None):
+    """out[out_offsets[b] : out_offsets[b + 1]] = utterance b of `wav` (fp32 or int16) through the polyphase filter
+    taps fp32 [phases][K] / first int32 [phases] (data/resample.py: ResamplePlan).  Bases int64 [B]: absolute index of the
+    first sample held / first output wanted (None: 0, the offline case)."""
+    assert wav.dtype in (torch.float32, torch.int16) and out.dtype == torch.float32
+    assert taps.dtype == torch.float32 and taps.dim() == 2 and taps.is_contiguous() and first.dtype == torch.int32
+    assert in_offsets.dtype == torch.int64 and out_offsets.dtype == torch.int64
+    phases, Kt = taps.shape
+    fn = _lib.lib().ea_resample_batch if wav.dtype == torch.float32 else _lib.lib().ea_resample_batch_i16
+    check(
+        fn(_p(wav), _p(in_offsets), _p(in_base), _p(out), _p(out_offsets), _p(out_base), B, _p(taps), _p(first), phases, Kt,
+           in_unit, max_out, _stream()),
+        "ea_resample_batch",
+    )
+    return out
+
+
 def feature_stats(feat, lengths, acc):
     """acc fp64 [2*nmel+1] += (sum, sum of squares, frames) over the valid frames of feat fp32 [B][Tmax][nmel]."""
     B, Tmax, nmel = feat.shape

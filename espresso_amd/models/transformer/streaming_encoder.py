@@ -21,7 +21,7 @@ refused.
 
 LayerNorm, the QKV / out-proj / FFN GEMMs and the sub-sampler are the offline path's kernels, run on the [sum n_new][C] rows
 of all streams that have a chunk ready."""
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -121,6 +121,7 @@ class StreamingEncoder:
                     self._bn_mr.append(K.bn_from_running(bn.running_mean, bn.running_var, bn.eps))
                     self._dw_w.append(l.conv_module.depthwise_conv.weight.detach().float().reshape(self.C, self.KW).contiguous())
         self.streams: Dict[object, _Stream] = {}
+        self.resampler = None  # a StreamResampler, once a stream is opened at another rate than the front-end's
         self._free = list(range(self.max_streams - 1, -1, -1))
         self._zero_table = None
         with torch.no_grad():
@@ -146,7 +147,17 @@ class StreamingEncoder:
         return len(self.caches) * self.W * 2 * self.C * 2 + len(self.carries) * (self.KW - 1) * self.C * 2
 
     # ---- stream management ---------------------------------------------------------------------------------------------
-    def open(self, stream_ids: Sequence):
+    def open(self, stream_ids: Sequence, rates: Optional[Sequence[int]] = None):
+        """rates: the sample rate of the audio `accept_waveform` will get for each stream (None: the front-end's).  A stream at
+        another rate is converted piece by piece (data/resample.py: StreamResampler), to the bits of an offline conversion."""
+        if rates is not None and self.frontend is not None:
+            odd = [(sid, int(r)) for sid, r in zip(stream_ids, rates) if int(r) != self.frontend.sample_rate]
+            if odd:
+                if self.resampler is None:
+                    from ...data.resample import StreamResampler
+
+                    self.resampler = StreamResampler(self.device, self.frontend.sample_rate)
+                self.resampler.open([sid for sid, _ in odd], [r for _, r in odd])
         for sid in stream_ids:
             if sid in self.streams:
                 raise ValueError(f"stream {sid!r} is already open")
@@ -162,15 +173,25 @@ class StreamingEncoder:
         for sid in stream_ids:
             st = self.streams.pop(sid)
             self._free.append(st.slot)
+        if self.resampler is not None:
+            self.resampler.close(stream_ids)
 
     # ---- input ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def accept_waveform(self, stream_ids, waves: Sequence[torch.Tensor], final):
-        """waves: one 1-D fp32 tensor of new samples per stream (int16 scale, as the front-end expects).  Kaldi fbank frames
-        are independent of each other (snip_edges): frame t covers samples [t*shift, t*shift + frame_len)."""
+        """waves: one 1-D fp32 tensor of new samples per stream (int16 scale, as the front-end expects; at the rate the stream
+        was opened with).  Kaldi fbank frames are independent of each other (snip_edges): frame t covers samples
+        [t*shift, t*shift + frame_len)."""
         fe = self.frontend
         assert fe is not None, "accept_waveform needs the GpuFbankFrontend given at construction"
         final = [final] * len(stream_ids) if isinstance(final, bool) else list(final)
+        if self.resampler is not None:
+            odd = [b for b, sid in enumerate(stream_ids) if sid in self.resampler.streams]
+            if odd:
+                conv = self.resampler.accept([stream_ids[b] for b in odd], [waves[b] for b in odd], [final[b] for b in odd])
+                waves = list(waves)
+                for b, w in zip(odd, conv):
+                    waves[b] = w
         pend, counts = [], []
         for sid, w in zip(stream_ids, waves):
             st = self.streams[sid]
@@ -232,10 +253,16 @@ class StreamingEncoder:
         return (flat[0] if len(flat) == 1 else torch.cat(flat)), counts
 
     # ---- chunk scheduling (host integers only) ----------------------------------------------------------------------------
-    def max_rows_per_accept(self, n_samples: int) -> int:
+    def max_rows_per_accept(self, n_samples: int, rate: Optional[int] = None) -> int:
         """An upper bound on the encoder frames one `accept_waveform` of at most n_samples new samples returns for a stream: the
         rows of the new feature frames, plus what the stream held back (less than a chunk and the receptive field of its last
-        row), which a final piece flushes."""
+        row), which a final piece flushes.  rate: the rate n_samples are counted at (None: the front-end's); what the resampler
+        held back of earlier pieces (its filter's reach, K inputs) comes out with a later one."""
+        if rate is not None and int(rate) != self.frontend.sample_rate:
+            from ...data.resample import resample_plan
+
+            fo = self.frontend.sample_rate
+            n_samples = -(-(n_samples + resample_plan(int(rate), fo).K + 1) * fo // int(rate)) + 1
         n = n_samples // self.frontend.frame_shift + 2  # the samples left over from the last piece complete one more frame
         return -(-n // self.stride) + self.cs + -(-(self.rf + 1) // self.stride) + 1
 

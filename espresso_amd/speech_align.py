@@ -28,7 +28,8 @@ from typing import Dict, List
 
 import torch
 
-from .speech_recognize import _load_file, collate, load_member, make_batches, read_scp, read_wav, resolve_model_config, shard_batches
+from .speech_recognize import (_load_file, audio_seconds, collate, lengths_at, load_member, make_batches, read_scp, read_wav,  # noqa: F401
+                               read_waves, resolve_model_config, shard_batches)
 
 DEFAULT_SEGMENT_MAX_S, DEFAULT_SEGMENT_MIN_SILENCE_S = 20.0, 0.3  # option defaults, uncalibrated
 
@@ -219,8 +220,9 @@ def main(argv=None):
     if missing:
         raise ValueError(f"--text has no transcript for {len(missing)} utterance(s), e.g. {missing[0]}")
     targets = {u: tokenize(d, texts[u], blank) for u in utt_ids}
-    waves = [read_wav(scp[u]) for u in utt_ids]
+    waves, rates = read_waves([scp[u] for u in utt_ids])
     task.build_frontend(dev)
+    fo = task.frontend.sample_rate
     spf = frame_seconds(model, task.frontend.frame_shift / task.frontend.sample_rate)
     results, t_align, audio_s = {}, 0.0, 0.0
     if args.long_form:  # one recording at a time: its windows' stitched log-probs, then the tiled Viterbi search
@@ -229,23 +231,23 @@ def main(argv=None):
         junctions = LF.LongFormModel(model, aligner.long_form)  # (for `log_worst`: the cuts of every recording)
         for i in range(args.shard_id, len(utt_ids), args.num_shards):
             t0 = time.perf_counter()
-            r = aligner.align(waves[i], targets[utt_ids[i]])  # (one host copy per recording)
+            r = aligner.align(waves[i], targets[utt_ids[i]], rates[i])  # (one host copy per recording)
             t_align += time.perf_counter() - t0
-            audio_s += len(waves[i]) / float(task.frontend.sample_rate)
+            audio_s += len(waves[i]) / float(rates[i])
             results[utt_ids[i]] = r
             junctions.junctions.append((torch.from_numpy(r["cuts"]), torch.from_numpy(r["cut_scores"])))
         LF.log_worst(junctions, sys.stderr)
         batches = []
     else:
-        batches = shard_batches(make_batches(utt_ids, [len(w) for w in waves], args.max_tokens, args.batch_size), args.num_shards,
+        batches = shard_batches(make_batches(utt_ids, lengths_at(waves, rates, fo), args.max_tokens, args.batch_size), args.num_shards,
                                 args.shard_id)
     for ids in batches:
-        sample = collate(ids, utt_ids, waves, dev)
+        sample = collate(ids, utt_ids, waves, dev, rates, fo)
         t0 = time.perf_counter()
         s = task.prepare_sample(sample, train=False)
         out = aligner.align(s, [targets[u] for u in sample["utt_ids"]])  # (one host copy per batch)
         t_align += time.perf_counter() - t0
-        audio_s += sum(sample["num_samples"]) / float(task.frontend.sample_rate)
+        audio_s += audio_seconds(sample, fo)
         results.update(zip(sample["utt_ids"], out))
 
     order = [u for u in utt_ids if u in results]  # wav.scp order

@@ -29,7 +29,8 @@ from typing import Dict, List
 import numpy as np
 import torch
 
-from .speech_recognize import _load_file, collate, load_member, make_batches, read_scp, read_wav, resolve_model_config, shard_batches
+from .speech_recognize import (_load_file, collate, lengths_at, load_member, make_batches, read_scp, read_wav, read_waves,  # noqa: F401
+                               resolve_model_config, shard_batches)
 
 
 def get_parser():
@@ -110,15 +111,17 @@ def write_hits(results: Dict[str, List[Dict]], order, seconds_per_frame: float, 
             print(output_line(u, h, seconds_per_frame), file=out)
 
 
-def spot_streaming(task, model, spotter, utt_ids, waves, seconds_per_frame, chunk_ms=400, streams=16, out=None):
+def spot_streaming(task, model, spotter, utt_ids, waves, seconds_per_frame, chunk_ms=400, streams=16, out=None, rates=None):
     """utterance -> hits from a streamed pass: every utterance is read in pieces of `chunk_ms`, `streams` of them in flight; a
-    finished utterance frees its slot for the next one (wav.scp order).  A `K-` line per hit as soon as it is read."""
+    finished utterance frees its slot for the next one (wav.scp order).  A `K-` line per hit as soon as it is read.
+    rates: the sample rate of every entry of `waves` (None: the front-end's); pieces are cut at the utterance's own rate."""
     from .models.transformer.streaming_encoder import StreamingEncoder
     from .tools.keyword_spotter import hit_seconds
 
     out = sys.stdout if out is None else out
     se = StreamingEncoder(model, streams, frontend=task.frontend)
-    piece = max(1, int(16000 * chunk_ms / 1000))
+    rates = [task.frontend.sample_rate] * len(waves) if rates is None else [int(r) for r in rates]
+    piece_of = [max(1, int(r * chunk_ms / 1000)) for r in rates]
     pending = list(range(len(utt_ids)))
     live = {}  # utterance index -> samples consumed
     results = {u: [] for u in utt_ids}
@@ -126,7 +129,7 @@ def spot_streaming(task, model, spotter, utt_ids, waves, seconds_per_frame, chun
     def report(i, hits):
         for h in hits:
             s, e = hit_seconds(h, seconds_per_frame)
-            print("K-{}\t{:.2f}\t{:.3f}\t{:.3f}\t{:.4f}\t{}".format(utt_ids[i], live[i] / 16000.0, s, e, h["confidence"], h["text"]),
+            print("K-{}\t{:.2f}\t{:.3f}\t{:.3f}\t{:.4f}\t{}".format(utt_ids[i], live[i] / float(rates[i]), s, e, h["confidence"], h["text"]),
                   file=out)
         results[utt_ids[i]] += hits
 
@@ -134,13 +137,13 @@ def spot_streaming(task, model, spotter, utt_ids, waves, seconds_per_frame, chun
         while pending and len(live) < streams:
             i = pending.pop(0)
             live[i] = 0
-            se.open([i])
+            se.open([i], **({} if rates[i] == task.frontend.sample_rate else {"rates": [rates[i]]}))
             spotter.open([i])
         ids = list(live)
         pieces, final = [], []
         for i in ids:
             a = live[i]
-            b = min(len(waves[i]), a + piece)
+            b = min(len(waves[i]), a + piece_of[i])
             pieces.append(torch.from_numpy(np.ascontiguousarray(waves[i][a:b])).float())
             live[i] = b
             final.append(b >= len(waves[i]))
@@ -197,8 +200,9 @@ def main(argv=None):
 
     scp = read_scp(args.wav_scp)
     utt_ids = list(scp.keys())
-    waves = [read_wav(scp[u]) for u in utt_ids]
+    waves, rates = read_waves([scp[u] for u in utt_ids])
     task.build_frontend(dev)
+    fo = task.frontend.sample_rate
     spf = frame_seconds(model, task.frontend.frame_shift / task.frontend.sample_rate)
     spotter = CTCKeywordSpotter(d, keywords, max_streams=streams if args.streaming else 1, hold_frames=hold_frames(args.hold_ms, spf),
                                 max_hits=args.max_hits)
@@ -209,18 +213,19 @@ def main(argv=None):
                                                     args.batch_size))
         results = {}
         for i in range(args.shard_id, len(utt_ids), args.num_shards):
-            out = lf(waves[i])
+            out = lf(waves[i], rates[i])
             results[utt_ids[i]] = spotter.spot_lprobs(out["_lprobs"], out["src_lengths"][0])[0]
         LF.log_worst(lf, sys.stderr)
     elif args.streaming:
         mine = [i for i in range(len(utt_ids)) if i % args.num_shards == args.shard_id]
-        results = spot_streaming(task, model, spotter, [utt_ids[i] for i in mine], [waves[i] for i in mine], spf, chunk_ms, streams)
+        results = spot_streaming(task, model, spotter, [utt_ids[i] for i in mine], [waves[i] for i in mine], spf, chunk_ms, streams,
+                                 rates=[rates[i] for i in mine])
     else:
         results = {}
-        batches = shard_batches(make_batches(utt_ids, [len(w) for w in waves], args.max_tokens, args.batch_size), args.num_shards,
+        batches = shard_batches(make_batches(utt_ids, lengths_at(waves, rates, fo), args.max_tokens, args.batch_size), args.num_shards,
                                 args.shard_id)
         for ids in batches:
-            sample = collate(ids, utt_ids, waves, dev)
+            sample = collate(ids, utt_ids, waves, dev, rates, fo)
             s = task.prepare_sample(sample, train=False)
             results.update(zip(sample["utt_ids"], spotter.spot(model, s)))  # (one host copy per batch)
     if dev.type == "cuda":
@@ -234,7 +239,7 @@ def main(argv=None):
     finally:
         if out is not sys.stdout:
             out.close()
-    audio_s = sum(len(w) for u, w in zip(utt_ids, waves) if u in results) / float(task.frontend.sample_rate)
+    audio_s = sum(len(w) / float(r) for u, w, r in zip(utt_ids, waves, rates) if u in results)
     print("| {} hits of {} keywords in {} utterances in {:.1f}s, RTF {:.4f}{}".format(
         sum(len(results[u]) for u in order), len(keywords), len(order), t_spot, t_spot / max(audio_s, 1e-9),
         " ({} hits lost to --max-hits)".format(spotter.overflowed) if spotter.overflowed else ""), file=sys.stderr)

@@ -27,7 +27,29 @@ import numpy as np
 import torch
 
 
-from .data.audio_utils import read_wav  # noqa: E402,F401
+from .data.audio_utils import get_waveform, read_wav  # noqa: E402,F401
+from .data.resample import resampled_length  # noqa: E402
+
+
+def read_waves(paths: List[str]):
+    """(waveforms, their sample rates): the rate travels with the samples, and the front-end converts what is not its own."""
+    pairs = [get_waveform(p) for p in paths]
+    return [w for w, _ in pairs], [int(r) for _, r in pairs]
+
+
+def lengths_at(waves, rates, fo: int) -> List[int]:
+    """Sample counts after conversion to `fo`: what batches are budgeted with and frame counts are taken from."""
+    if rates is None:
+        return [len(w) for w in waves]
+    return [resampled_length(len(w), r, fo) for w, r in zip(waves, rates)]
+
+
+def audio_seconds(sample, fo: int = 16000) -> float:
+    """Duration of a collated batch, every utterance at its own rate."""
+    rates = sample.get("wav_rates")
+    if rates is None:
+        return sum(sample["num_samples"]) / float(fo)
+    return sum(n / float(r) for n, r in zip(sample["num_samples"], rates))
 
 
 def read_scp(path: str) -> Dict[str, str]:
@@ -88,7 +110,7 @@ def recognize(task, model, generator, batches: Iterable[dict], dictionary, refs:
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         t_gen += time.perf_counter() - t0
-        audio_s += sum(sample["num_samples"]) / 16000.0
+        audio_s += audio_seconds(sample)
         enc_lens = None
         if attn_plot_dir is not None:  # valid encoder frames of every utterance (the plot drops the padded rows)
             enc_lens = model.encoder.output_lengths(s["net_input"]["src_lengths"]).tolist()
@@ -144,12 +166,18 @@ def write_results(results_path: str, scorer, has_target: bool):
         write("aligned_results.txt", scorer.print_aligned_results())
 
 
-def collate(ids: List[int], utt_ids: List[str], waves: List[np.ndarray], device):
+def collate(ids: List[int], utt_ids: List[str], waves: List[np.ndarray], device, rates: Optional[List[int]] = None,
+            sample_rate: int = 16000):
+    """rates: the sample rate of every entry of `waves` (None: all at `sample_rate`).  The batch carries `wav_rates` only when one
+    of its utterances is at another rate than `sample_rate`; `num_samples` stay counts at the utterance's own rate."""
     lens = [len(waves[i]) for i in ids]
     offs = np.zeros(len(ids) + 1, dtype=np.int64)
     offs[1:] = np.cumsum(lens)
-    return {"utt_ids": [utt_ids[i] for i in ids], "wav": torch.from_numpy(np.concatenate([waves[i] for i in ids])).to(device),
-            "wav_offsets": torch.from_numpy(offs).to(device), "num_samples": lens, "net_input": {}}
+    sample = {"utt_ids": [utt_ids[i] for i in ids], "wav": torch.from_numpy(np.concatenate([waves[i] for i in ids])).to(device),
+              "wav_offsets": torch.from_numpy(offs).to(device), "num_samples": lens, "net_input": {}}
+    if rates is not None and any(int(rates[i]) != sample_rate for i in ids):
+        sample["wav_rates"] = [int(rates[i]) for i in ids]
+    return sample
 
 
 def build_generator(args, model, dictionary, lm=None, ngram=None, context_graph=None):
@@ -626,7 +654,8 @@ def check_streaming_args(args):
 
 def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=400, streams=16, refs=None, out=sys.stdout,
                         quiet=False, scorer=None, summary_out=None, search="ctc", max_num_expansions_per_step=2, lexicon_beam=None,
-                        partials=False, stream_beam=None, ctc_stream_beam=None, ctm_hyps=None, endpoint=None, seconds_per_frame=None):
+                        partials=False, stream_beam=None, ctc_stream_beam=None, ctm_hyps=None, endpoint=None, seconds_per_frame=None,
+                        rates=None):
     """The output of `recognize` from a streamed pass: every utterance is read in pieces of `chunk_ms`, `streams` of them in
     flight; a finished utterance frees its slot for the next one (wav.scp order).  search "ctc_beam": lexicon_beam holds the
     arguments of StreamingCTCLexiconBeamDecoder after `dictionary` (n-gram LM, lexicon) and its options; its prefix tables are
@@ -642,7 +671,10 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
     ("room").  A closed segment prints `S-<utt>`, its start and end in seconds (seconds_per_frame per encoder frame; default:
     the encoder's stride x the front-end's frame shift), the rule and its text; the segment the audio's end closes is "final".
     Segments end on piece boundaries.  The utterance's hypothesis is the segments' joined: tokens concatenated, scores summed,
-    times shifted by each segment's first frame.  The stable field of a `P-` line starts with the closed segments' text."""
+    times shifted by each segment's first frame.  The stable field of a `P-` line starts with the closed segments' text.
+
+    rates: the sample rate of every entry of `waves` (None: the front-end's).  Pieces of `chunk_ms` are cut at the utterance's own
+    rate and converted by the encoder's StreamResampler; every time printed stays in seconds of the recording."""
     from .models.transformer.streaming_encoder import StreamingEncoder
     from .tools.streaming_ctc_decoder import StreamingCTCDecoder
     from .tools.streaming_ctc_lexicon_beam_decoder import StreamingCTCLexiconBeamDecoder
@@ -657,8 +689,10 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
     se = StreamingEncoder(model, streams, frontend=task.frontend)
     partial_of = None  # a decoder's partial -> (tokens of the best hypothesis, how many of them are stable)
     # the longest utterance's encoder frames: what a slot of the three beam searches is sized for
-    max_frames = max([1] + [-(-task.frontend.num_frames(len(w)) // se.stride) for w in waves])
-    piece = max(1, int(16000 * chunk_ms / 1000))
+    fo = task.frontend.sample_rate
+    rates = [fo] * len(waves) if rates is None else [int(r) for r in rates]
+    max_frames = max([1] + [-(-task.frontend.num_frames(n) // se.stride) for n in lengths_at(waves, rates, fo)])
+    piece_of = [max(1, int(r * chunk_ms / 1000)) for r in rates]  # samples per piece, at the utterance's own rate
     if endpoint is not None:
         if search not in ("ctc_stream_beam", "transducer_stream_beam"):
             raise NotImplementedError("endpointing (--stream-endpoint) is implemented for --search ctc_stream_beam and --search "
@@ -667,7 +701,8 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
         if opts.get("nbest", 1) != 1:
             raise NotImplementedError("endpointing (--stream-endpoint) joins the 1-best of consecutive segments: no --nbest > 1 with it")
         if endpoint.segment_frames > 0:  # a constant of the options: memory per stream no longer grows with the audio
-            max_frames = endpoint.segment_frames + se.max_rows_per_accept(piece)
+            max_frames = endpoint.segment_frames + max([se.max_rows_per_accept(max(1, int(fo * chunk_ms / 1000)))] +
+                                                       [se.max_rows_per_accept(p, r) for p, r in zip(piece_of, rates) if r != fo])
         opts = dict(opts, endpoint=endpoint)
         ctc_stream_beam, stream_beam = (opts, stream_beam) if search == "ctc_stream_beam" else (ctc_stream_beam, opts)
         if seconds_per_frame is None:
@@ -728,14 +763,14 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
         while pending and len(live) < streams:
             i = pending.pop(0)
             live[i] = 0
-            se.open([i])
+            se.open([i], **({} if rates[i] == fo else {"rates": [rates[i]]}))
             dec.open([i])
             seg_frames[i] = [0, 0]
         ids = list(live)
         pieces, final = [], []
         for i in ids:
             a = live[i]
-            b = min(len(waves[i]), a + piece)
+            b = min(len(waves[i]), a + piece_of[i])
             pieces.append(torch.from_numpy(np.ascontiguousarray(waves[i][a:b])).float())
             live[i] = b
             final.append(b >= len(waves[i]))
@@ -758,7 +793,7 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
                     texts = (" ".join(t for t in [t for _, _, t in segs[i]] + [texts[0]] if t), texts[1])
                 if shown.get(i) != texts:
                     shown[i] = texts
-                    print("P-{}\t{:.2f}\t{}\t{}".format(utt_ids[i], live[i] / 16000.0, *texts), file=out)
+                    print("P-{}\t{:.2f}\t{}\t{}".format(utt_ids[i], live[i] / float(rates[i]), *texts), file=out)
         for i, f in zip(ids, final):
             if f:
                 se.close([i])
@@ -786,7 +821,7 @@ def recognize_streaming(task, model, dictionary, utt_ids, waves, dev, chunk_ms=4
                 num_tok += len(hypo["tokens"])
                 if ctm_hyps is not None:
                     ctm_hyps[utt] = (hypo, strip)
-        audio_s += len(waves[i]) / 16000.0
+        audio_s += len(waves[i]) / float(rates[i])
     n = len(utt_ids)
     lines = ["NOTE: hypothesis and token scores are output in base 2",
              "Recognized {:,} utterances ({} tokens) in {:.1f}s ({:.2f} sentences/s, {:.2f} tokens/s), RTF {:.4f}".format(
@@ -986,17 +1021,19 @@ def main(argv=None):
         gen = build_generator(args, members if len(members) > 1 else model, task.target_dictionary, lm, ngram, context_graph)
     scp = read_scp(args.wav_scp)
     utt_ids = list(scp.keys())
-    waves = [read_wav(scp[u]) for u in utt_ids]
+    waves, rates = read_waves([scp[u] for u in utt_ids])
     refs = read_scp(args.text) if args.text else None
     task.build_frontend(dev)
-    batches = shard_batches(make_batches(utt_ids, [len(w) for w in waves], args.max_tokens, args.batch_size), args.num_shards, args.shard_id)
+    fo = getattr(task.frontend, "sample_rate", 16000)
+    batches = shard_batches(make_batches(utt_ids, lengths_at(waves, rates, fo), args.max_tokens, args.batch_size), args.num_shards,
+                            args.shard_id)
     if args.num_shards > 1:  # (the defaults come from WORLD_SIZE / RANK: say that this process decodes — and scores — a part only)
         print(f"| decoding shard {args.shard_id} of {args.num_shards}: {sum(len(b) for b in batches)} of {len(utt_ids)} utterances; "
               "WER / CER below cover this shard only", file=sys.stderr)
     from .tools.wer import Scorer
 
     scorer = Scorer(task.target_dictionary, wer_output_filter=args.wer_output_filter)
-    stream = (collate(b, utt_ids, waves, dev) for b in batches)
+    stream = (collate(b, utt_ids, waves, dev, rates, fo) for b in batches)
     lf_model = None
     if args.long_form:  # one recording at a time, its windows are the batch; the generator reads the stitched log-probs
         lf_model = LF.LongFormModel(model, LF.LongFormCTC(task, LF.plan_from_args(args, task.frontend, model), task.target_dictionary.bos(),
@@ -1005,7 +1042,9 @@ def main(argv=None):
         if args.long_form_posteriors:  # after the search, per hypothesis, on the matrix the search read
             gen = LF.LongFormPosteriors(gen, lf_model, task.target_dictionary)
         batches = shard_batches([[i] for i in range(len(utt_ids))], args.num_shards, args.shard_id)
-        stream = ({"utt_ids": [utt_ids[i]], "num_samples": [len(waves[i])], "net_input": {"wave": waves[i]}} for (i,) in batches)
+        stream = ({"utt_ids": [utt_ids[i]], "num_samples": [len(waves[i])],
+                   **({"wav_rates": [rates[i]], "net_input": {"wave": waves[i], "rate": rates[i]}} if rates[i] != fo else
+                      {"net_input": {"wave": waves[i]}})} for (i,) in batches)
     ctm_hyps = {} if args.ctm else None
 
     from .tools.forced_aligner import frame_seconds
@@ -1021,9 +1060,10 @@ def main(argv=None):
         mine = [i for b in batches for i in b]
         mine.sort()
         s_ids, s_waves = [utt_ids[i] for i in mine], [waves[i] for i in mine]
+        s_rates = [rates[i] for i in mine]
         kw = dict(chunk_ms=args.stream_chunk_ms or 400, streams=args.streams or 16, refs=refs, quiet=args.quiet, scorer=scorer,
                   search=args.search, max_num_expansions_per_step=args.max_num_expansions_per_step, partials=args.stream_partials,
-                  ctm_hyps=ctm_hyps)
+                  ctm_hyps=ctm_hyps, rates=s_rates)
         if getattr(args, "stream_endpoint", False):
             kw.update(endpoint_options(args, frame_seconds(model, task.frontend.frame_shift / task.frontend.sample_rate)))
         if args.search == "ctc_beam":

@@ -250,7 +250,7 @@ class SpeechRecognitionEspressoTask:
         if "wav" not in sample:
             return sample
         feat, lengths, _ = self.frontend(sample["wav"], sample["wav_offsets"], sample["num_samples"], train=train,
-                                         epoch=self.epoch, indices=sample.get("id_list"))
+                                         epoch=self.epoch, indices=sample.get("id_list"), rates=sample.get("wav_rates"))
         out = dict(sample)
         out["net_input"] = dict(sample.get("net_input", {}))
         out["net_input"]["src_tokens"] = feat

@@ -30,8 +30,9 @@ def get_parser():
     return p
 
 
-def accumulate(waves, frontend, acc, device):
-    """One launch pair over a list of host waveforms: fbank (no CMVN) + statistics."""
+def accumulate(waves, frontend, acc, device, rates=None):
+    """One launch pair over a list of host waveforms: fbank (no CMVN) + statistics.  rates: their sample rates (None: the
+    front-end's); audio at another rate is resampled on the device first."""
     from .. import kernels as K
 
     lens = [len(w) for w in waves]
@@ -42,7 +43,7 @@ def accumulate(waves, frontend, acc, device):
     for k, w in enumerate(waves):
         buf[offs[k]:offs[k + 1]] = w
     feat, out_len, _ = frontend(pinned.to(device, non_blocking=True), torch.from_numpy(offs).to(device, non_blocking=True), lens,
-                                train=False)
+                                train=False, rates=rates)
     K.feature_stats(feat, out_len, acc)
 
 
@@ -62,16 +63,16 @@ def compute(rxfiles, feat_dim=80, device="cuda:0", num_workers=20, batch_seconds
     acc = torch.zeros(2 * feat_dim + 1, dtype=torch.float64, device=device)
     budget = int(batch_seconds * 16000)
     with ThreadPoolExecutor(max_workers=num_workers) as ex:
-        pending, held = [], 0
+        pending, rates, held = [], [], 0
         for wav, sr in ex.map(get_waveform, rxfiles):
-            assert sr == 16000, "the front-end tables are built for 16 kHz audio"
             pending.append(wav)
-            held += len(wav)
+            rates.append(int(sr))
+            held += len(wav) * 16000 // max(int(sr), 1)
             if held >= budget:
-                accumulate(pending, frontend, acc, device)
-                pending, held = [], 0
+                accumulate(pending, frontend, acc, device, rates)
+                pending, rates, held = [], [], 0
         if pending:
-            accumulate(pending, frontend, acc, device)
+            accumulate(pending, frontend, acc, device, rates)
     return finalize(acc, feat_dim)
 
 

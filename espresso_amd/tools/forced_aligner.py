@@ -119,12 +119,15 @@ class LongFormCTCAligner:
         self.token_posteriors = bool(token_posteriors)
 
     @torch.no_grad()
-    def align(self, wave, tokens) -> Dict:
-        """wave: the recording's samples (host); tokens: its transcript's ids.  Returns the keys of an entry of
+    def align(self, wave, tokens, rate=None) -> Dict:
+        """wave: the recording's samples (host), at `rate` (None: the front-end's); tokens: its transcript's ids.  Returns the keys of an entry of
         `CTCForcedAligner.align` (tokens, start / end in the recording's encoder frames, score, frames, feasible) and frame_lp
         (host fp32 [T]: the log-prob of the chosen label in every frame, 0 when nothing was aligned), cuts and cut_scores (the
         junctions of `LongFormCTC.encode`); with token_posteriors also the three keys of tools/token_posteriors.py for the
         transcript.  One host copy."""
+        from .long_form import at_frontend_rate
+
+        wave = at_frontend_rate(self.long_form.task.frontend, wave, rate)  # (once, on the device; the grid below is the front-end's)
         lprobs, _, cuts, cut_scores = self.long_form.encode(self.model, wave)
         T, V = lprobs.shape[1], lprobs.shape[2]
         tg = torch.as_tensor(list(tokens), dtype=torch.int32).to(lprobs.device)

@@ -19,6 +19,7 @@ import math
 import os
 from typing import List, Optional
 
+import numpy as np
 import torch
 
 from .. import kernels as K
@@ -117,6 +118,19 @@ def window_frames(frontend, model, plan: LongFormPlan, n_samples: int) -> List[i
     return [int(model.output_lengths(frontend.num_frames(ln))) for _, ln in plan.windows(n_samples)]
 
 
+def at_frontend_rate(frontend, wave, rate=None):
+    """The recording at the front-end's rate (host fp32): one pass of the device resampler over the whole recording when `rate`
+    is another one, the samples themselves otherwise.  Window plans, cuts and times then live on the front-end's grid, whose
+    seconds are the recording's (data/resample.py preserves durations)."""
+    if rate is None or int(rate) == frontend.sample_rate:
+        return wave
+    dev = frontend.device
+    x = torch.from_numpy(np.ascontiguousarray(wave, dtype=np.float32)).to(dev)
+    off = torch.tensor([0, len(wave)], dtype=torch.int64).to(dev)
+    y, _, _ = frontend.resampler(x, off, [len(wave)], [int(rate)])
+    return y.cpu().numpy()
+
+
 class LongFormCTC:
     """The front part of long-form recognition: `encode` turns one recording into stitched log-probs."""
 
@@ -172,24 +186,25 @@ class LongFormCTC:
         return out.view(1, T, V), torch.tensor([T], dtype=torch.int32).to(logits.device), cuts, scores
 
     @torch.no_grad()
-    def encode(self, model, wave):
-        """One recording (host samples) -> (lprobs fp32 [1][T][V], in_len, cuts, scores)."""
-        logits, counts = self.window_logits(model, wave)
+    def encode(self, model, wave, rate=None):
+        """One recording (host samples, at `rate`; None: the front-end's) -> (lprobs fp32 [1][T][V], in_len, cuts, scores)."""
+        logits, counts = self.window_logits(model, at_frontend_rate(self.task.frontend, wave, rate))
         return self.stitch(logits, counts)
 
 
 class LongFormModel:
     """What the CTC decoders ask of a model -- a forward and `get_normalized_probs` -- answered from stitched log-probs, so that
     `CTCDecoder`, `CTCPrefixBeamSearchDecoder` and `CTCLexiconBeamSearchDecoder` decode a recording as they decode an utterance.
-    A sample's net_input is {"wave": the recording's samples (host)}.  `junctions` collects (cuts, scores) per recording."""
+    A sample's net_input is {"wave": the recording's samples (host)}, with "rate" when they are not at the front-end's rate.
+    `junctions` collects (cuts, scores) per recording."""
 
     def __init__(self, model, long_form: LongFormCTC):
         self.model, self.long_form = model, long_form
         self.junctions = []
         self.lprobs = None  # the last recording's matrix [1][T][V] (what `LongFormPosteriors` scores the hypotheses on)
 
-    def __call__(self, wave):
-        lprobs, in_len, cuts, scores = self.long_form.encode(self.model, wave)
+    def __call__(self, wave, rate=None):
+        lprobs, in_len, cuts, scores = self.long_form.encode(self.model, wave, **({} if rate is None else {"rate": rate}))
         self.junctions.append((cuts, scores))
         self.lprobs = lprobs
         return {"_lprobs": lprobs, "src_lengths": [in_len], "encoder_padding_mask": [torch.zeros(1, lprobs.shape[1], dtype=torch.bool,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """`<utt-id> <num_frames>` lines from a wav.scp, read from the WAV headers only (espresso/tools/wav2num_frames.py:41-63;
-frame count = 1 + (N - 400) // 160 as in espresso/tools/utils.py:478-486)."""
+frame count = 1 + (N - 400) // 160 as in espresso/tools/utils.py:478-486, N = the sample count once the audio is at 16 kHz: a
+file at another rate is resampled by the front-end to ceil(n * 16000 / rate) samples, and that is what --max-tokens budgets)."""
 import argparse
 import re
 import sys
@@ -16,11 +17,12 @@ def get_parser():
 
 def process(line: str) -> str:
     from ..data.asr_dataset import samples_to_frames
-    from ..data.audio_utils import num_samples
+    from ..data.audio_utils import samples_and_rate
+    from ..data.resample import resampled_length
 
     utt_id, rxfile = line.rstrip().split(None, 1)
     assert re.search(r"\.ark:\d+$", rxfile.strip()) is None, "Please provide raw waveform files"
-    return utt_id + " " + str(samples_to_frames(num_samples(rxfile)))
+    return utt_id + " " + str(samples_to_frames(resampled_length(*samples_and_rate(rxfile), 16000)))
 
 
 def main(args, out=sys.stdout):

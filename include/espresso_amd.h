@@ -906,6 +906,23 @@ int ea_fbank_batch_i16(const int16_t* wav, const long* offsets, int B, const flo
 int ea_specaugment(float* feat, const int* lengths, const float* utt_sum, const int* fmask, const int* tmask,
                    int nf, int nt, int B, int Tmax, int nmel, int use_mean, float mask_value, ea_stream_t stream);
 
+/* Polyphase resampler in front of the fbank (csrc/resample.hip; the Hann-windowed sinc of Kaldi's LinearResample, built on the
+ * host by espresso_amd/data/resample.py): taps fp32 [phases][K], first int32 [phases].  Output j (ABSOLUTE index) has phase
+ * p = j % phases and unit u = j / phases, and is  y[j] = sum_k taps[p][k] * x[first[p] + u * in_unit + k]  with
+ * acc = +0; for k ascending: acc = fmaf(taps[p][k], x_k, acc)  in fp32 — the same bits for an utterance resampled at once and
+ * in pieces.  in: concatenated samples, in_offsets int64 [B+1]; in_base int64 [B] = absolute index of the first sample held
+ * for utterance b (samples outside [in_base[b], in_base[b] + len_b) read as 0); out fp32, out_offsets int64 [B+1] = where and
+ * how many, out_base int64 [B] = absolute index of the first output to produce.  NULL bases mean 0 (offline).  max_out >= the
+ * largest output count.  One launch, no host synchronisation, no atomics.  B <= 0 or max_out <= 0 returns 0; K outside
+ * [1, 4096], phases <= 0, in_unit <= 0 or B > 65535 returns -2; no output is written in either case. */
+int ea_resample_batch(const float* in, const long* in_offsets, const long* in_base, float* out, const long* out_offsets,
+                      const long* out_base, int B, const float* taps, const int* first, int phases, int K, int in_unit,
+                      long max_out, ea_stream_t stream);
+/* the same on int16 samples: the conversion to fp32 is exact, the outputs are bit-identical */
+int ea_resample_batch_i16(const int16_t* in, const long* in_offsets, const long* in_base, float* out, const long* out_offsets,
+                      const long* out_base, int B, const float* taps, const int* first, int phases, int K, int in_unit,
+                      long max_out, ea_stream_t stream);
+
 /* Global CMVN statistics on the device — espresso/tools/compute_global_cmvn_stats.py:55-120 (per-utterance numpy
  * sum / variance merged on the host).  acc fp64 [2*nmel+1] = (sum[f], sum of squares[f], frame count), accumulated
  * across calls over the valid frames (t < lengths[b]) of feat fp32 [B][Tmax][nmel]; zeroed by the caller once. */
