@@ -2025,3 +2025,32 @@ def longform_stitch(logits, counts, cuts, V, Hf, T, out=None):
     check(_lib.lib().ea_longform_stitch(_p(logits), is_bf16, ld, _p(counts), _p(cuts) if Nw > 1 else None, Nw, Tw, V, Hf, T, _p(out),
                                         out.stride(0), _stream()), "ea_longform_stitch")
     return out
+
+
+def longform_feature_cuts(x, counts, D, Hf, edge, guard):
+    """Long-form junction cuts on encoder outputs (include/espresso_amd.h, "Long-form recognition for transducer models").
+    x [Nw][Tw][ld >= D] bf16 or fp32, counts int32 [Nw] on the device -> (cuts int32 [Nw - 1], scores fp32 [Nw - 1], <= 0)."""
+    Nw, Tw, ld, is_bf16 = _longform_args(x, counts, D)
+    cuts = torch.empty(Nw - 1, dtype=torch.int32, device=x.device)
+    scores = torch.empty(Nw - 1, dtype=torch.float32, device=x.device)
+    check(_lib.lib().ea_longform_feature_cuts(_p(x), is_bf16, ld, _p(counts), Nw, Tw, D, Hf, edge, guard, _p(cuts), _p(scores),
+                                              _stream()), "ea_longform_feature_cuts")
+    return cuts, scores
+
+
+def longform_stitch_rows(x, counts, cuts, D, Hf, T, out=None):
+    """The stitched encoder outputs [T][D] of a recording, in x's element type: row t is the bit copy of frame t's row in the window
+    that owns it under `cuts`.  `out` ([T][ldo >= D], x's dtype, rows contiguous) is written in columns < D only.  The kernel
+    moves bytes: any dtype of 2 or 4 bytes per element."""
+    assert x.dim() == 3 and x.is_contiguous() and x.element_size() in (2, 4)
+    Nw, Tw, ld = x.shape
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == Nw and counts.device == x.device
+    assert 1 <= D <= ld
+    assert Nw == 1 or (cuts.dtype == torch.int32 and cuts.is_contiguous() and cuts.numel() == Nw - 1)
+    if out is None:
+        out = torch.empty(T, D, dtype=x.dtype, device=x.device)
+    assert out.dtype == x.dtype and out.dim() == 2 and out.shape[0] == T and out.stride(1) == 1 and out.shape[1] >= D
+    assert out.device == x.device
+    check(_lib.lib().ea_longform_stitch_rows(_p(x), x.element_size(), ld, _p(counts), _p(cuts) if Nw > 1 else None, Nw, Tw, D, Hf, T,
+                                             _p(out), out.stride(0), _stream()), "ea_longform_stitch_rows")
+    return out

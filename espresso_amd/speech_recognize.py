@@ -14,7 +14,10 @@ with the stdlib) and optional `text` (`utt_id tokens...`) files; the front-end (
 `--long-form` (--search ctc / ctc_beam, an offline encoder-only CTC model) decodes every recording, of any length, as one
 utterance: overlapping windows are the batch of the offline forward, their logits are joined on the device into one log-prob
 matrix on the recording's own frame axis, and the search reads that (tools/long_form.py; the reference
-has no such path)."""
+has no such path).  `--long-form-transducer` (--search transducer_greedy / transducer_frame_beam, an offline transducer model)
+does the same for the project's other model family: the windows' encoder outputs are joined on the device where the two
+windows agree, and the frame-synchronous search runs over the recording's frames as over one utterance's (DESIGN.md section
+3.12)."""
 import argparse
 import os
 import json
@@ -383,6 +386,14 @@ def get_parser():
     from .tools.long_form import add_long_form_args
 
     add_long_form_args(p)  # --long-form: recordings of any length through an offline CTC model (--search ctc / ctc_beam)
+    p.add_argument("--long-form-transducer", action="store_true",
+                   help="transducer_greedy / transducer_frame_beam: decode every recording as overlapping windows of an offline "
+                        "transducer model, their encoder outputs joined on the device into one matrix on the recording's own frame "
+                        "axis, which the search reads as one utterance's (any length; one recording per sample; --lm-path, "
+                        "--token-ngram-lm, --transducer-hotwords, --nbest and --ctm work as they do on an utterance, times are the "
+                        "recording's).  A cut between two windows goes where their encoder outputs agree best; --long-form-window-s, "
+                        "--long-form-overlap-s, --long-form-edge-frames and --long-form-guard-frames configure it as they configure "
+                        "--long-form.  The agreement rule and these defaults are uncalibrated: no WER on real long recordings has been measured")
     p.add_argument("--long-form-posteriors", action="store_true",
                    help="--long-form (ctc / ctc_beam without --ngram-lm): after every `H-<utt>` line print `C-<utt>` as --confidence "
                         "does, computed after the search for hypotheses of any length by the tiled kernel of "
@@ -911,6 +922,9 @@ def load_member(state, name, block, task, dev):
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
+    from .tools.long_form import check_long_form_transducer_args
+
+    check_long_form_transducer_args(args)  # first: its refusals name --long-form-transducer, not the search
     check_ctm_args(args)
     check_confidence_args(args)
     check_token_ngram_args(args)
@@ -947,6 +961,8 @@ def main(argv=None):
     model_name, model_cfg = resolve_model_config(args.model, args.model_config, state)
     if args.long_form:  # before the weights are loaded: an encoder-only CTC model
         LF.require_ctc_model(model_name)
+    if args.long_form_transducer:  # likewise: a transducer model
+        LF.require_transducer_model(model_name)
     autoregressive = args.search == "beam"
     # the criterion the checkpoint was trained with decides whether "<s>" is the blank (speech_recognition.py:324, 345-347)
     crit = {"beam": "label_smoothed_cross_entropy_v2", "ctc": "ctc_loss", "ctc_beam": "ctc_loss", "ctc_stream_beam": "ctc_loss"}.get(args.search, "transducer_loss")
@@ -1017,7 +1033,7 @@ def main(argv=None):
                 lm = TensorizedLookaheadLanguageModel(lm, task.target_dictionary, oov_penalty=args.oov_penalty,
                                                       open_vocab=not args.disable_open_vocab)
     gen = None  # (the streamed beam searches build their own decoders in recognize_streaming, which validates the same options)
-    if args.search not in ("transducer_stream_beam", "ctc_stream_beam") and not args.long_form:
+    if args.search not in ("transducer_stream_beam", "ctc_stream_beam") and not args.long_form and not args.long_form_transducer:
         gen = build_generator(args, members if len(members) > 1 else model, task.target_dictionary, lm, ngram, context_graph)
     scp = read_scp(args.wav_scp)
     utt_ids = list(scp.keys())
@@ -1045,6 +1061,16 @@ def main(argv=None):
         stream = ({"utt_ids": [utt_ids[i]], "num_samples": [len(waves[i])],
                    **({"wav_rates": [rates[i]], "net_input": {"wave": waves[i], "rate": rates[i]}} if rates[i] != fo else
                       {"net_input": {"wave": waves[i]}})} for (i,) in batches)
+    lft_model = None
+    if args.long_form_transducer:  # one recording at a time; the generator's encoder pass is the stitched encoder outputs
+        frame_beam = args.search == "transducer_frame_beam"
+        lft_model = LF.LongFormTransducerModel(
+            model, LF.LongFormTransducer(task, LF.plan_from_args(args, task.frontend, model.encoder), args.max_tokens, args.batch_size),
+            search=(args.beam, args.nbest, context_graph is not None, bool(args.ctm)) if frame_beam else None)
+        gen = build_generator(args, lft_model, task.target_dictionary, lm, ngram, context_graph)
+        batches = shard_batches([[i] for i in range(len(utt_ids))], args.num_shards, args.shard_id)
+        stream = ({"utt_ids": [utt_ids[i]], "num_samples": [len(waves[i])], **({"wav_rates": [rates[i]]} if rates[i] != fo else {}),
+                   "net_input": lft_model.net_input(waves[i], rates[i] if rates[i] != fo else None)} for (i,) in batches)
     ctm_hyps = {} if args.ctm else None
 
     from .tools.forced_aligner import frame_seconds
@@ -1052,6 +1078,8 @@ def main(argv=None):
     def finish_ctm():
         if lf_model is not None:
             LF.log_worst(lf_model, sys.stderr)
+        if lft_model is not None:
+            LF.log_worst_features(lft_model, sys.stderr)
         if ctm_hyps is not None:
             write_ctm(args.ctm, utt_ids, ctm_hyps, task.target_dictionary, args.ctm_unit,
                       frame_seconds(model, task.frontend.frame_shift / task.frontend.sample_rate))

@@ -1500,6 +1500,29 @@ int ea_longform_cuts(const void* logits, int is_bf16, long ld, const int* counts
                      int guard, int* cuts, float* scores, ea_stream_t stream);
 int ea_longform_stitch(const void* logits, int is_bf16, long ld, const int* counts, const int* cuts, int Nw, int Tw, int V, int Hf,
                        long T, float* out, long ldo, ea_stream_t stream);
+/* Long-form recognition for transducer models: the join of the windows' ENCODER OUTPUTS (`_x_bt`, not logits) into one [T][D]
+ * matrix on the recording's own frame axis, which `joint_encoder_branch` and the frame-synchronous searches then read as one
+ * utterance's.  There is no blank column to cut at: the cut goes where the two windows' encoders agree.
+ *
+ * x: [Nw][Tw][ld >= D], bf16 (is_bf16 != 0) or fp32; counts, Nw, Tw, Hf, the windows' frames and the overlap [lo, hi) of junction
+ * n exactly as above.
+ * ea_longform_feature_cuts: for overlap frame j, a = window n's row of it (row j - n * Hf) and b = window n + 1's (row j - lo),
+ *   columns < D; num = sum_k (a_k - b_k)^2, den = sum_k a_k^2 + sum_k b_k^2, both accumulated in fp32; d(j) = num / den if den > 0,
+ *   else 0, so 0 <= d <= 2 and 0 means identical rows.  s(j) = -d(j) takes the place of b(j); everything after it is the rule of
+ *   ea_longform_cuts unchanged: score(c) = min of s over [c - guard, c + guard) within [lo, hi) with the same fallback for an
+ *   empty range, candidates lo + edge <= c <= hi - edge, the order (score descending, |2c - (lo + hi)|, c), floor((lo + hi) / 2)
+ *   without candidates, cuts[n] = lo and scores[n] = 0 for an empty overlap.  Scores are <= 0; 0: both windows give the same
+ *   features around the cut.  Nw == 1 launches nothing.  Tw - Hf <= 12288.  Rows >= counts[n] and columns >= D are never read.
+ *   The order in which a sum's terms are added is not part of the rule; each sum is within (D + 3) * 2^-24 of exact, relatively.
+ * ea_longform_stitch_rows: out [T][ldo >= D] of the same element type, elem_bytes = 2 or 4; row t = the bit copy of the D
+ *   elements of frame t's row in the window that owns it under `cuts` (the owner rule of ea_longform_stitch); columns >= D of
+ *   out are not written, rows of other windows are not read.  T <= (Nw - 1) * Hf + Tw and T <= INT_MAX; Tw < 2 * Hf for Nw > 1;
+ *   cuts may be NULL for Nw == 1; a frame whose owner under `cuts` does not hold it is left unwritten.
+ * Bad arguments return -2 and launch nothing. */
+int ea_longform_feature_cuts(const void* x, int is_bf16, long ld, const int* counts, int Nw, int Tw, int D, int Hf, int edge, int guard,
+                             int* cuts, float* scores, ea_stream_t stream);
+int ea_longform_stitch_rows(const void* x, int elem_bytes, long ld, const int* counts, const int* cuts, int Nw, int Tw, int D, int Hf,
+                            long T, void* out, long ldo, ea_stream_t stream);
 /* Joint network element-wise stages (espresso/models/transformer/speech_transformer_transducer_base.py:276-299):
  * Z[b][t][u] = relu(E[b][t] + D[b][u]) (bf16, E [B*T][J], D [B*U1][J], Z [B*T*U1][J], J % 8 == 0) and its backward
  * reductions dE[b][t] = sum_u dZ[b][t][u], dD[b][u] = sum_t dZ[b][t][u] (either output may be NULL). */
